@@ -240,6 +240,45 @@ def step_work(steps, to_right_first, bond_dims, pdims, wdims):
     return matvecs, flops
 
 
+DUMP_SITE_ELEMS = 32768          # --dump-outputs: elements kept per site tensor (50 sites x 32768 x 16 B = 26 MB)
+DUMP_LIMIT_BYTES = 64 << 20      # all files together; longer chains keep fewer elements per site
+
+
+def dump_outputs(dirname, mps, mpo, occ):
+    """--dump-outputs: what the timed path handed its caller after the last timed step, as float64 .npy files.
+
+    site_NNN.npy   the site tensors of the evolved MPS, as (..., 2) = (real, imag); a tensor larger than
+                   n = min(DUMP_SITE_ELEMS, what DUMP_LIMIT_BYTES allows per site) elements is a fixed sample of its
+                   flattened elements (positions drawn without replacement by numpy's default_rng(site index),
+                   sorted), shape (n, 2)
+    site_shapes.npy, bond_dims.npy, coeff.npy (real, imag of the MPS coefficient)
+    e_occupations.npy, energy.npy   gauge-independent observables of the same state
+    Only trajectory 0 of rank 0 is written."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    shapes = []
+    sites = mps.to_arrays()
+    keep = min(DUMP_SITE_ELEMS, (DUMP_LIMIT_BYTES // 2) // (16 * len(sites)))
+    for i, t in enumerate(sites):
+        shapes.append(t.shape)
+        flat = t.reshape(-1)
+        if flat.size > keep:
+            idx = np.sort(np.random.default_rng(i).choice(flat.size, keep, replace=False))
+            t = flat[idx]
+        arrays["site_%03d" % i] = np.stack([np.real(t), np.imag(t)], axis=-1)
+    arrays["site_shapes"] = np.array(shapes)
+    arrays["bond_dims"] = np.array(mps.bond_dims)
+    arrays["coeff"] = np.array([np.real(mps.coeff), np.imag(mps.coeff)])
+    arrays["e_occupations"] = np.asarray(occ)
+    e = complex(mps.expectation(mpo))
+    arrays["energy"] = np.array([e.real, e.imag])
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit"
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def _redone():
     """evolve steps (whole run, warm-up included) the optimistic block QR discarded and repeated on verified
     decompositions (mps/mps.py::_evolve_tdvp_ps)"""
@@ -311,7 +350,12 @@ def main():
     ap.add_argument("--dist-backend", default="rccl", choices=["rccl", "gloo"],
                     help="gloo + --share-gpu exercises the multi-rank flow on a single GPU (testing only)")
     ap.add_argument("--share-gpu", action="store_true", help="all ranks use GPU 0 (testing only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the state the last one computed (sampled site tensors, "
+                         "occupations, energy) as float64 DIR/<name>.npy, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # --gpus N is the number of ranks.  Under a launcher (RANK / WORLD_SIZE set) the two must agree; without one this
     # process starts the N ranks itself
@@ -458,6 +502,9 @@ def main():
     distinct = len({tuple(np.round(r, 10)) for r in occ_table})
     if world > 1 and rank == 0:
         print(f"[rank 0] gathered populations of {world} trajectories, {distinct} distinct", file=sys.stderr, flush=True)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, mps, mpo, row[:-5])
 
     if rank == 0:
         # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE;

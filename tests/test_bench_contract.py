@@ -1,11 +1,14 @@
 """The JSON line of bench.py as the driver reads it: the latest committed line (profiles/rNN_bench_20steps.json, printed
 by `python bench.py --gpus 1 --steps 20 --warmup 5` on an MI355X) carries every field of the contract, is consistent with
-itself, and names BASELINE.json's metric; bench.py accepts the driver's flags.  No GPU needed."""
+itself, and names BASELINE.json's metric; bench.py accepts the driver's flags.  No GPU needed, except for the
+small --dump-outputs run (pytest -m gpu)."""
 import glob
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,3 +64,33 @@ def test_bench_accepts_the_driver_flags():
     assert out.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup"):
         assert flag in out.stdout
+
+
+def test_bench_offers_dump_outputs():
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0 and "--dump-outputs" in out.stdout
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_small_chain(tmp_path):
+    """A small chain through the timed path: --steps sets the timed steps, the line carries ms_per_step, and
+    --dump-outputs writes the evolved state as float64 .npy files (normalised occupations, one file per site)."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--cpu-updates", "0", "--nmol", "3", "--pdim", "4", "--bond-dim", "16", "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    files = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    nsite = d["config"]["nsite"]
+    assert {"e_occupations", "energy", "bond_dims", "coeff", "site_shapes"} <= set(files)
+    assert sorted(k for k in files if k.startswith("site_") and k != "site_shapes") == [f"site_{i:03d}" for i in range(nsite)]
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["bond_dims"].tolist() == d["config"]["bond_dims"]
+    assert abs(files["e_occupations"].sum() - 1.0) < 1e-9
+    for i in range(nsite):
+        assert files[f"site_{i:03d}"].shape == tuple(files["site_shapes"][i].astype(int)) + (2,)
