@@ -17,8 +17,9 @@
 //   R = R_3 R_2 R_1 (tile products riding on the TRSM launches of passes 2 and 3).
 // Pass 1 is shifted (s = 11 (m n + n (n + 1)) u trace(G) >= the bound of Fukaya et al., SIAM J. Sci. Comput. 42 (2020)
 // A477, which uses |A|_2^2): it cannot break down and leaves kappa(A_1) <~ 1e8 for kappa(A) up to ~1e15; passes 2 and 3
-// are plain CholeskyQR2.  When the Gram matrix of pass 3 is the identity to first order (n max|G - I| <= 1e-9) its
-// factor is written down (R = I + striu(E) + diag(E) / 2, error O(|E|^2)) and the triangular solve becomes a product.
+// are plain CholeskyQR2.  When the Gram matrix of pass 2 or 3 is the identity to first order (n max|G - I| <= 1e-9)
+// its factor is written down (R = I + striu(E) + diag(E) / 2, error O(|E|^2)) and the triangular solve becomes a
+// product.
 //
 // Rank-deficient / too ill-conditioned blocks (the 1e-10 padding of expand_bond_dimension in the first steps of a
 // run: profiles/r05_qr_cond_step2.md - 4 of 98 decompositions; none of 98 at step 13) make a pivot of pass 2 / 3
@@ -375,7 +376,7 @@ __device__ __forceinline__ void panel_eliminate(double2 (*tiles)[256], int W, in
 // operands read from the tiles already written (global memory / L2, same workgroup); the diagonal tile is factorised
 // in the registers of wave 0 (lane j = column j, rows by v_readlane broadcasts), the rest of the row panel solved
 // by forward substitution, one thread per column.
-// status[0] |= 1 on a breakdown; status[1 + block] = 1 when the first-order factor was taken (pass 3 only).
+// status[0] |= 1 on a breakdown; status[1 + block] = 1 when the first-order factor was taken (pass 2 or 3).
 template <bool CPLX>
 __global__ __launch_bounds__(512) void k_cq_chol(const double* __restrict__ G, const double* __restrict__ tinfo,
                                                   double* __restrict__ R, const CqBlk* __restrict__ blks,
@@ -651,7 +652,7 @@ __global__ __launch_bounds__(512) void k_cq_chol_rl(const double* __restrict__ G
 //     p = w, w + 4, .. as MFMA accumulators; for q = 0 .. P-1 the owner solves X_q R_qq = A_q by substitution inside the
 //     accumulator layout (lane = (row group, column): the finished column t of X_q is broadcast along the 16-lane rows
 //     by DPP row_share), stores X_q and publishes it through LDS as the A operand of the updates A_p -= X_q R(q, p).
-//     mode 1 (first-order factor R = I + U of pass 3): X_p = A_p - sum_{q<=p} A_q U(q, p), no dependent chain.
+//     mode 1 (first-order factor R = I + U of pass 2 or 3): X_p = A_p - sum_{q<=p} A_q U(q, p), no dependent chain.
 //   the other workgroups: one tile each of Rout = Rcur . Rprev (the accumulated triangular factor).
 template <bool CPLX>
 __global__ __launch_bounds__(256) void k_cq_trsm(double* __restrict__ ws, const double* __restrict__ R,

@@ -349,7 +349,7 @@ int publish_wait_seq(mpse_ctx* ctx, double seq, const double* dsrc, int count, i
 // reductions (mpse_vec.hip): results land in ctx->pinned after a stream sync
 int dotc_sync(mpse_ctx* ctx, int dtype, const void* x, const void* y, int64_t n, double* re, double* im);
 
-// Householder building blocks on column-major workspaces (mpse_qr.hip), shared with the SVD
+// Householder QR on column-major workspaces (mpse_qr2.hip), shared by mpse_block_qr and the SVD
 struct HhParam {  // per reflector: H = I - tau v v^H, v = (1, scale * tail)
   double tau_re, tau_im;
   double scale_re, scale_im;
@@ -358,12 +358,7 @@ struct HhParam {  // per reflector: H = I - tau v v^H, v = (1, scale * tail)
   // applications need for T
   double g[6];
 };
-int hh_factor_colmajor(mpse_ctx* ctx, bool cplx, double* ws, int mm, int nn, int k, HhParam* prm);
-// nq >= k columns of Q are formed (columns beyond k span the orthogonal complement)
-int hh_formq_colmajor(mpse_ctx* ctx, bool cplx, double* q, const double* ws, int mm, int k, const HhParam* prm,
-                      int nq);
-
-// Batched panel-blocked Householder QR (mpse_qr2.hip): blocks live in one column-major workspace
+// one block of a QR: the blocks of a call live in one column-major workspace
 struct QrBlk {
   long long ws_off;  // element offset of the mm x nn block inside the workspace
   long long q_off;   // element offset of its mm x k Q inside the Q buffer
@@ -372,12 +367,12 @@ struct QrBlk {
   int nq = 0;        // columns of Q to form (0 -> k); columns beyond k complete the basis (full_matrices SVD)
   long long row_off = 0, col_off = 0;   // block_qr: where the block's row / column index lists start (device lists)
 };
-constexpr int HH_BATCH_MAX_ROWS = 4096;
+constexpr int HH_BATCH_MAX_ROWS = 4096;                      // taller blocks: unblocked kernels, one block at a time
 constexpr unsigned long long GEMM_TRACE_CAP = 1ull << 21;   // records
 constexpr int GEMM_TRACE_WORDS = 10;                         // 64-bit words per record
-// ``blks_dev``: the same descriptors already on the device (else they are uploaded here)
-int hh_qr_batched(mpse_ctx* ctx, bool cplx, double* ws, double* q, HhParam* prm, const QrBlk* blks_host, int nblk,
-                  bool form_q, const QrBlk* blks_dev = nullptr);
+// any block height; ``blks_dev``: the same descriptors already on the device (else they are uploaded here)
+int hh_qr(mpse_ctx* ctx, bool cplx, double* ws, double* q, HhParam* prm, const QrBlk* blks_host, int nblk, bool form_q,
+          const QrBlk* blks_dev = nullptr);
 // Shifted Cholesky-QR of tall blocks on MFMA (mpse_cholqr.hip).  The blocks are factorised in place in their column-major
 // workspaces and scattered to U / Vt like mpse_block_qr does; *ok = false when a block was rank deficient or too ill
 // conditioned for the scheme (device flag, one read-back): the caller then runs the Householder path on fresh copies.

@@ -5,152 +5,13 @@
 // a fixed-bond TDVP sweep are numerically rank deficient most of the time: Gram-matrix
 // (Cholesky) schemes break down there, Householder always returns an exact isometry.
 // Layout: each block is gathered into a column-major workspace so that the column-wise
-// reductions are coalesced; one workgroup owns one column.
-//   factorisation : one launch per reflector j - workgroup c applies H_j^H to column c > j
-//                   (dot + update, column stays in L2) and the owner of column j+1 then
-//                   derives the next reflector's parameters in the same launch;
-//   Q formation   : ONE launch - column c of Q = H_0 ... H_c e_c is independent of all other
-//                   columns, so workgroup c applies its reflectors back to back.
+// reductions are coalesced; the factorisation and the explicit Q are hh_qr's (mpse_qr2.hip),
+// tall blocks may go through the shifted Cholesky-QR first (mpse_cholqr.hip).
+#include "mpse_cx.h"
 #include "mpse_device.h"
 #include "mpse_internal.h"
 
 namespace {
-
-template <bool CPLX>
-struct Cx;
-template <>
-struct Cx<true> {
-  static constexpr int E = 2;
-  __device__ static double2 ld(const double* p, long long i) { return reinterpret_cast<const double2*>(p)[i]; }
-  __device__ static void st(double* p, long long i, double2 v) { reinterpret_cast<double2*>(p)[i] = v; }
-};
-template <>
-struct Cx<false> {
-  static constexpr int E = 1;
-  __device__ static double2 ld(const double* p, long long i) { return make_double2(p[i], 0.0); }
-  __device__ static void st(double* p, long long i, double2 v) { p[i] = v.x; }
-};
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 cmulc(double2 a, double2 b) {  // conj(a) * b
-  return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x);
-}
-
-// reflector parameters for column j from its current content (rows >= j); one workgroup.
-template <bool CPLX>
-__device__ void hh_make_params(double* a, int mm, int j, HhParam* prm) {
-  double* col = a + (long long)j * mm * Cx<CPLX>::E;
-  double s = 0, z = 0;
-  for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
-    const double2 v = Cx<CPLX>::ld(col, r);
-    s += v.x * v.x + v.y * v.y;
-  }
-  block_allsum2(s, z);
-  if (threadIdx.x == 0) {
-    const double2 alpha = Cx<CPLX>::ld(col, j);
-    HhParam p;
-    if (s == 0.0 && alpha.y == 0.0) {
-      p.tau_re = p.tau_im = p.scale_re = p.scale_im = 0.0;  // H = I
-    } else {
-      const double nrm = sqrt(alpha.x * alpha.x + alpha.y * alpha.y + s);
-      const double beta = alpha.x >= 0.0 ? -nrm : nrm;
-      p.tau_re = (beta - alpha.x) / beta;
-      p.tau_im = -alpha.y / beta;
-      const double dr = alpha.x - beta, di = alpha.y;  // scale = 1 / (alpha - beta)
-      const double den = dr * dr + di * di;
-      p.scale_re = dr / den;
-      p.scale_im = -di / den;
-      Cx<CPLX>::st(col, j, make_double2(beta, 0.0));
-    }
-    prm[j] = p;
-  }
-}
-
-template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_hh_first(double* a, int mm, HhParam* prm) {
-  hh_make_params<CPLX>(a, mm, 0, prm);
-}
-
-// apply H_j^H to column c = j + 1 + blockIdx.x ; then (c == j+1) derive reflector j+1
-template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_hh_apply(double* a, int mm, int kref, int j, HhParam* prm) {
-  constexpr int E = Cx<CPLX>::E;
-  const int c = j + 1 + blockIdx.x;
-  const double* vj = a + (long long)j * mm * E;
-  double* col = a + (long long)c * mm * E;
-  const HhParam p = prm[j];
-  const double2 tau = make_double2(p.tau_re, p.tau_im), scale = make_double2(p.scale_re, p.scale_im);
-  if (tau.x != 0.0 || tau.y != 0.0) {
-    double dr = 0, di = 0;
-    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
-      const double2 t = cmulc(Cx<CPLX>::ld(vj, r), Cx<CPLX>::ld(col, r));
-      dr += t.x;
-      di += t.y;
-    }
-    block_allsum2(dr, di);
-    // dot = v^H col = col[j] + conj(scale) * sum conj(tail) col
-    const double2 head = Cx<CPLX>::ld(col, j);
-    const double2 sc = cmulc(scale, make_double2(dr, di));
-    const double2 dot = make_double2(head.x + sc.x, head.y + sc.y);
-    const double2 f = cmulc(tau, dot);          // conj(tau) * dot
-    const double2 fs = cmul(f, scale);
-    __syncthreads();  // everyone has read col[j] before thread 0 overwrites it
-    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
-      const double2 t = cmul(fs, Cx<CPLX>::ld(vj, r));
-      double2 x = Cx<CPLX>::ld(col, r);
-      x.x -= t.x;
-      x.y -= t.y;
-      Cx<CPLX>::st(col, r, x);
-    }
-    if (threadIdx.x == 0) Cx<CPLX>::st(col, j, make_double2(head.x - f.x, head.y - f.y));
-  }
-  if (blockIdx.x == 0 && j + 1 < kref) {
-    __syncthreads();
-    hh_make_params<CPLX>(a, mm, j + 1, prm);
-  }
-}
-
-// column c of Q (mm x k, column-major) = H_0 H_1 ... H_c e_c
-template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_hh_formq(double* q, const double* __restrict__ a, int mm, int kref,
-                                                          const HhParam* __restrict__ prm) {
-  constexpr int E = Cx<CPLX>::E;
-  const int c = blockIdx.x;
-  double* col = q + (long long)c * mm * E;
-  for (int r = threadIdx.x; r < mm; r += RED_THREADS) Cx<CPLX>::st(col, r, make_double2(r == c ? 1.0 : 0.0, 0.0));
-  __syncthreads();
-  // columns c >= kref (orthogonal complement, used for full_matrices SVD) receive all reflectors
-  for (int j = (c < kref ? c : kref - 1); j >= 0; --j) {
-    const HhParam p = prm[j];
-    const double2 tau = make_double2(p.tau_re, p.tau_im), scale = make_double2(p.scale_re, p.scale_im);
-    if (tau.x == 0.0 && tau.y == 0.0) continue;
-    const double* vj = a + (long long)j * mm * E;
-    double dr = 0, di = 0;
-    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
-      const double2 t = cmulc(Cx<CPLX>::ld(vj, r), Cx<CPLX>::ld(col, r));
-      dr += t.x;
-      di += t.y;
-    }
-    block_allsum2(dr, di);
-    const double2 head = Cx<CPLX>::ld(col, j);
-    const double2 sc = cmulc(scale, make_double2(dr, di));
-    const double2 dot = make_double2(head.x + sc.x, head.y + sc.y);
-    const double2 f = cmul(tau, dot);  // H (not H^H)
-    const double2 fs = cmul(f, scale);
-    __syncthreads();  // everyone has read col[j]
-    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
-      const double2 t = cmul(fs, Cx<CPLX>::ld(vj, r));
-      double2 x = Cx<CPLX>::ld(col, r);
-      x.x -= t.x;
-      x.y -= t.y;
-      Cx<CPLX>::st(col, r, x);
-    }
-    if (threadIdx.x == 0) Cx<CPLX>::st(col, j, make_double2(head.x - f.x, head.y - f.y));
-    __syncthreads();
-  }
-}
 
 // gather the blocks into their column-major workspaces, ws[r + c*mm] - all blocks of a decomposition in one launch
 // (blockIdx.y = block, descriptors and index lists on the device):
@@ -226,38 +87,7 @@ __global__ void k_scatter_blocks(double* U, double* Vt, const double* __restrict
   }
 }
 
-inline int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace
-
-// Householder factorisation of a column-major mm x nn workspace in place (k = min(mm,nn)
-// reflectors; R ends up in the upper triangle, reflector tails below the diagonal).
-int hh_factor_colmajor(mpse_ctx* ctx, bool cplx, double* ws, int mm, int nn, int k, HhParam* prm) {
-  if (k <= 0) return MPSE_OK;
-  if (mm <= HH_BATCH_MAX_ROWS) {
-    QrBlk b{0, 0, mm, nn, k, 0};
-    return hh_qr_batched(ctx, cplx, ws, nullptr, prm, &b, 1, false);
-  }
-  if (cplx)
-    hipLaunchKernelGGL((k_hh_first<true>), dim3(1), dim3(RED_THREADS), 0, ctx->stream, ws, mm, prm);
-  else
-    hipLaunchKernelGGL((k_hh_first<false>), dim3(1), dim3(RED_THREADS), 0, ctx->stream, ws, mm, prm);
-  for (int j = 0; j < k; ++j) {
-    const int ncols_right = nn - j - 1;
-    if (ncols_right <= 0) break;
-    if (cplx)
-      hipLaunchKernelGGL((k_hh_apply<true>), dim3(ncols_right), dim3(RED_THREADS), 0, ctx->stream, ws, mm, k, j, prm);
-    else
-      hipLaunchKernelGGL((k_hh_apply<false>), dim3(ncols_right), dim3(RED_THREADS), 0, ctx->stream, ws, mm, k, j, prm);
-  }
-  MPSE_HIP(ctx, hipGetLastError());
-  return MPSE_OK;
-}
 
 int qr_words(mpse_ctx* ctx) {
   if (ctx->qr_words_dev) return MPSE_OK;
@@ -265,19 +95,6 @@ int qr_words(mpse_ctx* ctx) {
   MPSE_TRY(mpse_malloc(ctx, 16, &p));
   ctx->qr_words_dev = static_cast<int*>(p);
   return device_zero(ctx, ctx->qr_words_dev, 16);
-}
-
-// explicit Q (mm x k, column-major) from a factored workspace
-int hh_formq_colmajor(mpse_ctx* ctx, bool cplx, double* q, const double* ws, int mm, int k, const HhParam* prm,
-                      int nq) {
-  if (k <= 0) return MPSE_OK;
-  if (nq < k) nq = k;
-  if (cplx)
-    hipLaunchKernelGGL((k_hh_formq<true>), dim3(nq), dim3(RED_THREADS), 0, ctx->stream, q, ws, mm, k, prm);
-  else
-    hipLaunchKernelGGL((k_hh_formq<false>), dim3(nq), dim3(RED_THREADS), 0, ctx->stream, q, ws, mm, k, prm);
-  MPSE_HIP(ctx, hipGetLastError());
-  return MPSE_OK;
 }
 
 namespace {
@@ -289,7 +106,6 @@ int block_qr_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, i
                   int64_t K) {
   constexpr size_t es = CPLX ? 16 : 8;
   int64_t ktot = 0, ws_tot = 0, q_tot = 0;
-  int max_mm = 0;
   std::vector<QrBlk> blks;
   std::vector<int> which;  // index of the source block
   for (int b = 0; b < nblocks; ++b) {
@@ -303,7 +119,6 @@ int block_qr_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, i
     ws_tot += mm * nn;
     q_tot += mm * k;
     ktot += k;
-    if (mm > max_mm) max_mm = (int)mm;
   }
   if (ktot != K) return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_qr: K=%lld but blocks give %lld", (long long)K, (long long)ktot);
   if (ktot == 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "Invalid quantum number");
@@ -334,7 +149,6 @@ int block_qr_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, i
   memcpy(host.data() + ib, blks.data(), db);
   // (replaying the launch sequence from a HIP graph measured no gain - 0.411 vs 0.414 ms per d = 2 decomposition: the
   // ~4 us between the dependent panel / update kernels are spent on the device, not by the host - and was removed)
-  const bool batched = max_mm <= HH_BATCH_MAX_ROWS;
   TmpBuf IDX(ctx), WS(ctx), Q(ctx), PRM(ctx);
   MPSE_TRY(IDX.alloc(ib + db));
   MPSE_TRY(WS.alloc(size_t(ws_tot) * es));
@@ -343,7 +157,6 @@ int block_qr_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, i
   const long long* dcols = drows + nri;
   const QrBlk* dblk = reinterpret_cast<const QrBlk*>(static_cast<const char*>(IDX.p) + ib);
   double* ws = static_cast<double*>(WS.p);
-  constexpr int E = CPLX ? 2 : 1;
   ++ctx->qr_calls;
   hipLaunchKernelGGL((k_gather_blocks<CPLX>), dim3(ew_blocks(max_el), (unsigned)blks.size()), dim3(256), 0, ctx->stream, ws,
                      (const double*)coef, (long long)ncol, drows, dcols, dblk, herm);
@@ -367,14 +180,7 @@ int block_qr_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, i
   MPSE_TRY(PRM.alloc(size_t(ktot + 1) * sizeof(HhParam)));
   double* q = static_cast<double*>(Q.p);
   HhParam* prm = static_cast<HhParam*>(PRM.p);
-  if (batched) {
-    MPSE_TRY(hh_qr_batched(ctx, CPLX, ws, q, prm, blks.data(), (int)blks.size(), true, dblk));
-  } else {
-    for (const QrBlk& B : blks) {
-      MPSE_TRY(hh_factor_colmajor(ctx, CPLX, ws + B.ws_off * E, B.mm, B.nn, B.k, prm + B.prm_off));
-      MPSE_TRY(hh_formq_colmajor(ctx, CPLX, q + B.q_off * E, ws + B.ws_off * E, B.mm, B.k, prm + B.prm_off, B.k));
-    }
-  }
+  MPSE_TRY(hh_qr(ctx, CPLX, ws, q, prm, blks.data(), (int)blks.size(), true, dblk));
   hipLaunchKernelGGL((k_scatter_blocks<CPLX>), dim3(ew_blocks(max_sc), (unsigned)blks.size()), dim3(256), 0, ctx->stream,
                      (double*)U, (double*)Vt, (const double*)q, (const double*)ws, (long long)K, (long long)ncol, drows, dcols,
                      dblk, herm);

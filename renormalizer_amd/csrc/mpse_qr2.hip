@@ -1,55 +1,30 @@
-// Batched, panel-blocked Householder QR on column-major workspaces.
+// Householder QR on column-major workspaces: every block height, one entry point (hh_qr).
 //
-// All quantum-number blocks of a decomposition are factorised by the SAME launches (grid.y =
-// block), and the dependent chain of reflectors is cut into panels of NB columns:
-//   k_hh_panel       : ONE workgroup (256 or 512 threads by block height) per block keeps the
-//                      m x NB panel in registers and factorises it: one block-wide reduction per
-//                      column delivers the column norm and all inner products with the remaining
-//                      panel columns at once (eight values through a halving DPP butterfly), the
-//                      dot and update phases are branch free;
-//   k_hh_apply_panel : one 256-thread workgroup per trailing column keeps that column in
-//                      registers and applies the NB new reflectors back to back (reflector tails
-//                      stream from L2);
-//   k_hh_formq_b     : one workgroup per column of Q, column in registers, reflectors applied
-//                      in reverse.
-// Per NB columns this costs 2 launches instead of NB, and the trailing matrix is read and written
-// once per panel instead of once per reflector.  The default path applies the panels in compact-WY form
-// (k_hh_apply_wy / k_hh_formq_wy: one reduction round per panel instead of one per reflector); the inner products
-// of the reflector tails that T needs fall out of the panel kernel's own reduction rounds (retired columns stay in
-// its register ring), so the applying workgroups only reduce V^H x.  Blocks of at most 1024 rows run one launch
-// per panel (k_hh_step: the panel's workgroup first gives its columns the previous panel's reflectors, the trailing
-// update of that panel runs beside it); taller blocks keep the two launches: there the update of the four panel
-// columns alone fills its compute unit's FP64 pipe for longer than the second launch costs.  Conventions are LAPACK's (?geqr2 / ?ung2r):
-// H_j = I - tau_j v_j v_j^H, v_j = (0.., 1, scale_j * tail_j), tails stored UNSCALED below the
-// diagonal, R on and above it.
-#include <cstdlib>
-
+// Blocks of at most HH_BATCH_MAX_ROWS rows: all quantum-number blocks of a decomposition are factorised by the SAME
+// launches (grid.y = block), and the dependent chain of reflectors is cut into panels of four columns:
+//   k_hh_panel    : ONE workgroup (256 or 512 threads by block height) per block keeps the m x 4 panel in registers
+//                   and factorises it: one block-wide reduction per column delivers the column norm and all inner
+//                   products with the remaining panel columns at once (eight values through a halving DPP butterfly),
+//                   the dot and update phases are branch free;
+//   k_hh_apply_wy : the trailing columns receive the panel's reflectors in compact-WY form (one reduction round per
+//                   panel instead of one per reflector); the inner products of the reflector tails that T needs fall
+//                   out of the panel kernel's own reduction rounds (retired columns stay in its register ring), so
+//                   the applying workgroups only reduce V^H x;
+//   k_hh_formq_wy : one workgroup per column of Q, column in registers, panels applied in reverse.
+// Blocks of at most 1024 rows run one launch per panel (k_hh_step: the panel's workgroup first gives its columns the
+// previous panel's reflectors, the trailing update of that panel runs beside it); taller blocks keep the two launches:
+// there the update of the four panel columns alone fills its compute unit's FP64 pipe for longer than the second
+// launch costs.
+// Taller blocks (no configuration produces one) go one at a time through the unblocked kernels: k_hh_apply
+// applies reflector j to every column right of it and derives reflector j + 1, a launch per reflector; k_hh_formq
+// forms Q in one launch, a workgroup per column.
+// Conventions are LAPACK's (?geqr2 / ?ung2r): H_j = I - tau_j v_j v_j^H, v_j = (0.., 1, scale_j * tail_j), tails
+// stored UNSCALED below the diagonal, R on and above it.
+#include "mpse_cx.h"
 #include "mpse_device.h"
 #include "mpse_internal.h"
 
 namespace {
-
-template <bool CPLX>
-struct Cx;
-template <>
-struct Cx<true> {
-  static constexpr int E = 2;
-  __device__ static double2 ld(const double* p, long long i) { return reinterpret_cast<const double2*>(p)[i]; }
-  __device__ static void st(double* p, long long i, double2 v) { reinterpret_cast<double2*>(p)[i] = v; }
-};
-template <>
-struct Cx<false> {
-  static constexpr int E = 1;
-  __device__ static double2 ld(const double* p, long long i) { return make_double2(p[i], 0.0); }
-  __device__ static void st(double* p, long long i, double2 v) { p[i] = v.x; }
-};
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 cmulc(double2 a, double2 b) {  // conj(a) * b
-  return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x);
-}
 
 __device__ __forceinline__ void make_reflector(double2 alpha, double s, HhParam* p, double* beta_out) {
   const double n2 = alpha.x * alpha.x + alpha.y * alpha.y + s;
@@ -391,154 +366,6 @@ __global__ __launch_bounds__(NT) void k_hh_panel(double* ws_base, const QrBlk* _
   hh_panel_role<CPLX, NT, RPT, NB, false>(ws_base, B, prm_base, j0);
 }
 
-// ---- apply reflectors j0 .. j0+nbb-1 (H^H, in order) to trailing column c; 256 threads, rows tid + 256 q
-template <bool CPLX, int RPT>
-__global__ __launch_bounds__(256) void k_hh_apply_panel(double* ws_base, const QrBlk* __restrict__ blks,
-                                                        const HhParam* __restrict__ prm_base, int j0, int nb) {
-  constexpr int E = Cx<CPLX>::E;
-  __shared__ double s_head[2];
-  const QrBlk B = blks[blockIdx.y];
-  if (j0 >= B.k) return;
-  const int nbb = min(nb, B.k - j0);
-  const int c = j0 + nbb + blockIdx.x;
-  if (c >= B.nn) return;
-  const int mm = B.mm;
-  double* a = ws_base + B.ws_off * E;
-  const HhParam* prm = prm_base + B.prm_off;
-  double* col = a + (long long)c * mm * E;
-  const int tid = threadIdx.x;
-  double2 x[RPT];
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int r = tid + 256 * q;
-    x[q] = (r >= j0 && r < mm) ? Cx<CPLX>::ld(col, r) : make_double2(0.0, 0.0);
-  }
-  // reflector tails stream from L2: the loads for reflector jj+1 are issued before the reduction of jj
-  double2 v[RPT], vn[RPT];
-  auto load_v = [&](int jj, double2* dst) {
-    const int j = j0 + jj;
-    const double* vj = a + (long long)j * mm * E;
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-      const int r = tid + 256 * q;
-      dst[q] = (r > j && r < mm) ? Cx<CPLX>::ld(vj, r) : make_double2(0.0, 0.0);
-    }
-  };
-  load_v(0, v);
-  for (int jj = 0; jj < nbb; ++jj) {
-    const int j = j0 + jj;
-    if (jj + 1 < nbb) load_v(jj + 1, vn);
-    const HhParam p = prm[j];
-    const double2 tau = make_double2(p.tau_re, p.tau_im), scale = make_double2(p.scale_re, p.scale_im);
-    if (tau.x != 0.0 || tau.y != 0.0) {  // block-uniform
-      double dr = 0, di = 0;
-#pragma unroll
-      for (int q = 0; q < RPT; ++q) {
-        const int r = tid + 256 * q;
-        const double2 t2 = cmulc(v[q], x[q]);
-        dr += t2.x;
-        di += t2.y;
-        if (r == j) {
-          s_head[0] = x[q].x;
-          s_head[1] = x[q].y;
-        }
-      }
-      block_allsum2(dr, di);  // two barriers inside: s_head is visible afterwards
-      const double2 head = make_double2(s_head[0], s_head[1]);
-      const double2 sc = cmulc(scale, make_double2(dr, di));
-      const double2 f = cmulc(tau, make_double2(head.x + sc.x, head.y + sc.y));
-      const double2 fs = cmul(f, scale);
-#pragma unroll
-      for (int q = 0; q < RPT; ++q) {
-        const int r = tid + 256 * q;
-        const double2 t2 = cmul(fs, v[q]);  // v is zero outside the tail
-        x[q].x -= t2.x;
-        x[q].y -= t2.y;
-        if (r == j) {
-          x[q].x -= f.x;
-          x[q].y -= f.y;
-        }
-      }
-      __syncthreads();  // s_head reused by the next reflector
-    }
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) v[q] = vn[q];
-  }
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int r = tid + 256 * q;
-    if (r >= j0 && r < mm) Cx<CPLX>::st(col, r, x[q]);
-  }
-}
-
-// ---- column c of Q = H_0 ... H_c e_c ; 256 threads, column in registers
-template <bool CPLX, int RPT>
-__global__ __launch_bounds__(256) void k_hh_formq_b(double* q_base, const double* __restrict__ ws_base,
-                                                    const QrBlk* __restrict__ blks,
-                                                    const HhParam* __restrict__ prm_base) {
-  constexpr int E = Cx<CPLX>::E;
-  __shared__ double s_head[2];
-  const QrBlk B = blks[blockIdx.y];
-  // A workgroup runs on die (launch position mod 8).  Column c starts at panel c / 4 and walks down: neighbouring
-  // columns are at the same panel at the same time.  Every die therefore takes a contiguous range of columns, so
-  // that its workgroups read the same reflector panel while it is in that die's L2 (with the columns dealt round
-  // robin, a die held workgroups at 16 different panels and streamed the reflectors 456 MB per launch through).
-  int c = blockIdx.x;
-  if ((gridDim.x & 7) == 0) c = (c & 7) * (gridDim.x >> 3) + (c >> 3);
-  if (c >= (B.nq > B.k ? B.nq : B.k)) return;
-  const int mm = B.mm;
-  const double* a = ws_base + B.ws_off * E;
-  const HhParam* prm = prm_base + B.prm_off;
-  double* col = q_base + (B.q_off + (long long)c * mm) * E;
-  const int tid = threadIdx.x;
-  double2 x[RPT];
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) x[q] = make_double2((tid + 256 * q) == c ? 1.0 : 0.0, 0.0);
-  // columns c >= k (orthogonal complement) receive all reflectors
-  for (int j = (c < B.k ? c : B.k - 1); j >= 0; --j) {
-    const HhParam p = prm[j];
-    const double2 tau = make_double2(p.tau_re, p.tau_im), scale = make_double2(p.scale_re, p.scale_im);
-    if (tau.x == 0.0 && tau.y == 0.0) continue;
-    const double* vj = a + (long long)j * mm * E;
-    double2 v[RPT];
-    double dr = 0, di = 0;
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-      const int r = tid + 256 * q;
-      v[q] = (r > j && r < mm) ? Cx<CPLX>::ld(vj, r) : make_double2(0.0, 0.0);
-      const double2 t2 = cmulc(v[q], x[q]);
-      dr += t2.x;
-      di += t2.y;
-      if (r == j) {
-        s_head[0] = x[q].x;
-        s_head[1] = x[q].y;
-      }
-    }
-    block_allsum2(dr, di);
-    const double2 head = make_double2(s_head[0], s_head[1]);
-    const double2 sc = cmulc(scale, make_double2(dr, di));
-    const double2 f = cmul(tau, make_double2(head.x + sc.x, head.y + sc.y));  // H, not H^H
-    const double2 fs = cmul(f, scale);
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-      const int r = tid + 256 * q;
-      const double2 t2 = cmul(fs, v[q]);
-      x[q].x -= t2.x;
-      x[q].y -= t2.y;
-      if (r == j) {
-        x[q].x -= f.x;
-        x[q].y -= f.y;
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int r = tid + 256 * q;
-    if (r < mm) Cx<CPLX>::st(col, r, x[q]);
-  }
-}
-
 // ---- compact-WY forms: the NB (<= 4) reflectors of a panel act through  Q_p = H_1 .. H_nb = I - V T V^H  with
 // T^{-1} = strict_upper(V^H V) + diag(1 / tau)  (LAPACK ?larft, forward / columnwise).  One reduction round delivers
 // V^H x for the columns a workgroup owns; the six inner products of V^H V come from the panel kernel, which meets
@@ -810,8 +637,6 @@ __global__ __launch_bounds__(NT) void k_hh_formq_wy(double* q_base, const double
   }
 }
 
-inline bool qr_use_wy() { return true; }
-
 template <bool CPLX>
 int run_batched(mpse_ctx* ctx, double* ws, double* q, HhParam* prm, const QrBlk* dblk, int nblk, int max_mm,
                 int max_nn, int max_k, int max_q, int max_tail, bool form_q) {
@@ -822,11 +647,9 @@ int run_batched(mpse_ctx* ctx, double* ws, double* q, HhParam* prm, const QrBlk*
   // Rows per thread follow the tallest block (256 x 1..4 up to 1024 rows, 512 x 5..8 above 2048): the panel is bound
   // by the FP64 vector work of its CU, and row slots that do not exist still cost their share of it (headline: 400
   // rows -> 256 x 2 instead of 256 x 4: -16 % per d = 2 QR; 3200 rows -> 512 x 7).
-  constexpr bool fit = true;
   const int cfg = max_mm <= 1024 ? 0 : max_mm <= 2048 ? 1 : 2;
-  const int rpt = !fit ? (cfg == 2 ? 8 : 4) : cfg == 0 ? (max_mm + 255) / 256 : cfg == 2 ? (max_mm + 511) / 512 : 4;
+  const int rpt = cfg == 0 ? (max_mm + 255) / 256 : cfg == 2 ? (max_mm + 511) / 512 : 4;
   const int nb = 4;
-  const bool wy = qr_use_wy();
 #define MPSE_QR_CASES_256(KERNEL, GRID, ...)                                                                        \
   switch (rpt) {                                                                                                    \
     case 1: hipLaunchKernelGGL((KERNEL<CPLX, 256, 1 __VA_OPT__(,) __VA_ARGS__>), GRID, dim3(256), 0, ctx->stream, ARGS); break; \
@@ -841,8 +664,7 @@ int run_batched(mpse_ctx* ctx, double* ws, double* q, HhParam* prm, const QrBlk*
     case 7: hipLaunchKernelGGL((KERNEL<CPLX, 512, 7 __VA_OPT__(,) __VA_ARGS__>), GRID, dim3(512), 0, ctx->stream, ARGS); break; \
     default: hipLaunchKernelGGL((KERNEL<CPLX, 512, 8 __VA_OPT__(,) __VA_ARGS__>), GRID, dim3(512), 0, ctx->stream, ARGS);       \
   }
-  constexpr bool look = true;
-  if (look && wy && cfg == 0) {
+  if (cfg == 0) {
     // the extra step after the last panel only carries the trailing update of blocks wider than their rank
     for (int j0 = 0; j0 < max_k + (max_tail > 0 ? nb : 0); j0 += nb) {
       const int cols = j0 == 0 ? 0 : max_nn - (j0 - nb) - 1;   // upper bound on columns the update role can own
@@ -850,46 +672,31 @@ int run_batched(mpse_ctx* ctx, double* ws, double* q, HhParam* prm, const QrBlk*
       MPSE_QR_CASES_256(k_hh_step, dim3(1 + (cols + 1) / 2, nblk), 2)
 #undef ARGS
     }
-  } else
-  for (int j0 = 0; j0 < max_k; j0 += nb) {
-#define ARGS ws, dblk, prm, j0
-    if (cfg == 0) {
-      MPSE_QR_CASES_256(k_hh_panel, dim3(nblk), 4)
-    } else if (cfg == 1) {
-      hipLaunchKernelGGL((k_hh_panel<CPLX, 512, 4, 4>), dim3(nblk), dim3(512), 0, ctx->stream, ws, dblk, prm, j0);
-    } else {
-      MPSE_QR_CASES_512(k_hh_panel, dim3(nblk), 4)
-    }
-#undef ARGS
-    const int trailing = max_nn - j0 - 1;  // upper bound on columns to the right of any block's panel
-    if (trailing > 0 && wy) {
-      // two columns per workgroup share the loads of V where the registers allow (the tallest configuration holds
-      // 4 reflector tails x 8 rows per thread: one column)
-      const dim3 grid2((trailing + 1) / 2, nblk), grid1(trailing, nblk);
-#define ARGS ws, dblk, prm, j0, nb
-      if (cfg == 0) {
-        MPSE_QR_CASES_256(k_hh_apply_wy, grid2, 2)
-      } else if (cfg == 1) {
-        hipLaunchKernelGGL((k_hh_apply_wy<CPLX, 256, 8, 2>), grid2, dim3(256), 0, ctx->stream, ws, dblk, prm, j0, nb);
+  } else {
+    for (int j0 = 0; j0 < max_k; j0 += nb) {
+      if (cfg == 1) {
+        hipLaunchKernelGGL((k_hh_panel<CPLX, 512, 4, 4>), dim3(nblk), dim3(512), 0, ctx->stream, ws, dblk, prm, j0);
       } else {
-        MPSE_QR_CASES_512(k_hh_apply_wy, grid1, 1)
-      }
+#define ARGS ws, dblk, prm, j0
+        MPSE_QR_CASES_512(k_hh_panel, dim3(nblk), 4)
 #undef ARGS
-    } else if (trailing > 0) {
-      dim3 grid(trailing, nblk);
-      switch (cfg) {
-        case 0:
-          hipLaunchKernelGGL((k_hh_apply_panel<CPLX, 4>), grid, dim3(256), 0, ctx->stream, ws, dblk, prm, j0, nb);
-          break;
-        case 1:
-          hipLaunchKernelGGL((k_hh_apply_panel<CPLX, 8>), grid, dim3(256), 0, ctx->stream, ws, dblk, prm, j0, nb);
-          break;
-        default:
-          hipLaunchKernelGGL((k_hh_apply_panel<CPLX, 16>), grid, dim3(256), 0, ctx->stream, ws, dblk, prm, j0, nb);
+      }
+      const int trailing = max_nn - j0 - 1;  // upper bound on columns to the right of any block's panel
+      if (trailing > 0) {
+        // two columns per workgroup share the loads of V where the registers allow (the tallest configuration holds
+        // 4 reflector tails x 8 rows per thread: one column)
+        if (cfg == 1) {
+          hipLaunchKernelGGL((k_hh_apply_wy<CPLX, 256, 8, 2>), dim3((trailing + 1) / 2, nblk), dim3(256), 0, ctx->stream,
+                             ws, dblk, prm, j0, nb);
+        } else {
+#define ARGS ws, dblk, prm, j0, nb
+          MPSE_QR_CASES_512(k_hh_apply_wy, dim3(trailing, nblk), 1)
+#undef ARGS
+        }
       }
     }
   }
-  if (form_q && max_q > 0 && wy) {
+  if (form_q && max_q > 0) {
     dim3 grid(max_q, nblk);
 #define ARGS q, ws, dblk, prm
     if (cfg == 0) {
@@ -900,18 +707,6 @@ int run_batched(mpse_ctx* ctx, double* ws, double* q, HhParam* prm, const QrBlk*
       MPSE_QR_CASES_512(k_hh_formq_wy, grid)
     }
 #undef ARGS
-  } else if (form_q && max_q > 0) {
-    dim3 grid(max_q, nblk);
-    switch (cfg) {
-      case 0:
-        hipLaunchKernelGGL((k_hh_formq_b<CPLX, 4>), grid, dim3(256), 0, ctx->stream, q, ws, dblk, prm);
-        break;
-      case 1:
-        hipLaunchKernelGGL((k_hh_formq_b<CPLX, 8>), grid, dim3(256), 0, ctx->stream, q, ws, dblk, prm);
-        break;
-      default:
-        hipLaunchKernelGGL((k_hh_formq_b<CPLX, 16>), grid, dim3(256), 0, ctx->stream, q, ws, dblk, prm);
-    }
   }
 #undef MPSE_QR_CASES_256
 #undef MPSE_QR_CASES_512
@@ -919,13 +714,9 @@ int run_batched(mpse_ctx* ctx, double* ws, double* q, HhParam* prm, const QrBlk*
   return MPSE_OK;
 }
 
-}  // namespace
-
-// Factorise (and optionally form Q for) nblk column-major blocks living in one workspace.
-// Requires max mm <= HH_BATCH_MAX_ROWS; callers fall back to the unblocked kernels otherwise.
-int hh_qr_batched(mpse_ctx* ctx, bool cplx, double* ws, double* q, HhParam* prm, const QrBlk* blks_host, int nblk,
-                  bool form_q, const QrBlk* blks_dev) {
-  if (nblk <= 0) return MPSE_OK;
+// blocks of at most HH_BATCH_MAX_ROWS rows, all in the same launches; ``blks_dev``: their descriptors on the device
+int qr_batched(mpse_ctx* ctx, bool cplx, double* ws, double* q, HhParam* prm, const QrBlk* blks_host, int nblk,
+               bool form_q, const QrBlk* blks_dev) {
   int max_mm = 0, max_nn = 0, max_k = 0, max_q = 0, max_tail = 0;
   for (int b = 0; b < nblk; ++b) {
     max_tail = blks_host[b].nn - blks_host[b].k > max_tail ? blks_host[b].nn - blks_host[b].k : max_tail;
@@ -935,7 +726,6 @@ int hh_qr_batched(mpse_ctx* ctx, bool cplx, double* ws, double* q, HhParam* prm,
     const int nq = blks_host[b].nq > blks_host[b].k ? blks_host[b].nq : blks_host[b].k;
     max_q = nq > max_q ? nq : max_q;
   }
-  if (max_mm > HH_BATCH_MAX_ROWS) return mpse_fail(ctx, MPSE_ERR_SHAPE, "hh_qr_batched: block too tall");
   TmpBuf DB(ctx);
   if (!blks_dev) {
     MPSE_TRY(DB.alloc(size_t(nblk) * sizeof(QrBlk)));
@@ -944,4 +734,150 @@ int hh_qr_batched(mpse_ctx* ctx, bool cplx, double* ws, double* q, HhParam* prm,
   }
   if (cplx) return run_batched<true>(ctx, ws, q, prm, blks_dev, nblk, max_mm, max_nn, max_k, max_q, max_tail, form_q);
   return run_batched<false>(ctx, ws, q, prm, blks_dev, nblk, max_mm, max_nn, max_k, max_q, max_tail, form_q);
+}
+
+// ---- unblocked kernels for blocks taller than HH_BATCH_MAX_ROWS; RED_THREADS threads, one workgroup per column
+
+// reflector j from the current content of column j (rows >= j); one workgroup
+template <bool CPLX>
+__device__ void hh_reflector(double* a, int mm, int j, HhParam* prm) {
+  double* col = a + (long long)j * mm * Cx<CPLX>::E;
+  double s = 0, z = 0;
+  for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
+    const double2 v = Cx<CPLX>::ld(col, r);
+    s += v.x * v.x + v.y * v.y;
+  }
+  block_allsum2(s, z);
+  if (threadIdx.x == 0) {
+    const double2 alpha = Cx<CPLX>::ld(col, j);
+    HhParam p;
+    double beta;
+    make_reflector(alpha, s, &p, &beta);
+    Cx<CPLX>::st(col, j, make_double2(beta, (p.tau_re == 0.0 && p.tau_im == 0.0) ? alpha.y : 0.0));   // H = I: unchanged
+    prm[j] = p;
+  }
+}
+
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_hh_first(double* a, int mm, HhParam* prm) {
+  hh_reflector<CPLX>(a, mm, 0, prm);
+}
+
+// apply H_j^H to column c = j + 1 + blockIdx.x ; then (c == j+1) derive reflector j+1
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_hh_apply(double* a, int mm, int kref, int j, HhParam* prm) {
+  constexpr int E = Cx<CPLX>::E;
+  const int c = j + 1 + blockIdx.x;
+  const double* vj = a + (long long)j * mm * E;
+  double* col = a + (long long)c * mm * E;
+  const HhParam p = prm[j];
+  const double2 tau = make_double2(p.tau_re, p.tau_im), scale = make_double2(p.scale_re, p.scale_im);
+  if (tau.x != 0.0 || tau.y != 0.0) {
+    double dr = 0, di = 0;
+    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
+      const double2 t = cmulc(Cx<CPLX>::ld(vj, r), Cx<CPLX>::ld(col, r));
+      dr += t.x;
+      di += t.y;
+    }
+    block_allsum2(dr, di);
+    // dot = v^H col = col[j] + conj(scale) * sum conj(tail) col
+    const double2 head = Cx<CPLX>::ld(col, j);
+    const double2 sc = cmulc(scale, make_double2(dr, di));
+    const double2 dot = make_double2(head.x + sc.x, head.y + sc.y);
+    const double2 f = cmulc(tau, dot);          // conj(tau) * dot
+    const double2 fs = cmul(f, scale);
+    __syncthreads();  // everyone has read col[j] before thread 0 overwrites it
+    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
+      const double2 t = cmul(fs, Cx<CPLX>::ld(vj, r));
+      double2 x = Cx<CPLX>::ld(col, r);
+      x.x -= t.x;
+      x.y -= t.y;
+      Cx<CPLX>::st(col, r, x);
+    }
+    if (threadIdx.x == 0) Cx<CPLX>::st(col, j, make_double2(head.x - f.x, head.y - f.y));
+  }
+  if (blockIdx.x == 0 && j + 1 < kref) {
+    __syncthreads();
+    hh_reflector<CPLX>(a, mm, j + 1, prm);
+  }
+}
+
+// column c of Q (mm x nq, column-major) = H_0 H_1 ... H_c e_c
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_hh_formq(double* q, const double* __restrict__ a, int mm, int kref,
+                                                          const HhParam* __restrict__ prm) {
+  constexpr int E = Cx<CPLX>::E;
+  const int c = blockIdx.x;
+  double* col = q + (long long)c * mm * E;
+  for (int r = threadIdx.x; r < mm; r += RED_THREADS) Cx<CPLX>::st(col, r, make_double2(r == c ? 1.0 : 0.0, 0.0));
+  __syncthreads();
+  // columns c >= kref (orthogonal complement, used for full_matrices SVD) receive all reflectors
+  for (int j = (c < kref ? c : kref - 1); j >= 0; --j) {
+    const HhParam p = prm[j];
+    const double2 tau = make_double2(p.tau_re, p.tau_im), scale = make_double2(p.scale_re, p.scale_im);
+    if (tau.x == 0.0 && tau.y == 0.0) continue;
+    const double* vj = a + (long long)j * mm * E;
+    double dr = 0, di = 0;
+    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
+      const double2 t = cmulc(Cx<CPLX>::ld(vj, r), Cx<CPLX>::ld(col, r));
+      dr += t.x;
+      di += t.y;
+    }
+    block_allsum2(dr, di);
+    const double2 head = Cx<CPLX>::ld(col, j);
+    const double2 sc = cmulc(scale, make_double2(dr, di));
+    const double2 dot = make_double2(head.x + sc.x, head.y + sc.y);
+    const double2 f = cmul(tau, dot);  // H (not H^H)
+    const double2 fs = cmul(f, scale);
+    __syncthreads();  // everyone has read col[j]
+    for (int r = j + 1 + threadIdx.x; r < mm; r += RED_THREADS) {
+      const double2 t = cmul(fs, Cx<CPLX>::ld(vj, r));
+      double2 x = Cx<CPLX>::ld(col, r);
+      x.x -= t.x;
+      x.y -= t.y;
+      Cx<CPLX>::st(col, r, x);
+    }
+    if (threadIdx.x == 0) Cx<CPLX>::st(col, j, make_double2(head.x - f.x, head.y - f.y));
+    __syncthreads();
+  }
+}
+
+// one block by the unblocked kernels: a launch per reflector, then Q in one launch
+template <bool CPLX>
+int qr_unblocked(mpse_ctx* ctx, double* ws, double* q, HhParam* prm, const QrBlk& B, bool form_q) {
+  if (B.k <= 0) return MPSE_OK;
+  constexpr int E = Cx<CPLX>::E;
+  double* a = ws + B.ws_off * E;
+  HhParam* p = prm + B.prm_off;
+  hipLaunchKernelGGL((k_hh_first<CPLX>), dim3(1), dim3(RED_THREADS), 0, ctx->stream, a, B.mm, p);
+  for (int j = 0; j < B.k && j + 1 < B.nn; ++j)
+    hipLaunchKernelGGL((k_hh_apply<CPLX>), dim3(B.nn - j - 1), dim3(RED_THREADS), 0, ctx->stream, a, B.mm, B.k, j, p);
+  if (form_q)
+    hipLaunchKernelGGL((k_hh_formq<CPLX>), dim3(B.nq > B.k ? B.nq : B.k), dim3(RED_THREADS), 0, ctx->stream,
+                       q + B.q_off * E, (const double*)a, B.mm, B.k, (const HhParam*)p);
+  MPSE_HIP(ctx, hipGetLastError());
+  return MPSE_OK;
+}
+
+}  // namespace
+
+// Factorise (and optionally form Q for) nblk column-major blocks living in one workspace, blocks of any height.
+// When every block has at most HH_BATCH_MAX_ROWS rows they share the batched launches (``blks_dev``: their descriptors
+// already on the device); otherwise the shorter blocks are batched on their own and the taller ones follow one at a time.
+int hh_qr(mpse_ctx* ctx, bool cplx, double* ws, double* q, HhParam* prm, const QrBlk* blks_host, int nblk, bool form_q,
+          const QrBlk* blks_dev) {
+  if (nblk <= 0) return MPSE_OK;
+  bool tall = false;
+  for (int b = 0; b < nblk; ++b) tall = tall || blks_host[b].mm > HH_BATCH_MAX_ROWS;
+  if (!tall) return qr_batched(ctx, cplx, ws, q, prm, blks_host, nblk, form_q, blks_dev);
+  std::vector<QrBlk> shorter;
+  for (int b = 0; b < nblk; ++b)
+    if (blks_host[b].mm <= HH_BATCH_MAX_ROWS) shorter.push_back(blks_host[b]);
+  if (!shorter.empty()) MPSE_TRY(qr_batched(ctx, cplx, ws, q, prm, shorter.data(), (int)shorter.size(), form_q, nullptr));
+  for (int b = 0; b < nblk; ++b) {
+    if (blks_host[b].mm <= HH_BATCH_MAX_ROWS) continue;
+    MPSE_TRY(cplx ? qr_unblocked<true>(ctx, ws, q, prm, blks_host[b], form_q)
+                  : qr_unblocked<false>(ctx, ws, q, prm, blks_host[b], form_q));
+  }
+  return MPSE_OK;
 }

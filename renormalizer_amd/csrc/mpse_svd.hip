@@ -1,375 +1,27 @@
 // Quantum-number blocked economic SVD by one-sided (Hestenes) Jacobi on the device.
 // Replaces scipy.linalg.svd(gesdd) per block in mps/svd_qn.py:12-49,177-213.
 //
-// Per block (mm >= nn; wide blocks are processed as their adjoint):
-//   * the block is gathered column-major, V = I;
-//   * round-robin sweeps: every launch orthogonalises nn/2 disjoint column pairs, one
-//     workgroup per pair (Gram entries by wavefront-shuffle reductions, then the plane
-//     rotation on the A and V columns); a sweep without rotations ends the iteration;
-//   * sigma_j = |a_j| are read back, sorted on the host (descending, like LAPACK);
-//   * columns are normalised; numerically null columns are zeroed and the left basis is
-//     completed to an exact isometry by a Householder QR of the normalised matrix
-//     (Q R with |R_jj| = 1 on the non-null columns), which is what LAPACK's economic U
-//     guarantees and what the sweep algorithms above this layer rely on.
+// All quantum-number blocks of a decomposition share every launch (blockIdx.y = block; mm >= nn, wide blocks are
+// processed as their adjoint):
+//   * the block is gathered column-major and QR factorised (hh_qr; Q1 gets the null-space columns the caller asked for);
+//   * one-sided Jacobi on the square problem X = R^H, V = I: every launch is a block step over pairs of column blocks
+//     (k_jacobi_block in LDS where the column blocks fit, k_jacobi_gram otherwise); a sweep without rotations ends the
+//     iteration of a block, and the convergence of a sweep is read once for all blocks;
+//   * sigma_j = |x_j| are read back, sorted on the host (descending, like LAPACK);
+//   * columns are normalised; numerically null columns are zeroed and the basis is completed to an exact isometry by
+//     a Householder QR of the normalised matrix (Q R with |R_jj| = 1 on the non-null columns), which is what LAPACK's
+//     economic U guarantees and what the sweep algorithms above this layer rely on;
+//   * the tall side's vectors are Q1[:, :nn] V.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
 
+#include "mpse_cx.h"
 #include "mpse_device.h"
 #include "mpse_internal.h"
 
 namespace {
 
-template <bool CPLX>
-struct Cx;
-template <>
-struct Cx<true> {
-  static constexpr int E = 2;
-  __device__ static double2 ld(const double* p, long long i) { return reinterpret_cast<const double2*>(p)[i]; }
-  __device__ static void st(double* p, long long i, double2 v) { reinterpret_cast<double2*>(p)[i] = v; }
-};
-template <>
-struct Cx<false> {
-  static constexpr int E = 1;
-  __device__ static double2 ld(const double* p, long long i) { return make_double2(p[i], 0.0); }
-  __device__ static void st(double* p, long long i, double2 v) { p[i] = v.x; }
-};
-
-inline int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-template <bool CPLX>
-__global__ void k_gather_block(double* ws, const double* __restrict__ coef, long long ncol,
-                               const long long* __restrict__ rows, const long long* __restrict__ cols, int mm, int nn,
-                               int herm) {
-  const long long total = (long long)mm * nn;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    if (!herm) {
-      const int c = (int)(t % nn), r = (int)(t / nn);
-      Cx<CPLX>::st(ws, r + (long long)c * mm, Cx<CPLX>::ld(coef, rows[r] * ncol + cols[c]));
-    } else {
-      const int r = (int)(t % mm), c = (int)(t / mm);
-      double2 v = Cx<CPLX>::ld(coef, rows[c] * ncol + cols[r]);
-      v.y = -v.y;
-      Cx<CPLX>::st(ws, r + (long long)c * mm, v);
-    }
-  }
-}
-
-template <bool CPLX>
-__global__ void k_set_identity(double* v, int n) {
-  const long long total = (long long)n * n;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride)
-    Cx<CPLX>::st(v, t, make_double2((t % n) == (t / n) ? 1.0 : 0.0, 0.0));
-}
-
-// one round-robin step: workgroup b handles the pair (p,q) of step `step` (circle method on N = even(nn))
-template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_jacobi_step(double* a, double* v, int mm, int nn, int N, int step,
-                                                             double tol, double null2, int* nrot) {
-  constexpr int E = Cx<CPLX>::E;
-  const int kk = blockIdx.x;
-  int p, q;
-  if (kk == 0) {
-    p = step % (N - 1);
-    q = N - 1;
-  } else {
-    p = (step + kk) % (N - 1);
-    q = (step - kk + (N - 1)) % (N - 1);
-  }
-  if (p > q) {
-    const int t = p;
-    p = q;
-    q = t;
-  }
-  if (q >= nn) return;  // padding column of an odd nn
-  double* ap = a + (long long)p * mm * E;
-  double* aq = a + (long long)q * mm * E;
-  double alpha = 0, beta = 0, gr = 0, gi = 0;
-  for (int r = threadIdx.x; r < mm; r += RED_THREADS) {
-    const double2 x = Cx<CPLX>::ld(ap, r), y = Cx<CPLX>::ld(aq, r);
-    alpha += x.x * x.x + x.y * x.y;
-    beta += y.x * y.x + y.y * y.y;
-    gr += x.x * y.x + x.y * y.y;  // conj(x) * y
-    gi += x.x * y.y - x.y * y.x;
-  }
-  block_allsum2(alpha, beta);
-  block_allsum2(gr, gi);
-  const double g = sqrt(gr * gr + gi * gi);
-  // A column whose norm is below (largest column norm) * eps * m can only belong to singular values that are
-  // numerically zero; it is zeroed and replaced by the null-space completion afterwards, so rotating it
-  // (endlessly, at rounding level) is pointless.  Also avoids forming alpha*beta, which underflows.
-  if (g == 0.0 || alpha <= null2 || beta <= null2) return;
-  if (!(g > tol * sqrt(alpha) * sqrt(beta))) return;  // already orthogonal (block-uniform decision)
-  // phase of gamma and the real Jacobi rotation for [[alpha, g], [g, beta]]
-  const double pr = gr / g, pi = gi / g;
-  const double zeta = (beta - alpha) / (2.0 * g);
-  const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-  // a_p' = c a_p - s e^{-i phi} a_q ; a_q' = s a_p + c e^{-i phi} a_q     (e^{-i phi} = (pr, -pi))
-  for (int r = threadIdx.x; r < mm; r += RED_THREADS) {
-    const double2 x = Cx<CPLX>::ld(ap, r), y0 = Cx<CPLX>::ld(aq, r);
-    const double2 y = make_double2(y0.x * pr + y0.y * pi, y0.y * pr - y0.x * pi);
-    Cx<CPLX>::st(ap, r, make_double2(c * x.x - s * y.x, c * x.y - s * y.y));
-    Cx<CPLX>::st(aq, r, make_double2(s * x.x + c * y.x, s * x.y + c * y.y));
-  }
-  double* vp = v + (long long)p * nn * E;
-  double* vq = v + (long long)q * nn * E;
-  for (int r = threadIdx.x; r < nn; r += RED_THREADS) {
-    const double2 x = Cx<CPLX>::ld(vp, r), y0 = Cx<CPLX>::ld(vq, r);
-    const double2 y = make_double2(y0.x * pr + y0.y * pi, y0.y * pr - y0.x * pi);
-    Cx<CPLX>::st(vp, r, make_double2(c * x.x - s * y.x, c * x.y - s * y.y));
-    Cx<CPLX>::st(vq, r, make_double2(s * x.x + c * y.x, s * x.y + c * y.y));
-  }
-  if (threadIdx.x == 0) atomicAdd(nrot, 1);
-}
-
-// sig[c] = |a_c|
-template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_col_norms(const double* __restrict__ a, int mm, double* sig) {
-  const double* col = a + (long long)blockIdx.x * mm * Cx<CPLX>::E;
-  double s = 0, z = 0;
-  for (int r = threadIdx.x; r < mm; r += RED_THREADS) {
-    const double2 x = Cx<CPLX>::ld(col, r);
-    s += x.x * x.x + x.y * x.y;
-  }
-  block_allsum2(s, z);
-  if (threadIdx.x == 0) sig[blockIdx.x] = sqrt(s);
-}
-
-// dst[:, j] = src[:, perm[j]] / sig[perm[j]]  (zero when sig <= thresh): columns in descending-sigma
-// order, so that numerically null columns come last and the completing QR has a diagonal R on the rest
-template <bool CPLX>
-__global__ void k_normalise_perm(double* dst, const double* __restrict__ src, int mm, int nn,
-                                 const double* __restrict__ sig, const long long* __restrict__ perm, double thresh) {
-  const long long total = (long long)mm * nn;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int j = (int)(t / mm), r = (int)(t % mm);
-    const int pj = (int)perm[j];
-    const double sg = sig[pj];
-    double2 x = Cx<CPLX>::ld(src, r + (long long)pj * mm);
-    if (sg > thresh) {
-      x.x /= sg;
-      x.y /= sg;
-    } else {
-      x = make_double2(0.0, 0.0);
-    }
-    Cx<CPLX>::st(dst, t, x);
-  }
-}
-
-// scatter the factors of one block.  un: normalised, sigma-ordered and factored workspace (R_jj on its
-// diagonal), q: completed isometry (mm x nn col-major, sigma-ordered), vm: V (nn x nn col-major, Jacobi order),
-// perm: column order (descending sigma).
-//   !herm: U[rows[r], koff+j] = q[r,j] * d_j ; Vt[koff+j, cols[c]] = conj(vm[c,pj])
-//    herm: Vt[koff+j, cols[r]] = conj(q[r,j] * d_j) ; U[rows[c], koff+j] = vm[c,pj]
-//   d_j = R_jj (unit modulus) for a regular column, 1 for a completed null column
-template <bool CPLX>
-__global__ void k_scatter_svd(double* U, double* Vt, const double* __restrict__ un, const double* __restrict__ q,
-                              const double* __restrict__ vm, const long long* __restrict__ perm, long long K,
-                              long long ncol, const long long* __restrict__ rows, const long long* __restrict__ cols,
-                              int mm, int nn, long long koff, int herm) {
-  // K is the leading dimension of U (number of columns of the output U)
-  const long long totq = (long long)mm * nn, totv = (long long)nn * nn;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < totq + totv; t += stride) {
-    if (t < totq) {
-      int j, r;
-      if (!herm) {
-        j = (int)(t % nn);
-        r = (int)(t / nn);
-      } else {
-        r = (int)(t % mm);
-        j = (int)(t / mm);
-      }
-      double2 d = Cx<CPLX>::ld(un, j + (long long)j * mm);
-      if (d.x == 0.0 && d.y == 0.0) d = make_double2(1.0, 0.0);
-      const double2 x = Cx<CPLX>::ld(q, r + (long long)j * mm);
-      double2 y = make_double2(x.x * d.x - x.y * d.y, x.x * d.y + x.y * d.x);
-      if (!herm) {
-        Cx<CPLX>::st(U, rows[r] * K + koff + j, y);
-      } else {
-        y.y = -y.y;
-        Cx<CPLX>::st(Vt, (koff + j) * ncol + cols[r], y);
-      }
-    } else {
-      const long long t2 = t - totq;
-      int j, c;
-      if (!herm) {
-        c = (int)(t2 % nn);
-        j = (int)(t2 / nn);
-      } else {
-        j = (int)(t2 % nn);
-        c = (int)(t2 / nn);
-      }
-      const int pj = (int)perm[j];
-      double2 x = Cx<CPLX>::ld(vm, c + (long long)pj * nn);
-      if (!herm) {
-        x.y = -x.y;
-        Cx<CPLX>::st(Vt, (koff + j) * ncol + cols[c], x);
-      } else {
-        Cx<CPLX>::st(U, rows[c] * K + koff + j, x);
-      }
-    }
-  }
-}
-
-// null-space vectors of the tall side: columns nn .. nn+extra-1 of the completed isometry q
-//   !herm: U[rows[r], uoff+e] = q[r, nn+e]   ;   herm: Vt[voff+e, cols[r]] = conj(q[r, nn+e])
-template <bool CPLX>
-__global__ void k_scatter_null(double* U, double* Vt, const double* __restrict__ q, long long ldU, long long ncol,
-                               const long long* __restrict__ rows, const long long* __restrict__ cols, int mm, int nn,
-                               int extra, long long off, int herm) {
-  const long long total = (long long)mm * extra;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    if (!herm) {
-      const int e = (int)(t % extra), r = (int)(t / extra);
-      Cx<CPLX>::st(U, rows[r] * ldU + off + e, Cx<CPLX>::ld(q, r + (long long)(nn + e) * mm));
-    } else {
-      const int r = (int)(t % mm), e = (int)(t / mm);
-      double2 x = Cx<CPLX>::ld(q, r + (long long)(nn + e) * mm);
-      x.y = -x.y;
-      Cx<CPLX>::st(Vt, (off + e) * ncol + cols[r], x);
-    }
-  }
-}
-
-template <bool CPLX>
-int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, int nblocks, const int64_t* row_idx,
-                      const int64_t* row_off, const int64_t* col_idx, const int64_t* col_off, void* U, void* Vt,
-                      double* S_host, int64_t K, const int64_t* extra_host, int64_t KU, int64_t KV);
-
-template <bool CPLX>
-int block_svd_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, int nblocks, const int64_t* row_idx,
-                   const int64_t* row_off, const int64_t* col_idx, const int64_t* col_off, void* U, void* Vt,
-                   double* S_host, int64_t K, const int64_t* extra_host, int64_t KU, int64_t KV) {
-  constexpr size_t es = CPLX ? 16 : 8;
-  int64_t ktot = 0, maxws = 0, maxk = 0, maxq = 0, nu = 0, nv = 0, maxrows = 0;
-  for (int b = 0; b < nblocks; ++b) {
-    const int64_t m = row_off[b + 1] - row_off[b], n = col_off[b + 1] - col_off[b];
-    if (m < 0 || n < 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: negative block extent");
-    const int64_t k = std::min(m, n);
-    if (k > 0) maxrows = std::max(maxrows, std::max(m, n));
-    ktot += k;
-    maxws = std::max(maxws, m * n);
-    maxk = std::max(maxk, k);
-    int64_t ex = extra_host ? extra_host[b] : 0;
-    if (ex < 0 || ex > std::max(m, n) - k) return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: bad extra count");
-    if (k == 0) ex = 0;
-    maxq = std::max(maxq, std::max(m, n) * (k + ex));
-    if (m >= n) nu += ex; else nv += ex;
-  }
-  if (KU != ktot + nu || KV != ktot + nv)
-    return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: KU/KV (%lld,%lld) do not match the blocks (%lld,%lld)",
-                     (long long)KU, (long long)KV, (long long)(ktot + nu), (long long)(ktot + nv));
-  if (ktot != K) return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: K=%lld but blocks give %lld", (long long)K, (long long)ktot);
-  if (ktot == 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "Invalid quantum number");
-  if (maxrows <= HH_BATCH_MAX_ROWS)   // every block fits the register-resident Householder kernels: batched path
-    return block_svd_batched<CPLX>(ctx, coef, nrow, ncol, nblocks, row_idx, row_off, col_idx, col_off, U, Vt, S_host, K,
-                                   extra_host, KU, KV);
-  MPSE_TRY(mpse_memset_zero(ctx, U, size_t(nrow * KU) * es));
-  MPSE_TRY(mpse_memset_zero(ctx, Vt, size_t(KV * ncol) * es));
-  const int64_t nri = row_off[nblocks], nci = col_off[nblocks];
-  long long uoff = K, voff = K;  // where the next block's null vectors go
-  TmpBuf IDX(ctx), WS(ctx), Q(ctx), VM(ctx), PRM(ctx), SIG(ctx), PERM(ctx), CNT(ctx);
-  MPSE_TRY(IDX.alloc(size_t(nri + nci) * 8));
-  MPSE_TRY(WS.alloc(size_t(std::max(maxws, maxq)) * es));
-  MPSE_TRY(Q.alloc(size_t(maxws) * es));
-  MPSE_TRY(VM.alloc(size_t(maxk * maxk) * es));
-  MPSE_TRY(PRM.alloc(size_t(maxk + 1) * sizeof(HhParam)));
-  MPSE_TRY(SIG.alloc(size_t(maxk) * 8));
-  MPSE_TRY(PERM.alloc(size_t(maxk) * 8));
-  MPSE_TRY(CNT.alloc(64));
-  MPSE_TRY(stage_h2d(ctx, IDX.p, row_idx, size_t(nri) * 8));
-  MPSE_TRY(stage_h2d(ctx, IDX.as<char>() + size_t(nri) * 8, col_idx, size_t(nci) * 8));
-  const long long* drows = IDX.as<long long>();
-  const long long* dcols = IDX.as<long long>() + nri;
-  std::vector<double> sig;
-  std::vector<long long> perm;
-  int64_t koff = 0;
-  for (int b = 0; b < nblocks; ++b) {
-    const int m = (int)(row_off[b + 1] - row_off[b]), n = (int)(col_off[b + 1] - col_off[b]);
-    const int k = std::min(m, n);
-    if (k == 0) continue;
-    const int herm = m < n ? 1 : 0;
-    const int mm = herm ? n : m, nn = herm ? m : n;  // mm >= nn == k
-    const long long* rows = drows + row_off[b];
-    const long long* cols = dcols + col_off[b];
-    double* ws = WS.as<double>();
-    double* vm = VM.as<double>();
-    hipLaunchKernelGGL((k_gather_block<CPLX>), dim3(ew_blocks((int64_t)mm * nn)), dim3(256), 0, ctx->stream, ws,
-                       (const double*)coef, (long long)ncol, rows, cols, mm, nn, herm);
-    hipLaunchKernelGGL((k_set_identity<CPLX>), dim3(ew_blocks((int64_t)nn * nn)), dim3(256), 0, ctx->stream, vm, nn);
-    if (nn > 1) {
-      const int N = (nn + 1) & ~1;
-      const double tol = 2.220446049250313e-16 * sqrt((double)mm);
-      hipLaunchKernelGGL((k_col_norms<CPLX>), dim3(nn), dim3(RED_THREADS), 0, ctx->stream, (const double*)ws, mm,
-                         SIG.as<double>());
-      sig.resize(nn);
-      MPSE_TRY(mpse_memcpy_d2h(ctx, sig.data(), SIG.p, size_t(nn) * 8));
-      double cmax = 0.0;
-      for (double x : sig) cmax = x > cmax ? x : cmax;
-      const double nullnorm = cmax * 2.220446049250313e-16 * (double)mm;
-      const double null2 = nullnorm * nullnorm;
-      bool converged = false;
-      for (int sweep = 0; sweep < 60 && !converged; ++sweep) {
-        MPSE_HIP(ctx, hipMemsetAsync(CNT.p, 0, sizeof(int), ctx->stream));
-        for (int step = 0; step < N - 1; ++step)
-          hipLaunchKernelGGL((k_jacobi_step<CPLX>), dim3(N / 2), dim3(RED_THREADS), 0, ctx->stream, ws, vm, mm, nn, N,
-                             step, tol, null2, CNT.as<int>());
-        MPSE_HIP(ctx, hipGetLastError());
-        MPSE_TRY(publish_and_wait(ctx, CNT.as<double>(), 1, 8));
-        converged = (*reinterpret_cast<int*>(ctx->pinned + 8) == 0);
-      }
-      if (!converged) return mpse_fail(ctx, MPSE_ERR_NOCONV, "block_svd: Jacobi did not converge (block %d, %dx%d)", b, m, n);
-    }
-    hipLaunchKernelGGL((k_col_norms<CPLX>), dim3(nn), dim3(RED_THREADS), 0, ctx->stream, (const double*)ws, mm,
-                       SIG.as<double>());
-    sig.resize(nn);
-    MPSE_TRY(mpse_memcpy_d2h(ctx, sig.data(), SIG.p, size_t(nn) * 8));
-    perm.resize(nn);
-    std::iota(perm.begin(), perm.end(), 0LL);
-    std::stable_sort(perm.begin(), perm.end(), [&](long long x, long long y) { return sig[x] > sig[y]; });
-    for (int j = 0; j < nn; ++j) S_host[koff + j] = sig[perm[j]];
-    MPSE_TRY(stage_h2d(ctx, PERM.p, perm.data(), size_t(nn) * 8));
-    const double smax = sig[perm[0]];
-    const double thresh = smax * 2.220446049250313e-16 * (double)mm;
-    double* un = Q.as<double>();
-    hipLaunchKernelGGL((k_normalise_perm<CPLX>), dim3(ew_blocks((int64_t)mm * nn)), dim3(256), 0, ctx->stream, un,
-                       (const double*)ws, mm, nn, SIG.as<const double>(), PERM.as<const long long>(), thresh);
-    MPSE_TRY(hh_factor_colmajor(ctx, CPLX, un, mm, nn, nn, PRM.as<HhParam>()));
-    const int extra = extra_host ? (int)extra_host[b] : 0;
-    MPSE_TRY(hh_formq_colmajor(ctx, CPLX, ws, un, mm, nn, PRM.as<HhParam>(), nn + extra));
-    hipLaunchKernelGGL((k_scatter_svd<CPLX>), dim3(ew_blocks((int64_t)mm * nn + (int64_t)nn * nn)), dim3(256), 0,
-                       ctx->stream, (double*)U, (double*)Vt, (const double*)un, (const double*)ws,
-                       (const double*)vm, PERM.as<const long long>(), (long long)KU, (long long)ncol, rows, cols, mm,
-                       nn, (long long)koff, herm);
-    if (extra > 0) {
-      long long& off = herm ? voff : uoff;
-      hipLaunchKernelGGL((k_scatter_null<CPLX>), dim3(ew_blocks((int64_t)mm * extra)), dim3(256), 0, ctx->stream,
-                         (double*)U, (double*)Vt, (const double*)ws, (long long)KU, (long long)ncol, rows, cols, mm, nn,
-                         extra, off, herm);
-      off += extra;
-    }
-    MPSE_HIP(ctx, hipGetLastError());
-    // PERM / SIG are rewritten for the next block only after this block's scatter: same stream, in order
-    koff += k;
-  }
-  return MPSE_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Batched variant: all quantum-number blocks of a decomposition share every launch (blockIdx.y = block), the
-// convergence of a sweep is read once for all blocks, column norms once for all blocks.  Same algorithm and
-// thresholds as above.
 struct SvdBlk {
   long long ws_off, v_off, q_off;   // element offsets: column-major block (mm x nn), V (nn x nn), completed Q (mm x nq)
   long long row_off, col_off;       // into the concatenated row / column index lists
@@ -450,174 +102,6 @@ __global__ void k_sweep_end(int nblk, int* nrot, int* done) {
   if (b >= nblk) return;
   if (nrot[b] == 0) done[b] = 1;
   nrot[b] = 0;
-}
-
-template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_jacobi_step_b(double* ws, double* vbase,
-                                                               const SvdBlk* __restrict__ blks, int step,
-                                                               const double* __restrict__ null2v, int* nrot,
-                                                               const int* __restrict__ done) {
-  constexpr int E = Cx<CPLX>::E;
-  const int b = blockIdx.y;
-  if (done[b]) return;
-  const SvdBlk B = blks[b];
-  const int N = B.N, nn = B.nn, mm = B.mm;
-  const int kk = blockIdx.x;
-  if (step >= N - 1 || kk >= N / 2) return;
-  int p, q;
-  if (kk == 0) {
-    p = step % (N - 1);
-    q = N - 1;
-  } else {
-    p = (step + kk) % (N - 1);
-    q = (step - kk + (N - 1)) % (N - 1);
-  }
-  if (p > q) {
-    const int t = p;
-    p = q;
-    q = t;
-  }
-  if (q >= nn) return;
-  double* a = ws + B.ws_off * E;
-  double* v = vbase + B.v_off * E;
-  double* ap = a + (long long)p * mm * E;
-  double* aq = a + (long long)q * mm * E;
-  double alpha = 0, beta = 0, gr = 0, gi = 0;
-  for (int r = threadIdx.x; r < mm; r += RED_THREADS) {
-    const double2 x = Cx<CPLX>::ld(ap, r), y = Cx<CPLX>::ld(aq, r);
-    alpha += x.x * x.x + x.y * x.y;
-    beta += y.x * y.x + y.y * y.y;
-    gr += x.x * y.x + x.y * y.y;
-    gi += x.x * y.y - x.y * y.x;
-  }
-  block_allsum2(alpha, beta);
-  block_allsum2(gr, gi);
-  const double g = sqrt(gr * gr + gi * gi);
-  const double null2 = null2v[b];
-  if (g == 0.0 || alpha <= null2 || beta <= null2) return;
-  if (!(g > B.tol * sqrt(alpha) * sqrt(beta))) return;
-  const double pr = gr / g, pi = gi / g;
-  const double zeta = (beta - alpha) / (2.0 * g);
-  const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-  for (int r = threadIdx.x; r < mm; r += RED_THREADS) {
-    const double2 x = Cx<CPLX>::ld(ap, r), y0 = Cx<CPLX>::ld(aq, r);
-    const double2 y = make_double2(y0.x * pr + y0.y * pi, y0.y * pr - y0.x * pi);
-    Cx<CPLX>::st(ap, r, make_double2(c * x.x - s * y.x, c * x.y - s * y.y));
-    Cx<CPLX>::st(aq, r, make_double2(s * x.x + c * y.x, s * x.y + c * y.y));
-  }
-  double* vp = v + (long long)p * nn * E;
-  double* vq = v + (long long)q * nn * E;
-  for (int r = threadIdx.x; r < nn; r += RED_THREADS) {
-    const double2 x = Cx<CPLX>::ld(vp, r), y0 = Cx<CPLX>::ld(vq, r);
-    const double2 y = make_double2(y0.x * pr + y0.y * pi, y0.y * pr - y0.x * pi);
-    Cx<CPLX>::st(vp, r, make_double2(c * x.x - s * y.x, c * x.y - s * y.y));
-    Cx<CPLX>::st(vq, r, make_double2(s * x.x + c * y.x, s * x.y + c * y.y));
-  }
-  if (threadIdx.x == 0) atomicAdd(nrot + b, 1);
-}
-
-// The same step with ONE WAVE per column pair (four pairs per workgroup): for the square problems of the
-// preconditioned iteration a column is a few hundred elements - the Gram entries are wavefront shuffles, there is no
-// LDS traffic and no barrier, and the columns stay in registers between the Gram pass and the rotation (up to
-// JW_ROWS x 64 rows; taller columns are read again).
-constexpr int JW_ROWS = 8;
-template <bool CPLX>
-__global__ __launch_bounds__(256) void k_jacobi_step_w(double* ws, double* vbase, const SvdBlk* __restrict__ blks,
-                                                       int step, const double* __restrict__ null2v, int* nrot,
-                                                       const int* __restrict__ done) {
-  constexpr int E = Cx<CPLX>::E;
-  const int b = blockIdx.y;
-  if (done[b]) return;
-  const SvdBlk B = blks[b];
-  const int N = B.N, nn = B.nn, mm = B.mm;
-  const int lane = threadIdx.x & 63;
-  const int kk = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (step >= N - 1 || kk >= N / 2) return;
-  int p, q;
-  if (kk == 0) {
-    p = step % (N - 1);
-    q = N - 1;
-  } else {
-    p = (step + kk) % (N - 1);
-    q = (step - kk + (N - 1)) % (N - 1);
-  }
-  if (p > q) {
-    const int t = p;
-    p = q;
-    q = t;
-  }
-  if (q >= nn) return;
-  double* a = ws + B.ws_off * E;
-  double* v = vbase + B.v_off * E;
-  double* ap = a + (long long)p * mm * E;
-  double* aq = a + (long long)q * mm * E;
-  const bool cached = mm <= JW_ROWS * 64;
-  double2 xs[JW_ROWS], ys[JW_ROWS];
-  double alpha = 0, beta = 0, gr = 0, gi = 0;
-  if (cached) {
-#pragma unroll
-    for (int i = 0; i < JW_ROWS; ++i) {
-      const int r = lane + 64 * i;
-      xs[i] = ys[i] = make_double2(0.0, 0.0);
-      if (r < mm) {
-        xs[i] = Cx<CPLX>::ld(ap, r);
-        ys[i] = Cx<CPLX>::ld(aq, r);
-      }
-      alpha += xs[i].x * xs[i].x + xs[i].y * xs[i].y;
-      beta += ys[i].x * ys[i].x + ys[i].y * ys[i].y;
-      gr += xs[i].x * ys[i].x + xs[i].y * ys[i].y;
-      gi += xs[i].x * ys[i].y - xs[i].y * ys[i].x;
-    }
-  } else {
-    for (int r = lane; r < mm; r += 64) {
-      const double2 x = Cx<CPLX>::ld(ap, r), y = Cx<CPLX>::ld(aq, r);
-      alpha += x.x * x.x + x.y * x.y;
-      beta += y.x * y.x + y.y * y.y;
-      gr += x.x * y.x + x.y * y.y;
-      gi += x.x * y.y - x.y * y.x;
-    }
-  }
-  alpha = wave_sum(alpha);
-  beta = wave_sum(beta);
-  gr = wave_sum(gr);
-  gi = wave_sum(gi);
-  const double g = sqrt(gr * gr + gi * gi);
-  const double null2 = null2v[b];
-  if (g == 0.0 || alpha <= null2 || beta <= null2) return;
-  if (!(g > B.tol * sqrt(alpha) * sqrt(beta))) return;
-  const double pr = gr / g, pi = gi / g;
-  const double zeta = (beta - alpha) / (2.0 * g);
-  const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-  if (cached) {
-#pragma unroll
-    for (int i = 0; i < JW_ROWS; ++i) {
-      const int r = lane + 64 * i;
-      if (r < mm) {
-        const double2 x = xs[i], y0 = ys[i];
-        const double2 y = make_double2(y0.x * pr + y0.y * pi, y0.y * pr - y0.x * pi);
-        Cx<CPLX>::st(ap, r, make_double2(c * x.x - sn * y.x, c * x.y - sn * y.y));
-        Cx<CPLX>::st(aq, r, make_double2(sn * x.x + c * y.x, sn * x.y + c * y.y));
-      }
-    }
-  } else {
-    for (int r = lane; r < mm; r += 64) {
-      const double2 x = Cx<CPLX>::ld(ap, r), y0 = Cx<CPLX>::ld(aq, r);
-      const double2 y = make_double2(y0.x * pr + y0.y * pi, y0.y * pr - y0.x * pi);
-      Cx<CPLX>::st(ap, r, make_double2(c * x.x - sn * y.x, c * x.y - sn * y.y));
-      Cx<CPLX>::st(aq, r, make_double2(sn * x.x + c * y.x, sn * x.y + c * y.y));
-    }
-  }
-  double* vp = v + (long long)p * nn * E;
-  double* vq = v + (long long)q * nn * E;
-  for (int r = lane; r < nn; r += 64) {
-    const double2 x = Cx<CPLX>::ld(vp, r), y0 = Cx<CPLX>::ld(vq, r);
-    const double2 y = make_double2(y0.x * pr + y0.y * pi, y0.y * pr - y0.x * pi);
-    Cx<CPLX>::st(vp, r, make_double2(c * x.x - sn * y.x, c * x.y - sn * y.y));
-    Cx<CPLX>::st(vq, r, make_double2(sn * x.x + c * y.x, sn * x.y + c * y.y));
-  }
-  if (lane == 0) atomicAdd(nrot + b, 1);
 }
 
 // Block step of the iteration on the square problems: a workgroup takes a PAIR OF COLUMN BLOCKS (JB_COLS columns
@@ -800,7 +284,7 @@ __global__ __launch_bounds__(64 * JB_COLS) void k_jacobi_block(double* ws, doubl
 
 // Block step on the Gram matrix (round 6): a pair of JG-column blocks of X and V is rotated through its 2 JG x 2 JG Gram
 // matrix instead of through its columns - the step for blocks too wide for the column kernel above (its LDS holds
-// 4 JB_COLS columns of nn rows: nn <= 256 complex), where the alternative is one launch per rotation step.
+// 4 JB_COLS columns of nn rows: nn <= 256 complex), where the alternative was one launch per rotation step.
 //   1. G = Y^H Y of the 2 JG = 32 columns Y of the pair, on MFMA straight from memory (rows dealt to the 4 waves, partial
 //      sums added through LDS in a fixed order).  Only the first launch of a sweep forms all three tiles: the diagonal
 //      tiles of a column block travel with it (dgin / dgout: what the rotations of the previous launch made of them),
@@ -1444,7 +928,7 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
       const SvdBlk& B = tall[b];
       qb[b] = QrBlk{B.ws_off, B.q1_off, B.mm, B.nn, B.nn, B.sig_off, B.nn + B.extra};
     }
-    MPSE_TRY(hh_qr_batched(ctx, CPLX, ws, Q1.as<double>(), PRM1.as<HhParam>(), qb.data(), nblk, true));
+    MPSE_TRY(hh_qr(ctx, CPLX, ws, Q1.as<double>(), PRM1.as<HhParam>(), qb.data(), nblk, true));
   }
   // ---- 2. X = R^H, V = I, one-sided Jacobi on the square problems
   // (X is formed in the buffer of the normalised copy and sorted into its own: columns by decreasing norm)
@@ -1470,11 +954,11 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
     MPSE_HIP(ctx, hipGetLastError());
   }
   // Which block step runs the sweeps: the column kernel in LDS (k_jacobi_block) where the column blocks of X and V fit
-  // (nn <= 256 complex, 512 real), the Gram kernel (k_jacobi_gram) for wider blocks, where the alternative is a launch
-  // per rotation step.  MPSE_SVD_GRAM=2: the Gram kernel for every size, =0: never (read per call: tests switch it).
-  const int gram_mode = [] {
+  // (nn <= 256 complex, 512 real), the Gram kernel (k_jacobi_gram) for wider blocks.  MPSE_SVD_GRAM=2: the Gram kernel
+  // for every size (read per call: tests switch it).
+  const bool gram_all = [] {
     const char* e = getenv("MPSE_SVD_GRAM");
-    return e ? atoi(e) : 1;
+    return e && atoi(e) >= 2;
   }();
   const int gram_r_env = [] {
     const char* e = getenv("MPSE_SVD_GRAM_R");     // row slabs per column-block pair (default: a 16-row tile per wave)
@@ -1509,7 +993,10 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
       return a == hipSuccess && b == hipSuccess;
     }();
     const bool cols_fit = blk_lds <= (lds_attr ? size_t(150) : size_t(64)) * 1024;
-    const bool use_gram = gram_attr && (gram_mode >= 2 || (gram_mode == 1 && !cols_fit));
+    const bool use_gram = gram_all || !cols_fit;
+    if (use_gram && !gram_attr)
+      return mpse_fail(ctx, MPSE_ERR_HIP, "block_svd: the runtime refused %zu bytes of dynamic LDS to the Gram step",
+                       gram_lds);
     int gram_R = 1;
     if (use_gram) {
       MPSE_TRY(X2.alloc(size_t(x_tot) * es));
@@ -1537,20 +1024,11 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
                              (const int*)done);
           cur ^= 1;
         }
-      } else if (cols_fit) {
+      } else {
         const int nbmax = ((maxnn + JB_COLS - 1) / JB_COLS + 1) & ~1;
         for (int step = 0; step < nbmax - 1; ++step)
           hipLaunchKernelGGL((k_jacobi_block<CPLX>), dim3(nbmax / 2, nblk), dim3(64 * JB_COLS), blk_lds, ctx->stream, xs,
                              vm, dsq, step, (const double*)null2, nrot, (const int*)done);
-      } else {
-        for (int step = 0; step < maxN - 1; ++step) {
-          if (maxnn <= 2048)     // square problems: a wave per column pair
-            hipLaunchKernelGGL((k_jacobi_step_w<CPLX>), dim3((maxN / 2 + 3) / 4, nblk), dim3(256), 0, ctx->stream, xs, vm,
-                               dsq, step, (const double*)null2, nrot, (const int*)done);
-          else
-            hipLaunchKernelGGL((k_jacobi_step_b<CPLX>), dim3(maxN / 2, nblk), dim3(RED_THREADS), 0, ctx->stream, xs, vm,
-                               dsq, step, (const double*)null2, nrot, (const int*)done);
-        }
       }
       hipLaunchKernelGGL(k_sweep_end, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, nblk, nrot, done);
       MPSE_HIP(ctx, hipGetLastError());
@@ -1597,7 +1075,7 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
       const SvdBlk& B = sq[b];
       qb[b] = QrBlk{B.ws_off, B.q_off, B.nn, B.nn, B.nn, B.sig_off, B.nn};
     }
-    MPSE_TRY(hh_qr_batched(ctx, CPLX, un, QX.as<double>(), PRM2.as<HhParam>(), qb.data(), nblk, true));
+    MPSE_TRY(hh_qr(ctx, CPLX, un, QX.as<double>(), PRM2.as<HhParam>(), qb.data(), nblk, true));
   }
   // ---- 4. left vectors of the tall blocks: Q1[:, :nn] Vx through the contraction kernel (into the workspace the
   // factored block no longer needs), then both sides to their places
@@ -1636,6 +1114,31 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
   }
   (void)E;
   return MPSE_OK;
+}
+
+// argument and shape checks; every block height then takes the path above
+template <bool CPLX>
+int block_svd_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, int nblocks, const int64_t* row_idx,
+                   const int64_t* row_off, const int64_t* col_idx, const int64_t* col_off, void* U, void* Vt,
+                   double* S_host, int64_t K, const int64_t* extra_host, int64_t KU, int64_t KV) {
+  int64_t ktot = 0, nu = 0, nv = 0;
+  for (int b = 0; b < nblocks; ++b) {
+    const int64_t m = row_off[b + 1] - row_off[b], n = col_off[b + 1] - col_off[b];
+    if (m < 0 || n < 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: negative block extent");
+    const int64_t k = std::min(m, n);
+    ktot += k;
+    int64_t ex = extra_host ? extra_host[b] : 0;
+    if (ex < 0 || ex > std::max(m, n) - k) return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: bad extra count");
+    if (k == 0) ex = 0;
+    if (m >= n) nu += ex; else nv += ex;
+  }
+  if (KU != ktot + nu || KV != ktot + nv)
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: KU/KV (%lld,%lld) do not match the blocks (%lld,%lld)",
+                     (long long)KU, (long long)KV, (long long)(ktot + nu), (long long)(ktot + nv));
+  if (ktot != K) return mpse_fail(ctx, MPSE_ERR_SHAPE, "block_svd: K=%lld but blocks give %lld", (long long)K, (long long)ktot);
+  if (ktot == 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "Invalid quantum number");
+  return block_svd_batched<CPLX>(ctx, coef, nrow, ncol, nblocks, row_idx, row_off, col_idx, col_off, U, Vt, S_host, K,
+                                 extra_host, KU, KV);
 }
 
 }  // namespace

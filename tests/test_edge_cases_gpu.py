@@ -145,8 +145,17 @@ def test_block_qr_columns_with_denormal_squared_norms(eng):
     """state preparation meets columns of norm 1e-160 and below: the squared norm is denormal or zero.  Such columns
     get H = I (their sub-diagonal part, < 1e-140 in absolute terms, is dropped); nothing may turn into NaN
     (regression: NaN in the bond expansion of the headline state)"""
+    _check_denormal_columns(eng, 300)
+
+
+def test_block_qr_columns_with_denormal_squared_norms_tall_block(eng):
+    """the same columns in a block taller than the batched Householder kernels hold (unblocked kernels)"""
+    _check_denormal_columns(eng, 5000)
+
+
+def _check_denormal_columns(eng, m):
     rng = np.random.default_rng(7)
-    m, n = 300, 12
+    n = 12
     a = rng.standard_normal((m, n)) + 1j * rng.standard_normal((m, n))
     a = a * np.array([1.0, 1e-100, 1e-150, 1e-160, 1e-165, 1e-170, 1e-200, 0.0, 1.0, 1e-158, 1e-162, 3.0])
     qnl, qnr = np.zeros((m, 1), dtype=int), np.zeros((n, 1), dtype=int)

@@ -2,7 +2,7 @@
 """Timing and accuracy of the blocked SVD entry point in isolation (GPU box): two-site centres of the headline chain
 (256 x 2 x 16 x 256 -> 512 x 4096 in two quantum-number blocks) with a decaying spectrum, real and complex.
 
-    python tools/svd_bench.py [out.md [case substring]]      MPSE_SVD_GRAM=0 selects the column kernel of rounds 4 - 5
+    python tools/svd_bench.py [out.md [case substring]]
 
 Per case: ms per decomposition (20 calls), sweeps per call (the engine's profile counter), largest deviation of the
 singular values from LAPACK's relative to the largest one, orthogonality of both factors, reconstruction."""
@@ -71,6 +71,6 @@ for name, (Dl, dl, dr, Dr, nq, cplx, decay) in {
     shapes = ", ".join(f"{len(b[2])} x {len(b[3])}" for b in blocks)
     lines.append(f"| {name} | {shapes} | {dt * 1e3:.2f} | {dev:.1e} | {ou:.1e} | {ov:.1e} | {rec:.1e} |")
     print(lines[-1], flush=True)
-txt = "\n".join(lines) + f"\n\nMPSE_SVD_GRAM={os.environ.get('MPSE_SVD_GRAM', '(default: 1)')}  MPSE_SVD_GRAM_R={os.environ.get('MPSE_SVD_GRAM_R', '(default)')}\n"
+txt = "\n".join(lines) + f"\n\nMPSE_SVD_GRAM={os.environ.get('MPSE_SVD_GRAM', '(default)')}  MPSE_SVD_GRAM_R={os.environ.get('MPSE_SVD_GRAM_R', '(default)')}\n"
 if len(sys.argv) > 1:
     open(sys.argv[1], "w").write(txt)
