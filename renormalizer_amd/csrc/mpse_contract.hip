@@ -238,25 +238,29 @@ __global__ __launch_bounds__(256) void k_wmix(const WmixArgs g) {
 }
 
 int copy_call(mpse_ctx* ctx, int dtype, const void* src, void* dst, mpse_index mi, mpse_index ni, mpse_index mo,
-              mpse_index no) {
+              mpse_index no, const int* skip) {
   const long long total = mi.ext * ni.ext;
   if (total <= 0) return MPSE_OK;
   long long nb = (total + 255) / 256;
   if (nb > 65536) nb = 65536;
   if (dtype == MPSE_C128)
     hipLaunchKernelGGL((k_copy_strided<double2>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, (double2*)dst,
-                       (const double2*)src, mi, ni, mo, no, ctx->skip_flag);
+                       (const double2*)src, mi, ni, mo, no, skip);
   else
     hipLaunchKernelGGL((k_copy_strided<double>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, (double*)dst,
-                       (const double*)src, mi, ni, mo, no, ctx->skip_flag);
+                       (const double*)src, mi, ni, mo, no, skip);
   MPSE_HIP(ctx, hipGetLastError());
   return MPSE_OK;
 }
 
 }  // namespace
 
-static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in[B_COUNT]) {
+// sc: the solve the plan runs in, mv: the requests of the matvec it computes (both may be null)
+static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in[B_COUNT],
+                    const SolveScope* sc = nullptr, MatvecReq* mv = nullptr) {
   if (p.error) return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s", p.error);
+  const int* skip = sc ? sc->skip : nullptr;
+  MatvecReq::Dot* dot = mv && mv->dot.y ? &mv->dot : nullptr;
   const void* bufs[B_COUNT];
   for (int i = 0; i < B_COUNT; ++i) bufs[i] = bufs_in[i];
   TmpBuf t1(ctx), t2(ctx), t3(ctx);
@@ -306,7 +310,7 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
       g.T2 = (double*)const_cast<void*>(bufs[s.c]);
       g.W = (const double*)bufs[s.a];
       g.Da = (int)s.w_Da, g.d = (int)s.w_d, g.wl = (int)s.w_wl, g.wr = (int)s.w_wr, g.N = (int)s.w_N;
-      g.skip = ctx->skip_flag;
+      g.skip = skip;
       g.slices = slices_used > 0 ? SLC.as<const double>() : nullptr;
       g.nslices = slices_used, g.slice_stride = slice_elems, g.b_lo = (int)slice_b_lo, g.b_hi = (int)slice_b_hi;
       slices_used = 0;
@@ -327,7 +331,7 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
       g.ndst = (int)s.mix.size();
       g.Da = (int)s.wp_Da, g.d = (int)s.wp_d, g.wr = (int)s.wp_wr, g.Dk = (int)s.wp_Dk;
       g.nchunk = (g.d + WM_CHUNK - 1) / WM_CHUNK;
-      g.skip = ctx->skip_flag;
+      g.skip = skip;
       int nslot = 0;
       for (int j = 0; j < g.ndst; ++j) {
         const WMixDst& q = s.mix[j];
@@ -369,13 +373,13 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
       bool stable = true;
       if (s.scan_a.on && bufs[s.scan_a.buf]) {
         bool st = false;
-        MPSE_TRY(occ_mask_get(ctx, (const char*)bufs[s.scan_a.buf] + size_t(s.scan_a.off) * dtype_size(s.scan_a.dt),
+        MPSE_TRY(occ_mask_get(ctx, sc, (const char*)bufs[s.scan_a.buf] + size_t(s.scan_a.off) * dtype_size(s.scan_a.dt),
                               s.scan_a.dt, s.scan_a.r, s.scan_a.k, MA, &fa, &gd.am_pitch, &st));
         stable = stable && st;
       }
       if (s.scan_b.on && bufs[s.scan_b.buf]) {
         bool st = false;
-        MPSE_TRY(occ_mask_get(ctx, (const char*)bufs[s.scan_b.buf] + size_t(s.scan_b.off) * dtype_size(s.scan_b.dt),
+        MPSE_TRY(occ_mask_get(ctx, sc, (const char*)bufs[s.scan_b.buf] + size_t(s.scan_b.off) * dtype_size(s.scan_b.dt),
                               s.scan_b.dt, s.scan_b.r, s.scan_b.k, MB, &fb, &gd.bm_pitch, &st));
         stable = stable && st;
       }
@@ -386,8 +390,8 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
         const char* pc = (const char*)bufs[B_C];
         const int64_t K = s.kb.ext, N = s.nb.ext;
         const int64_t nkw = ((K + 15) / 16 + 7) / 8, ntn = (N + 63) / 64;
-        if (ctx->cmask.ptr && pc && pc >= ctx->cmask.lo && pc < ctx->cmask.hi && ctx->cmask.bytes == ntn * nkw * 8) {
-          cm = static_cast<const unsigned char*>(ctx->cmask.ptr);
+        if (sc && sc->in_krylov(pc) && sc->cmask.bytes == ntn * nkw * 8) {
+          cm = static_cast<const unsigned char*>(sc->cmask.ptr);
           cm_pitch = (int)(nkw * 8);
         }
       }
@@ -419,11 +423,9 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
         gd.c2 = const_cast<void*>(bufs[B_OUT2]);
       }
       // the last step completes the result: it carries the caller's dot request
-      if (ctx->dot_req.y && &s == &p.steps.back() && gd.ngrp == 1 && s.groups[0].cbuf == B_OUT && s.groups[0].c_off == 0)
-        ctx->dot_now = true;
-      const int st = gemm_grouped(ctx, gd);
-      ctx->dot_now = false;
-      MPSE_TRY(st);
+      const bool completes =
+          &s == &p.steps.back() && gd.ngrp == 1 && s.groups[0].cbuf == B_OUT && s.groups[0].c_off == 0;
+      MPSE_TRY(gemm_grouped(ctx, gd, sc, completes ? dot : nullptr));
       continue;
     }
     const char* a = (const char*)bufs[s.a] + size_t(s.a_off) * dtype_size(s.dta);
@@ -434,49 +436,42 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
     char* c = (char*)const_cast<void*>(bufs[s.c]) + size_t(s.c_off) * dtype_size(dtc);
     if (!bufs[s.a] || !bufs[s.b] || !bufs[s.c]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
     if (s.kind == K_COPY) {
-      MPSE_TRY(copy_call(ctx, dtc, a, c, s.ma, s.ka, s.mc, s.nc));
+      MPSE_TRY(copy_call(ctx, dtc, a, c, s.ma, s.ka, s.mc, s.nc, skip));
       continue;
     }
+    ProductReq rq;
     // the last step completes the result: it takes the caller's dot request along when it is a plain product into
     // the whole of `out`
-    if (ctx->dot_req.y && &s == &p.steps.back() && s.c == B_OUT && s.c_off == 0 && s.batch == 1)
-      ctx->dot_now = true;
+    if (&s == &p.steps.back() && s.c == B_OUT && s.c_off == 0 && s.batch == 1) rq.dot = dot;
     if (s.cin >= 0) {
       if (!bufs[s.cin]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing beta source");
-      ctx->cin_req.ptr = (const char*)bufs[s.cin] + size_t(s.cin_off) * dtype_size(dtc);
-      ctx->cin_req.m = s.mcin;
-      ctx->cin_req.n = s.ncin;
+      rq.cin = (const char*)bufs[s.cin] + size_t(s.cin_off) * dtype_size(dtc);
+      rq.cin_m = s.mcin;
+      rq.cin_n = s.ncin;
     }
     if (&s == slice_producer) {
       // room for four slices of this product's result (more: the product reduces them itself, as usual)
       const size_t blk = size_t(s.mc.ext) * size_t(s.nc.ext) * dtype_size(dtc);
       if (SLC.alloc(4 * blk) == MPSE_OK) {
-        ctx->slices_req.ptr = SLC.p;
-        ctx->slices_req.cap_bytes = 4 * blk;
-        ctx->slices_req.used = 0;
+        rq.slices = SLC.p;
+        rq.slices_cap = 4 * blk;
       }
     }
-    const int st = gemm_call(ctx, s.dta, s.dtb, s.conja, s.conjb, s.ma, s.ka, s.kb, s.nb, s.mc, s.nc, s.batch, s.sba,
-                             s.sbb, s.sbc, a, b, c, 1.0, s.beta, s.skip_zero);
-    if (&s == slice_producer) {
-      slices_used = ctx->slices_req.used;
-      ctx->slices_req = mpse_ctx::SlicesReq();
-      if (slices_used > 0) {
-        // rows of the product = (channel - b_lo | bra bond): which channels of T1 it forms
-        slice_elems = (long long)s.mc.ext * s.nc.ext;
-        slice_b_lo = s.c_off / (slice_consumer->w_Da * slice_consumer->w_d * slice_consumer->w_N);
-        slice_b_hi = slice_b_lo + s.mc.ext / slice_consumer->w_Da;
-      }
+    MPSE_TRY(gemm_call(ctx, s.dta, s.dtb, s.conja, s.conjb, s.ma, s.ka, s.kb, s.nb, s.mc, s.nc, s.batch, s.sba, s.sbb,
+                       s.sbc, a, b, c, 1.0, s.beta, s.skip_zero, sc, &rq));
+    if (rq.slices_used > 0) {
+      // rows of the product = (channel - b_lo | bra bond): which channels of T1 it forms
+      slices_used = rq.slices_used;
+      slice_elems = (long long)s.mc.ext * s.nc.ext;
+      slice_b_lo = s.c_off / (slice_consumer->w_Da * slice_consumer->w_d * slice_consumer->w_N);
+      slice_b_hi = slice_b_lo + s.mc.ext / slice_consumer->w_Da;
     }
-    // requests the call did not take (degenerate product, error) must not reach a later one
-    ctx->cin_req = mpse_ctx::CinReq();
-    ctx->dot_now = false;
-    MPSE_TRY(st);
   }
   return MPSE_OK;
 }
 
-extern "C" int mpse_heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out) {
+int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+               MatvecReq* mv) {
   if (!ctx || !h || !C || !out || !h->L || !h->R) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (dtype != MPSE_C128 && (h->l_dtype == MPSE_C128 || h->r_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
@@ -487,21 +482,21 @@ extern "C" int mpse_heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, con
     auto it = ctx->wsite_info.find(h->W0);
     if (it != ctx->wsite_info.end()) wi_keep = it->second.info;
   }
-  // a caller that takes the result in two parts (mpse_ctx::y2_req, the Lanczos solve) lets the last product run as
-  // halved tiles; `used` tells it whether the second part holds anything
-  mpse_ctx::PartsReq& pr = ctx->parts_req;
   {
     bool taken = false;
-    MPSE_TRY(heff_small_try(ctx, dtype, h, C, out, &taken));
-    if (taken) return MPSE_OK;     // (pr.used is set there: the result may be a sum of parts)
+    MPSE_TRY(heff_small_try(ctx, dtype, h, C, out, sc, mv, &taken));
+    if (taken) return MPSE_OK;     // (parts.used is set there: the result may be a sum of parts)
     const WSiteInfo* wi0 = static_cast<const WSiteInfo*>(wi_keep.get());
     const bool wi_ok = wi0 && h->nsite == 1 && wi0->wl == h->dims.wl && wi0->d == h->dims.d0 && wi0->wr == h->dims.wr;
-    MPSE_TRY(heff0_fused_try(ctx, dtype, h, C, wi_ok ? wi0->w.data() : nullptr, &taken));
-    if (taken) return MPSE_OK;     // (tile-masked parts: pr.used, pr.mask)
+    MPSE_TRY(heff0_fused_try(ctx, dtype, h, C, wi_ok ? wi0->w.data() : nullptr, sc, mv, &taken));
+    if (taken) return MPSE_OK;     // (tile-masked parts: parts.used, parts.mask)
   }
-  const bool two_ok = pr.ptr != nullptr && pr.cap_elems >= 2 * pr.n;
+  // a caller that takes the result in two parts (the Lanczos solve) lets the last product run as halved tiles; `used`
+  // tells it whether the second part holds anything
+  MatvecReq::Parts* pr = mv && mv->parts.ptr ? &mv->parts : nullptr;
+  const bool two_ok = pr && pr->cap_elems >= 2 * pr->n;
   Plan p = plan_heff(dtype, *h, static_cast<const WSiteInfo*>(wi_keep.get()), two_ok);
-  pr.used = 0;
+  if (pr) pr->used = 0;
   const void* bufs[B_COUNT] = {nullptr};
   bufs[B_L] = h->L;
   bufs[B_R] = h->R;
@@ -511,10 +506,14 @@ extern "C" int mpse_heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, con
   bufs[B_OUT] = out;
   // halved tiles: part 0 is `out` itself (it holds the beta term), part 1 the second slot of the caller's buffer;
   // split products: all parts in the caller's buffer (mpse_gemm.hip sets `used`)
-  if (p.two_results) bufs[B_OUT2] = static_cast<char*>(pr.ptr) + size_t(pr.n) * dtype_size(dtype);
-  const int st = run_plan(ctx, dtype, p, bufs);
-  if (st == MPSE_OK && p.two_results) pr.used = -2;     // (out, part 1)
-  return st;
+  if (p.two_results) bufs[B_OUT2] = static_cast<char*>(pr->ptr) + size_t(pr->n) * dtype_size(dtype);
+  MPSE_TRY(run_plan(ctx, dtype, p, bufs, sc, mv));
+  if (p.two_results) pr->used = -2;     // (out, part 1)
+  return MPSE_OK;
+}
+
+extern "C" int mpse_heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out) {
+  return heff_apply(ctx, dtype, h, C, out, nullptr, nullptr);
 }
 
 extern "C" int mpse_mpo_site_hint(mpse_ctx* ctx, const void* W_dev, const double* W_host, int64_t wl, int64_t d,

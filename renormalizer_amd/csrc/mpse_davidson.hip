@@ -230,6 +230,7 @@ struct Dav {
   int dtype;
   bool cplx;
   const mpse_heff* h;
+  const SolveScope* scope;
   int twolayer;
   const void* mask;
   int64_t n;
@@ -250,7 +251,7 @@ struct Dav {
     if (twolayer)
       MPSE_TRY(mpse_heff_apply2(ctx, dtype, h, x, y));
     else
-      MPSE_TRY(mpse_heff_apply(ctx, dtype, h, x, y));
+      MPSE_TRY(heff_apply(ctx, dtype, h, x, y, scope, nullptr));
     if (mask) MPSE_TRY(mpse_mul_real(ctx, dtype, y, mask, n));
     return MPSE_OK;
   }
@@ -352,7 +353,7 @@ extern "C" int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int t
   if ((s.Dl_bra > 0 && s.Dl_bra != s.Dl_ket) || (s.Dr_bra > 0 && s.Dr_bra != s.Dr_ket))
     return mpse_fail(ctx, MPSE_ERR_SHAPE, "davidson: the effective Hamiltonian must be square (bra bonds == ket bonds)");
   if (h->nsite != 1 && h->nsite != 2) return mpse_fail(ctx, MPSE_ERR_ARG, "davidson: one- or two-site centres");
-  SmallRtScope small_rt_scope(ctx);
+  SolveScope scope(ctx);   // (no occupancy caches: the transposed environments of the small matvecs are kept)
   const int64_t anc = s.danc > 0 ? s.danc : 1;
   int64_t n = s.Dl_ket * s.Dr_ket * s.d0 * anc;
   if (h->nsite == 2) n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
@@ -372,7 +373,8 @@ extern "C" int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int t
   MPSE_TRY(VB.alloc(size_t(cap) * n * es));
   MPSE_TRY(WB.alloc(size_t(cap) * n * es));
   Dav d;
-  d.ctx = ctx, d.dtype = dtype, d.cplx = cplx, d.h = h, d.twolayer = twolayer, d.mask = mask_f64, d.n = n, d.es = es;
+  d.ctx = ctx, d.dtype = dtype, d.cplx = cplx, d.h = h, d.scope = &scope, d.twolayer = twolayer, d.mask = mask_f64;
+  d.n = n, d.es = es;
   d.nb = dv_blocks(n * (cplx ? 2 : 1));
   MPSE_TRY(PB.alloc(size_t(DV_MAX) * d.nb * 2 * sizeof(double)));
   MPSE_TRY(SB.alloc(size_t(4 * DV_MAX) * sizeof(double)));

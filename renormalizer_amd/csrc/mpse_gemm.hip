@@ -115,7 +115,7 @@ struct GemmArgs {
   const unsigned long long* bmask;
   int nkw;
   unsigned long long* kt_counter;   // profiling only: every workgroup adds the number of K tiles it multiplied
-  const int* skip;                  // optional device flag: non-zero -> the launch does nothing (mpse_ctx::skip_flag)
+  const int* skip;                  // optional device flag: non-zero -> the launch does nothing (SolveScope::skip)
   // optional (batch == 1): the kernel that stores the final values of C also accumulates sum conj(C) . y over its
   // share of C (y laid out like C) and stores one (re, im) partial per workgroup at dot_part - the Lanczos
   // coefficient alpha_j = <H v_j, v_j> without a pass of its own over the two vectors
@@ -1233,7 +1233,9 @@ __global__ __launch_bounds__(256) void k_transpose_inner(double* out, const doub
 
 }  // namespace
 
-static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, const void* B, void* C, int skip_zero) {
+// sc: the solve the product runs in, rq: what run_plan asks of it beyond the descriptor (both may be null)
+static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, const void* B, void* C, int skip_zero,
+                     const SolveScope* sc, ProductReq* rq) {
   if (!ctx || !d) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if ((d->dtype_a != MPSE_F64 && d->dtype_a != MPSE_C128) || (d->dtype_b != MPSE_F64 && d->dtype_b != MPSE_C128))
@@ -1274,16 +1276,15 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
   g.beta_re = d->beta_re;
   g.beta_im = d->beta_im;
   g.use_beta = (d->beta_re != 0.0 || d->beta_im != 0.0);
-  // beta source of the caller (mpse_ctx::cin_req, set by run_plan for this one call)
+  // beta source of the caller (ProductReq::cin)
   g.Cin = nullptr;
-  if (ctx->cin_req.ptr) {
-    const mpse_ctx::CinReq rq = ctx->cin_req;
-    ctx->cin_req = mpse_ctx::CinReq();
-    if (d->batch != 1 || !g.use_beta || !to_map(rq.m, &g.mCin) || !to_map(rq.n, &g.nCin) || g.mCin.ext != g.mC.ext ||
-        g.nCin.ext != g.nC.ext)
+  if (rq && rq->cin) {
+    if (d->batch != 1 || !g.use_beta || !to_map(rq->cin_m, &g.mCin) || !to_map(rq->cin_n, &g.nCin) ||
+        g.mCin.ext != g.mC.ext || g.nCin.ext != g.nC.ext)
       return mpse_fail(ctx, MPSE_ERR_ARG, "mpse_gemm: beta source needs batch == 1, beta != 0 and the extents of C");
-    g.Cin = static_cast<const double*>(rq.ptr);
+    g.Cin = static_cast<const double*>(rq->cin);
   }
+  const int* skip = sc ? sc->skip : nullptr;
   const bool ca = d->dtype_a == MPSE_C128, cb = d->dtype_b == MPSE_C128;
   // split-K when the output tiles alone cannot fill the 256 CUs (skinny results with long K)
   const long long base_blocks = (long long)g.tiles_m * g.tiles_n * d->batch;
@@ -1293,7 +1294,7 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
   g.ws = nullptr;
   g.amask = g.bmask = nullptr;
   g.nkw = 0;
-  g.skip = ctx->skip_flag;
+  g.skip = skip;
   g.skew = 1;
   g.perm = nullptr;
   g.gg.ngrp = 0;
@@ -1332,12 +1333,12 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
       // the dot partner, and the update kernel streams 16 slices with a fraction of the reduction kernel's blocks.)
       const size_t esz = (ca || cb) ? 16 : 8;
       const size_t ws_bytes = size_t(d->batch) * g.ksplit * size_t(g.M) * size_t(g.N) * esz;
-      // slices for a consumer that adds them itself (mpse_ctx::slices_req): plain product into a compact result
+      // slices for a consumer that adds them itself (ProductReq::slices): plain product into a compact result
       const bool compact = is_single(g.mC) && is_single(g.nC) && g.mC.s_lo == g.N && (g.nC.s_lo == 1 || g.N == 1);
-      if (ctx->slices_req.ptr && !ctx->dot_now && d->batch == 1 && compact && !g.use_beta && d->alpha_re == 1.0 &&
-          d->alpha_im == 0.0 && ws_bytes <= ctx->slices_req.cap_bytes) {
-        g.ws = static_cast<double*>(ctx->slices_req.ptr);
-        ctx->slices_req.used = g.ksplit;
+      if (rq && rq->slices && !rq->dot && d->batch == 1 && compact && !g.use_beta && d->alpha_re == 1.0 &&
+          d->alpha_im == 0.0 && ws_bytes <= rq->slices_cap) {
+        g.ws = static_cast<double*>(rq->slices);
+        rq->slices_used = g.ksplit;
         leave_slices = true;
       } else {
         MPSE_TRY(WSB.alloc(ws_bytes));
@@ -1349,22 +1350,21 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
   long long nblk = base_blocks * g.ksplit;
   if (nblk > 0x7fffffffLL) return mpse_fail(ctx, MPSE_ERR_SHAPE, "mpse_gemm: grid too large");
 
-  // dot request of the caller (mpse_ctx::dot_req, armed by run_plan for the step that completes the result)
-  const bool want_dot = ctx->dot_now;
-  ctx->dot_now = false;
+  // dot request of the caller (ProductReq::dot: run_plan passes it to the step that completes the result)
+  MatvecReq::Dot* dot = rq ? rq->dot : nullptr;
   long long rgx = (g.N + 255) / 256 > 64 ? 64 : (g.N + 255) / 256;
   long long rgy = (long long)g.M * d->batch > 32768 ? 32768 : (long long)g.M * d->batch;
-  if (want_dot && d->batch == 1) {
+  if (dot && d->batch == 1) {
     long long producers = base_blocks;
     if (g.ksplit > 1) {
-      const long long cap_y = ctx->dot_req.cap / rgx;
+      const long long cap_y = dot->cap / rgx;
       if (cap_y >= 1 && rgy > cap_y) rgy = cap_y;
       producers = rgx * rgy;
     }
-    if (producers >= 1 && producers <= ctx->dot_req.cap) {
-      g.dot_y = static_cast<const double*>(ctx->dot_req.y);
-      g.dot_part = ctx->dot_req.part;
-      ctx->dot_req.nb_out = (int)producers;
+    if (producers >= 1 && producers <= dot->cap) {
+      g.dot_y = static_cast<const double*>(dot->y);
+      g.dot_part = dot->part;
+      dot->nb_out = (int)producers;
     }
   }
 
@@ -1386,12 +1386,8 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
     const size_t wa = size_t(d->batch) * g.mtiles_m * g.nkw, wb = size_t(d->batch) * g.mtiles_n * g.nkw;
     // skip_zero bit 0: scan A, bit 1: scan B (an operand that is as large as the product itself is not worth a pass)
     const bool sa = skip_zero & 1, sb_ = skip_zero & 2;
-    // Inside a Krylov solve the environments do not change: their masks are computed once and kept (mpse_internal.h)
-    auto cacheable = [&](const void* p) {
-      if (!ctx->occ_cache_on) return false;
-      const char* c = reinterpret_cast<const char*>(p);
-      return (c >= ctx->occ_lo[0] && c < ctx->occ_hi[0]) || (c >= ctx->occ_lo[1] && c < ctx->occ_hi[1]);
-    };
+    // Inside a Krylov solve the environments do not change: their masks are computed once and kept (SolveScope)
+    auto cacheable = [&](const void* p) { return sc && sc->in_env(p); };
     auto make_key = [&](const void* p, const IdxMap& rm, const IdxMap& km, long long sb, int nrows, int tiles, int cplx) {
       mpse_ctx::OccKey k;
       memset(&k, 0, sizeof(k));
@@ -1419,13 +1415,11 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
       if (void* hit = find(kb)) bmk = static_cast<unsigned long long*>(hit), scan_b = false;
     }
     // B is a Krylov vector of a solve whose caller supplied the structural mask of the centre tensor: no scan
-    if (scan_b && ctx->cmask.ptr && d->batch == 1 && (long long)(wb * sizeof(unsigned long long)) == ctx->cmask.bytes) {
-      const char* pb_ = reinterpret_cast<const char*>(g.B);
-      if (pb_ >= ctx->cmask.lo && pb_ < ctx->cmask.hi) {
-        bmk = static_cast<unsigned long long*>(const_cast<void*>(ctx->cmask.ptr));
-        scan_b = false;
-        b_structural = true;
-      }
+    if (scan_b && sc && sc->in_krylov(g.B) && d->batch == 1 &&
+        (long long)(wb * sizeof(unsigned long long)) == sc->cmask.bytes) {
+      bmk = static_cast<unsigned long long*>(const_cast<void*>(sc->cmask.ptr));
+      scan_b = false;
+      b_structural = true;
     }
     mask_a_stable = !sa || ca_ok;
     mask_b_stable = !sb_ || cb_ok || b_structural;
@@ -1462,7 +1456,7 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
       OccOperand ob{g.B, g.nB, g.kB, g.N, scan_b ? g.mtiles_n : 0, cb ? 1 : 0, g.b_kfast, g.sbB, reinterpret_cast<unsigned char*>(bmk)};
       const int tmax = (scan_a ? g.mtiles_m : 0) > (scan_b ? g.mtiles_n : 0) ? (scan_a ? g.mtiles_m : 0) : (scan_b ? g.mtiles_n : 0);
       const dim3 og((nkt_all + 3) / 4, tmax, (unsigned)(2 * d->batch));
-      hipLaunchKernelGGL(k_tile_occ, og, dim3(256), 0, ctx->stream, oa, ob, g.K, g.nkw, (int)d->batch, ctx->skip_flag);
+      hipLaunchKernelGGL(k_tile_occ, og, dim3(256), 0, ctx->stream, oa, ob, g.K, g.nkw, (int)d->batch, skip);
     }
     g.amask = sa ? am : nullptr;
     g.bmask = sb_ ? bmk : nullptr;
@@ -1472,7 +1466,7 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
   if (d->batch == 1 && (g.amask || g.bmask) && ntile_all * g.ksplit > 2 * n_cu && ntile_all <= 2048) {
     // inside a Krylov solve both masks are the solve's (cached environment mask, structural centre mask): one sort
     // serves every matvec of the solve
-    const bool keep = ctx->occ_cache_on && mask_a_stable && mask_b_stable;
+    const bool keep = sc && sc->occ_cache && mask_a_stable && mask_b_stable;
     int* pp = nullptr;
     if (keep)
       for (const auto& e : ctx->perm_cache)
@@ -1489,7 +1483,7 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
         pp = PERM.as<int>();
       }
       hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, ctx->stream, g.amask, g.bmask, g.nkw, nkt_all, g.tiles_m,
-                         g.tiles_n, 1, pp, ctx->skip_flag, GemmGroups(), (unsigned char*)nullptr, 0);
+                         g.tiles_n, 1, pp, skip, GemmGroups(), (unsigned char*)nullptr, 0);
     }
     g.perm = pp;
   }
@@ -1549,8 +1543,8 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
 // Tile-occupancy flags of one operand (rows through `r`, K through `k`, both from `ptr`): from the cache of the
 // running Krylov solve, else scanned now - into the cache when the operand lies inside the solve's environment
 // ranges, into `tmp` otherwise.  flags[t * pitch + kt], 64 rows per tile t.
-int occ_mask_get(mpse_ctx* ctx, const void* ptr, int dtype, mpse_index r, mpse_index k, TmpBuf& tmp,
-                 const unsigned char** flags, int* pitch, bool* stable) {
+int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,
+                 TmpBuf& tmp, const unsigned char** flags, int* pitch, bool* stable) {
   IdxMap rm, km;
   if (!to_map(r, &rm) || !to_map(k, &km) || !is_single(km))
     return mpse_fail(ctx, MPSE_ERR_SHAPE, "occupancy scan: K index must be single level");
@@ -1564,9 +1558,7 @@ int occ_mask_get(mpse_ctx* ctx, const void* ptr, int dtype, mpse_index r, mpse_i
   key.r_ext = rm.ext, key.r_lo = rm.lo, key.r_shi = rm.s_hi, key.r_slo = rm.s_lo;
   key.k_ext = km.ext, key.k_lo = km.lo, key.k_shi = km.s_hi, key.k_slo = km.s_lo;
   key.sb = 0, key.nrows = nrows, key.tiles = tiles, key.nkw = nkw, key.batch = 1, key.K = K, key.cplx = cplx ? 1 : 0;
-  const char* c = reinterpret_cast<const char*>(ptr);
-  const bool cacheable = ctx->occ_cache_on && ((c >= ctx->occ_lo[0] && c < ctx->occ_hi[0]) ||
-                                               (c >= ctx->occ_lo[1] && c < ctx->occ_hi[1]));
+  const bool cacheable = sc && sc->in_env(ptr);
   *pitch = nkw * 8;
   *stable = cacheable;
   if (cacheable)
@@ -1587,14 +1579,16 @@ int occ_mask_get(mpse_ctx* ctx, const void* ptr, int dtype, mpse_index r, mpse_i
   OccOperand oa{static_cast<const double*>(ptr), rm, km, nrows, tiles, cplx ? 1 : 0, kfast, 0, static_cast<unsigned char*>(pm)};
   OccOperand ob = oa;
   ob.tiles = 0;
-  hipLaunchKernelGGL(k_tile_occ, dim3((nkt + 3) / 4, tiles, 2), dim3(256), 0, ctx->stream, oa, ob, K, nkw, 1, ctx->skip_flag);
+  hipLaunchKernelGGL(k_tile_occ, dim3((nkt + 3) / 4, tiles, 2), dim3(256), 0, ctx->stream, oa, ob, K, nkw, 1,
+                     sc ? sc->skip : nullptr);
   MPSE_HIP(ctx, hipGetLastError());
   *flags = static_cast<const unsigned char*>(pm);
   return MPSE_OK;
 }
 
 // Grouped launch of the contraction kernel (mpse_internal.h GroupedDesc; folded one-site matvec of mpse_plans.h).
-int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d) {
+// dot: the caller's dot request when this launch completes a matvec result (one group only), else null.
+int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, MatvecReq::Dot* dot) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   if (d.ngrp < 1 || d.ngrp > GMAX_GRP) return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: 1 .. %d groups", GMAX_GRP);
@@ -1627,7 +1621,7 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d) {
   g.b_kfast = fast(g.kB) <= fast(g.nB);
   g.alpha_re = 1.0, g.beta_re = 1.0;
   g.ksplit = 1;
-  g.skip = ctx->skip_flag;
+  g.skip = sc ? sc->skip : nullptr;
   g.skew = 1;
   g.trace = gemm_trace_ptr(ctx);
   GemmGroups& gg = g.gg;
@@ -1662,14 +1656,11 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d) {
   const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
   const long long ntile = (long long)g.tiles_m * g.tiles_n;
   if (ntile > 0x7fffffffLL) return mpse_fail(ctx, MPSE_ERR_SHAPE, "grouped product: grid too large");
-  // the caller's dot request (the launch that completes a matvec result): one group only
-  const bool want_dot = ctx->dot_now;
-  ctx->dot_now = false;
   const long long nwg = ntile * (d.split2 ? 2 : 1);
-  if (want_dot && d.ngrp == 1 && nwg >= 1 && nwg <= ctx->dot_req.cap) {
-    g.dot_y = static_cast<const double*>(ctx->dot_req.y);
-    g.dot_part = ctx->dot_req.part;
-    ctx->dot_req.nb_out = (int)nwg;
+  if (dot && d.ngrp == 1 && nwg >= 1 && nwg <= dot->cap) {
+    g.dot_y = static_cast<const double*>(dot->y);
+    g.dot_part = dot->part;
+    dot->nb_out = (int)nwg;
   }
   mpse_ctx::ProfRec rec;
   const int variant = (ca ? 1 : 0) + (cb ? 2 : 0);
@@ -1688,7 +1679,7 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d) {
     int* pp = nullptr;
     const void *ka = gg.g[0].seg[0].am, *kb = gg.g[0].seg[0].bm;
     const int nkt_key = nkt_max + 1000 * d.ngrp;       // (grouped entries never collide with plain ones)
-    const bool keep = ctx->occ_cache_on && d.masks_stable;
+    const bool keep = sc && sc->occ_cache && d.masks_stable;
     if (keep)
       for (const auto& e : ctx->perm_cache)
         if (e.amask == ka && e.bmask == kb && e.tiles_m == g.tiles_m && e.tiles_n == g.tiles_n && e.nkt == nkt_key)
@@ -1707,7 +1698,7 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d) {
       }
       hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long*)nullptr,
                          (const unsigned long long*)nullptr, 0, nkt_max, g.tiles_m, g.tiles_n, d.split2 ? 0 : 1, pp,
-                         ctx->skip_flag, gg, reinterpret_cast<unsigned char*>(pp) + perm_bytes, (int)flag_pitch);
+                         g.skip, gg, reinterpret_cast<unsigned char*>(pp) + perm_bytes, (int)flag_pitch);
     }
     g.perm = pp;
     g.gg.flags = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(pp) + perm_bytes);
@@ -1745,12 +1736,13 @@ extern "C" int mpse_gemm(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, 
     ctx->defer_ops[ctx->defer_recording].push_back([ctx, dc, A, B, C] { return mpse_gemm(ctx, &dc, A, B, C); });
     return MPSE_OK;
   }
-  return gemm_impl(ctx, d, A, B, C, d ? (d->skip_zero_tiles & 3) : 0);
+  return gemm_impl(ctx, d, A, B, C, d ? (d->skip_zero_tiles & 3) : 0, nullptr, nullptr);
 }
 
 int gemm_call(mpse_ctx* ctx, int dta, int dtb, int conja, int conjb, mpse_index ma, mpse_index ka, mpse_index kb,
               mpse_index nb, mpse_index mc, mpse_index nc, int64_t batch, int64_t sba, int64_t sbb, int64_t sbc,
-              const void* A, const void* B, void* C, double alpha, double beta, int skip_zero) {
+              const void* A, const void* B, void* C, double alpha, double beta, int skip_zero, const SolveScope* sc,
+              ProductReq* rq) {
   mpse_gemm_desc d;
   d.dtype_a = dta;
   d.dtype_b = dtb;
@@ -1771,7 +1763,7 @@ int gemm_call(mpse_ctx* ctx, int dta, int dtb, int conja, int conjb, mpse_index 
   d.beta_re = beta;
   d.beta_im = 0.0;
   d.skip_zero_tiles = skip_zero;
-  return gemm_impl(ctx, &d, A, B, C, skip_zero);
+  return gemm_impl(ctx, &d, A, B, C, skip_zero, sc, rq);
 }
 
 extern "C" int mpse_transpose_inner(mpse_ctx* ctx, int dtype, void* out, const void* in, int64_t d0, int64_t d1,

@@ -648,13 +648,16 @@ void heff0_drop_cache(mpse_ctx* ctx) {
   ctx->f0 = mpse_ctx::F0Cache();
 }
 
-// Runs the fused matvec when the caller offered masked parts (mpse_ctx::parts_req.masked_ok) with room for all of them.
-// w_host: the MPO site (wl, d, d, wr) of a one-site centre as the host knows it (mpse_mpo_site_hint), else null.
-int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, const double* w_host, bool* taken) {
+// Runs the fused matvec inside a solve when the caller offered masked parts (MatvecReq::Parts::masked_ok) with room
+// for all of them.  w_host: the MPO site (wl, d, d, wr) of a one-site centre as the host knows it
+// (mpse_mpo_site_hint), else null.
+int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, const double* w_host,
+                    const SolveScope* sc, MatvecReq* mv, bool* taken) {
   *taken = false;
-  mpse_ctx::PartsReq& pr = ctx->parts_req;
   const int nparts = heff0_fused_parts(h, dtype);
-  if (nparts == 0 || !pr.ptr || !pr.masked_ok) return MPSE_OK;
+  if (nparts == 0 || !mv || !mv->parts.ptr || !mv->parts.masked_ok) return MPSE_OK;
+  MatvecReq::Parts& pr = mv->parts;
+  MatvecReq::Dot* dot = mv->dot.y ? &mv->dot : nullptr;
   const int Dl = (int)h->dims.Dl_ket, Dr = (int)h->dims.Dr_ket, wl = (int)h->dims.wl, wr = (int)h->dims.wr;
   const int d = h->nsite == 1 ? (int)h->dims.d0 : 1;
   if (h->nsite == 1 && !w_host) return MPSE_OK;
@@ -662,7 +665,7 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
   if (pr.n != n || pr.cap_elems < (long long)nparts * n) return MPSE_OK;
   const int ntl = Dl / 16, ntr = Dr / 16, nkc = (Dr + 63) / 64;
   const int nwg = ntl * nparts;
-  if (ctx->dot_req.y && nwg * d > ctx->dot_req.cap) return MPSE_OK;
+  if (dot && nwg * d > dot->cap) return MPSE_OK;
   // the terms of every right channel: the non-zero entries W[b, x, e, f] (a bond matrix: the channel itself, factor 1)
   std::vector<F0Term> terms(size_t(wr) * F0_TMAX);
   std::vector<int> nterm(wr, 0);
@@ -687,8 +690,8 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
   {
     const long long nkw = (ntl + 7) / 8;
     const char* pc = static_cast<const char*>(C);
-    if (ctx->cmask.ptr && pc >= ctx->cmask.lo && pc < ctx->cmask.hi && ctx->cmask.bytes == (long long)d * nkc * nkw * 8) {
-      FC = static_cast<const unsigned char*>(ctx->cmask.ptr);
+    if (sc && sc->in_krylov(pc) && sc->cmask.bytes == (long long)d * nkc * nkw * 8) {
+      FC = static_cast<const unsigned char*>(sc->cmask.ptr);
       fc_pitch = (int)(nkw * 8);
     }
   }
@@ -707,8 +710,8 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
       for (int q = 0; q < nterm[f]; ++q) c += terms[size_t(f) * F0_TMAX + q].x == x;
       if (c > 4) compact = false;
     }
-  const bool keep = ctx->occ_cache_on || ctx->small_rt_scope;
-  if (!keep) return MPSE_OK;     // (outside a solve nothing would own the flags and the mask until the consumer has run)
+  if (!sc) return MPSE_OK;     // (outside a solve nothing would own the flags and the mask until the consumer has run)
+  const int* skip = sc->skip;
   mpse_ctx::F0Cache& fc = ctx->f0;
   char* base = nullptr;
   const bool hit = fc.buf && fc.L == h->L && fc.R == h->R && fc.W == h->W0 && fc.cmask == (const void*)FC && fc.Dl == Dl &&
@@ -740,18 +743,18 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
     hipLaunchKernelGGL(k_f0_prepare, dim3(ntl * wl + ntr * wr + nb), dim3(256), 0, ctx->stream,
                        static_cast<const double2*>(h->L), static_cast<const double2*>(h->R), reinterpret_cast<double2*>(base),
                        reinterpret_cast<unsigned char*>(base + o_fl), reinterpret_cast<unsigned char*>(base + o_fr), Dl, Dr, wl,
-                       wr, ntl, ntr, ctx->skip_flag);
+                       wr, ntl, ntr, skip);
     if (order_on)
       hipLaunchKernelGGL(k_f0_plan, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const unsigned char*>(base + o_fl), FC,
                          reinterpret_cast<const unsigned char*>(base + o_fr), reinterpret_cast<const F0Term*>(base + o_tm),
                          reinterpret_cast<const int*>(base + o_nt), wl, wr, d, ntl, ntr, nkc, fc_pitch,
                          reinterpret_cast<unsigned long long*>(base + o_mk), ctx->n_cu > 0 ? ctx->n_cu : 256,
-                         reinterpret_cast<F0Info*>(base + o_od), compact ? 1 : 0, ctx->skip_flag);
+                         reinterpret_cast<F0Info*>(base + o_od), compact ? 1 : 0, skip);
     else
       hipLaunchKernelGGL(k_f0_valid, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const unsigned char*>(base + o_fl), FC,
                          reinterpret_cast<const unsigned char*>(base + o_fr), reinterpret_cast<const F0Term*>(base + o_tm),
                          reinterpret_cast<const int*>(base + o_nt), wl, wr, d, ntl, ntr, nkc, fc_pitch,
-                         reinterpret_cast<unsigned long long*>(base + o_mk), ctx->skip_flag);
+                         reinterpret_cast<unsigned long long*>(base + o_mk), skip);
   }
   F0Args g{};
   g.L = static_cast<const double*>(h->L);
@@ -764,15 +767,15 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
   g.terms = reinterpret_cast<const F0Term*>(base + o_tm);
   g.nterm = reinterpret_cast<const int*>(base + o_nt);
   g.mask = reinterpret_cast<const unsigned long long*>(base + o_mk);
-  g.skip = ctx->skip_flag;
+  g.skip = skip;
   g.info = order_on ? reinterpret_cast<const F0Info*>(base + o_od) : nullptr;
   g.trace = ctx->prof_on ? ctx->gemm_trace : nullptr;
   g.n = n;
   g.Dl = Dl, g.Dr = Dr, g.wl = wl, g.wr = wr, g.d = d, g.ntl = ntl, g.ntr = ntr, g.nkc = nkc, g.fc_pitch = fc_pitch;
-  if (ctx->dot_req.y) {
-    g.y = static_cast<const double*>(ctx->dot_req.y);
-    g.dot_part = ctx->dot_req.part;
-    ctx->dot_req.nb_out = nwg * d;
+  if (dot) {
+    g.y = static_cast<const double*>(dot->y);
+    g.dot_part = dot->part;
+    dot->nb_out = nwg * d;
   }
   {
     // sampled HIP-event bracket (variant 7 of mpse_prof_get): algorithmic flops of SURVEY.md 8(d) for this matvec

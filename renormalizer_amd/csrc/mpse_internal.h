@@ -68,8 +68,8 @@ struct mpse_ctx {
   double* dscratch = nullptr;   // device scratch for reductions (1<<16 doubles); the last 8 hold flag words
   unsigned int flag_gen = 0;    // generation stamp of the Lanczos convergence flag (no per-check memset)
   // Tile-occupancy masks of operands that stay constant over one Krylov solve (the two environments): computed by
-  // the first matvec, reused by the others.  Active only inside mpse_expm_lanczos, for operands inside the ranges
-  // registered there.
+  // the first matvec, reused by the others.  Kept only for operands inside the environment ranges of the running
+  // Lanczos solve (SolveScope), and dropped at its end.
   struct OccKey {
     const void* ptr;
     long long r_ext, r_lo, r_shi, r_slo, k_ext, k_lo, k_shi, k_slo, sb;
@@ -79,9 +79,6 @@ struct mpse_ctx {
     OccKey key;
     void* mask;
   };
-  // Device word that turns every contraction launch into a no-op once it is non-zero: set for the duration of an
-  // asynchronous Lanczos solve, whose iterations are enqueued ahead of the convergence decision (mpse_vec.hip)
-  const int* skip_flag = nullptr;
   // Krylov dimension of the last solve per problem class (number of sites, vector length): how far to run ahead
   std::unordered_map<unsigned long long, int> lz_hint;
   // Block structure of MPO sites the caller has described (mpse_mpo_site_hint), by device pointer: large one-site
@@ -101,60 +98,17 @@ struct mpse_ctx {
   int defer_armed = -1;
   bool defer_hold = false;                  // guarded by pool_mu
   std::vector<void*> defer_frees;           // guarded by pool_mu
-  // Request to the contraction plan that produces a matvec result (mpse_heff_apply): also accumulate
-  // sum conj(result) . y, as per-workgroup partials at `part` (room for `cap` of them); nb_out = number written
-  // (0: the plan could not take it, the caller runs its own reduction)
-  struct DotReq {
-    const void* y = nullptr;
-    double* part = nullptr;
-    int cap = 0;
-    int nb_out = 0;
-  } dot_req;
-  bool dot_now = false;   // set by run_plan for the one GEMM launch that completes the result
-  // A plan step whose CONSUMER adds the K slices of a split product while it reads them (the elementwise MPO step of
-  // the small sites): the product leaves its raw slices at ptr (slice s at ptr + s * M * N elements, compact like C)
-  // and launches no reduction; `used` = number of slices (0: the product stored C as usual)
-  struct SlicesReq {
-    void* ptr = nullptr;
-    size_t cap_bytes = 0;
-    int used = 0;
-  } slices_req;
-  // A caller of mpse_heff_apply that can take the result as the SUM of several tensors (the Lanczos update adds them
-  // while it reads) offers a buffer of cap_elems elements of the working dtype, n of them per part: the last product
-  // of the plan may then leave its K slices there instead of reducing them (mpse_gemm.hip: split products, halved
-  // tiles).  used = number of parts written at ptr, ptr + n, .. (0: the result is complete in `out`, as usual).
-  struct PartsReq {
-    void* ptr = nullptr;
-    long long cap_elems = 0, n = 0;
-    int used = 0;
-    // The caller can also take parts that hold only SOME 16 x 16 tiles of the result (mpse_heff0.hip): the callee then
-    // sets `mask` (device; one 64-bit word per tile of the result viewed as a matrix with rows of mask_row elements,
-    // mask_tiles tiles per tile row: bit s = part s holds the tile) and the consumer adds exactly the parts named there
-    bool masked_ok = false;
-    const unsigned long long* mask = nullptr;
-    int mask_row = 0, mask_tiles = 0;
-  } parts_req;
   // Tile-occupancy mask of the centre tensor as operand B of the first products of a matvec, supplied by the caller
-  // (mpse_expm_centre_mask: the structural pattern of the quantum numbers, the same for every Krylov vector).
-  // `pending` holds what the caller set for the next solve; during that solve lo / hi delimit the Krylov vectors.
+  // (mpse_expm_centre_mask: the structural pattern of the quantum numbers, the same for every Krylov vector) for the
+  // next solve, which takes it over (SolveScope::cmask)
   struct CMask {
     const void* ptr = nullptr;
     long long bytes = 0;
-    const char* lo = nullptr;
-    const char* hi = nullptr;
-  } cmask_pending, cmask;
-  // beta source for the next GEMM call (consumed by it): C = A.B + beta * Cin(i, j) with Cin's own index maps
-  struct CinReq {
-    const void* ptr = nullptr;
-    mpse_index m{}, n{};
-  } cin_req;
+  } cmask_pending;
   // Debug: per-workgroup timeline of the contraction kernel (MPSE_GEMM_TRACE=<file>): every workgroup appends one
   // record (grid, K tiles multiplied, s_memtime stamps of its phases); mpse_prof_get writes the file.
   unsigned long long* gemm_trace = nullptr;   // [1 + GEMM_TRACE_CAP * GEMM_TRACE_WORDS] words: counter, then records
   bool gemm_trace_checked = false;
-  bool occ_cache_on = false;
-  const char* occ_lo[2] = {nullptr, nullptr};
-  const char* occ_hi[2] = {nullptr, nullptr};
   std::vector<OccEntry> occ_cache;
   // launch orders of block-sparse products (k_tile_order), kept like the masks they were computed from
   struct PermEntry {
@@ -169,7 +123,6 @@ struct mpse_ctx {
     void* rt = nullptr;
     size_t bytes = 0;
   } small_rt;
-  bool small_rt_scope = false;   // a solver without occupancy caches (Davidson) keeps the transposed copy as well
   // Per-solve data of the fused 0-site matvec (mpse_heff0.hip): transposed right environment, tile flags, part mask
   struct F0Cache {
     void* buf = nullptr;
@@ -283,28 +236,107 @@ static inline mpse_index idx2(int64_t hi_ext, int64_t lo_ext, int64_t s_hi, int6
   return mpse_index{hi_ext * lo_ext, lo_ext > 0 ? lo_ext : 1, s_hi, s_lo};
 }
 
-// One-launch matvec of small 0- / 1-site centres (mpse_small.hip); *taken says whether it ran (else: the plans)
-int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, bool* taken);
-void heff_small_drop_cache(mpse_ctx* ctx);
-// Fused 0-site matvec for large complex bond matrices (mpse_heff0.hip): number of parts it would deliver (0 = not
-// eligible), the attempt itself (needs mpse_ctx::parts_req.masked_ok), and the release of its per-solve data
-int heff0_fused_parts(const mpse_heff* h, int dtype);
-int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, const double* w_host, bool* taken);
-void heff0_drop_cache(mpse_ctx* ctx);
-struct SmallRtScope {   // for the duration of one eigensolve: the right environment does not change
-  mpse_ctx* c;
-  explicit SmallRtScope(mpse_ctx* ctx) : c(ctx) { c->small_rt_scope = true; }
-  ~SmallRtScope() {
-    c->small_rt_scope = false;
-    heff_small_drop_cache(c);
+// What a solver fixes for the length of one solve (the Lanczos drivers of mpse_vec.hip, Davidson), handed by pointer to
+// every matvec of it; null outside a solve.  The per-solve caches of the context (occ_cache, perm_cache, small_rt, f0)
+// are kept only while a solve runs: its end drops them.
+struct SolveScope {
+  mpse_ctx* ctx;
+  // device word that turns every contraction launch into a no-op once it is non-zero: the asynchronous Lanczos solve,
+  // whose iterations are enqueued ahead of the convergence decision
+  const int* skip = nullptr;
+  // Lanczos: the environments [env_lo, env_hi), constant over the solve - the tile-occupancy masks of operands inside
+  // them are scanned once and kept, and so are the launch orders built on such masks
+  bool occ_cache = false;
+  const char* env_lo[2] = {nullptr, nullptr};
+  const char* env_hi[2] = {nullptr, nullptr};
+  // the caller's structural mask of the centre (taken over from mpse_ctx::cmask_pending): it describes the operands
+  // inside the Krylov basis [krylov_lo, krylov_hi)
+  mpse_ctx::CMask cmask;
+  const char* krylov_lo = nullptr;
+  const char* krylov_hi = nullptr;
+
+  explicit SolveScope(mpse_ctx* c) : ctx(c) {}
+  SolveScope(const SolveScope&) = delete;
+  SolveScope& operator=(const SolveScope&) = delete;
+  ~SolveScope();
+  bool in_env(const void* p) const {
+    const char* c = static_cast<const char*>(p);
+    return occ_cache && ((c >= env_lo[0] && c < env_hi[0]) || (c >= env_lo[1] && c < env_hi[1]));
+  }
+  bool in_krylov(const void* p) const {
+    const char* c = static_cast<const char*>(p);
+    return cmask.ptr && c && c >= krylov_lo && c < krylov_hi;
   }
 };
+
+// One matvec's requests from its caller (the asynchronous Lanczos solve), and what the callee made of them
+struct MatvecReq {
+  // also accumulate sum conj(result) . y, as per-workgroup partials at `part` (room for `cap` of them); nb_out = number
+  // written (0: the matvec could not take it, the caller runs its own reduction)
+  struct Dot {
+    const void* y = nullptr;
+    double* part = nullptr;
+    int cap = 0;
+    int nb_out = 0;
+  } dot;
+  // The caller can take the result as the SUM of several tensors (the Lanczos update adds them while it reads): it
+  // offers a buffer of cap_elems elements of the working dtype, n of them per part.  The last product of the plan may
+  // then leave its K slices there instead of reducing them (mpse_gemm.hip: split products, halved tiles).  used =
+  // number of parts written at ptr, ptr + n, .. (0: the result is complete in `out`, as usual; -2: `out` and the
+  // second slot).
+  struct Parts {
+    void* ptr = nullptr;
+    long long cap_elems = 0, n = 0;
+    int used = 0;
+    // The caller can also take parts that hold only SOME 16 x 16 tiles of the result (mpse_heff0.hip): the callee then
+    // sets `mask` (device; one 64-bit word per tile of the result viewed as a matrix with rows of mask_row elements,
+    // mask_tiles tiles per tile row: bit s = part s holds the tile) and the consumer adds exactly the parts named there
+    bool masked_ok = false;
+    const unsigned long long* mask = nullptr;
+    int mask_row = 0, mask_tiles = 0;
+  } parts;
+};
+
+// What run_plan asks of one product beyond its descriptor (gemm_call; gemm_grouped takes the dot request alone)
+struct ProductReq {
+  MatvecReq::Dot* dot = nullptr;   // the product completes the matvec result: it carries the caller's dot request
+  // beta source: C = A.B + beta * Cin(i, j) with Cin's own index maps
+  const void* cin = nullptr;
+  mpse_index cin_m{}, cin_n{};
+  // the CONSUMER adds the K slices of a split product while it reads them (the elementwise MPO step of the small
+  // sites): the product leaves its raw slices at `slices` (slice s at slices + s * M * N elements, compact like C) and
+  // launches no reduction; slices_used = number of slices (0: the product stored C as usual)
+  void* slices = nullptr;
+  size_t slices_cap = 0;
+  int slices_used = 0;
+};
+
+// The matvec behind mpse_heff_apply, for a caller inside a solve (sc) and / or with requests (mv); both may be null
+int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+               MatvecReq* mv);
+// One-launch matvec of small 0- / 1-site centres (mpse_small.hip); *taken says whether it ran (else: the plans)
+int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+                   MatvecReq* mv, bool* taken);
+void heff_small_drop_cache(mpse_ctx* ctx);
+// Fused 0-site matvec for large complex bond matrices (mpse_heff0.hip): number of parts it would deliver (0 = not
+// eligible), the attempt itself (needs a solve and MatvecReq::Parts::masked_ok), and the release of its per-solve data
+int heff0_fused_parts(const mpse_heff* h, int dtype);
+int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, const double* w_host,
+                    const SolveScope* sc, MatvecReq* mv, bool* taken);
+void heff0_drop_cache(mpse_ctx* ctx);
+inline SolveScope::~SolveScope() {
+  for (auto& e : ctx->occ_cache) mpse_free(ctx, e.mask);
+  ctx->occ_cache.clear();
+  for (auto& e : ctx->perm_cache) mpse_free(ctx, e.perm);
+  ctx->perm_cache.clear();
+  heff_small_drop_cache(ctx);
+}
 
 // convenience wrapper over mpse_gemm used by the contraction entry points
 int gemm_call(mpse_ctx* ctx, int dta, int dtb, int conja, int conjb, mpse_index ma, mpse_index ka,
               mpse_index kb, mpse_index nb, mpse_index mc, mpse_index nc, int64_t batch, int64_t sba,
               int64_t sbb, int64_t sbc, const void* A, const void* B, void* C, double alpha = 1.0,
-              double beta = 0.0, int skip_zero = 0);
+              double beta = 0.0, int skip_zero = 0, const SolveScope* sc = nullptr, ProductReq* rq = nullptr);
 
 // Grouped launch of the contraction kernel (mpse_gemm.hip): up to 8 groups of equal height dividing the tile rows, each
 // with its own result C (same index maps) and up to 4 (A, B) operand pairs whose products are summed (+ beta C, beta 0
@@ -333,9 +365,9 @@ struct GroupedDesc {
   bool split2 = false;
   void* c2 = nullptr;
 };
-int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d);
-int occ_mask_get(mpse_ctx* ctx, const void* ptr, int dtype, mpse_index r, mpse_index k, TmpBuf& tmp,
-                 const unsigned char** flags, int* pitch, bool* stable);
+int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, MatvecReq::Dot* dot);
+int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,
+                 TmpBuf& tmp, const unsigned char** flags, int* pitch, bool* stable);
 
 // Low-latency read-back of a few device doubles: a one-wave kernel copies them into the mapped pinned buffer
 // and then publishes a sequence number; the host spins on that number instead of going through a copy-engine

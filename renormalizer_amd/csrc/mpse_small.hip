@@ -11,10 +11,10 @@
 // with plain FP64 vector FMAs (the FP64 vector and matrix peaks of this part are equal; the products here are a few
 // rows tall, far below an MFMA tile).  Rt[(f,k),l] = R[l,f,k] is a transposed copy of the right environment, made
 // once per Krylov solve (the environments are constant over a solve), so that the last step reads coalesced rows.
-// The partial sums of <result, y> that the Lanczos update needs ride on the same launch (mpse_ctx::dot_req), one
+// The partial sums of <result, y> that the Lanczos update needs ride on the same launch (MatvecReq::dot), one
 // (re, im) pair per workgroup in a fixed order: results are bitwise reproducible run to run.
 //
-// When the caller takes the result as a sum of parts (mpse_ctx::parts_req: the Lanczos update adds them while it reads),
+// When the caller takes the result as a sum of parts (MatvecReq::parts: the Lanczos update adds them while it reads),
 // the ket bond k of R is cut into up to four slices over blockIdx.y: a workgroup then works on the columns (e, k) of C and
 // the rows (f, k) of Rt of its slice only and writes its own partial result - four times the compute units, a quarter of
 // the bytes per workgroup (27 -> 11.5 us per matvec at D = 64 together with the prefetch pipeline).
@@ -409,7 +409,8 @@ void heff_small_drop_cache(mpse_ctx* ctx) {
   ctx->small_rt = mpse_ctx::SmallRt();
 }
 
-int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, bool* taken) {
+int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+                   MatvecReq* mv, bool* taken) {
   *taken = false;
   const mpse_dims& s = h->dims;
   if (h->nsite != 0 && h->nsite != 1) return MPSE_OK;
@@ -430,12 +431,12 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
   // Slices of the ket bond of R: when the caller takes the result as a sum of parts (the Lanczos update adds them while
   // it reads), a row of L is worked on by KH workgroups, each with 1 / KH of the centre's columns and of R - the launch
   // covers KH times as many compute units and every workgroup streams 1 / KH of the bytes
-  mpse_ctx::PartsReq& pr = ctx->parts_req;
+  const MatvecReq::Parts pr = mv ? mv->parts : MatvecReq::Parts();
+  MatvecReq::Dot* dot = mv && mv->dot.y ? &mv->dot : nullptr;
   int64_t KH = 1;
   if (pr.ptr && pr.n == Dl * d * Dr) {
     for (int64_t c : {4, 2}) {
-      if (Dr % c == 0 && Dr / c >= 16 && Dl * c <= 512 && pr.cap_elems >= c * pr.n &&
-          (!ctx->dot_req.y || Dl * c <= ctx->dot_req.cap)) {
+      if (Dr % c == 0 && Dr / c >= 16 && Dl * c <= 512 && pr.cap_elems >= c * pr.n && (!dot || Dl * c <= dot->cap)) {
         KH = c;
         break;
       }
@@ -464,11 +465,12 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
   const int64_t lds = csr_doubles * 8 + el * int64_t(es);
   if (lds + 256 > lds_limit_bytes()) return MPSE_OK;     // (+ the static words of the block reduction)
 
-  // transposed right environment: once per solve (the cache lives as long as the solve's occupancy caches)
+  // transposed right environment: once per solve (the cache lives as long as the solve's SolveScope)
   const size_t rbytes = size_t(Dr) * wr * Dr * es;
   TmpBuf rt_tmp(ctx);
   const double* rt = nullptr;
-  const bool keep = ctx->occ_cache_on || ctx->small_rt_scope;
+  const bool keep = sc != nullptr;
+  const int* skip = sc ? sc->skip : nullptr;
   if (keep && ctx->small_rt.src == h->R && ctx->small_rt.bytes == rbytes && ctx->small_rt.rt) {
     rt = static_cast<const double*>(ctx->small_rt.rt);
   } else {
@@ -488,10 +490,10 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
     if (nb > 1024) nb = 1024;
     if (cplx)
       hipLaunchKernelGGL((k_env_transpose<true>), dim3(nb), dim3(SM_THREADS), 0, ctx->stream, (double*)dst,
-                         (const double*)h->R, (int)Dr, (int)wr, ctx->skip_flag);
+                         (const double*)h->R, (int)Dr, (int)wr, skip);
     else
       hipLaunchKernelGGL((k_env_transpose<false>), dim3(nb), dim3(SM_THREADS), 0, ctx->stream, (double*)dst,
-                         (const double*)h->R, (int)Dr, (int)wr, ctx->skip_flag);
+                         (const double*)h->R, (int)Dr, (int)wr, skip);
     rt = static_cast<const double*>(dst);
   }
 
@@ -503,23 +505,23 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
   g.out = KH > 1 ? static_cast<double*>(pr.ptr) : static_cast<double*>(out);
   g.kh = (int)kh;
   g.part_stride = pr.n;
-  g.skip = ctx->skip_flag;
+  g.skip = skip;
   g.Dl = (int)Dl, g.Dr = (int)Dr, g.d = (int)d, g.wl = (int)wl, g.wr = (int)wr;
   g.kg = kg;
   g.off_L = (int)off_L, g.off_T1 = (int)off_T1, g.off_X = (int)off_X, g.off_red = 0;
   g.csr_pitch = (int)pitch;
   g.cnt_dbl = (int)cnt_dbl, g.idx_dbl = (int)idx_dbl, g.csr_dbl = (int)csr_doubles;
-  if (ctx->dot_req.y && Dl * KH <= ctx->dot_req.cap) {
-    g.y = static_cast<const double*>(ctx->dot_req.y);
-    g.part = ctx->dot_req.part;
-    ctx->dot_req.nb_out = (int)(Dl * KH);
+  if (dot && Dl * KH <= dot->cap) {
+    g.y = static_cast<const double*>(dot->y);
+    g.part = dot->part;
+    dot->nb_out = (int)(Dl * KH);
   }
   if (cplx)
     hipLaunchKernelGGL((k_heff_small<true>), dim3((unsigned)Dl, (unsigned)KH), dim3(SM_THREADS), (size_t)lds, ctx->stream, g);
   else
     hipLaunchKernelGGL((k_heff_small<false>), dim3((unsigned)Dl, (unsigned)KH), dim3(SM_THREADS), (size_t)lds, ctx->stream, g);
   MPSE_HIP(ctx, hipGetLastError());
-  pr.used = KH > 1 ? (int)KH : 0;
+  if (mv) mv->parts.used = KH > 1 ? (int)KH : 0;
   *taken = true;
   return MPSE_OK;
 }

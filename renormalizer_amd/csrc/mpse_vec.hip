@@ -550,7 +550,7 @@ int read_scalar2(mpse_ctx* ctx, const double* dsrc, double* a, double* b) {
 // ------------------------------------------------------------------------------------------------------------
 // Asynchronous solve: the host enqueues Lanczos iterations ahead of the convergence decision.  The small-matrix
 // exponential, the closeness test of successive estimates and the decision itself run on the device; once the
-// decision has fallen every later launch of the solve (contractions included, mpse_ctx::skip_flag) returns at once.
+// decision has fallen every later launch of the solve (contractions included, SolveScope::skip) returns at once.
 // The host waits once per solve (when its guess of the Krylov dimension, taken from the last solve of the same
 // problem class, was right), instead of twice per convergence check.
 struct LzCtl {
@@ -840,26 +840,15 @@ int dotc_sync(mpse_ctx* ctx, int dtype, const void* x, const void* y, int64_t n,
 
 namespace {
 
-// the environments are constant over a solve: their tile-occupancy masks are scanned once (mpse_gemm.hip)
-struct OccScope {
-  mpse_ctx* c;
-  OccScope(mpse_ctx* ctx, const mpse_heff* h) : c(ctx) {
-    const mpse_dims& s = h->dims;
-    const size_t lb = size_t(s.Dl_ket) * s.wl * s.Dl_ket * (h->l_dtype == MPSE_C128 ? 16 : 8);
-    const size_t rb = size_t(s.Dr_ket) * s.wr * s.Dr_ket * (h->r_dtype == MPSE_C128 ? 16 : 8);
-    c->occ_lo[0] = static_cast<const char*>(h->L), c->occ_hi[0] = c->occ_lo[0] + lb;
-    c->occ_lo[1] = static_cast<const char*>(h->R), c->occ_hi[1] = c->occ_lo[1] + rb;
-    c->occ_cache_on = true;
-  }
-  ~OccScope() {
-    c->occ_cache_on = false;
-    for (auto& e : c->occ_cache) mpse_free(c, e.mask);
-    c->occ_cache.clear();
-    for (auto& e : c->perm_cache) mpse_free(c, e.perm);
-    c->perm_cache.clear();
-    heff_small_drop_cache(c);
-  }
-};
+// the environments are constant over a Lanczos solve: their tile-occupancy masks are scanned once (mpse_gemm.hip)
+void keep_env_masks(SolveScope& sc, const mpse_heff* h) {
+  const mpse_dims& s = h->dims;
+  const size_t lb = size_t(s.Dl_ket) * s.wl * s.Dl_ket * (h->l_dtype == MPSE_C128 ? 16 : 8);
+  const size_t rb = size_t(s.Dr_ket) * s.wr * s.Dr_ket * (h->r_dtype == MPSE_C128 ? 16 : 8);
+  sc.env_lo[0] = static_cast<const char*>(h->L), sc.env_hi[0] = sc.env_lo[0] + lb;
+  sc.env_lo[1] = static_cast<const char*>(h->R), sc.env_hi[1] = sc.env_lo[1] + rb;
+  sc.occ_cache = true;
+}
 
 constexpr int LZ_FALLBACK = -77;   // internal: the asynchronous solve hands the problem to the synchronous one
 
@@ -884,7 +873,7 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
   if (cap > limit + 1) cap = limit + 1;
   TmpBuf V(ctx), W(ctx), RES(ctx), SCAL(ctx);
   MPSE_TRY(V.alloc(size_t(cap) * n * es));
-  // the matvec result, with room for a second part (mpse_ctx::parts_req: halved tiles)
+  // the matvec result, with room for a second part (MatvecReq::parts: halved tiles)
   long long wcap = (n <= 65536 ? 4 : 2) * n;   // (small centres: up to four slices, mpse_small.hip)
   const int f0_parts = (cplx && (reinterpret_cast<uintptr_t>(Cin) & 15) == 0) ? heff0_fused_parts(h, dtype) : 0;
   if ((long long)f0_parts * n > wcap) wcap = (long long)f0_parts * n;   // tile-masked parts of the fused 0-site matvec
@@ -908,20 +897,11 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
   const double vbytes = double(n) * double(es);
   auto vec = [&](int j) { return V.as<char>() + size_t(j) * n * es; };
 
-  struct SkipScope {
-    mpse_ctx* c;
-    SkipScope(mpse_ctx* ctx, const int* f) : c(ctx) { c->skip_flag = f; }
-    ~SkipScope() { c->skip_flag = nullptr; }
-  } skip_scope(ctx, done);
-  OccScope occ_scope(ctx, h);
-  struct CMaskScope {   // the caller's structural mask applies to the Krylov vectors of THIS solve only
-    mpse_ctx* c;
-    CMaskScope(mpse_ctx* ctx) : c(ctx) {
-      c->cmask = c->cmask_pending;
-      c->cmask_pending = mpse_ctx::CMask();
-    }
-    ~CMaskScope() { c->cmask = mpse_ctx::CMask(); }
-  } cmask_scope(ctx);
+  SolveScope scope(ctx);
+  scope.skip = done;
+  keep_env_masks(scope, h);
+  scope.cmask = ctx->cmask_pending;   // the caller's structural mask applies to the Krylov vectors of THIS solve only
+  ctx->cmask_pending = mpse_ctx::CMask();
 
   // the structural mask of the centre also serves the vector kernels of this solve (square operators on complex vectors
   // whose rows are whole multiples of 64 elements)
@@ -931,12 +911,12 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
     const char* e = getenv("MPSE_VEC_MASK");
     return !(e && e[0] == '0');
   }();
-  if (vmask_on && vec16 && cplx && ctx->cmask.ptr && h->dims.Dl_ket > 0 && h->dims.Dl_bra == h->dims.Dl_ket &&
+  if (vmask_on && vec16 && cplx && scope.cmask.ptr && h->dims.Dl_ket > 0 && h->dims.Dl_bra == h->dims.Dl_ket &&
       h->dims.Dr_bra == h->dims.Dr_ket && n < (int64_t(1) << 31)) {
     const int64_t Dl = h->dims.Dl_ket, N = n / Dl;
     const int64_t nkw = ((Dl + 15) / 16 + 7) / 8;
-    if (N * Dl == n && N % 64 == 0 && ctx->cmask.bytes == (N / 64) * nkw * 8) {
-      vmask = static_cast<const unsigned char*>(ctx->cmask.ptr);
+    if (N * Dl == n && N % 64 == 0 && scope.cmask.bytes == (N / 64) * nkw * 8) {
+      vmask = static_cast<const unsigned char*>(scope.cmask.ptr);
       vm_row = (int)N;
       vm_kw = (int)(nkw * 8);
     }
@@ -985,33 +965,28 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
   LzCtl hc;
   memset(&hc, 0, sizeof(hc));
   for (int j = 0;; ++j) {
-    // <H U_j, U_j> rides on the launch that completes H U_j (mpse_ctx::dot_req); plans that cannot take it leave
-    // nb_out = 0 and the reduction runs as a pass of its own
-    ctx->dot_req.y = vec(j);
-    ctx->dot_req.part = part_a;
-    ctx->dot_req.cap = DOT_CAP;
-    ctx->dot_req.nb_out = 0;
-    ctx->cmask.lo = V.as<char>();
-    ctx->cmask.hi = V.as<char>() + size_t(cap) * n * es;
+    scope.krylov_lo = V.as<char>();   // (V moves when it grows)
+    scope.krylov_hi = V.as<char>() + size_t(cap) * n * es;
+    MatvecReq mv;
+    // <H U_j, U_j> rides on the launch that completes H U_j; matvecs that cannot take it leave nb_out = 0 and the
+    // reduction runs as a pass of its own
+    mv.dot.y = vec(j);
+    mv.dot.part = part_a;
+    mv.dot.cap = DOT_CAP;
     // the result may come as W + W2 (the update below reads both): the last product of a large one-site matvec then
     // runs as halved tiles, two workgroups per compute unit
-    ctx->parts_req.ptr = W.p;
-    ctx->parts_req.cap_elems = wcap;
-    ctx->parts_req.n = n;
-    ctx->parts_req.used = 0;
-    ctx->parts_req.masked_ok = f0_parts > 0 && vec16;
-    const int st_mv = mpse_heff_apply(ctx, dtype, h, vec(j), W.p);
-    const unsigned long long* pmask = ctx->parts_req.mask;
-    const int prow = ctx->parts_req.mask_row, ptiles = ctx->parts_req.mask_tiles;
-    const int used = ctx->parts_req.used;
+    mv.parts.ptr = W.p;
+    mv.parts.cap_elems = wcap;
+    mv.parts.n = n;
+    mv.parts.masked_ok = f0_parts > 0 && vec16;
+    MPSE_TRY(heff_apply(ctx, dtype, h, vec(j), W.p, &scope, &mv));
+    const unsigned long long* pmask = mv.parts.mask;
+    const int prow = mv.parts.mask_row, ptiles = mv.parts.mask_tiles;
+    const int used = mv.parts.used;
     const int nparts = used > 0 ? used : (used == -2 ? 2 : 1);
     const bool two = nparts > 1;
-    ctx->parts_req = mpse_ctx::PartsReq();
-    const bool dot_done = ctx->dot_req.nb_out > 0;
-    const int a_nb = dot_done ? ctx->dot_req.nb_out : nb;
-    ctx->dot_req = mpse_ctx::DotReq();
-    ctx->dot_now = false;
-    MPSE_TRY(st_mv);
+    const bool dot_done = mv.dot.nb_out > 0;
+    const int a_nb = dot_done ? mv.dot.nb_out : nb;
     if (!dot_done) {
       if (two) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: a two-part matvec result without its dot partials");
       dot_partials(W.p, vec(j), part_a);
@@ -1262,7 +1237,6 @@ int mpse_expm_lanczos(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re
   // of a bond factor) are issued here, before control goes back to the host language
   const int st = expm_lanczos_solve(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec);
   ctx->cmask_pending = mpse_ctx::CMask();   // a mask is good for the solve it was set for, whatever path that took
-  ctx->cmask = mpse_ctx::CMask();
   return defer_replay(ctx, st);
 }
 
@@ -1388,9 +1362,10 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
     return -1;
   };
 
-  OccScope occ_scope(ctx, h);
+  SolveScope scope(ctx);
+  keep_env_masks(scope, h);
   for (int j = 0;; ++j) {
-    MPSE_TRY(mpse_heff_apply(ctx, dtype, h, vec(j), W.p));
+    MPSE_TRY(heff_apply(ctx, dtype, h, vec(j), W.p, &scope, nullptr));
     dot_partials(W.p, vec(j), part_a);                             // alpha_j = Re <w, v_j> (partials)
     if (j == n - 1) {                                              // Krylov space == full space (krylov.py:59-61)
       hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(RED_THREADS), 0, ctx->stream, part_a, nb, scal + 4 + 4 * j,
