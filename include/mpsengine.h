@@ -282,6 +282,17 @@ int mpse_expm_centre_mask(mpse_ctx* ctx, const void* mask_dev, int64_t nbytes);
 
 int mpse_expm_lanczos(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im,
                       const void* C, void* out, double rtol, double atol, int max_dim, int* nvec);
+/* out[i] = expm(dt * Heff_i) C[i] for count independent members: h, C, out, nvec are arrays of count entries (C / out
+ * hold device pointers).  Every member's result and Krylov dimension are bitwise what mpse_expm_lanczos gives for it
+ * alone.  Members with equal (nsite, dims, dtypes) whose matvec takes the small-centre path and whose centre has more
+ * than 256 elements are solved together, up to 64 per launch set; every other member runs through mpse_expm_lanczos,
+ * one after another.  A pending mpse_expm_centre_mask is left for the next mpse_expm_lanczos.  On an error the status is
+ * that of the first failing member, named in mpse_last_error; the outputs are then unspecified.  Synchronous. */
+int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff* h, double dt_re, double dt_im,
+                            const void* const* C, void* const* out, double rtol, double atol, int max_dim, int* nvec);
+/* Cumulative counts of members solved by the batched kernels and of members that went through the single solve
+ * (grouping, size, need_host, 64-vector limit).  Diagnostics for tests; either pointer may be NULL. */
+int mpse_expm_lanczos_batch_stats(mpse_ctx* ctx, int64_t* batched_members, int64_t* single_members);
 
 /* Davidson eigensolver for the lowest nroots eigenpairs of the effective Hamiltonian, replaces
  * lib/davidson/davidson.py:154-441 as called at mps/gs.py:533-538 (diagonal preconditioner r / (hdiag - e + shift),

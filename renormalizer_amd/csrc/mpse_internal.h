@@ -139,6 +139,8 @@ struct mpse_ctx {
   // four device words of the block QR: [0] sticky breakdown flag of the optimistic mode, [2] blocks factorised by the
   // Cholesky-QR kernels, [3] of them finished after two passes (mpse_block_qr_pass_stats); allocated by qr_words()
   int* qr_words_dev = nullptr;
+  // mpse_expm_lanczos_batch: members solved by the batched kernels / through the single solve (mpse_expm_lanczos_batch_stats)
+  long long lz_batch_members = 0, lz_batch_single = 0;
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 
@@ -318,6 +320,33 @@ int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void
 int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
                    MatvecReq* mv, bool* taken);
 void heff_small_drop_cache(mpse_ctx* ctx);
+
+// Batched small-centre Krylov solves (mpse_expm_lanczos_batch, mpse_vec.hip): what differs between the members of one
+// launch set beyond their slab (vectors, scalars, partials and control block at member-0 addresses + m * mstride bytes)
+struct BatchMember {
+  const void* L;    // environments and MPO site of the member's effective Hamiltonian
+  const void* R;
+  const void* W;
+  void* Rt;         // its transposed right environment (mpse_small.hip)
+  const void* C;    // start vector
+  void* out;        // result
+};
+template <class T>
+__host__ __device__ inline T* member_ptr(T* p, unsigned m, long long mstride) {
+  return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + uintptr_t(m) * uintptr_t(mstride)) : p;
+}
+// The plan of the one-launch matvec for the request of the asynchronous Lanczos solve (result parts of up to 4 n
+// elements, dot_cap partials): false when h does not take that path with its dot request; else the bytes of a transposed
+// right environment, the number of result parts and the dot partials the launch writes
+bool heff_small_batch_plan(const mpse_heff* h, int dtype, int64_t n, int dot_cap, size_t* rt_bytes, int* nparts,
+                           int* nb_dot);
+// B transposed right environments (mem[m].R -> mem[m].Rt) in one launch; member m is skipped while its word is set
+int heff_small_batch_rt(mpse_ctx* ctx, int dtype, const mpse_heff* h, int B, const BatchMember* mem, const int* skip0,
+                        long long mstride);
+// H_m C_m for B members with the shape of h in one launch: result parts at parts0, <H C, C> partials at dot_part0
+int heff_small_batch_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, int B, const BatchMember* mem,
+                           const void* C0, void* parts0, int64_t n, double* dot_part0, int dot_cap, const int* skip0,
+                           long long mstride);
 // Fused 0-site matvec for large complex bond matrices (mpse_heff0.hip): number of parts it would deliver (0 = not
 // eligible), the attempt itself (needs a solve and MatvecReq::Parts::masked_ok), and the release of its per-solve data
 int heff0_fused_parts(const mpse_heff* h, int dtype);

@@ -89,8 +89,8 @@ struct Elem<false> {
 
 // Rt[(f, k), l] = R[l, f, k]
 template <bool CPLX>
-__global__ __launch_bounds__(SM_THREADS) void k_env_transpose(double* __restrict__ rt, const double* __restrict__ r, int D,
-                                                               int w, const int* __restrict__ skip) {
+__device__ __forceinline__ void env_transpose(double* __restrict__ rt, const double* __restrict__ r, int D, int w,
+                                              const int* __restrict__ skip) {
   using E = Elem<CPLX>;
   using T = typename E::T;
   if (skip && *skip) return;
@@ -101,6 +101,19 @@ __global__ __launch_bounds__(SM_THREADS) void k_env_transpose(double* __restrict
     const long long fk = i / D;       // f * D + k
     reinterpret_cast<T*>(rt)[i] = reinterpret_cast<const T*>(r)[(long long)l * w * D + fk];
   }
+}
+template <bool CPLX>
+__global__ __launch_bounds__(SM_THREADS) void k_env_transpose(double* __restrict__ rt, const double* __restrict__ r, int D,
+                                                               int w, const int* __restrict__ skip) {
+  env_transpose<CPLX>(rt, r, D, w, skip);
+}
+// the transposed right environments of a batched solve (mpse_expm_lanczos_batch): member blockIdx.z
+template <bool CPLX>
+__global__ __launch_bounds__(SM_THREADS) void k_env_transpose_b(const BatchMember* __restrict__ mem, int D, int w,
+                                                                 const int* __restrict__ skip0, long long mstride) {
+  const BatchMember mb = mem[blockIdx.z];
+  env_transpose<CPLX>(static_cast<double*>(mb.Rt), static_cast<const double*>(mb.R), D, w,
+                      member_ptr(skip0, blockIdx.z, mstride));
 }
 
 constexpr int SM_U = 8;   // loads in flight per column and lane
@@ -247,7 +260,7 @@ __device__ __forceinline__ void small_t3(const typename Elem<CPLX>::T* __restric
 }
 
 template <bool CPLX>
-__global__ __launch_bounds__(SM_THREADS) void k_heff_small(const SmallArgs g) {
+__device__ __forceinline__ void heff_small_body(const SmallArgs& g) {
   using E = Elem<CPLX>;
   using T = typename E::T;
   if (g.skip && *g.skip) return;
@@ -380,6 +393,28 @@ __global__ __launch_bounds__(SM_THREADS) void k_heff_small(const SmallArgs g) {
     }
   }
 }
+template <bool CPLX>
+__global__ __launch_bounds__(SM_THREADS) void k_heff_small(const SmallArgs g) {
+  heff_small_body<CPLX>(g);
+}
+// Batched form (mpse_expm_lanczos_batch): member blockIdx.z, with its own environments and W from the member table and
+// its vectors, partials and skip word at member-0 addresses + blockIdx.z * mstride bytes
+template <bool CPLX>
+__global__ __launch_bounds__(SM_THREADS) void k_heff_small_b(const SmallArgs g0, const BatchMember* __restrict__ mem,
+                                                              long long mstride) {
+  const unsigned m = blockIdx.z;
+  const BatchMember mb = mem[m];
+  SmallArgs g = g0;
+  g.L = static_cast<const double*>(mb.L);
+  g.Rt = static_cast<const double*>(mb.Rt);
+  g.W = g0.W ? static_cast<const double*>(mb.W) : nullptr;
+  g.C = member_ptr(g0.C, m, mstride);
+  g.out = member_ptr(g0.out, m, mstride);
+  g.y = member_ptr(g0.y, m, mstride);
+  g.part = member_ptr(g0.part, m, mstride);
+  g.skip = member_ptr(g0.skip, m, mstride);
+  heff_small_body<CPLX>(g);
+}
 
 // largest centre (elements) that takes this path; MPSE_SMALL=0 switches it off, MPSE_SMALL=<n> moves the limit
 long long small_limit() {
@@ -401,38 +436,33 @@ int lds_limit_bytes() {
   return v;
 }
 
-}  // namespace
-
-void heff_small_drop_cache(mpse_ctx* ctx) {
-  heff0_drop_cache(ctx);       // (the fused 0-site matvec keeps its per-solve data for the same span)
-  if (ctx->small_rt.rt) mpse_free(ctx, ctx->small_rt.rt);
-  ctx->small_rt = mpse_ctx::SmallRt();
-}
-
-int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
-                   MatvecReq* mv, bool* taken) {
-  *taken = false;
+// Launch plan of one small matvec: eligibility, slices of the ket bond, K groups, LDS layout, sparse-W sizes.  The
+// single matvec and the batched solve both take it from here, so a member of a batch runs exactly the launch its
+// single solve would.  False: the matvec does not take this path.
+struct SmallPlan {
+  int64_t Dl, Dr, d, wl, wr, KH, kh, lds;
+  bool has_w;
+  SmallArgs g;     // every field but the operand pointers, the skip word and the dot request
+};
+bool small_plan(const mpse_heff* h, int dtype, const MatvecReq::Parts& pr, const MatvecReq::Dot* dot, SmallPlan* p) {
   const mpse_dims& s = h->dims;
-  if (h->nsite != 0 && h->nsite != 1) return MPSE_OK;
+  if (h->nsite != 0 && h->nsite != 1) return false;
   const long long lim = small_limit();
-  if (lim <= 0) return MPSE_OK;
+  if (lim <= 0) return false;
   const int64_t Dl = s.Dl_ket, Dr = s.Dr_ket, wl = s.wl, wr = s.wr;
   const int64_t d = h->nsite == 1 ? s.d0 : 1;
-  if ((s.Dl_bra > 0 && s.Dl_bra != Dl) || (s.Dr_bra > 0 && s.Dr_bra != Dr) || s.danc > 1) return MPSE_OK;
-  if (h->l_dtype != dtype || h->r_dtype != dtype) return MPSE_OK;
-  if (h->nsite == 1 && (!h->W0 || h->w_dtype != MPSE_F64)) return MPSE_OK;
-  if (h->nsite == 0 && wl != wr) return MPSE_OK;
+  if ((s.Dl_bra > 0 && s.Dl_bra != Dl) || (s.Dr_bra > 0 && s.Dr_bra != Dr) || s.danc > 1) return false;
+  if (h->l_dtype != dtype || h->r_dtype != dtype) return false;
+  if (h->nsite == 1 && (!h->W0 || h->w_dtype != MPSE_F64)) return false;
+  if (h->nsite == 0 && wl != wr) return false;
   if (Dl < 1 || Dr < 1 || Dl > 4096 || Dr > SM_THREADS || wl < 1 || wr < 1 || wl > SM_WMAX || wr > SM_WMAX || d < 1 ||
       d > SM_DMAX)
-    return MPSE_OK;
-  if (Dl * d * Dr > lim) return MPSE_OK;
-  const bool cplx = dtype == MPSE_C128;
+    return false;
+  if (Dl * d * Dr > lim) return false;
   const size_t es = dtype_size(dtype);
   // Slices of the ket bond of R: when the caller takes the result as a sum of parts (the Lanczos update adds them while
   // it reads), a row of L is worked on by KH workgroups, each with 1 / KH of the centre's columns and of R - the launch
   // covers KH times as many compute units and every workgroup streams 1 / KH of the bytes
-  const MatvecReq::Parts pr = mv ? mv->parts : MatvecReq::Parts();
-  MatvecReq::Dot* dot = mv && mv->dot.y ? &mv->dot : nullptr;
   int64_t KH = 1;
   if (pr.ptr && pr.n == Dl * d * Dr) {
     for (int64_t c : {4, 2}) {
@@ -463,7 +493,55 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
   const int64_t red_len = G * d * Dr;
   const int64_t el = std::max<int64_t>(off_X + x_len, red_len);
   const int64_t lds = csr_doubles * 8 + el * int64_t(es);
-  if (lds + 256 > lds_limit_bytes()) return MPSE_OK;     // (+ the static words of the block reduction)
+  if (lds + 256 > lds_limit_bytes()) return false;     // (+ the static words of the block reduction)
+
+  p->Dl = Dl, p->Dr = Dr, p->d = d, p->wl = wl, p->wr = wr, p->KH = KH, p->kh = kh, p->lds = lds, p->has_w = has_w;
+  SmallArgs& g = p->g;
+  g = SmallArgs{};
+  g.kh = (int)kh;
+  g.part_stride = pr.n;
+  g.Dl = (int)Dl, g.Dr = (int)Dr, g.d = (int)d, g.wl = (int)wl, g.wr = (int)wr;
+  g.kg = kg;
+  g.off_L = (int)off_L, g.off_T1 = (int)off_T1, g.off_X = (int)off_X, g.off_red = 0;
+  g.csr_pitch = (int)pitch;
+  g.cnt_dbl = (int)cnt_dbl, g.idx_dbl = (int)idx_dbl, g.csr_dbl = (int)csr_doubles;
+  return true;
+}
+
+int env_transpose_blocks(int64_t Dr, int64_t wr) {
+  const long long n = (long long)Dr * wr * Dr;
+  int nb = int((n + SM_THREADS - 1) / SM_THREADS);
+  if (nb > 1024) nb = 1024;
+  return nb;
+}
+
+// the request of the asynchronous Lanczos solve (expm_lanczos_async: result parts of 4 n elements, 4096 dot partials)
+MatvecReq::Parts lanczos_parts(int64_t n) {
+  MatvecReq::Parts pr;
+  pr.ptr = reinterpret_cast<void*>(uintptr_t(256));   // (any non-null address: the plan only asks whether there are parts)
+  pr.cap_elems = 4 * n;
+  pr.n = n;
+  return pr;
+}
+
+}  // namespace
+
+void heff_small_drop_cache(mpse_ctx* ctx) {
+  heff0_drop_cache(ctx);       // (the fused 0-site matvec keeps its per-solve data for the same span)
+  if (ctx->small_rt.rt) mpse_free(ctx, ctx->small_rt.rt);
+  ctx->small_rt = mpse_ctx::SmallRt();
+}
+
+int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+                   MatvecReq* mv, bool* taken) {
+  *taken = false;
+  const MatvecReq::Parts pr = mv ? mv->parts : MatvecReq::Parts();
+  MatvecReq::Dot* dot = mv && mv->dot.y ? &mv->dot : nullptr;
+  SmallPlan p;
+  if (!small_plan(h, dtype, pr, dot, &p)) return MPSE_OK;
+  const int64_t Dl = p.Dl, Dr = p.Dr, wr = p.wr, KH = p.KH;
+  const bool cplx = dtype == MPSE_C128;
+  const size_t es = dtype_size(dtype);
 
   // transposed right environment: once per solve (the cache lives as long as the solve's SolveScope)
   const size_t rbytes = size_t(Dr) * wr * Dr * es;
@@ -485,9 +563,7 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
       MPSE_TRY(rt_tmp.alloc(rbytes));
       dst = rt_tmp.p;
     }
-    const long long n = (long long)Dr * wr * Dr;
-    int nb = int((n + SM_THREADS - 1) / SM_THREADS);
-    if (nb > 1024) nb = 1024;
+    const int nb = env_transpose_blocks(Dr, wr);
     if (cplx)
       hipLaunchKernelGGL((k_env_transpose<true>), dim3(nb), dim3(SM_THREADS), 0, ctx->stream, (double*)dst,
                          (const double*)h->R, (int)Dr, (int)wr, skip);
@@ -497,31 +573,76 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
     rt = static_cast<const double*>(dst);
   }
 
-  SmallArgs g{};
+  SmallArgs g = p.g;
   g.L = static_cast<const double*>(h->L);
   g.Rt = rt;
-  g.W = has_w ? static_cast<const double*>(h->W0) : nullptr;
+  g.W = p.has_w ? static_cast<const double*>(h->W0) : nullptr;
   g.C = static_cast<const double*>(C);
   g.out = KH > 1 ? static_cast<double*>(pr.ptr) : static_cast<double*>(out);
-  g.kh = (int)kh;
-  g.part_stride = pr.n;
   g.skip = skip;
-  g.Dl = (int)Dl, g.Dr = (int)Dr, g.d = (int)d, g.wl = (int)wl, g.wr = (int)wr;
-  g.kg = kg;
-  g.off_L = (int)off_L, g.off_T1 = (int)off_T1, g.off_X = (int)off_X, g.off_red = 0;
-  g.csr_pitch = (int)pitch;
-  g.cnt_dbl = (int)cnt_dbl, g.idx_dbl = (int)idx_dbl, g.csr_dbl = (int)csr_doubles;
   if (dot && Dl * KH <= dot->cap) {
     g.y = static_cast<const double*>(dot->y);
     g.part = dot->part;
     dot->nb_out = (int)(Dl * KH);
   }
   if (cplx)
-    hipLaunchKernelGGL((k_heff_small<true>), dim3((unsigned)Dl, (unsigned)KH), dim3(SM_THREADS), (size_t)lds, ctx->stream, g);
+    hipLaunchKernelGGL((k_heff_small<true>), dim3((unsigned)Dl, (unsigned)KH), dim3(SM_THREADS), (size_t)p.lds, ctx->stream, g);
   else
-    hipLaunchKernelGGL((k_heff_small<false>), dim3((unsigned)Dl, (unsigned)KH), dim3(SM_THREADS), (size_t)lds, ctx->stream, g);
+    hipLaunchKernelGGL((k_heff_small<false>), dim3((unsigned)Dl, (unsigned)KH), dim3(SM_THREADS), (size_t)p.lds, ctx->stream, g);
   MPSE_HIP(ctx, hipGetLastError());
   if (mv) mv->parts.used = KH > 1 ? (int)KH : 0;
   *taken = true;
+  return MPSE_OK;
+}
+
+bool heff_small_batch_plan(const mpse_heff* h, int dtype, int64_t n, int dot_cap, size_t* rt_bytes, int* nparts,
+                           int* nb_dot) {
+  const MatvecReq::Parts pr = lanczos_parts(n);
+  MatvecReq::Dot dot;
+  dot.cap = dot_cap;
+  SmallPlan p;
+  if (!small_plan(h, dtype, pr, &dot, &p)) return false;
+  if (p.Dl * p.KH > dot_cap) return false;     // (the single solve would reduce <H U_j, U_j> in a pass of its own)
+  *rt_bytes = size_t(p.Dr) * p.wr * p.Dr * dtype_size(dtype);
+  *nparts = p.KH > 1 ? (int)p.KH : 1;
+  *nb_dot = (int)(p.Dl * p.KH);
+  return true;
+}
+
+int heff_small_batch_rt(mpse_ctx* ctx, int dtype, const mpse_heff* h, int B, const BatchMember* mem,
+                        const int* skip0, long long mstride) {
+  const int64_t Dr = h->dims.Dr_ket, wr = h->dims.wr;
+  const dim3 grid((unsigned)env_transpose_blocks(Dr, wr), 1, (unsigned)B);
+  if (dtype == MPSE_C128)
+    hipLaunchKernelGGL((k_env_transpose_b<true>), grid, dim3(SM_THREADS), 0, ctx->stream, mem, (int)Dr, (int)wr, skip0,
+                       mstride);
+  else
+    hipLaunchKernelGGL((k_env_transpose_b<false>), grid, dim3(SM_THREADS), 0, ctx->stream, mem, (int)Dr, (int)wr, skip0,
+                       mstride);
+  MPSE_HIP(ctx, hipGetLastError());
+  return MPSE_OK;
+}
+
+int heff_small_batch_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, int B, const BatchMember* mem,
+                           const void* C0, void* parts0, int64_t n, double* dot_part0, int dot_cap, const int* skip0,
+                           long long mstride) {
+  const MatvecReq::Parts pr = lanczos_parts(n);
+  MatvecReq::Dot dot;
+  dot.cap = dot_cap;
+  SmallPlan p;
+  if (!small_plan(h, dtype, pr, &dot, &p)) return mpse_fail(ctx, MPSE_ERR_ARG, "heff_small_batch: not a small centre");
+  SmallArgs g = p.g;
+  g.W = p.has_w ? static_cast<const double*>(h->W0) : nullptr;   // (non-null marks the one-site form; members bring theirs)
+  g.C = static_cast<const double*>(C0);
+  g.out = static_cast<double*>(parts0);
+  g.y = static_cast<const double*>(C0);
+  g.part = dot_part0;
+  g.skip = skip0;
+  const dim3 grid((unsigned)p.Dl, (unsigned)p.KH, (unsigned)B);
+  if (dtype == MPSE_C128)
+    hipLaunchKernelGGL((k_heff_small_b<true>), grid, dim3(SM_THREADS), (size_t)p.lds, ctx->stream, g, mem, mstride);
+  else
+    hipLaunchKernelGGL((k_heff_small_b<false>), grid, dim3(SM_THREADS), (size_t)p.lds, ctx->stream, g, mem, mstride);
+  MPSE_HIP(ctx, hipGetLastError());
   return MPSE_OK;
 }

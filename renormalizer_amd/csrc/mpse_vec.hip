@@ -235,22 +235,15 @@ __global__ __launch_bounds__(RED_THREADS) void k_lanczos_update(double* __restri
 template <bool VEC>
 // The matvec result arrives as the sum of nparts tensors y, y + part_stride, .. (doubles): the K slices of a split
 // product or the halves of halved tiles (mpse_gemm.hip), added here in slice order instead of by a launch of their own
-__global__ __launch_bounds__(RED_THREADS) void k_lanczos_update_u(double* __restrict__ u_next,
-                                                                  const double* __restrict__ y, int nparts,
-                                                                  long long part_stride,
-                                                                  const double* __restrict__ u1,
-                                                                  const double* __restrict__ u0, long long n_doubles,
-                                                                  const double* __restrict__ a_partial, int a_nb,
-                                                                  double* __restrict__ a_out,
-                                                                  const double* __restrict__ cur_partial, int cur_nb,
-                                                                  double* __restrict__ cur_out,
-                                                                  const double* __restrict__ prev2,
-                                                                  double* __restrict__ partial,
-                                                                  const int* __restrict__ done,
-                                                                  const unsigned long long* __restrict__ pmask,
-                                                                  int prow, int ptiles,
-                                                                  const unsigned char* __restrict__ cmask, int crow,
-                                                                  int ckw) {
+__device__ __forceinline__ void lanczos_update_u(double* __restrict__ u_next, const double* __restrict__ y, int nparts,
+                                                 long long part_stride, const double* __restrict__ u1,
+                                                 const double* __restrict__ u0, long long n_doubles,
+                                                 const double* __restrict__ a_partial, int a_nb, double* __restrict__ a_out,
+                                                 const double* __restrict__ cur_partial, int cur_nb,
+                                                 double* __restrict__ cur_out, const double* __restrict__ prev2,
+                                                 double* __restrict__ partial, const int* __restrict__ done,
+                                                 const unsigned long long* __restrict__ pmask, int prow, int ptiles,
+                                                 const unsigned char* __restrict__ cmask, int crow, int ckw) {
   // pmask (complex vectors, VEC): the parts hold only some 16 x 16 tiles of the result viewed as rows of prow elements
   // (fused 0-site matvec, mpse_heff0.hip): word [tile row * ptiles + tile column], bit s = part s holds the tile; the
   // parts named there are added in part order, the others were never written.
@@ -368,6 +361,44 @@ __global__ __launch_bounds__(RED_THREADS) void k_lanczos_update_u(double* __rest
     partial[2 * blockIdx.x] = s;
     partial[2 * blockIdx.x + 1] = 0.0;
   }
+}
+template <bool VEC>
+__global__ __launch_bounds__(RED_THREADS) void k_lanczos_update_u(double* __restrict__ u_next,
+                                                                  const double* __restrict__ y, int nparts,
+                                                                  long long part_stride,
+                                                                  const double* __restrict__ u1,
+                                                                  const double* __restrict__ u0, long long n_doubles,
+                                                                  const double* __restrict__ a_partial, int a_nb,
+                                                                  double* __restrict__ a_out,
+                                                                  const double* __restrict__ cur_partial, int cur_nb,
+                                                                  double* __restrict__ cur_out,
+                                                                  const double* __restrict__ prev2,
+                                                                  double* __restrict__ partial,
+                                                                  const int* __restrict__ done,
+                                                                  const unsigned long long* __restrict__ pmask,
+                                                                  int prow, int ptiles,
+                                                                  const unsigned char* __restrict__ cmask, int crow,
+                                                                  int ckw) {
+  lanczos_update_u<VEC>(u_next, y, nparts, part_stride, u1, u0, n_doubles, a_partial, a_nb, a_out, cur_partial, cur_nb,
+                        cur_out, prev2, partial, done, pmask, prow, ptiles, cmask, crow, ckw);
+}
+// Batched form (mpse_expm_lanczos_batch): member blockIdx.y, every pointer at its member-0 address + blockIdx.y * mstride
+// bytes (one slab per launch set); no part or centre masks
+template <bool VEC>
+__global__ __launch_bounds__(RED_THREADS) void k_lanczos_update_u_b(double* u_next, const double* y, int nparts,
+                                                                    long long part_stride, const double* u1,
+                                                                    const double* u0, long long n_doubles,
+                                                                    const double* a_partial, int a_nb, double* a_out,
+                                                                    const double* cur_partial, int cur_nb,
+                                                                    double* cur_out, const double* prev2,
+                                                                    double* partial, const int* done, long long mstride) {
+  const unsigned m = blockIdx.y;
+  lanczos_update_u<VEC>(member_ptr(u_next, m, mstride), member_ptr(y, m, mstride), nparts, part_stride,
+                        member_ptr(u1, m, mstride), member_ptr(u0, m, mstride), n_doubles,
+                        member_ptr(a_partial, m, mstride), a_nb, member_ptr(a_out, m, mstride),
+                        member_ptr(cur_partial, m, mstride), cur_nb, member_ptr(cur_out, m, mstride),
+                        member_ptr(prev2, m, mstride), member_ptr(partial, m, mstride), member_ptr(done, m, mstride),
+                        nullptr, 0, 0, nullptr, 0, 0);
 }
 
 // partial sums of |x_i|^2 / (atol + rtol max(|y1_i|, |y2_i|))^2  (error norm of an embedded Runge-Kutta pair)
@@ -572,9 +603,8 @@ constexpr int LZ_MAXM = 64;   // one wavefront holds the Krylov coefficients
 // A launch with two workgroups also delivers the coefficients of the check two iterations earlier (workgroup 0:
 // iteration j - 2, into coef + 2 LZ_MAXM; that check - the first of a solve - can never stop the iteration because there
 // is no estimate before it, so it is evaluated together with the second one).
-__global__ __launch_bounds__(64) void k_lz_coefs(double* __restrict__ scal, int j, double dt_re, double dt_im,
-                                                 double tiny, double* __restrict__ coef, LzCtl* ctl,
-                                                 const double* __restrict__ part, int nb) {
+__device__ __forceinline__ void lz_coefs(double* __restrict__ scal, int j, double dt_re, double dt_im, double tiny,
+                                         double* __restrict__ coef, LzCtl* ctl, const double* __restrict__ part, int nb) {
   if (ctl->done) return;
   const int lane = threadIdx.x;
   if (gridDim.x == 2 && blockIdx.x == 0) {   // the earlier check: its beta^2 is in scal already (summed by the update
@@ -672,6 +702,22 @@ __global__ __launch_bounds__(64) void k_lz_coefs(double* __restrict__ scal, int 
     coef[LZ_MAXM + lane] = lane < m ? yi * sc : 0.0;
   }
 }
+__global__ __launch_bounds__(64) void k_lz_coefs(double* __restrict__ scal, int j, double dt_re, double dt_im,
+                                                 double tiny, double* __restrict__ coef, LzCtl* ctl,
+                                                 const double* __restrict__ part, int nb) {
+  lz_coefs(scal, j, dt_re, dt_im, tiny, coef, ctl, part, nb);
+}
+// Batched form: member blockIdx.y (blockIdx.x / gridDim.x keep their meaning); a member whose kernels stopped
+// (LzCtl::pad[0], k_lz_decide_b) does nothing
+__global__ __launch_bounds__(64) void k_lz_coefs_b(double* scal, int j, double dt_re, double dt_im, double tiny,
+                                                   double* coef, LzCtl* ctl, const double* part, int nb,
+                                                   long long mstride) {
+  const unsigned m = blockIdx.y;
+  LzCtl* c = member_ptr(ctl, m, mstride);
+  if (c->pad[0]) return;
+  lz_coefs(member_ptr(scal, m, mstride), j, dt_re, dt_im, tiny, member_ptr(coef, m, mstride), c,
+           member_ptr(part, m, mstride), nb);
+}
 
 // the decision of the check at iteration j (its estimate went to buffer `which`).  ``pub`` != null: the host waits at this
 // check - the control block goes to the mapped pinned buffer and the sequence number after it (a k_publish launch did
@@ -701,6 +747,34 @@ __global__ void k_lz_decide(LzCtl* ctl, const unsigned int* __restrict__ flag, u
                             int which, double* pub, volatile double* seq_slot, double seq) {
   lz_decide(ctl, flag, gen, has_prev, j, which, pub, seq_slot, seq);
 }
+// Batched form: one lane per member (B <= 64).  A member whose decision has fallen, or that needs the host
+// (need_host, bad), raises its skip word LzCtl::pad[0]: every later kernel of that member returns at once.  ``pub``
+// != null: all B control blocks go to pub + 4 m, then one sequence number.
+__global__ __launch_bounds__(64) void k_lz_decide_b(LzCtl* ctl, const unsigned int* flag, unsigned int gen, int has_prev,
+                                                    int j, int which, int B, long long mstride, double* pub,
+                                                    volatile double* seq_slot, double seq) {
+  const int m = threadIdx.x;
+  constexpr int W = int(sizeof(LzCtl) / sizeof(double));
+  if (m < B) {
+    LzCtl* c = member_ptr(ctl, m, mstride);
+    if (!c->pad[0]) {
+      lz_decide(c, member_ptr(flag, m, mstride), gen, has_prev, j, which, nullptr, nullptr, 0.0);
+      if (c->done || c->need_host || c->bad) c->pad[0] = 1;
+    }
+    if (pub) {
+      const double* src = reinterpret_cast<const double*>(c);
+      for (int i = 0; i < W; ++i) pub[m * W + i] = src[i];
+    }
+  }
+  if (pub) {
+    __threadfence_system();
+    __syncthreads();
+    if (m == 0) {
+      *seq_slot = seq;
+      __threadfence_system();
+    }
+  }
+}
 
 // res = sum_{i<m} coef_i V_i with the coefficients in device memory; optional closeness flag as in k_lincomb
 // (Round 6, measured and dropped: the decision of the check riding on this launch - the workgroup that finishes last, by a
@@ -709,10 +783,11 @@ __global__ void k_lz_decide(LzCtl* ctl, const unsigned int* __restrict__ flag, u
 // ``m_early`` > 0: the estimate of the (deferred) first check, sum_{i < m_early} coef2_i V_i with coef2 = coef + 2 LZ_MAXM,
 // is formed in the same pass over the basis and takes the place of ``prev``.
 template <bool CPLX>
-__global__ void k_lincomb_dev(double* __restrict__ res, const double* __restrict__ V, long long n, int m,
-                              const double* __restrict__ coef, const double* __restrict__ prev, double rtol, double atol,
-                              unsigned int* __restrict__ flag, unsigned int gen, const LzCtl* __restrict__ ctl,
-                              int m_early, const unsigned char* __restrict__ cmask, int crow, int ckw) {
+__device__ __forceinline__ void lincomb_dev(double* __restrict__ res, const double* __restrict__ V, long long n, int m,
+                                            const double* __restrict__ coef, const double* __restrict__ prev, double rtol,
+                                            double atol, unsigned int* __restrict__ flag, unsigned int gen,
+                                            const LzCtl* __restrict__ ctl, int m_early,
+                                            const unsigned char* __restrict__ cmask, int crow, int ckw) {
   // cmask: as in k_lanczos_update_u - the basis vectors (and the earlier estimate) are exactly zero outside it
   if (ctl->done || ctl->need_host) return;
   __shared__ double cr[LZ_MAXM], ci[LZ_MAXM], er[LZ_MAXM], ei[LZ_MAXM];
@@ -774,12 +849,34 @@ __global__ void k_lincomb_dev(double* __restrict__ res, const double* __restrict
   }
   if ((prev || m_early > 0) && bad) atomicMax(flag, gen);
 }
+template <bool CPLX>
+__global__ void k_lincomb_dev(double* __restrict__ res, const double* __restrict__ V, long long n, int m,
+                              const double* __restrict__ coef, const double* __restrict__ prev, double rtol, double atol,
+                              unsigned int* __restrict__ flag, unsigned int gen, const LzCtl* __restrict__ ctl,
+                              int m_early, const unsigned char* __restrict__ cmask, int crow, int ckw) {
+  lincomb_dev<CPLX>(res, V, n, m, coef, prev, rtol, atol, flag, gen, ctl, m_early, cmask, crow, ckw);
+}
+// Batched form: member blockIdx.y.  The estimate goes to the member's own result (res_sel 0: mem[m].out) or to its spare
+// buffer (1: spare + m * mstride); ``prev_sel`` names the earlier estimate the same way (-1: none)
+template <bool CPLX>
+__global__ void k_lincomb_dev_b(const BatchMember* __restrict__ mem, double* spare, int res_sel, int prev_sel,
+                                const double* V, long long n, int m, const double* coef, double rtol, double atol,
+                                unsigned int* flag, unsigned int gen, const LzCtl* ctl, int m_early, long long mstride) {
+  const unsigned b = blockIdx.y;
+  const LzCtl* c = member_ptr(ctl, b, mstride);
+  if (c->pad[0]) return;
+  double* out = static_cast<double*>(mem[b].out);
+  double* sp = member_ptr(spare, b, mstride);
+  lincomb_dev<CPLX>(res_sel == 0 ? out : sp, member_ptr(V, b, mstride), n, m, member_ptr(coef, b, mstride),
+                    prev_sel < 0 ? nullptr : (prev_sel == 0 ? out : sp), rtol, atol, member_ptr(flag, b, mstride), gen,
+                    c, m_early, nullptr, 0, 0);
+}
 
 // Start of an asynchronous solve in one launch (three before: zero fill of the control block, copy of the start vector,
 // its norm partials): U_0 = C, partial[b] = sum over block b of |C_i|^2 in the order of k_dot_partial(C, C), *ctl = 0.
 template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_lz_start(double* __restrict__ u0, const double* __restrict__ c, long long n,
-                                                          double* __restrict__ partial, LzCtl* ctl) {
+__device__ __forceinline__ void lz_start(double* __restrict__ u0, const double* __restrict__ c, long long n,
+                                         double* __restrict__ partial, LzCtl* ctl) {
   if (blockIdx.x == 0 && threadIdx.x < int(sizeof(LzCtl) / sizeof(int))) reinterpret_cast<int*>(ctl)[threadIdx.x] = 0;
   double re = 0, im = 0;
   const long long stride = (long long)gridDim.x * RED_THREADS;
@@ -810,6 +907,19 @@ __global__ __launch_bounds__(RED_THREADS) void k_lz_start(double* __restrict__ u
     partial[2 * blockIdx.x] = re;
     partial[2 * blockIdx.x + 1] = im;
   }
+}
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_lz_start(double* __restrict__ u0, const double* __restrict__ c, long long n,
+                                                          double* __restrict__ partial, LzCtl* ctl) {
+  lz_start<CPLX>(u0, c, n, partial, ctl);
+}
+// Batched form: member blockIdx.y starts from mem[m].C
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_lz_start_b(const BatchMember* __restrict__ mem, double* u0, long long n,
+                                                            double* partial, LzCtl* ctl, long long mstride) {
+  const unsigned m = blockIdx.y;
+  lz_start<CPLX>(member_ptr(u0, m, mstride), static_cast<const double*>(mem[m].C), n, member_ptr(partial, m, mstride),
+                 member_ptr(ctl, m, mstride));
 }
 
 inline bool lanczos_async_enabled() {
@@ -1216,7 +1326,7 @@ int mpse_nrm2(mpse_ctx* ctx, int dtype, const void* x, int64_t n, double* out_ho
 }
 
 static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin,
-                              void* out, double rtol, double atol, int max_dim, int* nvec);
+                              void* out, double rtol, double atol, int max_dim, int* nvec, bool async_first = true);
 
 int mpse_expm_centre_mask(mpse_ctx* ctx, const void* mask_dev, int64_t nbytes) {
   if (!ctx || (nbytes > 0 && !mask_dev) || nbytes < 0) return MPSE_ERR_ARG;
@@ -1241,7 +1351,7 @@ int mpse_expm_lanczos(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re
 }
 
 static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin,
-                              void* out, double rtol, double atol, int max_dim, int* nvec) {
+                              void* out, double rtol, double atol, int max_dim, int* nvec, bool async_first) {
   const bool cplx = dtype == MPSE_C128;
   if (!cplx && dt_im != 0.0)
     return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: complex time step needs a complex128 centre tensor");
@@ -1254,7 +1364,7 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
   if (h->nsite == 2) n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
   if (n <= 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "expm_lanczos: empty centre tensor");
   if (max_dim <= 0 || max_dim > 128) max_dim = 128;
-  if (lanczos_async_enabled() && n > 256) {
+  if (async_first && lanczos_async_enabled() && n > 256) {
     const int st = expm_lanczos_async(ctx, dtype, h, std::complex<double>(dt_re, dt_im), Cin, out, rtol, atol, max_dim,
                                       nvec, n);
     if (st != LZ_FALLBACK) return st;
@@ -1472,6 +1582,318 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
                          (const int*)nullptr);
     if (spt) prof_end(ctx, srec);
   }
+}
+
+}  // extern "C"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------------------
+// Batched solve (mpse_expm_lanczos_batch): B members of one shape whose matvec takes the one-launch small-centre path
+// run the asynchronous solve above in lock-step, every launch of the chain covering all of them (blockIdx.y / z =
+// member).  Each member does the arithmetic of its single solve in the same order - the batched kernels apply the member
+// offset and run the bodies of the single kernels, with the same grids per member - and stops its own kernels when
+// its decision has fallen (LzCtl::pad[0]).  The host waits once per check for all B control blocks.
+constexpr int LZB_MAX = 64;            // members per launch set (one lane each in k_lz_decide_b)
+constexpr int LZB_SLOT = 3700;         // pinned doubles [3700, 3956): the control blocks of a waited check
+constexpr int LZB_DOT_CAP = 4096;      // the dot request of expm_lanczos_async
+static_assert(LZB_SLOT + LZB_MAX * int(sizeof(LzCtl) / sizeof(double)) < 3990, "batch slot clear of the QR status word");
+
+struct BatchSet {
+  const mpse_heff* h0;        // the shape (every member has the same nsite / dims / dtypes)
+  std::vector<int> idx;       // member -> position in the caller's arrays
+  int64_t n;
+  int nparts, nb_dot;
+  size_t rt_bytes;
+};
+
+// solves one launch set; members the batch cannot finish (need_host, bad start vector, the 64-vector limit) are marked in
+// `single` and left for the caller (their start vectors are untouched: out may alias C only for finished members)
+int expm_lanczos_batch_set(mpse_ctx* ctx, int dtype, const BatchSet& bs, const mpse_heff* hs, const void* const* Cs,
+                           void* const* outs, std::complex<double> dt, double rtol, double atol, int max_dim, int* nvec,
+                           std::vector<char>& single, std::vector<int>& st_out, std::vector<std::string>& msg) {
+  const int B = (int)bs.idx.size();
+  const int64_t n = bs.n;
+  const bool cplx = dtype == MPSE_C128;
+  const size_t es = dtype_size(dtype);
+  const int64_t nd = n * (cplx ? 2 : 1);
+  const double tiny = 100.0 * double(n) * 2.220446049250313e-16;
+  const int limit = max_dim < LZ_MAXM ? max_dim : LZ_MAXM;
+  const unsigned long long key = ((unsigned long long)bs.h0->nsite << 60) ^ ((unsigned long long)n << 1) ^ (cplx ? 1ull : 0ull);
+  int hint = 0;
+  {
+    auto it = ctx->lz_hint.find(key);
+    if (it != ctx->lz_hint.end()) hint = it->second;
+  }
+  int wait_from = hint > 0 ? hint - 1 : 6;
+  if (wait_from < 6) wait_from = 6;
+  int cap = hint + 4 > 16 ? hint + 4 : 16;
+  if (cap > limit + 1) cap = limit + 1;
+  const int nb = red_blocks(nd);
+
+  // per-member region of the slab (doubles, 256-byte aligned sections; the Krylov basis last so that it can grow):
+  // [scalars, control block, coefficients][flag word][dot partials][norm partials x 2][result parts][spare][basis]
+  auto al = [](int64_t x) { return (x + 31) & ~int64_t(31); };
+  const int SC_CTL = 4 + 4 * 130, SC_COEF = SC_CTL + 8;
+  const int64_t o_flag = al(SC_COEF + 4 * LZ_MAXM), o_pa = o_flag + 32, o_pb0 = o_pa + al(2 * int64_t(bs.nb_dot));
+  const int64_t o_pb1 = o_pb0 + al(2 * int64_t(nb)), o_w = o_pb1 + al(2 * int64_t(nb));
+  const int64_t o_res = o_w + al(bs.nparts * nd), o_v = o_res + al(nd);
+  int64_t ms = o_v + al(cap * nd);
+  TmpBuf SLAB(ctx), RT(ctx), MEM(ctx);
+  MPSE_TRY(SLAB.alloc(size_t(B) * ms * sizeof(double)));
+  MPSE_TRY(RT.alloc(size_t(B) * bs.rt_bytes));
+  MPSE_TRY(MEM.alloc(size_t(B) * sizeof(BatchMember)));
+  std::vector<BatchMember> mh(B);
+  for (int m = 0; m < B; ++m) {
+    const mpse_heff& h = hs[bs.idx[m]];
+    mh[m] = BatchMember{h.L, h.R, h.W0, RT.as<char>() + size_t(m) * bs.rt_bytes, Cs[bs.idx[m]], outs[bs.idx[m]]};
+  }
+  MPSE_TRY(stage_h2d(ctx, MEM.p, mh.data(), mh.size() * sizeof(BatchMember)));
+  const BatchMember* mem = MEM.as<const BatchMember>();
+  double* base = SLAB.as<double>();
+  long long mstride = ms * (long long)sizeof(double);
+  double* scal = base;
+  LzCtl* ctl = reinterpret_cast<LzCtl*>(scal + SC_CTL);
+  double* coef = scal + SC_COEF;
+  unsigned int* flag = reinterpret_cast<unsigned int*>(base + o_flag);
+  const int* skip0 = &ctl->pad[0];
+  double* part_a = base + o_pa;
+  double* part_b2[2] = {base + o_pb0, base + o_pb1};
+  double* W = base + o_w;
+  double* RES = base + o_res;
+  auto vec = [&](int j) { return SLAB.as<double>() + o_v + int64_t(j) * nd; };
+  const bool vec16 = true;   // (members are grouped only when every Krylov vector starts on a 16-byte boundary)
+  MPSE_HIP(ctx, hipMemset2DAsync(flag, size_t(mstride), 0, sizeof(unsigned int), size_t(B), ctx->stream));
+
+  if (cplx)
+    hipLaunchKernelGGL((k_lz_start_b<true>), dim3(nb, B), dim3(RED_THREADS), 0, ctx->stream, mem, vec(0), (long long)n,
+                       part_b2[0], ctl, mstride);
+  else
+    hipLaunchKernelGGL((k_lz_start_b<false>), dim3(nb, B), dim3(RED_THREADS), 0, ctx->stream, mem, vec(0), (long long)n,
+                       part_b2[0], ctl, mstride);
+  MPSE_HIP(ctx, hipGetLastError());
+  MPSE_TRY(heff_small_batch_rt(ctx, dtype, bs.h0, B, mem, skip0, mstride));
+
+  int prev_sel = -1;    // where the earlier estimate went: -1 none, 0 the result, 1 the spare buffer (the same for all)
+  bool waited = false;
+  std::vector<LzCtl> hc(B);
+  std::vector<char> fin(B, 0);
+  constexpr int CW = int(sizeof(LzCtl) / sizeof(double));
+  for (int j = 0;; ++j) {
+    MPSE_TRY(heff_small_batch_apply(ctx, dtype, bs.h0, B, mem, vec(j), W, n, part_a, LZB_DOT_CAP, skip0, mstride));
+    if (j + 2 > cap) {      // room for U_{j+1}: a new slab with a longer basis per member
+      const int ncap = cap * 2 < limit + 1 ? cap * 2 : limit + 1;
+      const int64_t nms = o_v + al(ncap * nd);
+      TmpBuf S2(ctx);
+      MPSE_TRY(S2.alloc(size_t(B) * nms * sizeof(double)));
+      MPSE_HIP(ctx, hipMemcpy2DAsync(S2.p, size_t(nms) * 8, SLAB.p, size_t(ms) * 8, size_t(ms) * 8, size_t(B),
+                                     hipMemcpyDeviceToDevice, ctx->stream));
+      std::swap(SLAB.p, S2.p);
+      ms = nms;
+      mstride = ms * (long long)sizeof(double);
+      cap = ncap;
+      base = SLAB.as<double>();
+      scal = base;
+      ctl = reinterpret_cast<LzCtl*>(scal + SC_CTL);
+      coef = scal + SC_COEF;
+      flag = reinterpret_cast<unsigned int*>(base + o_flag);
+      skip0 = &ctl->pad[0];
+      part_a = base + o_pa;
+      part_b2[0] = base + o_pb0, part_b2[1] = base + o_pb1;
+      W = base + o_w;
+      RES = base + o_res;
+    }
+    double* cur_part = part_b2[j & 1];
+    double* new_part = part_b2[(j + 1) & 1];
+    double* cur_out = j == 0 ? scal : scal + 6 + 4 * (j - 1);
+    const double* prev2 = j == 0 ? scal : (j == 1 ? scal : scal + 6 + 4 * (j - 2));
+    hipLaunchKernelGGL(k_lanczos_update_u_b<vec16>, dim3(nb, B), dim3(RED_THREADS), 0, ctx->stream, vec(j + 1),
+                       (const double*)W, bs.nparts, (long long)nd, (const double*)vec(j),
+                       j > 0 ? (const double*)vec(j - 1) : (const double*)nullptr, (long long)nd, (const double*)part_a,
+                       bs.nb_dot, scal + 4 + 4 * j, (const double*)cur_part, nb, cur_out, prev2, new_part, skip0, mstride);
+    bool check = (j > 3 && j % 2 == 0);
+    const bool last = (j + 1 >= limit);
+    bool merged = false;     // the deferred first check, as in expm_lanczos_async
+    if (check && prev_sel < 0 && j == 4 && j + 3 < limit) check = false;
+    if (check && prev_sel < 0 && j == 6) merged = true;
+    if (check) {
+      hipLaunchKernelGGL(k_lz_coefs_b, dim3(merged ? 2 : 1, B), dim3(64), 0, ctx->stream, scal, j, dt.real(), dt.imag(),
+                         tiny, coef, ctl, (const double*)new_part, nb, mstride);
+      const int res_sel = prev_sel == 0 ? 1 : 0;
+      unsigned int gen = 0;
+      if (prev_sel >= 0 || merged) {
+        gen = ++ctx->flag_gen;
+        if (gen == 0) {
+          MPSE_HIP(ctx, hipMemset2DAsync(flag, size_t(mstride), 0, sizeof(unsigned int), size_t(B), ctx->stream));
+          gen = ++ctx->flag_gen;
+        }
+      }
+      if (cplx)
+        hipLaunchKernelGGL((k_lincomb_dev_b<true>), dim3(ew_blocks(n), B), dim3(256), 0, ctx->stream, mem, RES, res_sel,
+                           prev_sel, (const double*)vec(0), (long long)n, j + 1, (const double*)coef, rtol, atol, flag,
+                           gen, (const LzCtl*)ctl, merged ? j - 1 : 0, mstride);
+      else
+        hipLaunchKernelGGL((k_lincomb_dev_b<false>), dim3(ew_blocks(n), B), dim3(256), 0, ctx->stream, mem, RES, res_sel,
+                           prev_sel, (const double*)vec(0), (long long)n, j + 1, (const double*)coef, rtol, atol, flag,
+                           gen, (const LzCtl*)ctl, merged ? j - 1 : 0, mstride);
+      const bool wait_here = j >= wait_from || waited || last;
+      const bool self_pub = wait_here && ctx->pinned_dev != nullptr;
+      const double seq = self_pub ? double(++ctx->publish_seq) : 0.0;
+      hipLaunchKernelGGL(k_lz_decide_b, dim3(1), dim3(64), 0, ctx->stream, ctl, (const unsigned int*)flag, gen,
+                         (prev_sel >= 0 || merged) ? 1 : 0, j, res_sel, B, mstride,
+                         self_pub ? ctx->pinned_dev + LZB_SLOT : (double*)nullptr,
+                         (volatile double*)(self_pub ? ctx->pinned_dev + 4095 : nullptr), seq);
+      prev_sel = res_sel;
+      MPSE_HIP(ctx, hipGetLastError());
+      if (wait_here) {
+        if (self_pub) MPSE_TRY(publish_wait_seq(ctx, seq, reinterpret_cast<const double*>(ctl), CW, LZB_SLOT));
+        if (!self_pub || ctx->pinned[4095] != seq) {   // (no mapped view, or the number never arrived: plain copies)
+          MPSE_HIP(ctx, hipMemcpy2DAsync(ctx->pinned + LZB_SLOT, sizeof(LzCtl), ctl, size_t(mstride), sizeof(LzCtl),
+                                         size_t(B), hipMemcpyDeviceToHost, ctx->stream));
+          MPSE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
+        memcpy(hc.data(), ctx->pinned + LZB_SLOT, size_t(B) * sizeof(LzCtl));
+        waited = true;
+        bool all = true;
+        for (int m = 0; m < B; ++m) {
+          if (hc[m].bad || hc[m].need_host) single[m] = 1;
+          else if (hc[m].done) fin[m] = 1;
+          else all = false;
+        }
+        if (all) break;
+      }
+    }
+    if (last) {     // beyond one wavefront of coefficients (or no convergence): the single solve decides
+      for (int m = 0; m < B; ++m)
+        if (!fin[m]) single[m] = 1;
+      break;
+    }
+  }
+  int best = 0;
+  for (int m = 0; m < B; ++m) {
+    if (!fin[m]) continue;
+    if (hc[m].which == 1)
+      MPSE_TRY(mpse_memcpy_d2d(ctx, outs[bs.idx[m]], member_ptr(RES, m, mstride), size_t(n) * es));
+    if (nvec) nvec[bs.idx[m]] = hc[m].nvec;
+    if (hc[m].nvec > best) best = hc[m].nvec;
+    st_out[bs.idx[m]] = MPSE_OK;
+  }
+  if (best > 0) ctx->lz_hint[key] = best;
+  // members the batch could not finish: the single solve from the copy of their start vector in the basis (bitwise C;
+  // out may alias C).  Where their own asynchronous solve would hand over to the synchronous one (need_host, the vector
+  // limit), that one runs directly - it starts from C and does not depend on the attempt before it
+  for (int m = 0; m < B; ++m) {
+    if (!single[m]) continue;
+    const int i = bs.idx[m];
+    ctx->cmask_pending = mpse_ctx::CMask();
+    int nv = 0;
+    const int st = expm_lanczos_solve(ctx, dtype, &hs[i], dt.real(), dt.imag(), member_ptr(vec(0), m, mstride), outs[i],
+                                      rtol, atol, max_dim, &nv, hc[m].bad != 0);
+    if (nvec) nvec[i] = nv;
+    st_out[i] = st;
+    if (st != MPSE_OK) msg[i] = ctx->err;
+  }
+  return MPSE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff* h, double dt_re, double dt_im,
+                            const void* const* C, void* const* out, double rtol, double atol, int max_dim, int* nvec) {
+  if (!ctx || count < 0 || (count > 0 && (!h || !C || !out))) return MPSE_ERR_ARG;
+  if (MPSE_RECORDING(ctx))
+    return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos_batch: cannot be recorded (mpse_defer_begin is open)");
+  if (count == 0) return MPSE_OK;
+  MPSE_BIND(ctx);
+  const int md = (max_dim <= 0 || max_dim > 128) ? 128 : max_dim;
+  const bool cplx = dtype == MPSE_C128;
+  const mpse_ctx::CMask saved_mask = ctx->cmask_pending;   // (left for the next mpse_expm_lanczos)
+  std::vector<int> st(count, MPSE_OK);
+  std::vector<std::string> msg(count);
+  std::vector<char> grouped(count, 0);
+  // launch sets: members of one shape, in the order of their first appearance, up to LZB_MAX each
+  std::vector<BatchSet> sets;
+  if (lanczos_async_enabled() && !(!cplx && dt_im != 0.0)) {
+    std::vector<BatchSet> open;   // (the last set of each shape, while it has room)
+    for (int i = 0; i < count; ++i) {
+      const mpse_heff& hi = h[i];
+      if (!C[i] || !out[i] || !hi.L || !hi.R) continue;
+      const mpse_dims& s = hi.dims;
+      if ((s.Dl_bra > 0 && s.Dl_bra != s.Dl_ket) || (s.Dr_bra > 0 && s.Dr_bra != s.Dr_ket)) continue;
+      int64_t n = s.Dl_ket * s.Dr_ket;
+      if (hi.nsite >= 1) n *= s.d0 * (s.danc > 0 ? s.danc : 1);
+      if (hi.nsite != 0 && hi.nsite != 1) continue;
+      if (n <= 256) continue;
+      if (!((cplx || n % 2 == 0) && (reinterpret_cast<uintptr_t>(C[i]) & 15) == 0)) continue;
+      size_t rtb = 0;
+      int np = 0, nbd = 0;
+      if (!heff_small_batch_plan(&hi, dtype, n, LZB_DOT_CAP, &rtb, &np, &nbd)) continue;
+      BatchSet* tgt = nullptr;
+      for (auto& o : open) {
+        const mpse_heff& h0 = *o.h0;
+        if (h0.nsite == hi.nsite && memcmp(&h0.dims, &hi.dims, sizeof(mpse_dims)) == 0 && h0.l_dtype == hi.l_dtype &&
+            h0.r_dtype == hi.r_dtype && h0.w_dtype == hi.w_dtype && (h0.W0 != nullptr) == (hi.W0 != nullptr)) {
+          tgt = &o;
+          break;
+        }
+      }
+      if (tgt && (int)tgt->idx.size() == LZB_MAX) {
+        sets.push_back(*tgt);
+        tgt->idx.clear();
+      }
+      if (!tgt) {
+        open.push_back(BatchSet{&hi, {}, n, np, nbd, rtb});
+        tgt = &open.back();
+      }
+      tgt->idx.push_back(i);
+    }
+    for (auto& o : open) sets.push_back(o);
+  }
+  for (const BatchSet& bs : sets) {
+    if (bs.idx.size() < 2) continue;    // (one member alone: its own solve)
+    std::vector<char> single(bs.idx.size(), 0);
+    MPSE_TRY(expm_lanczos_batch_set(ctx, dtype, bs, h, C, out, std::complex<double>(dt_re, dt_im), rtol, atol, md, nvec,
+                                    single, st, msg));
+    for (size_t m = 0; m < bs.idx.size(); ++m) {
+      grouped[bs.idx[m]] = 1;
+      if (single[m])
+        ++ctx->lz_batch_single;
+      else
+        ++ctx->lz_batch_members;
+    }
+  }
+  for (int i = 0; i < count; ++i) {
+    if (grouped[i]) continue;
+    ++ctx->lz_batch_single;
+    ctx->cmask_pending = mpse_ctx::CMask();
+    if (!C[i] || !out[i]) {
+      st[i] = mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: null vector");
+      msg[i] = ctx->err;
+      continue;
+    }
+    int nv = 0;
+    st[i] = expm_lanczos_solve(ctx, dtype, &h[i], dt_re, dt_im, C[i], out[i], rtol, atol, max_dim, &nv);
+    if (nvec) nvec[i] = nv;
+    if (st[i] != MPSE_OK) msg[i] = ctx->err;
+  }
+  ctx->cmask_pending = saved_mask;
+  int status = MPSE_OK;
+  for (int i = 0; i < count; ++i)
+    if (st[i] != MPSE_OK) {
+      status = mpse_fail(ctx, st[i], "expm_lanczos_batch: member %d: %s", i, msg[i].c_str());
+      break;
+    }
+  return defer_replay(ctx, status);
+}
+
+int mpse_expm_lanczos_batch_stats(mpse_ctx* ctx, int64_t* batched_members, int64_t* single_members) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (batched_members) *batched_members = ctx->lz_batch_members;
+  if (single_members) *single_members = ctx->lz_batch_single;
+  return MPSE_OK;
 }
 
 }  // extern "C"

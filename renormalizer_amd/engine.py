@@ -134,6 +134,10 @@ _SIGNATURES = {
     "mpse_env_unit_channel": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_double, _i64p],
     "mpse_expm_lanczos": [C.c_void_p, C.c_int, C.POINTER(mpse_heff), C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                           C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int)],
+    "mpse_expm_lanczos_batch": [C.c_void_p, C.c_int, C.c_int, C.POINTER(mpse_heff), C.c_double, C.c_double,
+                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int,
+                                C.POINTER(C.c_int)],
+    "mpse_expm_lanczos_batch_stats": [C.c_void_p, _i64p, _i64p],
     "mpse_davidson": [C.c_void_p, C.c_int, C.POINTER(mpse_heff), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                       C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _dblp, C.c_void_p,
                       C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -443,6 +447,13 @@ class Engine:
 
     def prof_reset(self):
         self._check(self.lib.mpse_prof_reset(self.ctx))
+
+    def lanczos_batch_stats(self):
+        """(members solved by the batched Krylov kernels, members of mpse_expm_lanczos_batch calls that took the single
+        solve), cumulative"""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self.lib.mpse_expm_lanczos_batch_stats(self.ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""

@@ -35,6 +35,54 @@ def expm_krylov(Afunc, dt, vstart, block_size=50, rtol=1e-5, atol=1e-8, out=None
     return _expm_krylov_generic(eng, Afunc, dt, v, block_size, rtol, atol)
 
 
+def expm_krylov_batch(hops, dt, vstarts, rtol=1e-5, atol=1e-8, outs=None):
+    """``[expm_krylov(h, dt, v, rtol=rtol, atol=atol, out=o)[0] ...], [Krylov dimensions]`` for independent problems:
+    engine ``Hop``s go to ``mpse_expm_lanczos_batch`` in one call (members of one shape on the small-centre path run
+    in lock-step, every result bitwise what ``expm_krylov`` gives for it alone); other operators run one by one through
+    ``expm_krylov``, and so do hops with a centre mask (large centres, which the batched kernels do not take)."""
+    eng = get_engine()
+    dt = complex(dt)
+    hops, vstarts = list(hops), list(vstarts)
+    if len(hops) != len(vstarts) or (outs is not None and len(outs) != len(hops)):
+        raise ValueError("expm_krylov_batch: hops, vstarts and outs differ in length")
+    res, dims = [None] * len(hops), [0] * len(hops)
+    eng_idx, heffs, vs, os_ = [], [], [], []
+    code = None
+    for i, (h, v0) in enumerate(zip(hops, vstarts)):
+        out = None if outs is None else outs[i]
+        if not isinstance(h, Hop):
+            res[i], dims[i] = expm_krylov(h, dt, v0, rtol=rtol, atol=atol)
+            continue
+        v = eng.asdevice(v0)
+        if (dt.imag != 0 or h.operator_is_complex) and not v.is_complex:
+            v = v.to_complex()
+        if out is None:
+            out = eng.empty(v.shape, v.dtype)
+        elif out.size != v.size or out.dtype != v.dtype:
+            raise ValueError("expm_krylov_batch: out does not match the start vector")
+        if (code is not None and v.code != code) or h.cmask is not None:
+            # one dtype per engine call; a hop with a centre mask keeps the single solve that uses it
+            res[i], dims[i] = expm_krylov(h, dt, v, rtol=rtol, atol=atol, out=out)
+            continue
+        code = v.code
+        eng_idx.append(i)
+        heffs.append(h.heff)
+        vs.append(v)
+        os_.append(out)
+        res[i] = out
+    if eng_idx:
+        cnt = len(eng_idx)
+        harr = (type(heffs[0]) * cnt)(*heffs)
+        carr = (C.c_void_p * cnt)(*[v.ptr for v in vs])
+        oarr = (C.c_void_p * cnt)(*[o.ptr for o in os_])
+        nv = (C.c_int * cnt)()
+        eng._check(eng.lib.mpse_expm_lanczos_batch(eng.ctx, code, cnt, harr, dt.real, dt.imag, carr, oarr, rtol, atol,
+                                                   0, nv))
+        for k, i in enumerate(eng_idx):
+            dims[i] = nv[k]
+    return res, dims
+
+
 def _combine(eng, V, coef, dtype):
     out = eng.zeros(V[0].shape, dtype)
     for c, vec in zip(coef, V):

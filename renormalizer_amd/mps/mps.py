@@ -1343,93 +1343,9 @@ class Mps:
         site of each half sweep is not split."""
         cfg = self.evolve_config
         eng = get_engine()
-        if np.iscomplex(evolve_dt):
-            mps = self.copy()
-        else:
-            mps = self.to_complex()
-        evolve_dt = complex(evolve_dt)
-        n = len(mps)
-        # Only the environments ahead of the sweep are needed: the reference builds both
-        # directions and discards half (mps.py:1281-1283).  The second half sweep of the previous step left exactly
-        # those environments behind, computed from the very site tensors this step starts with: they are taken over
-        # when every tensor they depend on is still the same object (site buffers are immutable by convention).
-        ahead = "R" if mps.to_right else "L"
-        environ = _carried_environ(mps, mpo, ahead)
-        if environ is None:
-            environ = Environ(mps, mpo, ahead)
-        local_steps = []
-        q = len(mps.qntot)
-        hh_sites = _householder_sites(mps)         # (site, direction) whose block QR broke the Cholesky-QR path before
-        hh_sites.tick()                            # one evolve less on the Householder kernels for every noted site
-        qr_redone = [eng.block_qr_stats()[2]]
-
-        def note_qr(imps):
-            if learn_qr:
-                now = eng.block_qr_stats()[2]
-                if now != qr_redone[0]:
-                    hh_sites.note((imps, mps.to_right))
-                qr_redone[0] = now
-
-        use_cmask = os.environ.get("MPSE_CENTRE_MASK", "1") != "0"
-
-        def prepare(imps, shape):
-            """Everything the update of site ``imps`` needs that does not depend on the preceding solve: the
-            effective-Hamiltonian descriptor and the quantum-number block plan of its QR.  Called BEFORE the solve whose
-            result the site waits for, so that the host has nothing left to do but enqueue when that solve returns."""
-            hop = hop_expr(environ.read("L", imps - 1), environ.read("R", imps + 1), [mpo.device(imps, eng)], shape)
-            split = (not mps.to_right and imps != 0) or (mps.to_right and imps != n - 1)
-            qnbigl = qnbigr = plan = None
-            if split:
-                qnbigl, qnbigr, _ = mps._get_big_qn([imps], need_mat=False)
-                plan = svd_qn.block_plan(qnbigl, qnbigr, mps.qntot)
-                # large centres: the engine skips the empty tiles of the Krylov vectors by the pattern of their
-                # quantum numbers instead of scanning every vector (row / column grouping as the QR sees the site)
-                if use_cmask and len(shape) == 3 and shape[0] * shape[0] * shape[1] * shape[2] >= (1 << 22):
-                    if mps.to_right:
-                        ql, qr = qnbigl, qnbigr
-                    else:               # sweeping left the QR groups the site as (a | sigma, b): regroup (a, sigma | b)
-                        ql = add_outer(np.array(mps.qn[imps]), mps._get_sigmaqn(imps))
-                        qr = np.array(mps.qn[imps + 1])
-                    hop.cmask = centre_tile_mask(eng, ql, qr, mps.qntot, shape)
-            return hop, split, qnbigl, qnbigr, plan
-
-        def split_site(imps, centre, ready, shape):
-            """What follows the forward step of a split site, on ``centre`` (the result of that step, or the buffer
-            that will receive it): QR / RQ by quantum-number block, installation of the isometry, one environment
-            update.  Returns the effective Hamiltonian of the bond factor, the bond factor and the site it goes to."""
-            hop, _, qnbigl, qnbigr, plan = ready
-            l_array, r_array = hop.l, hop.r
-            u, qnlset, v, qnrset = svd_qn.svd_qn(centre, qnbigl, qnbigr, mps.qntot, QR=True,
-                                                 system="L" if mps.to_right else "R", full_matrices=False, plan=plan,
-                                                 householder=(imps, mps.to_right) in hh_sites)
-            vt = v.T
-            if not mps.to_right:
-                mps[imps] = vt.reshape([-1] + shape[1:])
-                mps.qn[imps] = np.array(qnrset, dtype=int).reshape(-1, q)
-                mps.qnidx = imps - 1
-                r_array = environ.GetLR("R", imps, mps, mpo, itensor=r_array, method="System", canonical=True)
-                hop_b = hop_expr(l_array, r_array, [], u.shape)
-                if use_cmask and u.shape[0] * u.shape[1] >= (1 << 14):
-                    # structural tile mask of the bond factor (rows: the left bond, columns: the new bond's states)
-                    hop_b.cmask = centre_tile_mask(eng, qnbigl, np.array(qnrset, dtype=int).reshape(-1, q), mps.qntot,
-                                                   u.shape)
-                return hop_b, u, imps - 1
-            mps[imps] = u.reshape(shape[:-1] + [-1])
-            mps.qn[imps + 1] = np.array(qnlset, dtype=int).reshape(-1, q)
-            mps.qnidx = imps + 1
-            l_array = environ.GetLR("L", imps, mps, mpo, itensor=l_array, method="System", canonical=True)
-            hop_b = hop_expr(l_array, r_array, [], vt.shape)
-            if use_cmask and vt.shape[0] * vt.shape[1] >= (1 << 14):
-                hop_b.cmask = centre_tile_mask(eng, np.array(qnlset, dtype=int).reshape(-1, q), qnbigr, mps.qntot,
-                                               vt.shape)
-            return hop_b, vt, imps + 1
-
-        def absorb(bond, nbr):
-            """the evolved bond factor times the neighbouring site: the next centre"""
-            t = mps[nbr]
-            if mps.to_right:
-                return eng.matmul(bond, t.reshape(t.shape[0], -1)).reshape((bond.shape[0],) + t.shape[1:])
-            return eng.matmul(t.reshape(-1, t.shape[-1]), bond).reshape(t.shape[:-1] + (bond.shape[1],))
+        sw = _PsSweep(self, mpo, evolve_dt, learn_qr)
+        mps, evolve_dt, local_steps = sw.mps, sw.evolve_dt, sw.local_steps
+        prepare, split_site, absorb, note_qr = sw.prepare, sw.split_site, sw.absorb, sw.note_qr
 
         # The calls that follow a local solve do not depend on WHEN it converges, only on the buffer its result lands
         # in: they are recorded ahead (Engine.recording) and issued by the engine the moment the solve has been enqueued
@@ -1491,10 +1407,119 @@ class Mps:
         except BaseException:
             eng.defer_discard()
             raise
+        return sw.finish()
+
+
+class _PsSweep:
+    """One trajectory's TDVP-PS step (``Mps._evolve_tdvp_ps_sweeps``): the working copy of the state, its environments and
+    QR notes, and the per-site pieces of a sweep - ``prepare`` / ``split_site`` / ``absorb`` / ``note_qr``.  The single
+    path drives one of these with its recorded / armed pipeline; ``evolve_batch`` drives several in lock-step.
+    ``carry``: the holder of the carried environments (``_CARRY`` for the calling thread's single trajectory)."""
+
+    def __init__(self, src, mpo, evolve_dt, learn_qr=False, carry=None):
+        eng = get_engine()
+        self.eng, self.mpo, self.learn_qr = eng, mpo, learn_qr
+        self.carry = _CARRY if carry is None else carry
+        if np.iscomplex(evolve_dt):
+            mps = src.copy()
+        else:
+            mps = src.to_complex()
+        self.evolve_dt = complex(evolve_dt)
+        self.mps = mps
+        self.n = len(mps)
+        # Only the environments ahead of the sweep are needed: the reference builds both
+        # directions and discards half (mps.py:1281-1283).  The second half sweep of the previous step left exactly
+        # those environments behind, computed from the very site tensors this step starts with: they are taken over
+        # when every tensor they depend on is still the same object (site buffers are immutable by convention).
+        ahead = "R" if mps.to_right else "L"
+        environ = _carried_environ(mps, mpo, ahead, self.carry)
+        if environ is None:
+            environ = Environ(mps, mpo, ahead)
+        self.environ = environ
+        self.local_steps = []
+        self.q = len(mps.qntot)
+        self.hh_sites = _householder_sites(mps)    # (site, direction) whose block QR broke the Cholesky-QR path before
+        self.hh_sites.tick()                       # one evolve less on the Householder kernels for every noted site
+        self.qr_redone = eng.block_qr_stats()[2]
+        self.use_cmask = os.environ.get("MPSE_CENTRE_MASK", "1") != "0"
+
+    def note_qr(self, imps):
+        if self.learn_qr:
+            now = self.eng.block_qr_stats()[2]
+            if now != self.qr_redone:
+                self.hh_sites.note((imps, self.mps.to_right))
+            self.qr_redone = now
+
+    def prepare(self, imps, shape):
+        """Everything the update of site ``imps`` needs that does not depend on the preceding solve: the
+        effective-Hamiltonian descriptor and the quantum-number block plan of its QR.  Called BEFORE the solve whose
+        result the site waits for, so that the host has nothing left to do but enqueue when that solve returns."""
+        mps, eng, n = self.mps, self.eng, self.n
+        hop = hop_expr(self.environ.read("L", imps - 1), self.environ.read("R", imps + 1), [self.mpo.device(imps, eng)],
+                       shape)
+        split = (not mps.to_right and imps != 0) or (mps.to_right and imps != n - 1)
+        qnbigl = qnbigr = plan = None
+        if split:
+            qnbigl, qnbigr, _ = mps._get_big_qn([imps], need_mat=False)
+            plan = svd_qn.block_plan(qnbigl, qnbigr, mps.qntot)
+            # large centres: the engine skips the empty tiles of the Krylov vectors by the pattern of their
+            # quantum numbers instead of scanning every vector (row / column grouping as the QR sees the site)
+            if self.use_cmask and len(shape) == 3 and shape[0] * shape[0] * shape[1] * shape[2] >= (1 << 22):
+                if mps.to_right:
+                    ql, qr = qnbigl, qnbigr
+                else:               # sweeping left the QR groups the site as (a | sigma, b): regroup (a, sigma | b)
+                    ql = add_outer(np.array(mps.qn[imps]), mps._get_sigmaqn(imps))
+                    qr = np.array(mps.qn[imps + 1])
+                hop.cmask = centre_tile_mask(eng, ql, qr, mps.qntot, shape)
+        return hop, split, qnbigl, qnbigr, plan
+
+    def split_site(self, imps, centre, ready, shape):
+        """What follows the forward step of a split site, on ``centre`` (the result of that step, or the buffer
+        that will receive it): QR / RQ by quantum-number block, installation of the isometry, one environment
+        update.  Returns the effective Hamiltonian of the bond factor, the bond factor and the site it goes to."""
+        mps, eng, mpo, environ, q = self.mps, self.eng, self.mpo, self.environ, self.q
+        hop, _, qnbigl, qnbigr, plan = ready
+        l_array, r_array = hop.l, hop.r
+        u, qnlset, v, qnrset = svd_qn.svd_qn(centre, qnbigl, qnbigr, mps.qntot, QR=True,
+                                             system="L" if mps.to_right else "R", full_matrices=False, plan=plan,
+                                             householder=(imps, mps.to_right) in self.hh_sites)
+        vt = v.T
+        if not mps.to_right:
+            mps[imps] = vt.reshape([-1] + shape[1:])
+            mps.qn[imps] = np.array(qnrset, dtype=int).reshape(-1, q)
+            mps.qnidx = imps - 1
+            r_array = environ.GetLR("R", imps, mps, mpo, itensor=r_array, method="System", canonical=True)
+            hop_b = hop_expr(l_array, r_array, [], u.shape)
+            if self.use_cmask and u.shape[0] * u.shape[1] >= (1 << 14):
+                # structural tile mask of the bond factor (rows: the left bond, columns: the new bond's states)
+                hop_b.cmask = centre_tile_mask(eng, qnbigl, np.array(qnrset, dtype=int).reshape(-1, q), mps.qntot,
+                                               u.shape)
+            return hop_b, u, imps - 1
+        mps[imps] = u.reshape(shape[:-1] + [-1])
+        mps.qn[imps + 1] = np.array(qnlset, dtype=int).reshape(-1, q)
+        mps.qnidx = imps + 1
+        l_array = environ.GetLR("L", imps, mps, mpo, itensor=l_array, method="System", canonical=True)
+        hop_b = hop_expr(l_array, r_array, [], vt.shape)
+        if self.use_cmask and vt.shape[0] * vt.shape[1] >= (1 << 14):
+            hop_b.cmask = centre_tile_mask(eng, np.array(qnlset, dtype=int).reshape(-1, q), qnbigr, mps.qntot,
+                                           vt.shape)
+        return hop_b, vt, imps + 1
+
+    def absorb(self, bond, nbr):
+        """the evolved bond factor times the neighbouring site: the next centre"""
+        mps, eng = self.mps, self.eng
+        t = mps[nbr]
+        if mps.to_right:
+            return eng.matmul(bond, t.reshape(t.shape[0], -1)).reshape((bond.shape[0],) + t.shape[1:])
+        return eng.matmul(t.reshape(-1, t.shape[-1]), bond).reshape(t.shape[:-1] + (bond.shape[1],))
+
+    def finish(self):
+        """the Krylov statistics of the step, and the environments ahead of the next one to the carry holder"""
+        mps, local_steps = self.mps, self.local_steps
         mps.evolve_config.stat = dict(nobs=len(local_steps), min=int(np.min(local_steps)),
                                       max=int(np.max(local_steps)), mean=float(np.mean(local_steps)),
                                       steps=list(local_steps))
-        _carry_environ(mps, mpo, environ)
+        _carry_environ(mps, self.mpo, self.environ, self.carry)
         return mps
 
 
@@ -1548,14 +1573,14 @@ def _householder_sites(mps):
 _CARRY = threading.local()
 
 
-def _carry_environ(mps, mpo, environ):
+def _carry_environ(mps, mpo, environ, holder=_CARRY):
     ahead = "R" if mps.to_right else "L"
     environ.drop("L" if ahead == "R" else "R")
     # the take-over test compares the MPO sites as OBJECTS and by their content versions (Mpo.site_version: a host
     # snapshot per site): a site replaced (as try_swap_site does) or edited in place (a time-dependent Hamiltonian) drops
     # the carried environments AND the cached device copy of that site - the caller's arrays are left as they are
     sites = list(mpo._mp) if hasattr(mpo, "_mp") else None
-    _CARRY.slot = (mpo, sites, ahead, environ, list(mps._mp), _mpo_fingerprint(mpo, sites))
+    holder.slot = (mpo, sites, ahead, environ, list(mps._mp), _mpo_fingerprint(mpo, sites))
 
 
 def _mpo_fingerprint(mpo, sites):
@@ -1567,16 +1592,17 @@ def _mpo_fingerprint(mpo, sites):
 def clear_evolve_cache():
     """Drop the environments the calling thread's last TDVP-PS step left for the next one (they pin one set of
     environments and the site list in HBM until that thread evolves again).  ``MPSE_ENV_CARRY=0`` disables the
-    take-over altogether."""
+    take-over altogether.  Also drops the carried environments of the calling thread's ``evolve_batch``."""
     _CARRY.slot = None
+    _CARRY.batch = []
 
 
 Mps.clear_evolve_cache = staticmethod(clear_evolve_cache)
 
 
-def _carried_environ(mps, mpo, ahead):
-    slot = getattr(_CARRY, "slot", None)
-    _CARRY.slot = None
+def _carried_environ(mps, mpo, ahead, holder=_CARRY):
+    slot = getattr(holder, "slot", None)
+    holder.slot = None
     if slot is None or os.environ.get("MPSE_ENV_CARRY", "1") == "0":
         return None
     cmpo, cmpo_sites, cahead, environ, csites, cprint = slot
