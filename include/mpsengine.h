@@ -304,6 +304,9 @@ int mpse_expm_lanczos_batch_stats(mpse_ctx* ctx, int64_t* batched_members, int64
  *               (the reference compresses vectors to those entries on the host, mps/gs.py:260, 520-523)
  *   guess     : nguess start vectors of n elements each, contiguous (device);  x_out: nroots vectors (device)
  *   e_host    : nroots eigenvalues;  max_space <= 0 selects 12 + 3 (nroots - 1), max_cycle <= 0 selects 100
+ *   1 <= nroots <= 16 and max_space + nroots + 1 <= 80, else MPSE_ERR_ARG (both default spaces fit every nroots)
+ * When fewer than nroots eigenpairs exist in the masked space, the missing ones come back as NaN in e_host and zero
+ * vectors in x_out.  No start vector left after the mask and the lindep test: MPSE_ERR_ARG.
  * The subspace matrix grows by one batched reduction per new vector; subspace eigenproblems run on the host.
  * Synchronous. */
 int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, const void* hdiag_f64,

@@ -165,6 +165,50 @@ def hop_dense(ltensor, rtensor, cmo):
     return h.reshape(n, n)
 
 
+def hop_apply2(ltensor, rtensor, cmo, c):
+    """Two-layer effective Hamiltonian of the (H - omega)^2 functional (mps/hop_expr.py:24-52) applied to the centre.
+
+    L (Dl_in, wl, wl, Dl_out), R (Dr_in, wr, wr, Dr_out): the centre enters through the first bond index and leaves
+    through the last.  The same MPO sites serve both layers: the centre's physical leg meets the second index of a
+    site in the first layer, whose third index then meets the second index of the same site in the second layer
+    (abcd,befg,cfhi,jgik,aej->dhk ; two sites abcd,befg,cfhi,gjkl,ikmn,olnp,aejo->dhmp)."""
+    l = np.asarray(ltensor)
+    r = np.asarray(rtensor)
+    c = np.asarray(c)
+    if len(cmo) == 1:
+        w = np.asarray(cmo[0])
+        t = np.tensordot(c, l, ([0], [0]))                          # e j | b c d
+        t = np.tensordot(t, w, ([2, 0], [0, 1]))                    # j c d | f g       (first layer)
+        t = np.tensordot(t, w, ([1, 3], [0, 1]))                    # j d g | h i       (second layer)
+        return np.tensordot(t, r, ([0, 2, 4], [0, 1, 2]))           # d h k
+    if len(cmo) == 2:
+        w0 = np.asarray(cmo[0])
+        w1 = np.asarray(cmo[1])
+        t = np.tensordot(c, l, ([0], [0]))                          # e j o | b c d
+        t = np.tensordot(t, w0, ([3, 0], [0, 1]))                   # j o c d | f g
+        t = np.tensordot(t, w0, ([2, 4], [0, 1]))                   # j o d g | h i
+        t = np.tensordot(t, w1, ([3, 0], [0, 1]))                   # o d h i | k l
+        t = np.tensordot(t, w1, ([3, 4], [0, 1]))                   # o d h l | m n
+        t = np.tensordot(t, r, ([0, 3, 5], [0, 1, 2]))              # d h m p
+        return t
+    raise ValueError("two-layer centres have one or two sites")
+
+
+def hop_dense2(ltensor, rtensor, cmo):
+    """Dense two-layer effective Hamiltonian (row = out index, col = in index) of ``hop_apply2``."""
+    l = np.asarray(ltensor)
+    r = np.asarray(rtensor)
+    if len(cmo) == 1:
+        h = np.einsum("abcd,befg,cfhi,jgik->dhkaej", l, cmo[0], cmo[0], r, optimize=True)
+    elif len(cmo) == 2:
+        h = np.einsum("abcd,befg,cfhi,gjkl,ikmn,olnp->dhmpaejo", l, cmo[0], cmo[0], cmo[1], cmo[1], r,
+                      optimize=True)
+    else:
+        raise ValueError("two-layer centres have one or two sites")
+    n = int(np.prod(h.shape[: h.ndim // 2]))
+    return h.reshape(n, n)
+
+
 # ---------------------------------------------------------------------------
 # Lanczos exponential
 # ---------------------------------------------------------------------------

@@ -18,7 +18,10 @@ typedef std::complex<double> cd;
 
 namespace {
 
-constexpr int DV_MAX = 48;          // most basis vectors ever held
+// most basis vectors ever held: max_space + nroots + 1 for the largest default space, 12 + 3 (nroots - 1) at
+// nroots = 16 (57 + 16 + 1 = 74).  Sizes DvCoefs (a by-value kernel argument, 2 * 80 * 8 = 1280 bytes), hsub, the
+// partial sums and the vals slots.
+constexpr int DV_MAX = 80;
 constexpr int DV_RED_MAX_BLOCKS = 256;
 
 inline int dv_blocks(int64_t n_doubles) {
@@ -359,7 +362,9 @@ extern "C" int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int t
   if (h->nsite == 2) n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
   if (n <= 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "davidson: empty centre tensor");
   if (max_space <= 0) max_space = 12 + (nroots - 1) * 3;
-  if (max_space + nroots + 1 > DV_MAX) return mpse_fail(ctx, MPSE_ERR_ARG, "davidson: max_space too large");
+  if (max_space + nroots + 1 > DV_MAX)
+    return mpse_fail(ctx, MPSE_ERR_ARG, "davidson: max_space too large (max_space + nroots + 1 = %d > %d)",
+                     max_space + nroots + 1, DV_MAX);
   if (max_cycle <= 0) max_cycle = 100;
   const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
@@ -478,7 +483,17 @@ extern "C" int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int t
     int added = 0;
     for (int r : todo) {
       if (m >= cap - 1) break;
-      MPSE_TRY(mpse_davidson_precond(ctx, dtype, t, rs(r), hdiag_f64, mask_f64, n, ew[r], shift));
+      if (rn[r] * rn[r] <= lindep) continue;   // only residuals above lindep are preconditioned (davidson.py:381-397)
+      // the preconditioned residual is normalised BEFORE it is orthogonalised (davidson.py:386, 393), so that lindep
+      // bounds the squared norm of what is new in a unit vector; left at the size of the residual, a direction with
+      // |r| ~ 1e-6 fell under lindep = 1e-14 and ended the run above the convergence threshold.  The free slot m
+      // takes the raw direction, t the unit vector, and slot m again its orthonormalised remainder.
+      MPSE_TRY(mpse_davidson_precond(ctx, dtype, d.v(m), rs(r), hdiag_f64, mask_f64, n, ew[r], shift));
+      MPSE_TRY(d.dots(d.v(m), 1, d.v(m), d.vals + 2 * DV_MAX));
+      hipLaunchKernelGGL(k_scale_rsqrt, dim3(ew_blocks(n * (cplx ? 2 : 1))), dim3(256), 0, ctx->stream, (double*)t,
+                         (const double*)d.v(m), nullptr, nullptr, (long long)(n * (cplx ? 2 : 1)),
+                         (const double*)(d.vals + 2 * DV_MAX));
+      MPSE_HIP(ctx, hipGetLastError());
       MPSE_TRY(d.orthonormalise(t, nullptr, d.V, nullptr, m, d.v(m), nullptr));
       if (nroots == 1) {
         pending_check = true;      // verified at the top of the next cycle, together with its other read-backs

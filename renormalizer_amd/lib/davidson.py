@@ -8,10 +8,32 @@ import numpy as np
 from ..engine import get_engine
 from ..mps.hop_expr import Hop
 
+# limits of mpse_davidson (renormalizer_amd/csrc/mpse_davidson.hip): 1 <= nroots <= MAX_ROOTS, and the basis of
+# max_space + nroots + 1 vectors fits in MAX_BASIS
+MAX_ROOTS = 16
+MAX_BASIS = 80
+
+
+def default_max_space(nroots):
+    """The engine's default restart space, 12 + 3 (nroots - 1) (davidson.py of the reference)."""
+    return 12 + 3 * (nroots - 1)
+
+
+def check_limits(nroots, max_space=None):
+    """ValueError unless the engine's Davidson accepts ``nroots`` roots in a space of ``max_space`` vectors (None or
+    <= 0: the default space)."""
+    if not 1 <= nroots <= MAX_ROOTS:
+        raise ValueError(f"davidson: nroots = {nroots}, the engine solves 1 to {MAX_ROOTS} roots")
+    space = default_max_space(nroots) if max_space is None or max_space <= 0 else int(max_space)
+    if space + nroots + 1 > MAX_BASIS:
+        raise ValueError(f"davidson: max_space = {space} with nroots = {nroots} needs {space + nroots + 1} basis "
+                         f"vectors, the engine holds at most {MAX_BASIS}")
+
 
 def _solve(hop, guesses, hdiag, nroots, mask, tol, max_cycle, max_space, lindep, shift):
     if not isinstance(hop, Hop):
         raise TypeError("davidson: the operator must be an effective-Hamiltonian closure from hop_expr")
+    check_limits(nroots, max_space)
     eng = get_engine()
     cplx = hop.operator_is_complex or any(g.is_complex for g in guesses)
     dt = np.complex128 if cplx else np.float64

@@ -14,7 +14,7 @@ import logging
 import numpy as np
 
 from ..engine import get_engine, idx1
-from ..lib.davidson import davidson, davidson_multi
+from ..lib.davidson import MAX_ROOTS, davidson, davidson_multi
 from ..utils import CompressConfig, CompressCriteria
 from .hop_expr import hop_expr
 from .lib import Environ
@@ -114,6 +114,10 @@ def eigh_iterative(mps, qn_mask, ltensor, rtensor, cmo, cguess, twolayer=False):
                 tested), a restart space of max(15, 2 nroots + 7) vectors and the shift-free preconditioner
                 (``shift`` large against ``e`` is not available, so x / (hdiag - e + 1e-4) is kept: same fixed
                 point).  Same eigenpairs to the solver tolerance; iteration counts differ from the library's."""
+    nroots = mps.optimize_config.nroots
+    if nroots > MAX_ROOTS:
+        raise ValueError(f"optimize_config.nroots = {nroots}: the iterative eigensolver finds at most {MAX_ROOTS} "
+                         f"roots")
     eng = get_engine()
     inverse = float(mps.optimize_config.inverse)
     if inverse != 1.0:
@@ -130,7 +134,6 @@ def eigh_iterative(mps, qn_mask, ltensor, rtensor, cmo, cguess, twolayer=False):
     hop = hop_expr(ltensor, rtensor, cmo, cshape, twolayer)
     hdiag = _hdiag(eng, hop.l, hop.r, hop.cmo, twolayer)
     mask = eng.asdevice(qn_mask.astype(np.float64))
-    nroots = mps.optimize_config.nroots
     if hop.operator_is_complex:
         # complex MPO / environments with a real centre: the iteration runs in complex128 (NumPy promotes silently
         # in the reference, gs.py:520-538)
