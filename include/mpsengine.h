@@ -176,6 +176,25 @@ typedef struct {
 
 int mpse_gemm(mpse_ctx* ctx, const mpse_gemm_desc* desc, const void* A, const void* B, void* C);
 
+/* How the contraction kernel was launched: cumulative counts of this context, counted on the host where the launcher
+ * decides (a call that returns early or is refused counts nothing; a deferred call counts when it runs).  counts[i]
+ * for i < min(n, 13), in this order:
+ *    0  launches of the kernel by mpse_gemm and the contraction plans (grouped launches excepted)
+ *    1  of them through the general kernel (a two-level K index, a negative stride or an operand span of 4 GB or more)
+ *    2  eight waves per workgroup (one workgroup per compute unit or fewer, at least two K tiles)
+ *    3  split-K, batch == 1 (slices of one product run slice-fastest; a reduction launch follows)
+ *    4  split-K, batch > 1
+ *    5  die grouping 1: the workgroups of one die own whole tile rows
+ *    6  die grouping 2: whole tile columns
+ *    7  tile columns skewed by the tile row (unsplit, unsorted, not die grouped)
+ *    8  tile launch order sorted from the occupancy masks (block-sparse, batch == 1, many tiles)
+ *    9  occupancy masks read by the kernel (skip_zero_tiles; the general kernel visits every K tile)
+ *   10  of them read from global memory instead of LDS (more than 64 mask words, K > 8192)
+ *   11  grouped launches (the folded one-site matvec)
+ *   12  of them with every tile halved between two workgroups
+ * Diagnostics for tests (which path ran); no device work. */
+int mpse_gemm_path_stats(mpse_ctx* ctx, int64_t* counts, int n);
+
 /* out = transpose of `in` viewed as (d0,d1,d2) -> (d0,d2,d1); optional conjugation. */
 int mpse_transpose_inner(mpse_ctx* ctx, int dtype, void* out, const void* in,
                          int64_t d0, int64_t d1, int64_t d2, int conj);

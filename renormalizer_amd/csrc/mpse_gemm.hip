@@ -1518,6 +1518,21 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
   } while (0)
   // one workgroup per compute unit (or fewer): eight waves on the tile instead of four
   const bool wide = nblk <= n_cu && nkt_all >= 2;
+  {
+    long long* gp = ctx->gemm_paths;
+    const bool masked = ks && (g.amask || g.bmask);   // (the general kernel visits every K tile)
+    ++gp[mpse_ctx::GP_LAUNCH];
+    gp[mpse_ctx::GP_GENERAL] += !ks;
+    gp[mpse_ctx::GP_WIDE] += ks && wide;
+    gp[mpse_ctx::GP_SPLIT_B1] += g.ksplit > 1 && d->batch == 1;
+    gp[mpse_ctx::GP_SPLIT_BN] += g.ksplit > 1 && d->batch > 1;
+    gp[mpse_ctx::GP_DIE1] += g.die_group == 1;
+    gp[mpse_ctx::GP_DIE2] += g.die_group == 2;
+    gp[mpse_ctx::GP_SKEW] += g.skew && !g.perm && !g.die_group;
+    gp[mpse_ctx::GP_ORDER] += g.perm != nullptr;
+    gp[mpse_ctx::GP_MASK] += masked;
+    gp[mpse_ctx::GP_MASK_GLOBAL] += masked && g.nkw > 64;
+  }
   if (ca && cb)
     MPSE_LAUNCH(true, true);
   else if (ca)
@@ -1714,6 +1729,8 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, Matv
   }
   const dim3 grid((unsigned)nwg);
   const bool wide = nwg <= n_cu;
+  ++ctx->gemm_paths[mpse_ctx::GP_GROUPED];
+  ctx->gemm_paths[mpse_ctx::GP_GROUPED_SPLIT2] += gg.split2 != 0;
   if (ca) {
     if (wide)
       hipLaunchKernelGGL((k_gemm<true, true, true, 2, 1, true>), grid, dim3(512), 0, ctx->stream, g);
@@ -1737,6 +1754,12 @@ extern "C" int mpse_gemm(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, 
     return MPSE_OK;
   }
   return gemm_impl(ctx, d, A, B, C, d ? (d->skip_zero_tiles & 3) : 0, nullptr, nullptr);
+}
+
+extern "C" int mpse_gemm_path_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  for (int i = 0; i < n && i < mpse_ctx::GP_COUNT; ++i) counts[i] = ctx->gemm_paths[i];
+  return MPSE_OK;
 }
 
 int gemm_call(mpse_ctx* ctx, int dta, int dtb, int conja, int conjb, mpse_index ma, mpse_index ka, mpse_index kb,

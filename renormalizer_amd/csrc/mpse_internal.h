@@ -130,6 +130,12 @@ struct mpse_ctx {
     int Dl = 0, Dr = 0, w = 0, nsite = -1;
   } f0;
   long long f0_launches[2] = {0, 0};   // fused matvec launches: bond matrices, two-level sites
+  // launch decisions of the contraction kernel (mpse_gemm_path_stats; the order of include/mpsengine.h)
+  enum GemmPath {
+    GP_LAUNCH, GP_GENERAL, GP_WIDE, GP_SPLIT_B1, GP_SPLIT_BN, GP_DIE1, GP_DIE2, GP_SKEW, GP_ORDER, GP_MASK,
+    GP_MASK_GLOBAL, GP_GROUPED, GP_GROUPED_SPLIT2, GP_COUNT
+  };
+  long long gemm_paths[GP_COUNT] = {0};
   // mpse_block_qr: decompositions that took the Cholesky-QR path / that fell back from it to Householder
   long long qr_chol_calls = 0, qr_chol_fallbacks = 0, qr_calls = 0;
   // optimistic mode of the Cholesky-QR path (mpse_block_qr_optimistic): breakdowns raise this sticky device word

@@ -124,6 +124,7 @@ _SIGNATURES = {
     "mpse_defer_run": [C.c_void_p, C.c_int],
     "mpse_defer_discard": [C.c_void_p],
     "mpse_gemm": [C.c_void_p, C.POINTER(mpse_gemm_desc), C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpse_gemm_path_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_transpose_inner": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int],
     "mpse_env_update": [C.c_void_p, C.c_int, C.c_int, C.POINTER(mpse_dims), C.c_void_p, C.c_int, C.c_void_p,
                         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p],
@@ -466,6 +467,16 @@ class Engine:
         a, b = C.c_int64(), C.c_int64()
         self._check(self.lib.mpse_heff_fused_stats(self.ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    GEMM_PATHS = ("launches", "general", "eight_wave", "split_b1", "split_batched", "die_group1", "die_group2", "skew",
+                  "tile_order", "masks", "masks_global", "grouped", "grouped_split2")
+
+    def gemm_path_stats(self):
+        """{path: count}: how the contraction kernel was launched by this context, cumulative
+        (``mpse_gemm_path_stats``; the names follow the order of include/mpsengine.h)."""
+        v = (C.c_int64 * len(self.GEMM_PATHS))()
+        self._check(self.lib.mpse_gemm_path_stats(self.ctx, v, len(v)))
+        return dict(zip(self.GEMM_PATHS, (int(x) for x in v)))
 
     def block_qr_optimistic(self, on):
         """Optimistic mode of the Cholesky-QR path (``mpse_block_qr_optimistic``): breakdowns are not read back per
