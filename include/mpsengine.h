@@ -288,7 +288,12 @@ int mpse_heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C
  * expm_krylov as called at mps/mps.py:1300-1303, 1343-1346, 1377-1380 (same
  * recurrence without re-orthogonalisation, same stopping rule: successive
  * approximations allclose(rtol,atol) on even j > 3, breakdown at beta < 100 n eps).
- * Synchronous; *nvec receives the Krylov dimension. */
+ * Synchronous; *nvec receives the Krylov dimension.
+ * `out` may be `C` itself (the result then replaces the start vector on every path); an `out` that overlaps `C`
+ * without starting at the same address is refused with MPSE_ERR_ARG.  A zero or non-finite C is MPSE_ERR_ARG.  A
+ * nonzero C whose |C|^2 is subnormal or at least 1e300 is solved as 2^e C with its largest element in [1, 2) (atol
+ * scaled alike) and the result scaled back; inside that range the result for 2^k C is bitwise 2^k times the one for C
+ * with atol = 0, as long as no element involved leaves the normal range. */
 /* Optional, for the NEXT mpse_expm_lanczos on this context only: the tile-occupancy pattern of the centre tensor as
  * the sweep knows it from the quantum numbers (mps/mp.py:308-352: entry (a, sigma, b) can be non-zero only where the
  * bond and physical quantum numbers add up to the total) - the same for every Krylov vector of the solve, so the
@@ -312,6 +317,30 @@ int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff
 /* Cumulative counts of members solved by the batched kernels and of members that went through the single solve
  * (grouping, size, need_host, 64-vector limit).  Diagnostics for tests; either pointer may be NULL. */
 int mpse_expm_lanczos_batch_stats(mpse_ctx* ctx, int64_t* batched_members, int64_t* single_members);
+/* How the Lanczos solves of this context ran: cumulative counts, counted on the host where the solve decides (members
+ * solved by the batched kernels of mpse_expm_lanczos_batch count nothing here; the rest of a batch counts as single
+ * solves).  counts[i] for i < min(n, 18), in this order:
+ *    0  runs of the synchronous solve (centres of 256 elements or fewer, and every hand-over from the asynchronous
+ *       solve; a synchronous run that meets an out-of-range |C|^2 and restarts on the rescaled vector, 16, counts twice)
+ *    1  asynchronous solves (centres of more than 256 elements) finished on the device
+ *    2  hand-overs to the synchronous solve: need_host (|dt| * Gershgorin bound > 512) at the first check the host read
+ *    3  the same at a later check read by the host (an estimate of the solve was in `out` already)
+ *    4  hand-overs at the 64-vector limit of the asynchronous solve (or at max_dim below it)
+ *    5  solves ended by a breakdown (beta < 100 n eps) on the asynchronous path
+ *    6  the same on the synchronous path
+ *    7  synchronous solves that reached the full space (Krylov dimension == n) without a breakdown
+ *    8  solves ended by the convergence test (either path)
+ *    9  MPSE_ERR_NOCONV (max_dim reached)
+ *   10  merged first checks (the estimates of j = 4 and j = 6 formed in one pass; asynchronous path)
+ *   11  host waits of the asynchronous path
+ *   12  growths of the Krylov basis (either path)
+ *   13  asynchronous update launches that added a matvec result of two or more parts, or read a part mask
+ *   14  asynchronous update launches that applied the centre mask (mpse_expm_centre_mask) to the vectors
+ *   15  update launches with 8-byte accesses (an odd real length or a start vector off a 16-byte boundary; either path)
+ *   16  solves restarted on a start vector scaled by a power of two (|C|^2 out of the normal range)
+ *   17  hand-overs with out == C: C put back from its copy in the Krylov basis before the synchronous solve
+ * Diagnostics for tests (which path ran); no device work. */
+int mpse_expm_lanczos_path_stats(mpse_ctx* ctx, int64_t* counts, int n);
 
 /* Davidson eigensolver for the lowest nroots eigenpairs of the effective Hamiltonian, replaces
  * lib/davidson/davidson.py:154-441 as called at mps/gs.py:533-538 (diagonal preconditioner r / (hdiag - e + shift),

@@ -147,6 +147,12 @@ struct mpse_ctx {
   int* qr_words_dev = nullptr;
   // mpse_expm_lanczos_batch: members solved by the batched kernels / through the single solve (mpse_expm_lanczos_batch_stats)
   long long lz_batch_members = 0, lz_batch_single = 0;
+  // how the Lanczos solves of this context ran (mpse_expm_lanczos_path_stats; the order of include/mpsengine.h)
+  enum LzPath {
+    LP_SYNC, LP_ASYNC_DONE, LP_HOST_FIRST, LP_HOST_LATER, LP_LIMIT, LP_BD_ASYNC, LP_BD_SYNC, LP_FULL, LP_CONV,
+    LP_NOCONV, LP_MERGED, LP_WAITS, LP_GROW, LP_PARTS, LP_VMASK, LP_UNVEC, LP_RESCALE, LP_ALIAS_RESTART, LP_COUNT
+  };
+  long long lz_paths[LP_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

@@ -594,6 +594,9 @@ struct LzCtl {
   int pad[2];
 };
 constexpr int LZ_MAXM = 64;   // one wavefront holds the Krylov coefficients
+// |C|^2 of a start vector the unnormalised recurrence takes as it is: a normal double below 1e300 (1 / |C|^2 and the
+// squares of the matvec stay finite and keep all their digits); other nonzero vectors are scaled by a power of two first
+constexpr double LZ_N2_MIN = 2.2250738585072014e-308, LZ_N2_MAX = 1e300;
 
 // coef = |v| exp(dt T_m) e_1 for the Lanczos tridiagonal T_m (alpha_0.., beta_0..) by a scaled Taylor series, one lane
 // per component (lib/krylov/krylov.py:15-24 computes the same vector through eigh_tridiagonal).  Also applies the
@@ -624,7 +627,7 @@ __device__ __forceinline__ void lz_coefs(double* __restrict__ scal, int j, doubl
     __syncthreads();
   }
   const double n2 = scal[0];
-  if (!(n2 > 0.0) || !(n2 < 1e300)) {
+  if (!(n2 >= LZ_N2_MIN) || !(n2 < LZ_N2_MAX)) {
     if (lane == 0) {
       ctl->bad = 1;
       ctl->done = 1;
@@ -961,6 +964,7 @@ void keep_env_masks(SolveScope& sc, const mpse_heff* h) {
 }
 
 constexpr int LZ_FALLBACK = -77;   // internal: the asynchronous solve hands the problem to the synchronous one
+constexpr int LZ_BADSTART = -78;   // internal: |C|^2 outside [LZ_N2_MIN, LZ_N2_MAX) (expm_lanczos_rescaled decides)
 
 int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::complex<double> dt, const void* Cin, void* out,
                        double rtol, double atol, int max_dim, int* nvec, int64_t n) {
@@ -1071,6 +1075,15 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
 
   unsigned int* dflag = reinterpret_cast<unsigned int*>(ctx->dscratch + (size_t(1) << 16) - 8);
   void* prev = nullptr;
+  // The synchronous solve restarts from Cin.  Estimates of this solve may have gone to `out` already: when `out` is
+  // Cin, C is put back from its copy U_0 first (bitwise C; U_0 is never written after k_lz_start).
+  auto handover = [&]() -> int {
+    if (prev && out == Cin) {
+      ++ctx->lz_paths[mpse_ctx::LP_ALIAS_RESTART];
+      MPSE_TRY(mpse_memcpy_d2d(ctx, out, vec(0), size_t(n) * es));
+    }
+    return LZ_FALLBACK;
+  };
   bool waited = false;
   LzCtl hc;
   memset(&hc, 0, sizeof(hc));
@@ -1103,6 +1116,7 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
     }
     if (j + 2 > cap) {      // room for U_{j+1}
       int ncap = cap * 2 < limit + 1 ? cap * 2 : limit + 1;
+      ++ctx->lz_paths[mpse_ctx::LP_GROW];
       TmpBuf V2(ctx);
       MPSE_TRY(V2.alloc(size_t(ncap) * n * es));
       MPSE_TRY(mpse_memcpy_d2d(ctx, V2.p, V.p, size_t(cap) * n * es));
@@ -1114,6 +1128,9 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
     double* new_part = part_b2[(j + 1) & 1];
     double* cur_out = j == 0 ? scal : scal + 6 + 4 * (j - 1);
     const double* prev2 = j == 0 ? scal : (j == 1 ? scal : scal + 6 + 4 * (j - 2));
+    if (two || pmask) ++ctx->lz_paths[mpse_ctx::LP_PARTS];
+    if (!pmask && vmask) ++ctx->lz_paths[mpse_ctx::LP_VMASK];
+    if (!vec16) ++ctx->lz_paths[mpse_ctx::LP_UNVEC];
     bracket((j > 0 ? 4.0 : 3.0) * vbytes + (nparts - 1) * vbytes, [&] {
       if (vec16)
         hipLaunchKernelGGL(k_lanczos_update_u<true>, dim3(nb), dim3(RED_THREADS), 0, ctx->stream, (double*)vec(j + 1),
@@ -1138,6 +1155,7 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
     if (defer_first && check && !prev && j == 4 && j + 3 < limit) check = false;   // (its turn comes at j = 6)
     if (defer_first && check && !prev && j == 6) merged = true;
     if (check) {
+      if (merged) ++ctx->lz_paths[mpse_ctx::LP_MERGED];
       hipLaunchKernelGGL(k_lz_coefs, dim3(merged ? 2 : 1), dim3(64), 0, ctx->stream, scal, j, dt.real(), dt.imag(), tiny,
                          coef, ctl, (const double*)new_part, nb);
       void* dst = (prev == out) ? RES.p : out;
@@ -1172,10 +1190,17 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
           MPSE_TRY(publish_and_wait(ctx, reinterpret_cast<const double*>(ctl), int(sizeof(LzCtl) / sizeof(double)), 24));
         if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
         memcpy(&hc, ctx->pinned + 24, sizeof(LzCtl));
+        ++ctx->lz_paths[mpse_ctx::LP_WAITS];
+        const bool waited_before = waited;
         waited = true;
-        if (hc.bad) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: zero start vector");
-        if (hc.need_host) return LZ_FALLBACK;
+        if (hc.bad) return LZ_BADSTART;    // (done was raised with it: nothing went to `out`)
+        if (hc.need_host) {
+          ++ctx->lz_paths[waited_before ? mpse_ctx::LP_HOST_LATER : mpse_ctx::LP_HOST_FIRST];
+          return handover();
+        }
         if (hc.done) {
+          ++ctx->lz_paths[mpse_ctx::LP_ASYNC_DONE];
+          ++ctx->lz_paths[hc.forced_m > 0 ? mpse_ctx::LP_BD_ASYNC : mpse_ctx::LP_CONV];
           // the answer sits in the spare buffer (an even number of estimates): copied now - the host knows; before, a
           // conditional copy kernel was enqueued at every waited check
           if (hc.which == 1) MPSE_TRY(mpse_memcpy_d2d(ctx, out, RES.p, size_t(n) * es));
@@ -1183,7 +1208,10 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
         }
       }
     }
-    if (last) return LZ_FALLBACK;     // beyond one wavefront of coefficients (or no convergence): the synchronous solve decides
+    if (last) {     // beyond one wavefront of coefficients (or no convergence): the synchronous solve decides
+      ++ctx->lz_paths[mpse_ctx::LP_LIMIT];
+      return handover();
+    }
   }
   ctx->lz_hint[key] = hc.nvec;
   if (nvec) *nvec = hc.nvec;
@@ -1326,7 +1354,42 @@ int mpse_nrm2(mpse_ctx* ctx, int dtype, const void* x, int64_t n, double* out_ho
 }
 
 static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin,
-                              void* out, double rtol, double atol, int max_dim, int* nvec, bool async_first = true);
+                              void* out, double rtol, double atol, int max_dim, int* nvec, bool async_first = true,
+                              bool rescale_ok = true);
+
+// A start vector whose |C|^2 the recurrence cannot take as it is (LZ_BADSTART): zero or not finite - an error - or a
+// nonzero C whose squared norm is subnormal or beyond 1e300.  That one is solved as 2^e C, its largest element in
+// [1, 2), with atol scaled alike, and the result scaled back by 2^-e: the same stopping decisions, exact scalings.
+// Rare, and outside every iteration: C goes through the host once.
+static int expm_lanczos_rescaled(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im,
+                                 const void* Cin, void* out, double rtol, double atol, int max_dim, int* nvec, int64_t n,
+                                 const mpse_ctx::CMask& cmask, bool rescale_ok) {
+  const int64_t nd = n * (dtype == MPSE_C128 ? 2 : 1);
+  std::vector<double> hv(static_cast<size_t>(nd));
+  MPSE_TRY(mpse_memcpy_d2h(ctx, hv.data(), Cin, size_t(nd) * sizeof(double)));
+  double mx = 0.0;
+  for (double x : hv) {
+    if (!std::isfinite(x)) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: non-finite start vector");
+    mx = std::max(mx, std::fabs(x));
+  }
+  if (!(mx > 0.0)) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: zero start vector");
+  if (!rescale_ok) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: start vector out of range after scaling");
+  const int e = -std::ilogb(mx);
+  for (double& x : hv) x = std::ldexp(x, e);
+  TmpBuf S(ctx);
+  MPSE_TRY(S.alloc(size_t(nd) * sizeof(double)));
+  MPSE_TRY(mpse_memcpy_h2d(ctx, S.p, hv.data(), size_t(nd) * sizeof(double)));
+  ++ctx->lz_paths[mpse_ctx::LP_RESCALE];
+  ctx->cmask_pending = cmask;
+  const int st = expm_lanczos_solve(ctx, dtype, h, dt_re, dt_im, S.p, out, rtol, std::ldexp(atol, e), max_dim, nvec,
+                                    true, false);
+  if (st == MPSE_OK || st == MPSE_ERR_NOCONV) {   // (NOCONV leaves its last estimate in out as well)
+    hipLaunchKernelGGL((k_scal<false>), dim3(ew_blocks(nd)), dim3(256), 0, ctx->stream, (double*)out, (long long)nd,
+                       std::ldexp(1.0, -e), 0.0);
+    MPSE_HIP(ctx, hipGetLastError());
+  }
+  return st;
+}
 
 int mpse_expm_centre_mask(mpse_ctx* ctx, const void* mask_dev, int64_t nbytes) {
   if (!ctx || (nbytes > 0 && !mask_dev) || nbytes < 0) return MPSE_ERR_ARG;
@@ -1351,7 +1414,8 @@ int mpse_expm_lanczos(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re
 }
 
 static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin,
-                              void* out, double rtol, double atol, int max_dim, int* nvec, bool async_first) {
+                              void* out, double rtol, double atol, int max_dim, int* nvec, bool async_first,
+                              bool rescale_ok) {
   const bool cplx = dtype == MPSE_C128;
   if (!cplx && dt_im != 0.0)
     return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: complex time step needs a complex128 centre tensor");
@@ -1364,12 +1428,22 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
   if (h->nsite == 2) n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
   if (n <= 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "expm_lanczos: empty centre tensor");
   if (max_dim <= 0 || max_dim > 128) max_dim = 128;
+  const size_t es = dtype_size(dtype);
+  {   // out may be C itself (every path reads C before it writes out, or restores it first), not part of it
+    const char *c0 = static_cast<const char*>(Cin), *o0 = static_cast<const char*>(out);
+    const size_t bytes = size_t(n) * es;
+    if (o0 != c0 && o0 < c0 + bytes && c0 < o0 + bytes)
+      return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: out overlaps C without being C");
+  }
+  const mpse_ctx::CMask cmask = ctx->cmask_pending;   // (for a rescaled restart)
   if (async_first && lanczos_async_enabled() && n > 256) {
     const int st = expm_lanczos_async(ctx, dtype, h, std::complex<double>(dt_re, dt_im), Cin, out, rtol, atol, max_dim,
                                       nvec, n);
+    if (st == LZ_BADSTART)
+      return expm_lanczos_rescaled(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, n, cmask, rescale_ok);
     if (st != LZ_FALLBACK) return st;
   }
-  const size_t es = dtype_size(dtype);
+  ++ctx->lz_paths[mpse_ctx::LP_SYNC];
   const int64_t nd = n * (cplx ? 2 : 1);  // doubles per vector
   const std::complex<double> dt(dt_re, dt_im);
   const double tiny = 100.0 * double(n) * 2.220446049250313e-16;
@@ -1420,7 +1494,7 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
   MPSE_HIP(ctx, hipGetLastError());
 
   std::vector<double> alpha, beta;
-  double nrmv = 0.0;
+  double nrmv = 0.0, nrm2 = 0.0;
   bool have_res = false;
   void* res_prev = nullptr;
   int pending_m = 0;   // Krylov dimension of a first estimate whose formation is postponed to the next check
@@ -1431,6 +1505,7 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
     MPSE_TRY(publish_and_wait(ctx, scal, cnt, 16));
     if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
     const double* p = ctx->pinned + 16;
+    nrm2 = p[0];
     nrmv = sqrt(p[0]);
     for (int j = (int)alpha.size(); j <= upto; ++j) {
       alpha.push_back(p[4 + 4 * j]);
@@ -1481,13 +1556,16 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
       hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(RED_THREADS), 0, ctx->stream, part_a, nb, scal + 4 + 4 * j,
                          (const int*)nullptr);
       MPSE_TRY(fetch(j));
-      if (!(nrmv > 0)) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: zero start vector");
+      if (!(nrm2 >= LZ_N2_MIN && nrm2 < LZ_N2_MAX))
+        return expm_lanczos_rescaled(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, n, cmask, rescale_ok);
       int bd = breakdown_at(j - 1);
       const int m = bd >= 0 ? bd + 1 : j + 1;
+      ++ctx->lz_paths[bd >= 0 ? mpse_ctx::LP_BD_SYNC : mpse_ctx::LP_FULL];
       MPSE_TRY(finish(m, out, nullptr, nullptr));
       if (nvec) *nvec = m;
       return MPSE_OK;
     }
+    if (!vec16) ++ctx->lz_paths[mpse_ctx::LP_UNVEC];
     mpse_ctx::ProfRec urec;
     const bool upt = prof_begin(ctx, 4, 0.0, (j > 0 ? 4.0 : 3.0) * vbytes, &urec);
     if (vec16)
@@ -1517,9 +1595,11 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
     MPSE_HIP(ctx, hipGetLastError());
     if (sync_now) {
       MPSE_TRY(fetch(j));
-      if (!(nrmv > 0)) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: zero start vector");
+      if (!(nrm2 >= LZ_N2_MIN && nrm2 < LZ_N2_MAX))
+        return expm_lanczos_rescaled(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, n, cmask, rescale_ok);
       const int bd = breakdown_at(j);
       if (bd >= 0) {
+        ++ctx->lz_paths[mpse_ctx::LP_BD_SYNC];
         // what the reference would have returned at iteration bd - unless one of its convergence tests
         // (even jj > 3, jj < bd) had fired earlier: the deferred first estimate cannot fire (nothing to compare
         // with), later ones all ran here already and failed
@@ -1551,6 +1631,7 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
         MPSE_TRY(finish(j + 1, dst, res_prev, &flag));
         res_prev = dst;
         if (flag == 0) {
+          ++ctx->lz_paths[mpse_ctx::LP_CONV];
           if (dst != out) MPSE_TRY(mpse_memcpy_d2d(ctx, out, dst, size_t(n) * es));
           if (nvec) *nvec = j + 1;
           return MPSE_OK;
@@ -1558,11 +1639,13 @@ static int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, doub
       }
     }
     if (last) {
+      ++ctx->lz_paths[mpse_ctx::LP_NOCONV];
       if (nvec) *nvec = j + 1;
       if (res_prev && res_prev != out) MPSE_TRY(mpse_memcpy_d2d(ctx, out, res_prev, size_t(n) * es));
       return mpse_fail(ctx, MPSE_ERR_NOCONV, "expm_lanczos: no convergence within %d Krylov vectors", max_dim);
     }
     if (j + 2 > cap) {  // grow the Krylov basis (krylov.py:63-68)
+      ++ctx->lz_paths[mpse_ctx::LP_GROW];
       int ncap = cap * 2;
       TmpBuf V2(ctx);
       MPSE_TRY(V2.alloc(size_t(ncap) * n * es));
@@ -1828,6 +1911,11 @@ int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff
       if (hi.nsite != 0 && hi.nsite != 1) continue;
       if (n <= 256) continue;
       if (!((cplx || n % 2 == 0) && (reinterpret_cast<uintptr_t>(C[i]) & 15) == 0)) continue;
+      {   // (an out that overlaps C without being C: the single solve refuses it)
+        const char *c0 = static_cast<const char*>(C[i]), *o0 = static_cast<const char*>(out[i]);
+        const size_t bytes = size_t(n) * (cplx ? 16 : 8);
+        if (o0 != c0 && o0 < c0 + bytes && c0 < o0 + bytes) continue;
+      }
       size_t rtb = 0;
       int np = 0, nbd = 0;
       if (!heff_small_batch_plan(&hi, dtype, n, LZB_DOT_CAP, &rtb, &np, &nbd)) continue;
@@ -1887,6 +1975,12 @@ int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff
       break;
     }
   return defer_replay(ctx, status);
+}
+
+int mpse_expm_lanczos_path_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  for (int i = 0; i < n && i < mpse_ctx::LP_COUNT; ++i) counts[i] = ctx->lz_paths[i];
+  return MPSE_OK;
 }
 
 int mpse_expm_lanczos_batch_stats(mpse_ctx* ctx, int64_t* batched_members, int64_t* single_members) {

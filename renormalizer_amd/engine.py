@@ -139,6 +139,7 @@ _SIGNATURES = {
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int,
                                 C.POINTER(C.c_int)],
     "mpse_expm_lanczos_batch_stats": [C.c_void_p, _i64p, _i64p],
+    "mpse_expm_lanczos_path_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_davidson": [C.c_void_p, C.c_int, C.POINTER(mpse_heff), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                       C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _dblp, C.c_void_p,
                       C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -455,6 +456,17 @@ class Engine:
         a, b = C.c_int64(), C.c_int64()
         self._check(self.lib.mpse_expm_lanczos_batch_stats(self.ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    LANCZOS_PATHS = ("sync", "async_done", "host_first", "host_later", "limit", "breakdown_async", "breakdown_sync",
+                     "full_space", "converged", "noconv", "merged_first", "host_waits", "basis_growths", "update_parts",
+                     "update_vmask", "update_unvec", "rescaled", "alias_restart")
+
+    def lanczos_path_stats(self):
+        """{path: count}: how the Lanczos solves of this context ran, cumulative (``mpse_expm_lanczos_path_stats``;
+        the names follow the order of include/mpsengine.h)."""
+        v = (C.c_int64 * len(self.LANCZOS_PATHS))()
+        self._check(self.lib.mpse_expm_lanczos_path_stats(self.ctx, v, len(v)))
+        return dict(zip(self.LANCZOS_PATHS, (int(x) for x in v)))
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""

@@ -15,7 +15,8 @@ from ..mps.hop_expr import Hop
 
 def expm_krylov(Afunc, dt, vstart, block_size=50, rtol=1e-5, atol=1e-8, out=None):
     """``out``: (engine Hop only) an existing device tensor of the result's shape and dtype to receive it - calls
-    recorded with ``Engine.recording`` refer to it before the solve has run."""
+    recorded with ``Engine.recording`` refer to it before the solve has run.  ``out`` may be the start vector itself
+    (the result then replaces it); an ``out`` that only partly overlaps it is refused (mpse_expm_lanczos)."""
     eng = get_engine()
     dt = complex(dt)
     v = eng.asdevice(vstart)
