@@ -361,6 +361,47 @@ int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, co
                   const void* mask_f64, int nroots, int nguess, const void* guess, double tol, int max_cycle,
                   int max_space, double lindep, double shift, double* e_host, void* x_out, int* ncycle, int* nmatvec);
 
+/* Preconditioned conjugate gradients for a Hermitian positive definite projected operator, replaces the
+ * scipy.sparse.linalg.cg call of cv/zerot.py:231-290 (host vectors, one Python closure per matvec) for the correction
+ * vector ((H - e0 - omega)^2 + eta^2) x = b.  Vectors, scalars and the convergence decision stay on the device; the host
+ * enqueues iterations ahead and reads a pinned copy of the control block every fourth iteration.
+ *   A v       = mask * (Heff v) + shift * v, Heff applied by mpse_heff_apply2 (twolayer != 0) or mpse_heff_apply
+ *   diag_f64  : preconditioner z = r / diag (n doubles, device; the caller has added `shift`; every entry > 0, else
+ *               MPSE_ERR_ARG); NULL: plain conjugate gradients
+ *   mask_f64  : 0/1 weights of the symmetry-allowed entries or NULL (as mpse_davidson); b is read through the mask
+ *               and the start vector is masked in place on entry
+ *   x         : start vector on entry, solution on return (device); must not overlap b
+ *   tol       : stop when |r| <= tol |b| (scipy's rule with atol = 0, cv/zerot.py:288)
+ *   max_iter  : <= 0 selects 10 n (scipy's default).  Not converged within it: MPSE_ERR_NOCONV, x is the last iterate
+ *               and the three outputs are filled
+ *   iters_host, relres_host (|r| / |b| of the recurrence), lvalue_host (Re(x^H A x) - 2 Re(b^H x) of the returned x,
+ *               formed as -Re(b^H x) - Re(r^H x) in the last update pass: the reference spends one more matvec on it,
+ *               cv/zerot.py:296, which its hop count, taken before, does not include: that count is the matvec of
+ *               the start residual plus the iterations, *iters_host + 1 here); each may be NULL
+ * b == 0 under the mask: x = 0, zero iterations, MPSE_OK.  A curvature p^H A p that is not positive (operator not
+ * positive definite, or NaN) stops the solve with MPSE_ERR_ARG; x is the iterate before that step.  Once the decision
+ * has fallen on the device every launch the host has enqueued past it returns at once, so x is the iterate of the
+ * deciding iteration.  MPSE_F64 and MPSE_C128 (conjugated dot products).  Synchronous. */
+int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const void* diag_f64,
+             const void* mask_f64, const void* b, void* x, double tol, int max_iter, int* iters_host,
+             double* relres_host, double* lvalue_host);
+/* What the mpse_pcg solves of this context did, cumulative: counts[i], i < n, receives
+ *    0  solves that reached a decision on the device (a call that fails on an argument check of the host, an
+ *       allocation or the runtime is not counted; one refused for its diagonal is counted here and under no ending)
+ *    1  iterations (sum of the reported iteration counts)
+ *    2  matvecs issued by iterations (the one of the start residual b - A x0 is not counted): iterations plus what the
+ *       host had enqueued past the decision
+ *    3  host waits (reads of the pinned control block)
+ *    4  solves ended by the tolerance (b == 0 included)
+ *    5  solves ended by max_iter (MPSE_ERR_NOCONV)
+ *    6  solves ended by a non-positive curvature (MPSE_ERR_ARG)
+ *    7  two-layer solves
+ *    8  masked solves
+ *    9  not a count: the number of iterations between two host waits (the compile-time constant of mpse_pcg.hip;
+ *       entry 2 exceeds entry 1 by at most this number - 1 per solve that ended by the tolerance or max_iter)
+ * Diagnostics for tests; no device work. */
+int mpse_pcg_stats(mpse_ctx* ctx, int64_t* counts, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

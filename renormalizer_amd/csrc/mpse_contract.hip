@@ -597,7 +597,7 @@ extern "C" int mpse_env_update_multi(mpse_ctx* ctx, int dtype, int domain, const
   return run_plan(ctx, dtype, p, bufs);
 }
 
-extern "C" int mpse_heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out) {
+int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc) {
   if (!ctx || !h || !C || !out || !h->L || !h->R || !h->W0) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (dtype != MPSE_C128 && (h->l_dtype == MPSE_C128 || h->r_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
@@ -610,7 +610,11 @@ extern "C" int mpse_heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, co
   bufs[B_W1] = h->W1;
   bufs[B_C] = C;
   bufs[B_OUT] = out;
-  return run_plan(ctx, dtype, p, bufs);
+  return run_plan(ctx, dtype, p, bufs, sc);
+}
+
+extern "C" int mpse_heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out) {
+  return heff_apply2(ctx, dtype, h, C, out, nullptr);
 }
 
 extern "C" int mpse_env_unit_channel(mpse_ctx* ctx, int dtype, const void* env, int64_t D, int64_t w, double tol,

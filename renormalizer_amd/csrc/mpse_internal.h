@@ -153,6 +153,12 @@ struct mpse_ctx {
     LP_NOCONV, LP_MERGED, LP_WAITS, LP_GROW, LP_PARTS, LP_VMASK, LP_UNVEC, LP_RESCALE, LP_ALIAS_RESTART, LP_COUNT
   };
   long long lz_paths[LP_COUNT] = {0};
+  // what the conjugate-gradient solves of this context did (mpse_pcg_stats; the order of include/mpsengine.h)
+  enum PcgStat {
+    PS_SOLVES, PS_ITERS, PS_MATVECS, PS_WAITS, PS_END_TOL, PS_END_MAXITER, PS_END_CURVATURE, PS_TWOLAYER, PS_MASKED,
+    PS_COUNT
+  };
+  long long pcg_stats[PS_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 
@@ -328,6 +334,8 @@ struct ProductReq {
 // The matvec behind mpse_heff_apply, for a caller inside a solve (sc) and / or with requests (mv); both may be null
 int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
                MatvecReq* mv);
+// The two-layer matvec behind mpse_heff_apply2, for a caller inside a solve (sc may be null)
+int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc);
 // One-launch matvec of small 0- / 1-site centres (mpse_small.hip); *taken says whether it ran (else: the plans)
 int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
                    MatvecReq* mv, bool* taken);

@@ -1,0 +1,416 @@
+// Preconditioned conjugate gradients on the projected centre problem, vectors and decision resident on the device:
+// replaces the scipy.sparse.linalg.cg call of cv/zerot.py:231-290 (a Python closure per matvec on host vectors).
+//
+//   A v = mask * (Heff v) + shift * v          (Heff: mpse_heff_apply, or mpse_heff_apply2 for the (H - omega)^2 form)
+//   z   = r / diag                             (diag == NULL: z = r)
+//
+// One iteration is the matvec plus three vector launches:
+//   k_pcg_q     q = mask * y + shift * p, partial sums of p^H q
+//   k_pcg_step  alpha = (r^H z) / (p^H q) from the partials; x += alpha p; r -= alpha q; partial sums of r^H z, r^H r
+//               (z = r / diag formed on the fly, never stored) and of b^H x, r^H x for the functional
+//   k_pcg_dir   beta from the partials; p = z + beta p; workgroup 0 takes the decision (tolerance, iteration limit)
+//               and, at the iterations the host waits for, copies the control block to its pinned mirror
+// Every consumer re-sums the producer's per-block partials in the same order (sum_partials, mpse_device.h), so all
+// workgroups of a launch agree bitwise on alpha, beta and on a non-positive curvature, and no scalar leaves the device
+// between iterations.  Once PcgCtl::done is raised every later launch of the solve returns at once (the contractions of
+// the matvec through SolveScope::skip): x is final at the deciding iteration whatever the host has enqueued since.
+#include <cmath>
+
+#include "mpse_cx.h"
+#include "mpse_device.h"
+#include "mpse_internal.h"
+
+namespace {
+
+constexpr int PCG_K = 4;        // the host reads the pinned control block every PCG_K iterations: at most PCG_K - 1
+                                // matvecs are enqueued past the decision
+constexpr int PCG_SLOT = 40;    // pinned doubles [40, 48): the mirror of the control block
+
+enum { PCG_WHY_NONE = 0, PCG_WHY_TOL = 1, PCG_WHY_MAXITER = 2, PCG_WHY_CURVATURE = 3, PCG_WHY_DIAG = 4, PCG_WHY_ZERO_B = 5 };
+
+struct PcgCtl {
+  int done;        // decision has fallen: later launches do nothing
+  int status;      // MPSE_OK / MPSE_ERR_NOCONV / MPSE_ERR_ARG
+  int iters;       // iterations behind the x that is returned
+  int why;         // PCG_WHY_*
+  double relres2;  // |r|^2 / |b|^2 of that x
+  double lvalue;   // Re(x^H A x) - 2 Re(b^H x) = -Re(b^H x) - Re(r^H x) with r = b - A x
+  double bb;       // |mask * b|^2
+  double pad[3];
+};
+static_assert(sizeof(PcgCtl) == 8 * sizeof(double), "control block = 8 doubles");
+constexpr int PCG_CW = int(sizeof(PcgCtl) / sizeof(double));
+
+__device__ __forceinline__ void pcg_publish(const PcgCtl* ctl, double* pub, volatile double* seq_slot, double seq) {
+  const double* src = reinterpret_cast<const double*>(ctl);
+  for (int i = 0; i < PCG_CW; ++i) pub[i] = src[i];
+  __threadfence_system();
+  *seq_slot = seq;
+  __threadfence_system();
+}
+
+__device__ __forceinline__ double2 scale2(double2 v, double s) { return make_double2(v.x * s, v.y * s); }
+__device__ __forceinline__ double re_dotc(double2 a, double2 b) { return a.x * b.x + a.y * b.y; }   // Re conj(a) b
+
+// Entry: clears the control block, masks the start vector in place, partial sums of |mask * b|^2 and the number of
+// diagonal entries that are not positive (second slot of the pair).
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_prep(double* __restrict__ x, const double* __restrict__ b,
+                                                          const double* __restrict__ mask,
+                                                          const double* __restrict__ diag, long long n,
+                                                          double* __restrict__ part_bb, PcgCtl* ctl) {
+  if (blockIdx.x == 0 && threadIdx.x < PCG_CW) reinterpret_cast<double*>(ctl)[threadIdx.x] = 0.0;
+  double bb = 0, bad = 0;
+  const long long stride = (long long)gridDim.x * RED_THREADS;
+  for (long long i = (long long)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride) {
+    const double m = mask ? mask[i] : 1.0;
+    const double2 bv = scale2(Cx<CPLX>::ld(b, i), m);
+    bb += re_dotc(bv, bv);
+    if (mask) Cx<CPLX>::st(x, i, scale2(Cx<CPLX>::ld(x, i), m));
+    if (diag && !(diag[i] > 0.0)) bad += 1.0;
+  }
+  block_allsum2(bb, bad);
+  if (threadIdx.x == 0) {
+    part_bb[2 * blockIdx.x] = bb;
+    part_bb[2 * blockIdx.x + 1] = bad;
+  }
+}
+
+// r = b - A x0 from y = Heff x0, p = z = r / diag; partial sums (r^H z, r^H r) and (b^H x, r^H x).  A right-hand side
+// that vanishes under the mask ends the solve here with x = 0; a diagonal entry that is not positive with MPSE_ERR_ARG.
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_start(const double* __restrict__ y, const double* __restrict__ b,
+                                                           const double* __restrict__ mask,
+                                                           const double* __restrict__ diag, double* __restrict__ x,
+                                                           double* __restrict__ r, double* __restrict__ p,
+                                                           double shift, long long n,
+                                                           const double* __restrict__ part_bb, int nb,
+                                                           double* __restrict__ part_rz, double* __restrict__ part_bx,
+                                                           PcgCtl* ctl) {
+  double bb, bad;
+  sum_partials(part_bb, nb, bb, bad);
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  const long long stride = (long long)gridDim.x * RED_THREADS;
+  if (bad > 0.0) {
+    if (lead) ctl->done = 1, ctl->status = MPSE_ERR_ARG, ctl->why = PCG_WHY_DIAG;
+    return;
+  }
+  if (bb == 0.0) {
+    for (long long i = (long long)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride)
+      Cx<CPLX>::st(x, i, make_double2(0.0, 0.0));
+    if (lead) ctl->done = 1, ctl->status = MPSE_OK, ctl->why = PCG_WHY_ZERO_B;
+    return;
+  }
+  if (lead) ctl->bb = bb;
+  double rz = 0, rr = 0, bx = 0, rx = 0;
+  for (long long i = (long long)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride) {
+    const double m = mask ? mask[i] : 1.0;
+    const double2 bv = scale2(Cx<CPLX>::ld(b, i), m), yv = Cx<CPLX>::ld(y, i), xv = Cx<CPLX>::ld(x, i);
+    const double2 rv = make_double2(bv.x - (m * yv.x + shift * xv.x), bv.y - (m * yv.y + shift * xv.y));
+    const double2 zv = diag ? scale2(rv, 1.0 / diag[i]) : rv;
+    Cx<CPLX>::st(r, i, rv);
+    Cx<CPLX>::st(p, i, zv);
+    rz += re_dotc(rv, zv);
+    rr += re_dotc(rv, rv);
+    bx += re_dotc(bv, xv);
+    rx += re_dotc(rv, xv);
+  }
+  block_allsum2(rz, rr);
+  block_allsum2(bx, rx);
+  if (threadIdx.x == 0) {
+    part_rz[2 * blockIdx.x] = rz;
+    part_rz[2 * blockIdx.x + 1] = rr;
+    part_bx[2 * blockIdx.x] = bx;
+    part_bx[2 * blockIdx.x + 1] = rx;
+  }
+}
+
+// (a) q = mask * y + shift * p with y = Heff p; partial sums of p^H q (real for a Hermitian operator: the real part is kept)
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_q(const double* __restrict__ y, const double* __restrict__ p,
+                                                       const double* __restrict__ mask, double shift,
+                                                       double* __restrict__ q, long long n,
+                                                       double* __restrict__ part_pq, const PcgCtl* __restrict__ ctl) {
+  if (ctl->done) return;
+  double pq = 0, zero = 0;
+  const long long stride = (long long)gridDim.x * RED_THREADS;
+  for (long long i = (long long)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride) {
+    const double m = mask ? mask[i] : 1.0;
+    const double2 yv = Cx<CPLX>::ld(y, i), pv = Cx<CPLX>::ld(p, i);
+    const double2 qv = make_double2(m * yv.x + shift * pv.x, m * yv.y + shift * pv.y);
+    Cx<CPLX>::st(q, i, qv);
+    pq += re_dotc(pv, qv);
+  }
+  block_allsum2(pq, zero);
+  if (threadIdx.x == 0) {
+    part_pq[2 * blockIdx.x] = pq;
+    part_pq[2 * blockIdx.x + 1] = 0.0;
+  }
+}
+
+// (b) alpha = (r^H z) / (p^H q); x += alpha p; r -= alpha q; partial sums for the next beta, the residual test and the
+// functional.  part_cur holds the (r^H z, r^H r) of the residual this step starts from, part_new receives the new ones
+// (another area: workgroups read all of part_cur while others already write).  A curvature p^H q that is not positive
+// (operator not positive definite, or NaN) ends the solve: every workgroup sees the same sum and leaves x alone.
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_step(const double* __restrict__ p, const double* __restrict__ q,
+                                                          const double* __restrict__ b,
+                                                          const double* __restrict__ mask,
+                                                          const double* __restrict__ diag, double* __restrict__ x,
+                                                          double* __restrict__ r, long long n,
+                                                          const double* __restrict__ part_pq,
+                                                          const double* __restrict__ part_cur,
+                                                          double* __restrict__ part_new, double* __restrict__ part_bx,
+                                                          int nb, PcgCtl* ctl) {
+  // (a workgroup that starts after workgroup 0 has raised `done` for the curvature below leaves here instead of through
+  // its own test of p^H q: the same outcome, x and r untouched)
+  if (ctl->done) return;
+  // the first element of this thread is requested before the scalars are summed: its loads do not depend on them, and
+  // the block reductions otherwise stand in front of every trip to memory (as k_lanczos_update_u does)
+  const long long stride = (long long)gridDim.x * RED_THREADS;
+  const long long i0 = (long long)blockIdx.x * RED_THREADS + threadIdx.x;
+  struct Elem {
+    double2 p, q, x, r, b;
+    double d;
+  };
+  auto fetch = [&](long long i) {
+    Elem e;
+    e.p = Cx<CPLX>::ld(p, i), e.q = Cx<CPLX>::ld(q, i), e.x = Cx<CPLX>::ld(x, i), e.r = Cx<CPLX>::ld(r, i);
+    e.b = scale2(Cx<CPLX>::ld(b, i), mask ? mask[i] : 1.0);
+    e.d = diag ? diag[i] : 1.0;
+    return e;
+  };
+  Elem first;
+  if (i0 < n) first = fetch(i0);
+  asm volatile("" ::: "memory");
+  double pq, rz_cur, t0, t1;
+  sum_partials(part_pq, nb, pq, t0);
+  sum_partials(part_cur, nb, rz_cur, t1);
+  if (!(pq > 0.0)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->done = 1, ctl->status = MPSE_ERR_ARG, ctl->why = PCG_WHY_CURVATURE;
+    return;
+  }
+  const double alpha = rz_cur / pq;
+  double rz = 0, rr = 0, bx = 0, rx = 0;
+  for (long long i = i0; i < n; i += stride) {
+    const Elem e = i == i0 ? first : fetch(i);
+    const double2 xv = make_double2(e.x.x + alpha * e.p.x, e.x.y + alpha * e.p.y);
+    const double2 rv = make_double2(e.r.x - alpha * e.q.x, e.r.y - alpha * e.q.y);
+    const double2 zv = diag ? scale2(rv, 1.0 / e.d) : rv;
+    Cx<CPLX>::st(x, i, xv);
+    Cx<CPLX>::st(r, i, rv);
+    rz += re_dotc(rv, zv);
+    rr += re_dotc(rv, rv);
+    bx += re_dotc(e.b, xv);
+    rx += re_dotc(rv, xv);
+  }
+  block_allsum2(rz, rr);
+  block_allsum2(bx, rx);
+  if (threadIdx.x == 0) {
+    part_new[2 * blockIdx.x] = rz;
+    part_new[2 * blockIdx.x + 1] = rr;
+    part_bx[2 * blockIdx.x] = bx;
+    part_bx[2 * blockIdx.x + 1] = rx;
+  }
+}
+
+// (c) after k iterations: beta = (r^H z)_new / (r^H z)_old, p = z + beta p (k == 0: p = z stands from k_pcg_start);
+// workgroup 0 decides - |r|^2 <= tol^2 |b|^2, then the iteration limit - and publishes the control block when the host
+// waits at this iteration (pub != null), also when the decision fell earlier.
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_dir(const double* __restrict__ r, const double* __restrict__ diag,
+                                                         double* __restrict__ p, long long n,
+                                                         const double* __restrict__ part_new,
+                                                         const double* __restrict__ part_old,
+                                                         const double* __restrict__ part_bx, int nb, double tol2, int k,
+                                                         int max_iter, PcgCtl* ctl, double* pub,
+                                                         volatile double* seq_slot, double seq) {
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  // Workgroup 0 raises `done` inside this launch, possibly before other workgroups have started: those leave here and
+  // skip their part of p = z + beta p.  That is harmless because p is never read again once `done` is set (every later
+  // launch returns at its top), and this kernel writes neither x nor r: the returned x does not depend on the race.
+  if (ctl->done) {
+    if (pub && lead) pcg_publish(ctl, pub, seq_slot, seq);
+    return;
+  }
+  double rz_new, rr;
+  sum_partials(part_new, nb, rz_new, rr);
+  if (k > 0) {
+    double rz_old, t;
+    sum_partials(part_old, nb, rz_old, t);
+    const double beta = rz_new / rz_old;
+    const long long stride = (long long)gridDim.x * RED_THREADS;
+    for (long long i = (long long)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride) {
+      const double2 rv = Cx<CPLX>::ld(r, i), pv = Cx<CPLX>::ld(p, i);
+      const double2 zv = diag ? scale2(rv, 1.0 / diag[i]) : rv;
+      Cx<CPLX>::st(p, i, make_double2(zv.x + beta * pv.x, zv.y + beta * pv.y));
+    }
+  }
+  if (blockIdx.x != 0) return;
+  const double bb = ctl->bb;
+  const bool conv = rr <= tol2 * bb;
+  const bool stop = conv || k >= max_iter;     // (uniform over the workgroup: every thread holds the same sums)
+  double bx = 0, rx = 0;
+  if (stop) sum_partials(part_bx, nb, bx, rx);
+  if (lead) {
+    ctl->iters = k;
+    ctl->relres2 = rr / bb;
+    if (stop) {
+      ctl->lvalue = -bx - rx;
+      ctl->status = conv ? MPSE_OK : MPSE_ERR_NOCONV;
+      ctl->why = conv ? PCG_WHY_TOL : PCG_WHY_MAXITER;
+      ctl->done = 1;
+    }
+    if (pub) pcg_publish(ctl, pub, seq_slot, seq);
+  }
+}
+
+template <bool CPLX>
+int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const double* diag,
+            const double* mask, const double* b, double* x, double tol, int max_iter, int64_t n, PcgCtl* hc) {
+  const size_t es = dtype_size(dtype);
+  const int64_t nd = n * (CPLX ? 2 : 1);
+  const int nb = red_blocks(nd);
+  // one slab: control block, five areas of partials (|b|^2; p^H q; r^H z twice, by iteration parity; b^H x), then y, q, r, p
+  const size_t head = size_t(PCG_CW + 5 * 2 * nb) * sizeof(double);
+  const size_t head_al = (head + 255) & ~size_t(255);
+  TmpBuf slab(ctx);
+  MPSE_TRY(slab.alloc(head_al + 4 * size_t(n) * es));
+  PcgCtl* ctl = slab.as<PcgCtl>();
+  double* part = slab.as<double>() + PCG_CW;
+  double *part_bb = part, *part_pq = part + 2 * nb, *part_bx = part + 4 * nb;
+  double* part_rz[2] = {part + 6 * nb, part + 8 * nb};
+  char* vecs = slab.as<char>() + head_al;
+  double* y = reinterpret_cast<double*>(vecs);
+  double* q = reinterpret_cast<double*>(vecs + size_t(n) * es);
+  double* r = reinterpret_cast<double*>(vecs + 2 * size_t(n) * es);
+  double* p = reinterpret_cast<double*>(vecs + 3 * size_t(n) * es);
+
+  SolveScope scope(ctx);
+  scope.skip = &ctl->done;
+  auto matvec = [&](const void* in) -> int {
+    return twolayer ? heff_apply2(ctx, dtype, h, in, y, &scope) : heff_apply(ctx, dtype, h, in, y, &scope, nullptr);
+  };
+  const dim3 grid(nb), block(RED_THREADS);
+  const long long nn = (long long)n;
+  const double tol2 = tol * tol;
+  memset(hc, 0, sizeof(*hc));
+  // the host reads the control block that the k_pcg_dir launched last published (seq != 0) or fetches it itself
+  auto wait_here_for = [&](double seq) -> int {
+    if (seq != 0.0)
+      MPSE_TRY(publish_wait_seq(ctx, seq, reinterpret_cast<const double*>(ctl), PCG_CW, PCG_SLOT));
+    else
+      MPSE_TRY(publish_and_wait(ctx, reinterpret_cast<const double*>(ctl), PCG_CW, PCG_SLOT));
+    if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
+    memcpy(hc, ctx->pinned + PCG_SLOT, sizeof(PcgCtl));
+    ++ctx->pcg_stats[mpse_ctx::PS_WAITS];
+    return MPSE_OK;
+  };
+
+  hipLaunchKernelGGL(k_pcg_prep<CPLX>, grid, block, 0, ctx->stream, x, b, mask, diag, nn, part_bb, ctl);
+  MPSE_HIP(ctx, hipGetLastError());
+  MPSE_TRY(matvec(x));
+  hipLaunchKernelGGL(k_pcg_start<CPLX>, grid, block, 0, ctx->stream, (const double*)y, b, mask, diag, x, r, p, shift, nn,
+                     (const double*)part_bb, nb, part_rz[0], part_bx, ctl);
+  MPSE_HIP(ctx, hipGetLastError());
+  for (int k = 0;; ++k) {
+    if (k > 0) {
+      MPSE_TRY(matvec(p));
+      ++ctx->pcg_stats[mpse_ctx::PS_MATVECS];
+      hipLaunchKernelGGL(k_pcg_q<CPLX>, grid, block, 0, ctx->stream, (const double*)y, (const double*)p, mask, shift, q,
+                         nn, part_pq, (const PcgCtl*)ctl);
+      MPSE_HIP(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_pcg_step<CPLX>, grid, block, 0, ctx->stream, (const double*)p, (const double*)q, b, mask, diag,
+                         x, r, nn, (const double*)part_pq, (const double*)part_rz[(k - 1) & 1], part_rz[k & 1], part_bx,
+                         nb, ctl);
+      MPSE_HIP(ctx, hipGetLastError());
+    }
+    const bool wait_here = (k % PCG_K == PCG_K - 1) || k >= max_iter;
+    const bool self_pub = wait_here && ctx->pinned_dev != nullptr;
+    const double seq = self_pub ? double(++ctx->publish_seq) : 0.0;
+    hipLaunchKernelGGL(k_pcg_dir<CPLX>, grid, block, 0, ctx->stream, (const double*)r, diag, p, nn,
+                       (const double*)part_rz[k & 1], (const double*)part_rz[(k + 1) & 1], (const double*)part_bx, nb,
+                       tol2, k, max_iter, ctl, self_pub ? ctx->pinned_dev + PCG_SLOT : (double*)nullptr,
+                       (volatile double*)(self_pub ? ctx->pinned_dev + 4095 : nullptr), seq);
+    MPSE_HIP(ctx, hipGetLastError());
+    if (wait_here) {
+      MPSE_TRY(wait_here_for(seq));
+      if (hc->done) break;
+      if (k >= max_iter) return mpse_fail(ctx, MPSE_ERR_HIP, "pcg: no decision at the iteration limit");
+    }
+  }
+  return MPSE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const void* diag_f64,
+             const void* mask_f64, const void* b, void* x, double tol, int max_iter, int* iters_host,
+             double* relres_host, double* lvalue_host) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (!h || !b || !x || !h->L || !h->R || !h->W0) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: null argument");
+  MPSE_BIND(ctx);
+  if (dtype != MPSE_F64 && dtype != MPSE_C128) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: unknown dtype");
+  if (dtype != MPSE_C128 && (h->l_dtype == MPSE_C128 || h->r_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
+    return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: real vectors with complex operator parts");
+  if (!(tol >= 0.0) || !std::isfinite(shift)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: tol must be >= 0 and shift finite");
+  const mpse_dims& s = h->dims;
+  if ((s.Dl_bra > 0 && s.Dl_bra != s.Dl_ket) || (s.Dr_bra > 0 && s.Dr_bra != s.Dr_ket))
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg: the projected operator must be square (bra bonds == ket bonds)");
+  if (h->nsite != 1 && h->nsite != 2) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: one- or two-site centres");
+  if (twolayer && (s.danc > 1 || s.danc1 > 1)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: two-layer operators take no ancilla");
+  const int64_t anc = s.danc > 0 ? s.danc : 1;
+  int64_t n = s.Dl_ket * s.Dr_ket * s.d0 * anc;
+  if (h->nsite == 2) n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
+  if (n <= 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg: empty centre tensor");
+  const size_t bytes = size_t(n) * dtype_size(dtype);
+  const char *xb = static_cast<const char*>(x), *bb = static_cast<const char*>(b);
+  if (xb < bb + bytes && bb < xb + bytes) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: x must not overlap b");
+  if (max_iter <= 0) max_iter = n > (int64_t(1) << 27) ? (1 << 30) : int(10 * n);   // scipy's default, 10 n
+  wsite_written(ctx, x, bytes);
+
+  PcgCtl hc;
+  const double *diag = static_cast<const double*>(diag_f64), *mask = static_cast<const double*>(mask_f64);
+  const int st = dtype == MPSE_C128
+                     ? pcg_run<true>(ctx, dtype, h, twolayer, shift, diag, mask, static_cast<const double*>(b),
+                                     static_cast<double*>(x), tol, max_iter, n, &hc)
+                     : pcg_run<false>(ctx, dtype, h, twolayer, shift, diag, mask, static_cast<const double*>(b),
+                                      static_cast<double*>(x), tol, max_iter, n, &hc);
+  if (st != MPSE_OK) return st;      // (allocation or runtime failure: no solve is counted)
+  ++ctx->pcg_stats[mpse_ctx::PS_SOLVES];
+  if (twolayer) ++ctx->pcg_stats[mpse_ctx::PS_TWOLAYER];
+  if (mask_f64) ++ctx->pcg_stats[mpse_ctx::PS_MASKED];
+  ctx->pcg_stats[mpse_ctx::PS_ITERS] += hc.iters;
+  if (iters_host) *iters_host = hc.iters;
+  if (relres_host) *relres_host = std::sqrt(hc.relres2);
+  if (lvalue_host) *lvalue_host = hc.lvalue;
+  switch (hc.why) {
+    case PCG_WHY_TOL:
+    case PCG_WHY_ZERO_B:
+      ++ctx->pcg_stats[mpse_ctx::PS_END_TOL];
+      return MPSE_OK;
+    case PCG_WHY_MAXITER:
+      ++ctx->pcg_stats[mpse_ctx::PS_END_MAXITER];
+      return mpse_fail(ctx, MPSE_ERR_NOCONV, "pcg: |r| / |b| = %.3e after %d iterations (tol %.3e)", std::sqrt(hc.relres2),
+                       hc.iters, tol);
+    case PCG_WHY_CURVATURE:
+      ++ctx->pcg_stats[mpse_ctx::PS_END_CURVATURE];
+      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: curvature p^H A p <= 0 (or not a number) after %d iterations: the operator "
+                       "is not positive definite", hc.iters);
+    case PCG_WHY_DIAG:
+      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: the preconditioner diagonal has entries that are not positive");
+    default:
+      return mpse_fail(ctx, MPSE_ERR_HIP, "pcg: control block without a decision");
+  }
+}
+
+int mpse_pcg_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  for (int i = 0; i < n && i < mpse_ctx::PS_COUNT; ++i) counts[i] = ctx->pcg_stats[i];
+  if (n > mpse_ctx::PS_COUNT) counts[mpse_ctx::PS_COUNT] = PCG_K;
+  return MPSE_OK;
+}
+
+}  // extern "C"

@@ -12,20 +12,6 @@
 
 namespace {
 
-constexpr int RED_MAX_BLOCKS = 512;  // two blocks per CU; consumers of the partials re-sum all of them per block
-                                     // (1 024 / 2 048 measured: 586 / 582 against 589 site-updates/s, r06_ab_red_blocks.txt)
-
-// Two doubles per thread - one complex element - up to the cap.  Rounds 1 - 5 gave a thread eight: the vectors of the bond
-// and two-level-site solves (1 - 2 MB) then ran on 64 - 128 workgroups whose threads made two to four PASSES of dependent
-// trips to memory (mask word -> parts -> store) - latency bound by their own grid.  One pass per thread: k_lanczos_update_u
-// 45.9 -> 33.8 ms per two steps at four doubles already, +4.7 % on the headline at two (profiles/r06_ab_red_blocks.txt).
-inline int red_blocks(int64_t n_doubles) {
-  int64_t b = (n_doubles + RED_THREADS * 2 - 1) / (RED_THREADS * 2);
-  if (b < 1) b = 1;
-  if (b > RED_MAX_BLOCKS) b = RED_MAX_BLOCKS;
-  return (int)b;
-}
-
 // partial[b] = sum over this block's elements of conj(x) * y
 template <bool CPLX>
 __global__ __launch_bounds__(RED_THREADS) void k_dot_partial(const double* __restrict__ x, const double* __restrict__ y,
@@ -56,19 +42,6 @@ __global__ __launch_bounds__(RED_THREADS) void k_dot_partial(const double* __res
     partial[2 * blockIdx.x] = re;
     partial[2 * blockIdx.x + 1] = im;
   }
-}
-
-// Sum of a producer kernel's per-block partials, evaluated redundantly by every block of the consumer kernel
-// (same order everywhere, so all blocks see the same value): saves the single-block k_reduce_final launch
-// between producer and consumer.  blockDim.x must be RED_THREADS.
-__device__ __forceinline__ void sum_partials(const double* __restrict__ partial, int nb, double& re, double& im) {
-  re = 0;
-  im = 0;
-  for (int i = threadIdx.x; i < nb; i += RED_THREADS) {
-    re += partial[2 * i];
-    im += partial[2 * i + 1];
-  }
-  block_allsum2(re, im);
 }
 
 __global__ __launch_bounds__(RED_THREADS) void k_reduce_final(const double* __restrict__ partial, int nb,

@@ -5,6 +5,7 @@ HIP library is missing or no GPU is visible the engine refuses to start - there 
 deliberately no CPU fallback (the NumPy restatement lives in ``oracle/`` and is
 test infrastructure only).
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -22,6 +23,9 @@ MPSE_OK, MPSE_ERR_OOM, MPSE_ERR_SHAPE, MPSE_ERR_NOCONV, MPSE_ERR_HIP, MPSE_ERR_A
 DOMAIN_L, DOMAIN_R = 0, 1
 
 STATUS = {0: "OK", 1: "OOM", 2: "SHAPE", 3: "NOCONV", 4: "HIP", 5: "ARG"}
+
+
+PcgResult = collections.namedtuple("PcgResult", "status iters relres lvalue")
 
 
 class EngineError(RuntimeError):
@@ -143,6 +147,9 @@ _SIGNATURES = {
     "mpse_davidson": [C.c_void_p, C.c_int, C.POINTER(mpse_heff), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                       C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _dblp, C.c_void_p,
                       C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "mpse_pcg": [C.c_void_p, C.c_int, C.POINTER(mpse_heff), C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                 C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), _dblp, _dblp],
+    "mpse_pcg_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -467,6 +474,36 @@ class Engine:
         v = (C.c_int64 * len(self.LANCZOS_PATHS))()
         self._check(self.lib.mpse_expm_lanczos_path_stats(self.ctx, v, len(v)))
         return dict(zip(self.LANCZOS_PATHS, (int(x) for x in v)))
+
+    PCG_STATS = ("solves", "iterations", "matvecs", "host_waits", "end_tol", "end_max_iter", "end_curvature",
+                 "twolayer", "masked", "wait_interval")
+
+    def pcg_stats(self):
+        """{name: count}: what the conjugate-gradient solves of this context did, cumulative (``mpse_pcg_stats``; the
+        names follow the order of include/mpsengine.h).  ``wait_interval`` is no count: the engine's number of
+        iterations between two host reads of the control block."""
+        v = (C.c_int64 * len(self.PCG_STATS))()
+        self._check(self.lib.mpse_pcg_stats(self.ctx, v, len(v)))
+        return dict(zip(self.PCG_STATS, (int(x) for x in v)))
+
+    def pcg(self, hop, b, x, diag=None, mask=None, shift=0.0, tol=1e-5, max_iter=0, check=True):
+        """Solve ``(mask * hop + shift) x = b`` by preconditioned conjugate gradients inside the engine (``mpse_pcg``).
+        ``hop``: a ``hop_expr`` closure of a Hermitian positive definite operator (``twolayer`` is taken from it);
+        ``b`` and ``x`` device tensors of the working dtype, ``x`` holds the start vector and receives the solution;
+        ``diag`` (float64 device tensor, ``shift`` included) the preconditioner, ``mask`` (float64 0/1) the
+        symmetry-allowed entries.  Returns ``PcgResult(status, iters, relres, lvalue)``; status 3 (not converged
+        within ``max_iter``) is returned, any other failure raises unless ``check`` is False."""
+        n = int(np.prod(hop.cshape))
+        assert b.size == n and x.size == n and b.dtype == x.dtype, (b.shape, x.shape, hop.cshape)
+        assert diag is None or (diag.size == n and diag.dtype == np.float64)
+        assert mask is None or (mask.size == n and mask.dtype == np.float64)
+        it, rel, lv = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        st = self.lib.mpse_pcg(self.ctx, x.code, C.byref(hop.heff), int(hop.twolayer), float(shift),
+                               None if diag is None else diag.ptr, None if mask is None else mask.ptr, b.ptr, x.ptr,
+                               float(tol), int(max_iter), C.byref(it), C.byref(rel), C.byref(lv))
+        if check and st not in (0, 3):
+            self._check(st)
+        return PcgResult(int(st), it.value, rel.value, lv.value)
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""
