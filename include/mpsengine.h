@@ -284,6 +284,35 @@ int mpse_heff_fused_stats(mpse_ctx* ctx, int64_t* bond_launches, int64_t* site_l
  *   fields are ignored. */
 int mpse_heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out);
 
+/* Two MPO layers on a centre with TWO physical legs, each layer on the leg it names: one term of the finite-temperature
+ * correction-vector operator (omega - Liou)^2 X = a a X + 2 a X H + X H H, a = omega - H, on a site of an operator in
+ * MPS form (replaces the hop closure and the path1 environment chains of cv/finitet.py:215-299, 585-716).
+ *   C, out (Dl, d_up, d_down, Dr);  L (Dl, wl1, wl2, Dl), R (Dr, wr1, wr2, Dr): (bond of C, layer 1, layer 2, bond of out)
+ *   W1 (wl1, d, d, wr1), W2 (wl2, d, d, wr2), d the extent of the leg the layer acts on; layer 1 acts first
+ *   trans == 0: leg'[x] = sum_y W[., x, y, .] leg[y];  trans != 0: leg'[y] = sum_x W[., x, y, .] leg[x]
+ * Both layers MPSE_LEG_UP (d_down passes through), both MPSE_LEG_DOWN, or layer 1 up and layer 2 down, side by side
+ * (the other order is refused with MPSE_ERR_SHAPE: such layers commute).  One-site centres only.  With d_down == 1,
+ * both layers up, transposed, on the same site this is mpse_heff_apply2 step by step. */
+enum { MPSE_LEG_UP = 0, MPSE_LEG_DOWN = 1 };
+typedef struct {
+  int64_t Dl, Dr, d_up, d_down;
+  int64_t wl1, wr1, wl2, wr2;
+  int leg1, leg2;
+  int trans1, trans2;
+  const void* L; int l_dtype;
+  const void* R; int r_dtype;
+  const void* W1; const void* W2; int w_dtype;
+} mpse_heff_ft;
+
+int mpse_heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out);
+
+/* The environment of such a term moved over one site X (Dl, d_up, d_down, Dr): the bra is conj(X), the ket X, each
+ * layer contracts its own leg between them and the leg no layer touches is contracted directly.
+ *   MPSE_DOMAIN_L: env (Dl, wl1, wl2, Dl) -> out (Dr, wr1, wr2, Dr);  MPSE_DOMAIN_R: env (Dr, wr1, wr2, Dr) ->
+ *   out (Dl, wl1, wl2, Dl); index order as L / R above.  h->L, h->R and their dtypes are not read. */
+int mpse_env_update_ft(mpse_ctx* ctx, int dtype, int domain, const mpse_heff_ft* h, const void* env, int env_dtype,
+                       const void* X, void* out);
+
 /* Lanczos exponential out = expm(dt*Heff) C, replaces lib/krylov/krylov.py:27-82
  * expm_krylov as called at mps/mps.py:1300-1303, 1343-1346, 1377-1380 (same
  * recurrence without re-orthogonalisation, same stopping rule: successive
@@ -401,6 +430,32 @@ int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double 
  *       entry 2 exceeds entry 1 by at most this number - 1 per solve that ended by the tolerance or max_iter)
  * Diagnostics for tests; no device work. */
 int mpse_pcg_stats(mpse_ctx* ctx, int64_t* counts, int n);
+
+/* mpse_pcg over a weighted sum of mpse_heff_ft terms: (mask * sum_t weight[t] * A_t + shift) x = b with 1 <= nterms <= 4,
+ * the centre system of the finite-temperature correction vector (weights 1, 2, 1; replaces scipy.sparse.linalg.cg of
+ * cv/finitet.py:306-311).  All terms share Dl, Dr, d_up, d_down.  Every term writes a result vector of its own and the
+ * launch that forms q = mask * sum_t weight[t] y_t + shift * p reads them all (no pass per term); everything else -
+ * control block, host waits, endings, outputs - is mpse_pcg's.  A solve with one term of weight 1 that mpse_heff_apply2
+ * can express returns bit for bit what mpse_pcg (twolayer != 0) returns.  Counted in mpse_pcg_stats like any solve
+ * (entry 2 counts one matvec per iteration, not per term) and in mpse_pcg_sum_stats. */
+int mpse_pcg_sum(mpse_ctx* ctx, int dtype, int nterms, const mpse_heff_ft* terms, const double* weights_host,
+                 double shift, const void* diag_f64, const void* mask_f64, const void* b, void* x, double tol,
+                 int max_iter, int* iters_host, double* relres_host, double* lvalue_host);
+/* counts[i], i < n:  0 summed solves that reached a decision, 1 their iterations, 2 term applications issued by
+ * iterations (terms x matvecs), 3 their host waits, 4 preconditioner diagonals started by mpse_diag_ft
+ * (calls with accumulate == 0). */
+int mpse_pcg_sum_stats(mpse_ctx* ctx, int64_t* counts, int n);
+
+/* diag (Dl, d_up, d_down, Dr) (+)= weight * the diagonal of one mpse_heff_ft term (the pre_M1 / pre_M2 / pre_M4 of
+ * cv/finitet.py:233-275), formed on the device:
+ *   diag[a, u, v, j] += weight * sum_{b, c, g, i} L[a, b, c, a] S[b, c, u, v, g, i] R[j, g, i, j]
+ *   S (wl1, wl2, d_up, d_down, wr1, wr2), real: the per-site factor of the two MPO sites, the same for every centre on
+ *   that site (both layers on one leg: sum_y W1[b, x, y, g] W2[c, y, x, i] resp. its transposed-order twin, constant
+ *   along the other leg; one layer per leg: W1[b, u, u, g] W2[c, v, v, i]); mpse_site_factor_ft forms it from h->W1 /
+ *   h->W2 once per site and frequency.  accumulate == 0 overwrites diag and adds `shift` first. */
+int mpse_site_factor_ft(mpse_ctx* ctx, const mpse_heff_ft* h, void* S_f64);
+int mpse_diag_ft(mpse_ctx* ctx, const mpse_heff_ft* h, const void* S_f64, double weight, double shift, int accumulate,
+                 void* diag_f64);
 
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per

@@ -617,6 +617,44 @@ extern "C" int mpse_heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, co
   return heff_apply2(ctx, dtype, h, C, out, nullptr);
 }
 
+// ---- two layers on a two-leg centre (finite-temperature correction vector): plans of mpse_plans.h
+int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out, const SolveScope* sc) {
+  if (!ctx || !h || !C || !out || !h->L || !h->R || !h->W1 || !h->W2) return MPSE_ERR_ARG;
+  MPSE_BIND(ctx);
+  if (dtype != MPSE_C128 && (h->l_dtype == MPSE_C128 || h->r_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
+    return mpse_fail(ctx, MPSE_ERR_ARG, "heff_apply_ft: real centre with complex operator parts");
+  Plan p = plan_heff_ft(dtype, *h);
+  const void* bufs[B_COUNT] = {nullptr};
+  bufs[B_L] = h->L;
+  bufs[B_R] = h->R;
+  bufs[B_W0] = h->W1;
+  bufs[B_W1] = h->W2;
+  bufs[B_C] = C;
+  bufs[B_OUT] = out;
+  return run_plan(ctx, dtype, p, bufs, sc);
+}
+
+extern "C" int mpse_heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out) {
+  return heff_apply_ft(ctx, dtype, h, C, out, nullptr);
+}
+
+extern "C" int mpse_env_update_ft(mpse_ctx* ctx, int dtype, int domain, const mpse_heff_ft* h, const void* env,
+                                  int env_dtype, const void* X, void* out) {
+  if (!ctx || !h || !env || !X || !out || !h->W1 || !h->W2) return MPSE_ERR_ARG;
+  MPSE_BIND(ctx);
+  if (dtype != MPSE_C128 && (env_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
+    return mpse_fail(ctx, MPSE_ERR_ARG, "env_update_ft: real site with complex env/mpo");
+  Plan p = plan_env_ft(dtype, domain, *h, env_dtype);
+  const void* bufs[B_COUNT] = {nullptr};
+  bufs[B_L] = env;
+  bufs[B_W0] = h->W1;
+  bufs[B_W1] = h->W2;
+  bufs[B_C] = X;
+  bufs[B_BRA] = X;
+  bufs[B_OUT] = out;
+  return run_plan(ctx, dtype, p, bufs);
+}
+
 extern "C" int mpse_env_unit_channel(mpse_ctx* ctx, int dtype, const void* env, int64_t D, int64_t w, double tol,
                                      int64_t* unit_host) {
   if (!ctx || !env || !unit_host) return MPSE_ERR_ARG;

@@ -159,6 +159,9 @@ struct mpse_ctx {
     PS_COUNT
   };
   long long pcg_stats[PS_COUNT] = {0};
+  // the summed solves among them (mpse_pcg_sum_stats)
+  enum PcgSumStat { PSS_SOLVES, PSS_ITERS, PSS_TERM_APPLIES, PSS_WAITS, PSS_DIAGS, PSS_COUNT };
+  long long pcg_sum_stats[PSS_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 
@@ -336,6 +339,8 @@ int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void
                MatvecReq* mv);
 // The two-layer matvec behind mpse_heff_apply2, for a caller inside a solve (sc may be null)
 int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc);
+// One term of the finite-temperature correction-vector operator (mpse_heff_apply_ft), inside a solve (sc may be null)
+int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out, const SolveScope* sc);
 // One-launch matvec of small 0- / 1-site centres (mpse_small.hip); *taken says whether it ran (else: the plans)
 int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
                    MatvecReq* mv, bool* taken);

@@ -148,6 +148,52 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_q(const double* __restrict_
   }
 }
 
+// (a) for a weighted sum of operators: q = mask * (sum_t w_t y_t) + shift * p from the results of all terms in ONE pass,
+// where accumulating products (beta = 1) would tie the bits of q to how the contraction kernel splits its K loop and a
+// pass per term would read and write the vectors three times over.  The partial sums are those of k_pcg_q.
+struct PcgTerms {
+  const double* y[4];
+  double w[4];
+  int n;
+};
+template <bool CPLX>
+__device__ __forceinline__ double2 pcg_term_sum(const PcgTerms& t, long long i) {
+  double2 s = scale2(Cx<CPLX>::ld(t.y[0], i), t.w[0]);
+  for (int k = 1; k < t.n; ++k) {
+    const double2 v = Cx<CPLX>::ld(t.y[k], i);
+    s.x += t.w[k] * v.x, s.y += t.w[k] * v.y;
+  }
+  return s;
+}
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_q_sum(const PcgTerms t, const double* __restrict__ p,
+                                                           const double* __restrict__ mask, double shift,
+                                                           double* __restrict__ q, long long n,
+                                                           double* __restrict__ part_pq, const PcgCtl* __restrict__ ctl) {
+  if (ctl->done) return;
+  double pq = 0, zero = 0;
+  const long long stride = (long long)gridDim.x * RED_THREADS;
+  for (long long i = (long long)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride) {
+    const double m = mask ? mask[i] : 1.0;
+    const double2 yv = pcg_term_sum<CPLX>(t, i), pv = Cx<CPLX>::ld(p, i);
+    const double2 qv = make_double2(m * yv.x + shift * pv.x, m * yv.y + shift * pv.y);
+    Cx<CPLX>::st(q, i, qv);
+    pq += re_dotc(pv, qv);
+  }
+  block_allsum2(pq, zero);
+  if (threadIdx.x == 0) {
+    part_pq[2 * blockIdx.x] = pq;
+    part_pq[2 * blockIdx.x + 1] = 0.0;
+  }
+}
+// the same sum written into the first term's vector: the start residual (once per solve) goes through k_pcg_start
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_combine(const PcgTerms t, double* y, long long n) {
+  const long long stride = (long long)gridDim.x * RED_THREADS;
+  for (long long i = (long long)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride)
+    Cx<CPLX>::st(y, i, pcg_term_sum<CPLX>(t, i));
+}
+
 // (b) alpha = (r^H z) / (p^H q); x += alpha p; r -= alpha q; partial sums for the next beta, the residual test and the
 // functional.  part_cur holds the (r^H z, r^H r) of the residual this step starts from, part_new receives the new ones
 // (another area: workgroups read all of part_cur while others already write).  A curvature p^H q that is not positive
@@ -267,15 +313,17 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_dir(const double* __restric
 
 template <bool CPLX>
 int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const double* diag,
-            const double* mask, const double* b, double* x, double tol, int max_iter, int64_t n, PcgCtl* hc) {
+            const double* mask, const double* b, double* x, double tol, int max_iter, int64_t n, PcgCtl* hc,
+            int nterms = 0, const mpse_heff_ft* terms = nullptr, const double* weights = nullptr) {
   const size_t es = dtype_size(dtype);
   const int64_t nd = n * (CPLX ? 2 : 1);
   const int nb = red_blocks(nd);
   // one slab: control block, five areas of partials (|b|^2; p^H q; r^H z twice, by iteration parity; b^H x), then y, q, r, p
+  // (a summed solve: one more y per further term, behind p)
   const size_t head = size_t(PCG_CW + 5 * 2 * nb) * sizeof(double);
   const size_t head_al = (head + 255) & ~size_t(255);
   TmpBuf slab(ctx);
-  MPSE_TRY(slab.alloc(head_al + 4 * size_t(n) * es));
+  MPSE_TRY(slab.alloc(head_al + (4 + size_t(nterms > 1 ? nterms - 1 : 0)) * size_t(n) * es));
   PcgCtl* ctl = slab.as<PcgCtl>();
   double* part = slab.as<double>() + PCG_CW;
   double *part_bb = part, *part_pq = part + 2 * nb, *part_bx = part + 4 * nb;
@@ -288,7 +336,21 @@ int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double s
 
   SolveScope scope(ctx);
   scope.skip = &ctl->done;
+  // a single term of weight one is the plain solve on that term's result
+  const bool summed = nterms > 1 || (nterms == 1 && weights[0] != 1.0);
+  PcgTerms ts;
+  memset(&ts, 0, sizeof(ts));
+  ts.n = nterms;
+  for (int t = 0; t < nterms; ++t) {
+    ts.y[t] = t == 0 ? y : reinterpret_cast<double*>(vecs + (3 + size_t(t)) * size_t(n) * es);
+    ts.w[t] = weights[t];
+  }
   auto matvec = [&](const void* in) -> int {
+    if (nterms > 0) {
+      for (int t = 0; t < nterms; ++t)
+        MPSE_TRY(heff_apply_ft(ctx, dtype, &terms[t], in, const_cast<double*>(ts.y[t]), &scope));
+      return MPSE_OK;
+    }
     return twolayer ? heff_apply2(ctx, dtype, h, in, y, &scope) : heff_apply(ctx, dtype, h, in, y, &scope, nullptr);
   };
   const dim3 grid(nb), block(RED_THREADS);
@@ -304,12 +366,17 @@ int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double s
     if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
     memcpy(hc, ctx->pinned + PCG_SLOT, sizeof(PcgCtl));
     ++ctx->pcg_stats[mpse_ctx::PS_WAITS];
+    if (nterms > 0) ++ctx->pcg_sum_stats[mpse_ctx::PSS_WAITS];
     return MPSE_OK;
   };
 
   hipLaunchKernelGGL(k_pcg_prep<CPLX>, grid, block, 0, ctx->stream, x, b, mask, diag, nn, part_bb, ctl);
   MPSE_HIP(ctx, hipGetLastError());
   MPSE_TRY(matvec(x));
+  if (summed) {
+    hipLaunchKernelGGL(k_pcg_combine<CPLX>, grid, block, 0, ctx->stream, ts, y, nn);
+    MPSE_HIP(ctx, hipGetLastError());
+  }
   hipLaunchKernelGGL(k_pcg_start<CPLX>, grid, block, 0, ctx->stream, (const double*)y, b, mask, diag, x, r, p, shift, nn,
                      (const double*)part_bb, nb, part_rz[0], part_bx, ctl);
   MPSE_HIP(ctx, hipGetLastError());
@@ -317,8 +384,13 @@ int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double s
     if (k > 0) {
       MPSE_TRY(matvec(p));
       ++ctx->pcg_stats[mpse_ctx::PS_MATVECS];
-      hipLaunchKernelGGL(k_pcg_q<CPLX>, grid, block, 0, ctx->stream, (const double*)y, (const double*)p, mask, shift, q,
-                         nn, part_pq, (const PcgCtl*)ctl);
+      ctx->pcg_sum_stats[mpse_ctx::PSS_TERM_APPLIES] += nterms;
+      if (summed)
+        hipLaunchKernelGGL(k_pcg_q_sum<CPLX>, grid, block, 0, ctx->stream, ts, (const double*)p, mask, shift, q, nn,
+                           part_pq, (const PcgCtl*)ctl);
+      else
+        hipLaunchKernelGGL(k_pcg_q<CPLX>, grid, block, 0, ctx->stream, (const double*)y, (const double*)p, mask, shift, q,
+                           nn, part_pq, (const PcgCtl*)ctl);
       MPSE_HIP(ctx, hipGetLastError());
       hipLaunchKernelGGL(k_pcg_step<CPLX>, grid, block, 0, ctx->stream, (const double*)p, (const double*)q, b, mask, diag,
                          x, r, nn, (const double*)part_pq, (const double*)part_rz[(k - 1) & 1], part_rz[k & 1], part_bx,
@@ -343,6 +415,115 @@ int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double s
 }
 
 }  // namespace
+
+namespace {
+
+// ---- preconditioner of the summed solve: the diagonal of each term from the environment diagonals and a per-site factor
+// element of an MPO site W (wl, d, d, wr) that takes leg value `in` to `out` under the layer's transposition flag
+__device__ __forceinline__ double ft_w_elem(const double* W, int trans, long long d, long long wr, long long b, long long in,
+                                            long long out, long long f) {
+  return trans ? W[((b * d + in) * d + out) * wr + f] : W[((b * d + out) * d + in) * wr + f];
+}
+
+struct FtShape {
+  long long Dl, Dr, du, dv, wl1, wr1, wl2, wr2;
+  int leg1, leg2, trans1, trans2;
+};
+
+// S[b, c, u, v, g, i]: both layers on one leg: sum_x W1(leg -> x)[b, g] W2(x -> leg)[c, i]; one per leg: the two diagonals
+__global__ __launch_bounds__(256) void k_site_factor_ft(const FtShape h, const double* __restrict__ W1,
+                                                        const double* __restrict__ W2, double* __restrict__ S) {
+  const long long total = h.wl1 * h.wl2 * h.du * h.dv * h.wr1 * h.wr2;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  long long r = idx;
+  const long long i = r % h.wr2; r /= h.wr2;
+  const long long g = r % h.wr1; r /= h.wr1;
+  const long long v = r % h.dv; r /= h.dv;
+  const long long u = r % h.du; r /= h.du;
+  const long long c = r % h.wl2;
+  const long long b = r / h.wl2;
+  double acc = 0.0;
+  if (h.leg1 == h.leg2) {
+    const long long d = h.leg1 == MPSE_LEG_UP ? h.du : h.dv, e = h.leg1 == MPSE_LEG_UP ? u : v;
+    for (long long x = 0; x < d; ++x)
+      acc += ft_w_elem(W1, h.trans1, d, h.wr1, b, e, x, g) * ft_w_elem(W2, h.trans2, d, h.wr2, c, x, e, i);
+  } else {
+    acc = ft_w_elem(W1, h.trans1, h.du, h.wr1, b, u, u, g) * ft_w_elem(W2, h.trans2, h.dv, h.wr2, c, v, v, i);
+  }
+  S[idx] = acc;
+}
+
+// diag[a, u, v, j] (+)= weight * sum_{b, c, g, i} Re(L[a, b, c, a] R[j, g, i, j]) S[b, c, u, v, g, i]; one thread per entry
+template <bool LC, bool RC>
+__global__ __launch_bounds__(256) void k_diag_ft(const FtShape h, const double* __restrict__ L,
+                                                 const double* __restrict__ R, const double* __restrict__ S, double weight,
+                                                 double shift, int accumulate, double* __restrict__ diag) {
+  const long long total = h.Dl * h.du * h.dv * h.Dr;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  long long r = idx;
+  const long long j = r % h.Dr; r /= h.Dr;
+  const long long v = r % h.dv; r /= h.dv;
+  const long long u = r % h.du;
+  const long long a = r / h.du;
+  double acc = 0.0;
+  for (long long b = 0; b < h.wl1; ++b)
+    for (long long c = 0; c < h.wl2; ++c) {
+      const long long lo = ((a * h.wl1 + b) * h.wl2 + c) * h.Dl + a;
+      const double lr = LC ? L[2 * lo] : L[lo], li = LC ? L[2 * lo + 1] : 0.0;
+      for (long long g = 0; g < h.wr1; ++g)
+        for (long long i = 0; i < h.wr2; ++i) {
+          const long long ro = ((j * h.wr1 + g) * h.wr2 + i) * h.Dr + j;
+          const double rr = RC ? R[2 * ro] : R[ro], ri = RC ? R[2 * ro + 1] : 0.0;
+          acc += (lr * rr - li * ri) * S[((((b * h.wl2 + c) * h.du + u) * h.dv + v) * h.wr1 + g) * h.wr2 + i];
+        }
+    }
+  diag[idx] = (accumulate ? diag[idx] : shift) + weight * acc;
+}
+
+FtShape ft_shape(const mpse_heff_ft& h) {
+  return FtShape{h.Dl, h.Dr, h.d_up, h.d_down, h.wl1, h.wr1, h.wl2, h.wr2, h.leg1, h.leg2, h.trans1, h.trans2};
+}
+int ft_shape_ok(mpse_ctx* ctx, const mpse_heff_ft& h, const char* who) {
+  if (h.Dl <= 0 || h.Dr <= 0 || h.d_up <= 0 || h.d_down <= 0 || h.wl1 <= 0 || h.wr1 <= 0 || h.wl2 <= 0 || h.wr2 <= 0)
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: empty extent", who);
+  if ((h.leg1 != MPSE_LEG_UP && h.leg1 != MPSE_LEG_DOWN) || (h.leg2 != MPSE_LEG_UP && h.leg2 != MPSE_LEG_DOWN) ||
+      (h.leg1 == MPSE_LEG_DOWN && h.leg2 == MPSE_LEG_UP))
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: layers act up/up, down/down or up/down", who);
+  return MPSE_OK;
+}
+
+}  // namespace
+
+// counts a solve that reached its decision and turns the control block into outputs and status
+static int pcg_report(mpse_ctx* ctx, const PcgCtl& hc, bool masked, double tol, int* iters_host, double* relres_host,
+                      double* lvalue_host) {
+  ++ctx->pcg_stats[mpse_ctx::PS_SOLVES];
+  if (masked) ++ctx->pcg_stats[mpse_ctx::PS_MASKED];
+  ctx->pcg_stats[mpse_ctx::PS_ITERS] += hc.iters;
+  if (iters_host) *iters_host = hc.iters;
+  if (relres_host) *relres_host = std::sqrt(hc.relres2);
+  if (lvalue_host) *lvalue_host = hc.lvalue;
+  switch (hc.why) {
+    case PCG_WHY_TOL:
+    case PCG_WHY_ZERO_B:
+      ++ctx->pcg_stats[mpse_ctx::PS_END_TOL];
+      return MPSE_OK;
+    case PCG_WHY_MAXITER:
+      ++ctx->pcg_stats[mpse_ctx::PS_END_MAXITER];
+      return mpse_fail(ctx, MPSE_ERR_NOCONV, "pcg: |r| / |b| = %.3e after %d iterations (tol %.3e)", std::sqrt(hc.relres2),
+                       hc.iters, tol);
+    case PCG_WHY_CURVATURE:
+      ++ctx->pcg_stats[mpse_ctx::PS_END_CURVATURE];
+      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: curvature p^H A p <= 0 (or not a number) after %d iterations: the operator "
+                       "is not positive definite", hc.iters);
+    case PCG_WHY_DIAG:
+      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: the preconditioner diagonal has entries that are not positive");
+    default:
+      return mpse_fail(ctx, MPSE_ERR_HIP, "pcg: control block without a decision");
+  }
+}
 
 extern "C" {
 
@@ -379,37 +560,98 @@ int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double 
                      : pcg_run<false>(ctx, dtype, h, twolayer, shift, diag, mask, static_cast<const double*>(b),
                                       static_cast<double*>(x), tol, max_iter, n, &hc);
   if (st != MPSE_OK) return st;      // (allocation or runtime failure: no solve is counted)
-  ++ctx->pcg_stats[mpse_ctx::PS_SOLVES];
   if (twolayer) ++ctx->pcg_stats[mpse_ctx::PS_TWOLAYER];
-  if (mask_f64) ++ctx->pcg_stats[mpse_ctx::PS_MASKED];
-  ctx->pcg_stats[mpse_ctx::PS_ITERS] += hc.iters;
-  if (iters_host) *iters_host = hc.iters;
-  if (relres_host) *relres_host = std::sqrt(hc.relres2);
-  if (lvalue_host) *lvalue_host = hc.lvalue;
-  switch (hc.why) {
-    case PCG_WHY_TOL:
-    case PCG_WHY_ZERO_B:
-      ++ctx->pcg_stats[mpse_ctx::PS_END_TOL];
-      return MPSE_OK;
-    case PCG_WHY_MAXITER:
-      ++ctx->pcg_stats[mpse_ctx::PS_END_MAXITER];
-      return mpse_fail(ctx, MPSE_ERR_NOCONV, "pcg: |r| / |b| = %.3e after %d iterations (tol %.3e)", std::sqrt(hc.relres2),
-                       hc.iters, tol);
-    case PCG_WHY_CURVATURE:
-      ++ctx->pcg_stats[mpse_ctx::PS_END_CURVATURE];
-      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: curvature p^H A p <= 0 (or not a number) after %d iterations: the operator "
-                       "is not positive definite", hc.iters);
-    case PCG_WHY_DIAG:
-      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: the preconditioner diagonal has entries that are not positive");
-    default:
-      return mpse_fail(ctx, MPSE_ERR_HIP, "pcg: control block without a decision");
-  }
+  return pcg_report(ctx, hc, mask_f64 != nullptr, tol, iters_host, relres_host, lvalue_host);
 }
 
 int mpse_pcg_stats(mpse_ctx* ctx, int64_t* counts, int n) {
   if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
   for (int i = 0; i < n && i < mpse_ctx::PS_COUNT; ++i) counts[i] = ctx->pcg_stats[i];
   if (n > mpse_ctx::PS_COUNT) counts[mpse_ctx::PS_COUNT] = PCG_K;
+  return MPSE_OK;
+}
+
+int mpse_pcg_sum(mpse_ctx* ctx, int dtype, int nterms, const mpse_heff_ft* terms, const double* weights_host,
+                 double shift, const void* diag_f64, const void* mask_f64, const void* b, void* x, double tol,
+                 int max_iter, int* iters_host, double* relres_host, double* lvalue_host) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (!terms || !weights_host || !b || !x) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: null argument");
+  MPSE_BIND(ctx);
+  if (nterms < 1 || nterms > 4) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: 1 to 4 terms, got %d", nterms);
+  if (dtype != MPSE_F64 && dtype != MPSE_C128) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: unknown dtype");
+  if (!(tol >= 0.0) || !std::isfinite(shift)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: tol must be >= 0 and shift finite");
+  for (int t = 0; t < nterms; ++t) {
+    const mpse_heff_ft& h = terms[t];
+    if (!h.L || !h.R || !h.W1 || !h.W2) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: null operator part in term %d", t);
+    MPSE_TRY(ft_shape_ok(ctx, h, "pcg_sum"));
+    if (!std::isfinite(weights_host[t])) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: weight %d is not finite", t);
+    if (dtype != MPSE_C128 && (h.l_dtype == MPSE_C128 || h.r_dtype == MPSE_C128 || h.w_dtype == MPSE_C128))
+      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: real vectors with complex operator parts");
+    if (h.Dl != terms[0].Dl || h.Dr != terms[0].Dr || h.d_up != terms[0].d_up || h.d_down != terms[0].d_down)
+      return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg_sum: term %d acts on another centre shape", t);
+  }
+  const int64_t n = terms[0].Dl * terms[0].d_up * terms[0].d_down * terms[0].Dr;
+  const size_t bytes = size_t(n) * dtype_size(dtype);
+  const char *xb = static_cast<const char*>(x), *bb = static_cast<const char*>(b);
+  if (xb < bb + bytes && bb < xb + bytes) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: x must not overlap b");
+  if (max_iter <= 0) max_iter = n > (int64_t(1) << 27) ? (1 << 30) : int(10 * n);
+  wsite_written(ctx, x, bytes);
+
+  PcgCtl hc;
+  const double *diag = static_cast<const double*>(diag_f64), *mask = static_cast<const double*>(mask_f64);
+  const int st = dtype == MPSE_C128
+                     ? pcg_run<true>(ctx, dtype, nullptr, 0, shift, diag, mask, static_cast<const double*>(b),
+                                     static_cast<double*>(x), tol, max_iter, n, &hc, nterms, terms, weights_host)
+                     : pcg_run<false>(ctx, dtype, nullptr, 0, shift, diag, mask, static_cast<const double*>(b),
+                                      static_cast<double*>(x), tol, max_iter, n, &hc, nterms, terms, weights_host);
+  if (st != MPSE_OK) return st;
+  ++ctx->pcg_sum_stats[mpse_ctx::PSS_SOLVES];
+  ctx->pcg_sum_stats[mpse_ctx::PSS_ITERS] += hc.iters;
+  return pcg_report(ctx, hc, mask_f64 != nullptr, tol, iters_host, relres_host, lvalue_host);
+}
+
+int mpse_pcg_sum_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  for (int i = 0; i < n; ++i) counts[i] = i < mpse_ctx::PSS_COUNT ? ctx->pcg_sum_stats[i] : 0;
+  return MPSE_OK;
+}
+
+int mpse_site_factor_ft(mpse_ctx* ctx, const mpse_heff_ft* h, void* S_f64) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (!h || !S_f64 || !h->W1 || !h->W2) return mpse_fail(ctx, MPSE_ERR_ARG, "site_factor_ft: null argument");
+  MPSE_BIND(ctx);
+  MPSE_TRY(ft_shape_ok(ctx, *h, "site_factor_ft"));
+  if (h->w_dtype != MPSE_F64) return mpse_fail(ctx, MPSE_ERR_ARG, "site_factor_ft: real MPO sites only");
+  const long long total = h->wl1 * h->wl2 * h->d_up * h->d_down * h->wr1 * h->wr2;
+  hipLaunchKernelGGL(k_site_factor_ft, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ft_shape(*h),
+                     static_cast<const double*>(h->W1), static_cast<const double*>(h->W2), static_cast<double*>(S_f64));
+  MPSE_HIP(ctx, hipGetLastError());
+  return MPSE_OK;
+}
+
+int mpse_diag_ft(mpse_ctx* ctx, const mpse_heff_ft* h, const void* S_f64, double weight, double shift, int accumulate,
+                 void* diag_f64) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (!h || !S_f64 || !diag_f64 || !h->L || !h->R) return mpse_fail(ctx, MPSE_ERR_ARG, "diag_ft: null argument");
+  MPSE_BIND(ctx);
+  MPSE_TRY(ft_shape_ok(ctx, *h, "diag_ft"));
+  const long long total = h->Dl * h->d_up * h->d_down * h->Dr;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  const FtShape fs = ft_shape(*h);
+  const double *L = static_cast<const double*>(h->L), *R = static_cast<const double*>(h->R);
+  const double* S = static_cast<const double*>(S_f64);
+  double* dg = static_cast<double*>(diag_f64);
+  const bool lc = h->l_dtype == MPSE_C128, rc = h->r_dtype == MPSE_C128;
+  if (lc && rc)
+    hipLaunchKernelGGL((k_diag_ft<true, true>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  else if (lc)
+    hipLaunchKernelGGL((k_diag_ft<true, false>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  else if (rc)
+    hipLaunchKernelGGL((k_diag_ft<false, true>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  else
+    hipLaunchKernelGGL((k_diag_ft<false, false>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  MPSE_HIP(ctx, hipGetLastError());
+  if (!accumulate) ++ctx->pcg_sum_stats[mpse_ctx::PSS_DIAGS];
   return MPSE_OK;
 }
 

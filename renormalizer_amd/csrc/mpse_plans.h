@@ -933,4 +933,153 @@ inline Plan plan_heff2(int dtype, const mpse_heff& h) {
   return p;
 }
 
+// Two MPO layers on a centre with two physical legs (a site of an operator in MPS form: C (Dl, d_up, d_down, Dr)),
+// each layer on a leg of its own choice: the three terms of ((omega - Liou)^2) X = a a X + 2 a X H + X H H with
+// a = omega - H (cv/finitet.py:215-299).  Labels:
+//   L (a, b, c, d)  a = bond towards the centre (ket), b / c = MPO bonds of layer 1 / 2, d = bond of the result (bra)
+//   R (j, g, i, k)  the same on the right;   C (a, u, v, j);   out (d, u', v', k)
+//   layer n, MPO site W_n (wl_n, d, d, wr_n): trans == 0: leg'[x] = sum_y W_n[., x, y, .] leg[y]; trans != 0:
+//   leg'[y] = sum_x W_n[., x, y, .] leg[x].  The leg no layer touches passes through.
+// Both layers up is plan_heff2 with d_down as its batch index (the same steps, so the same bits); both down moves the
+// spectator into the batch of the MPO steps; one on each leg (up first) runs the second layer as a batch over
+// (bond, MPO bond, up leg).  Nothing is transposed in memory: every permutation is in the views.
+inline View ft_w_view(int buf, int dt, bool trans, char lb, int64_t wl, char in, char out, int64_t d, char rb,
+                      int64_t wr) {
+  return trans ? View(buf, dt, {{lb, wl}, {in, d}, {out, d}, {rb, wr}}) : View(buf, dt, {{lb, wl}, {out, d}, {in, d}, {rb, wr}});
+}
+
+inline const char* ft_check(const mpse_heff_ft& h) {
+  if (h.Dl <= 0 || h.Dr <= 0 || h.d_up <= 0 || h.d_down <= 0 || h.wl1 <= 0 || h.wr1 <= 0 || h.wl2 <= 0 || h.wr2 <= 0)
+    return "heff_ft: empty extent";
+  if ((h.leg1 != MPSE_LEG_UP && h.leg1 != MPSE_LEG_DOWN) || (h.leg2 != MPSE_LEG_UP && h.leg2 != MPSE_LEG_DOWN))
+    return "heff_ft: a layer acts on MPSE_LEG_UP or MPSE_LEG_DOWN";
+  if (h.leg1 == MPSE_LEG_DOWN && h.leg2 == MPSE_LEG_UP)
+    return "heff_ft: layers on different legs commute - give the one on the up leg first";
+  return nullptr;
+}
+
+// largest intermediate of a chain: left to right T1 (b, c), T2 (c, g), T3 (g, i); right to left T1 (g, i), T2 (b, i), T3 (b, c)
+inline int64_t ft_tmp_elems(const mpse_heff_ft& h, bool right_to_left = false) {
+  const int64_t mid = right_to_left ? h.wl1 * h.wr2 : h.wl2 * h.wr1;
+  return std::max(h.wl1 * h.wl2, std::max(mid, h.wr1 * h.wr2)) * h.Dl * h.d_up * h.d_down * h.Dr;
+}
+
+// Left-to-right part shared by the matvec and the left environment update: T3 = W_2 W_1 (L . C); *up / *down receive
+// the labels of the two legs in T3, *kr the order in which the last product runs over (j, g, i).
+inline View ft_chain_l(Plan& p, int dtype, const mpse_heff_ft& h, char* up, char* down, std::string* kr) {
+  const int64_t Dl = h.Dl, Dr = h.Dr, du = h.d_up, dv = h.d_down;
+  View L(B_L, h.l_dtype, {{'a', Dl}, {'b', h.wl1}, {'c', h.wl2}, {'d', Dl}});
+  View C(B_C, dtype, {{'a', Dl}, {'u', du}, {'v', dv}, {'j', Dr}});
+  View T1(B_T1, dtype, {{'b', h.wl1}, {'c', h.wl2}, {'d', Dl}, {'u', du}, {'v', dv}, {'j', Dr}});
+  contract(p, L, C, T1, "bcd", "a", "uvj");
+  const bool t1 = h.trans1 != 0, t2 = h.trans2 != 0;
+  if (h.leg1 == MPSE_LEG_UP && h.leg2 == MPSE_LEG_UP) {
+    View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'u', 'x', du, 'g', h.wr1);
+    View W2 = ft_w_view(B_W1, h.w_dtype, t2, 'c', h.wl2, 'x', 'y', du, 'i', h.wr2);
+    View T2(B_T2, dtype, {{'c', h.wl2}, {'d', Dl}, {'x', du}, {'g', h.wr1}, {'v', dv}, {'j', Dr}});
+    contract(p, W1, T1, T2, "xg", "bu", "vj", "cd");
+    View T3(B_T3, dtype, {{'d', Dl}, {'y', du}, {'v', dv}, {'j', Dr}, {'g', h.wr1}, {'i', h.wr2}});
+    contract(p, W2, T2, T3, "yi", "cx", "vjg", "d");
+    *up = 'y', *down = 'v', *kr = "jgi";
+    return T3;
+  }
+  if (h.leg1 == MPSE_LEG_DOWN && h.leg2 == MPSE_LEG_DOWN) {
+    View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'v', 's', dv, 'g', h.wr1);
+    View W2 = ft_w_view(B_W1, h.w_dtype, t2, 'c', h.wl2, 's', 't', dv, 'i', h.wr2);
+    View T2(B_T2, dtype, {{'c', h.wl2}, {'d', Dl}, {'u', du}, {'s', dv}, {'g', h.wr1}, {'j', Dr}});
+    contract(p, W1, T1, T2, "sg", "bv", "j", "cdu");
+    View T3(B_T3, dtype, {{'d', Dl}, {'u', du}, {'t', dv}, {'j', Dr}, {'g', h.wr1}, {'i', h.wr2}});
+    contract(p, W2, T2, T3, "ti", "cs", "jg", "du");
+    *up = 'u', *down = 't', *kr = "jgi";
+    return T3;
+  }
+  // layer 1 on the up leg, layer 2 on the down leg, side by side
+  View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'u', 'x', du, 'g', h.wr1);
+  View W2 = ft_w_view(B_W1, h.w_dtype, t2, 'c', h.wl2, 'v', 's', dv, 'i', h.wr2);
+  View T2(B_T2, dtype, {{'c', h.wl2}, {'d', Dl}, {'g', h.wr1}, {'x', du}, {'v', dv}, {'j', Dr}});
+  contract(p, W1, T1, T2, "xg", "bu", "vj", "cd");
+  View T3(B_T3, dtype, {{'d', Dl}, {'g', h.wr1}, {'x', du}, {'s', dv}, {'i', h.wr2}, {'j', Dr}});
+  contract(p, W2, T2, T3, "si", "cv", "j", "dgx");
+  *up = 'x', *down = 's', *kr = "gij";
+  return T3;
+}
+
+// out (Dl, d_up, d_down, Dr) = term applied to C
+inline Plan plan_heff_ft(int dtype, const mpse_heff_ft& h) {
+  Plan p;
+  if ((p.error = ft_check(h))) return p;
+  p.tmp_elems[0] = p.tmp_elems[1] = p.tmp_elems[2] = ft_tmp_elems(h);
+  char up, down;
+  std::string kr;
+  View T3 = ft_chain_l(p, dtype, h, &up, &down, &kr);
+  View R(B_R, h.r_dtype, {{'j', h.Dr}, {'g', h.wr1}, {'i', h.wr2}, {'k', h.Dr}});
+  View O(B_OUT, dtype, {{'d', h.Dl}, {up, h.d_up}, {down, h.d_down}, {'k', h.Dr}});
+  contract(p, T3, R, O, std::string("d") + up + down, kr, "k");
+  return p;
+}
+
+// Environment of a term moved over one site X (Dl, d_up, d_down, Dr): bra = conj(X), ket = X, every layer contracts its
+// own leg between them, the untouched leg is contracted directly.  Buffers: B_L = incoming environment (L (Dl, wl1, wl2,
+// Dl) for MPSE_DOMAIN_L, R (Dr, wr1, wr2, Dr) for MPSE_DOMAIN_R; h.L / h.R are not read), B_C = B_BRA = X,
+// B_OUT = (Dr, wr1, wr2, Dr) resp. (Dl, wl1, wl2, Dl), index order (ket bond, layer 1, layer 2, bra bond).
+inline Plan plan_env_ft(int dtype, int domain, const mpse_heff_ft& h, int env_dtype) {
+  Plan p;
+  if ((p.error = ft_check(h))) return p;
+  p.tmp_elems[0] = p.tmp_elems[1] = p.tmp_elems[2] = ft_tmp_elems(h, domain == MPSE_DOMAIN_R);
+  const int64_t Dl = h.Dl, Dr = h.Dr, du = h.d_up, dv = h.d_down;
+  const int conj = dtype == MPSE_C128 ? 1 : 0;
+  if (domain == MPSE_DOMAIN_L) {
+    mpse_heff_ft hl = h;
+    hl.l_dtype = env_dtype;
+    char up, down;
+    std::string kr;
+    View T3 = ft_chain_l(p, dtype, hl, &up, &down, &kr);
+    View BRA(B_BRA, dtype, {{'d', Dl}, {up, du}, {down, dv}, {'k', Dr}});
+    View O(B_OUT, dtype, {{'j', Dr}, {'g', h.wr1}, {'i', h.wr2}, {'k', Dr}});
+    contract(p, BRA, T3, O, "k", std::string("d") + up + down, kr, "", "", conj);
+    return p;
+  }
+  if (domain != MPSE_DOMAIN_R) {
+    p.error = "env: bad domain";
+    return p;
+  }
+  const bool t1 = h.trans1 != 0, t2 = h.trans2 != 0;
+  View X(B_C, dtype, {{'a', Dl}, {'u', du}, {'v', dv}, {'j', Dr}});
+  View R(B_L, env_dtype, {{'j', Dr}, {'g', h.wr1}, {'i', h.wr2}, {'k', Dr}});
+  View T1(B_T1, dtype, {{'a', Dl}, {'u', du}, {'v', dv}, {'g', h.wr1}, {'i', h.wr2}, {'k', Dr}});
+  contract(p, X, R, T1, "auv", "j", "gik");
+  View O(B_OUT, dtype, {{'a', Dl}, {'b', h.wl1}, {'c', h.wl2}, {'d', Dl}});
+  if (h.leg1 == MPSE_LEG_UP && h.leg2 == MPSE_LEG_UP) {
+    View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'u', 'x', du, 'g', h.wr1);
+    View W2 = ft_w_view(B_W1, h.w_dtype, t2, 'c', h.wl2, 'x', 'y', du, 'i', h.wr2);
+    View T2(B_T2, dtype, {{'a', Dl}, {'b', h.wl1}, {'x', du}, {'v', dv}, {'i', h.wr2}, {'k', Dr}});
+    contract(p, W1, T1, T2, "bx", "ug", "vik", "a");
+    View T3(B_T3, dtype, {{'a', Dl}, {'b', h.wl1}, {'c', h.wl2}, {'y', du}, {'v', dv}, {'k', Dr}});
+    contract(p, W2, T2, T3, "cy", "xi", "vk", "ab");
+    View BRA(B_BRA, dtype, {{'d', Dl}, {'y', du}, {'v', dv}, {'k', Dr}});
+    contract(p, BRA, T3, O, "d", "yvk", "abc", "", "", conj);
+    return p;
+  }
+  if (h.leg1 == MPSE_LEG_DOWN && h.leg2 == MPSE_LEG_DOWN) {
+    View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'v', 's', dv, 'g', h.wr1);
+    View W2 = ft_w_view(B_W1, h.w_dtype, t2, 'c', h.wl2, 's', 't', dv, 'i', h.wr2);
+    View T2(B_T2, dtype, {{'a', Dl}, {'u', du}, {'b', h.wl1}, {'s', dv}, {'i', h.wr2}, {'k', Dr}});
+    contract(p, W1, T1, T2, "bs", "vg", "ik", "au");
+    View T3(B_T3, dtype, {{'a', Dl}, {'u', du}, {'b', h.wl1}, {'c', h.wl2}, {'t', dv}, {'k', Dr}});
+    contract(p, W2, T2, T3, "ct", "si", "k", "aub");
+    View BRA(B_BRA, dtype, {{'d', Dl}, {'u', du}, {'t', dv}, {'k', Dr}});
+    contract(p, BRA, T3, O, "d", "utk", "abc", "", "", conj);
+    return p;
+  }
+  View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'u', 'x', du, 'g', h.wr1);
+  View W2 = ft_w_view(B_W1, h.w_dtype, t2, 'c', h.wl2, 'v', 's', dv, 'i', h.wr2);
+  View T2(B_T2, dtype, {{'a', Dl}, {'b', h.wl1}, {'x', du}, {'v', dv}, {'i', h.wr2}, {'k', Dr}});
+  contract(p, W1, T1, T2, "bx", "ug", "vik", "a");
+  View T3(B_T3, dtype, {{'a', Dl}, {'b', h.wl1}, {'x', du}, {'c', h.wl2}, {'s', dv}, {'k', Dr}});
+  contract(p, W2, T2, T3, "cs", "vi", "k", "abx");
+  View BRA(B_BRA, dtype, {{'d', Dl}, {'x', du}, {'s', dv}, {'k', Dr}});
+  contract(p, BRA, T3, O, "d", "xsk", "abc", "", "", conj);
+  return p;
+}
+
 }  // namespace mpse_plan

@@ -1,8 +1,10 @@
 """Frequency-domain spectra by the correction vector (dynamical DMRG), counterpart of renormalizer/cv/.
 
-Zero temperature only (``SpectraZtCV``): the centre problems ((H - e0 - omega)^2 + eta^2) x = b are solved inside the
-engine by ``mpse_pcg`` (include/mpsengine.h)."""
+Zero temperature (``SpectraZtCV``): the centre problems ((H - e0 - omega)^2 + eta^2) x = b are solved inside the engine
+by ``mpse_pcg``.  Finite temperature (``SpectraFtCV``): the correction vector is an operator, the centre problems
+((omega - Liou)^2 + eta^2) x = b are a sum of three two-layer terms solved by ``mpse_pcg_sum`` (include/mpsengine.h)."""
+from .finitet import SpectraFtCV
 from .spectra_cv import SpectraCv, batch_run
 from .zerot import SpectraZtCV
 
-__all__ = ["SpectraCv", "SpectraZtCV", "batch_run"]
+__all__ = ["SpectraCv", "SpectraFtCV", "SpectraZtCV", "batch_run"]

@@ -64,6 +64,18 @@ class mpse_heff(C.Structure):
                 ("l_unit", C.c_int64), ("r_unit", C.c_int64)]
 
 
+LEG_UP, LEG_DOWN = 0, 1
+
+
+class mpse_heff_ft(C.Structure):
+    _fields_ = [("Dl", C.c_int64), ("Dr", C.c_int64), ("d_up", C.c_int64), ("d_down", C.c_int64),
+                ("wl1", C.c_int64), ("wr1", C.c_int64), ("wl2", C.c_int64), ("wr2", C.c_int64),
+                ("leg1", C.c_int), ("leg2", C.c_int), ("trans1", C.c_int), ("trans2", C.c_int),
+                ("L", C.c_void_p), ("l_dtype", C.c_int),
+                ("R", C.c_void_p), ("r_dtype", C.c_int),
+                ("W1", C.c_void_p), ("W2", C.c_void_p), ("w_dtype", C.c_int)]
+
+
 def idx1(ext, stride):
     return mpse_index(int(ext), max(int(ext), 1), 0, int(stride))
 
@@ -150,6 +162,14 @@ _SIGNATURES = {
     "mpse_pcg": [C.c_void_p, C.c_int, C.POINTER(mpse_heff), C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                  C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), _dblp, _dblp],
     "mpse_pcg_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_heff_apply_ft": [C.c_void_p, C.c_int, C.POINTER(mpse_heff_ft), C.c_void_p, C.c_void_p],
+    "mpse_env_update_ft": [C.c_void_p, C.c_int, C.c_int, C.POINTER(mpse_heff_ft), C.c_void_p, C.c_int, C.c_void_p,
+                           C.c_void_p],
+    "mpse_pcg_sum": [C.c_void_p, C.c_int, C.c_int, C.POINTER(mpse_heff_ft), _dblp, C.c_double, C.c_void_p, C.c_void_p,
+                     C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), _dblp, _dblp],
+    "mpse_pcg_sum_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_site_factor_ft": [C.c_void_p, C.POINTER(mpse_heff_ft), C.c_void_p],
+    "mpse_diag_ft": [C.c_void_p, C.POINTER(mpse_heff_ft), C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -501,6 +521,83 @@ class Engine:
         st = self.lib.mpse_pcg(self.ctx, x.code, C.byref(hop.heff), int(hop.twolayer), float(shift),
                                None if diag is None else diag.ptr, None if mask is None else mask.ptr, b.ptr, x.ptr,
                                float(tol), int(max_iter), C.byref(it), C.byref(rel), C.byref(lv))
+        if check and st not in (0, 3):
+            self._check(st)
+        return PcgResult(int(st), it.value, rel.value, lv.value)
+
+    # -- two MPO layers on a two-leg centre: the terms of the finite-temperature correction-vector operator
+    def ft_term(self, w1, w2, leg1, leg2, trans1, trans2, shape, L=None, R=None):
+        """Descriptor (``mpse_heff_ft``) of one term on a centre / site of ``shape`` (Dl, d_up, d_down, Dr): MPO sites
+        ``w1`` (layer 1) and ``w2`` on the legs ``leg1`` / ``leg2``; ``L`` / ``R`` the term's environments (not needed
+        for an environment update).  The descriptor keeps no reference: the caller holds the tensors."""
+        h = mpse_heff_ft()
+        h.Dl, h.d_up, h.d_down, h.Dr = [int(v) for v in shape]
+        h.wl1, h.wr1, h.wl2, h.wr2 = w1.shape[0], w1.shape[3], w2.shape[0], w2.shape[3]
+        h.leg1, h.leg2, h.trans1, h.trans2 = int(leg1), int(leg2), int(bool(trans1)), int(bool(trans2))
+        assert w1.dtype == w2.dtype
+        h.W1, h.W2, h.w_dtype = w1.ptr, w2.ptr, w1.code
+        if L is not None:
+            assert L.shape == (h.Dl, h.wl1, h.wl2, h.Dl), (L.shape, shape)
+            h.L, h.l_dtype = L.ptr, L.code
+        if R is not None:
+            assert R.shape == (h.Dr, h.wr1, h.wr2, h.Dr), (R.shape, shape)
+            h.R, h.r_dtype = R.ptr, R.code
+        return h
+
+    def heff_apply_ft(self, term, c):
+        """``term`` applied to the centre ``c`` (``mpse_heff_apply_ft``)."""
+        out = self.empty(c.shape, c.dtype)
+        self._check(self.lib.mpse_heff_apply_ft(self.ctx, c.code, C.byref(term), c.ptr, out.ptr))
+        return out
+
+    def env_update_ft(self, term, domain, env, x):
+        """The environment ``env`` of ``term`` moved over the site ``x`` (bra = conj(x)); ``domain`` "L" or "R"
+        (``mpse_env_update_ft``).  Returns the new environment (ket bond, layer 1, layer 2, bra bond)."""
+        left = domain == "L"
+        oshape = (term.Dr, term.wr1, term.wr2, term.Dr) if left else (term.Dl, term.wl1, term.wl2, term.Dl)
+        dt = np.complex128 if (x.is_complex or env.is_complex) else np.float64
+        assert x.dtype == dt, "the site must have the working dtype"
+        out = self.empty(oshape, dt)
+        self._check(self.lib.mpse_env_update_ft(self.ctx, x.code, DOMAIN_L if left else DOMAIN_R, C.byref(term),
+                                                env.ptr, env.code, x.ptr, out.ptr))
+        return out
+
+    def site_factor_ft(self, term):
+        """Per-site factor of the diagonal of ``term`` (``mpse_site_factor_ft``): depends on the two MPO sites only."""
+        s = self.empty((term.wl1, term.wl2, term.d_up, term.d_down, term.wr1, term.wr2), np.float64)
+        self._check(self.lib.mpse_site_factor_ft(self.ctx, C.byref(term), s.ptr))
+        return s
+
+    def diag_ft_sum(self, terms, factors, weights, shift):
+        """``shift + sum_t weights[t] * diag(terms[t])`` as a float64 device tensor of the centre's shape."""
+        t0 = terms[0]
+        diag = self.empty((t0.Dl, t0.d_up, t0.d_down, t0.Dr), np.float64)
+        for k, (t, s, w) in enumerate(zip(terms, factors, weights)):
+            self._check(self.lib.mpse_diag_ft(self.ctx, C.byref(t), s.ptr, float(w), float(shift), int(k > 0), diag.ptr))
+        return diag
+
+    PCG_SUM_STATS = ("solves", "iterations", "term_applies", "host_waits", "diagonals")
+
+    def pcg_sum_stats(self):
+        """{name: count} of the summed conjugate-gradient solves (``mpse_pcg_sum_stats``), cumulative."""
+        v = (C.c_int64 * len(self.PCG_SUM_STATS))()
+        self._check(self.lib.mpse_pcg_sum_stats(self.ctx, v, len(v)))
+        return dict(zip(self.PCG_SUM_STATS, (int(x) for x in v)))
+
+    def pcg_sum(self, terms, weights, b, x, diag=None, mask=None, shift=0.0, tol=1e-5, max_iter=0, check=True):
+        """Solve ``(mask * sum_t weights[t] * terms[t] + shift) x = b`` (``mpse_pcg_sum``); arguments and result as
+        ``pcg``, ``terms`` a list of ``ft_term`` descriptors."""
+        nt = len(terms)
+        arr = (mpse_heff_ft * nt)(*terms)
+        w = (C.c_double * nt)(*[float(v) for v in weights])
+        n = x.size
+        assert b.size == n and b.dtype == x.dtype
+        assert diag is None or (diag.size == n and diag.dtype == np.float64)
+        assert mask is None or (mask.size == n and mask.dtype == np.float64)
+        it, rel, lv = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        st = self.lib.mpse_pcg_sum(self.ctx, x.code, nt, arr, w, float(shift), None if diag is None else diag.ptr,
+                                   None if mask is None else mask.ptr, b.ptr, x.ptr, float(tol), int(max_iter),
+                                   C.byref(it), C.byref(rel), C.byref(lv))
         if check and st not in (0, 3):
             self._check(st)
         return PcgResult(int(st), it.value, rel.value, lv.value)
