@@ -431,6 +431,50 @@ int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double 
  * Diagnostics for tests; no device work. */
 int mpse_pcg_stats(mpse_ctx* ctx, int64_t* counts, int n);
 
+/* count independent systems with the semantics of mpse_pcg, member by member: h, shift_host, b, x and the four outputs
+ * are arrays of count entries (b / x hold device pointers; diag_f64 / mask_f64 arrays of device pointers, the array or
+ * single entries may be NULL); dtype, twolayer, tol and max_iter serve all members (max_iter <= 0: 10 n of each member).
+ * The stopping rule, the b == 0 ending, the curvature and diagonal refusals and lvalue are mpse_pcg's.
+ *   status_host[i] : the member's own MPSE_OK / MPSE_ERR_NOCONV / MPSE_ERR_ARG (MPSE_ERR_SHAPE for a member mpse_pcg
+ *                    refuses for its shape); a member that does not converge or is refused does not disturb the others
+ *   return value   : non-zero only for argument, allocation or runtime errors of the call as a whole
+ * Members with twolayer != 0 on a one-site centre whose shape passes the rule of mpse_pcg_batch_plan (bra bonds == ket
+ * bonds, no ancilla, L and R of the working dtype, real W) are solved together, members of equal (Dl, d, Dr, wl, wr) in
+ * launch sets of up to 32: the matvec is ONE launch for the whole set (mpse_small2.hip; it also forms q = mask * y +
+ * shift * p and the partial sums of p^H q), every vector kernel of the iteration carries a member index, each member has
+ * its own control block and partials, a member whose decision has fallen does nothing in later launches, and the host
+ * reads the pinned mirrors of all control blocks every fourth iteration until every member has decided.  Every other
+ * member (one layer, two sites, outside the rule) runs through mpse_pcg unchanged, one after another, and returns bit
+ * for bit what mpse_pcg returns.
+ * Determinism: a member's x, iters, relres and lvalue are bitwise the same whatever else is in the batch - alone
+ * (count == 1), with any neighbours, at any position, on either side of a launch-set boundary; its path depends on its
+ * own shape only.  The batched path uses another matvec than mpse_pcg (other summation order), so a batched member
+ * agrees with mpse_pcg on the same system to the solver tolerance, not bitwise.  Synchronous. */
+int mpse_pcg_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff* h, int twolayer, const double* shift_host,
+                   const void* const* diag_f64, const void* const* mask_f64, const void* const* b, void* const* x,
+                   double tol, int max_iter, int* status_host, int* iters_host, double* relres_host,
+                   double* lvalue_host);
+/* counts[i], i < n, cumulative:
+ *    0  members solved by the batched kernels
+ *    1  members handed to mpse_pcg
+ *    2  launch sets
+ *    3  batched matvec launches issued by iterations (one per iteration of a launch set, whatever its size; the one of
+ *       the start residuals is not counted; past the last decision the host has enqueued up to 3 more)
+ *    4  host waits of the launch sets
+ *    5  not a count: the member limit per launch set
+ * mpse_pcg_stats does not count the members solved by the batched kernels; members handed to mpse_pcg count there as
+ * any other solve.  Diagnostics for tests; no device work. */
+int mpse_pcg_batch_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The eligibility rule of the one-launch two-layer matvec, on the shape alone: returns 1 when a one-site two-layer
+ * centre (Dl, d, Dr) with MPO bonds wl, wr of working type dtype takes it, else 0.  Eligible: wl, wr <= info[0],
+ * d <= info[1], Dl, Dr <= info[2], and the launch plan (row of the transposed L, sparse W list, the intermediates of a
+ * slice of at least one ket-bond state of R) within info[3] bytes of LDS.  info[i], i < n (may be NULL):
+ *    0 - 3  the limits: MPO bond channels, physical dimension, bond dimension, LDS bytes per workgroup
+ *    4      LDS bytes of the plan (0: not eligible)    5  its slice width    6  its number of slices
+ *    7      entries of the sparse W list kept in LDS
+ * No context, no device work. */
+int mpse_pcg_batch_plan(int dtype, int64_t Dl, int64_t d, int64_t Dr, int64_t wl, int64_t wr, int64_t* info, int n);
+
 /* mpse_pcg over a weighted sum of mpse_heff_ft terms: (mask * sum_t weight[t] * A_t + shift) x = b with 1 <= nterms <= 4,
  * the centre system of the finite-temperature correction vector (weights 1, 2, 1; replaces scipy.sparse.linalg.cg of
  * cv/finitet.py:306-311).  All terms share Dl, Dr, d_up, d_down.  Every term writes a result vector of its own and the

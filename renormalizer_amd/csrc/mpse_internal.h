@@ -162,6 +162,9 @@ struct mpse_ctx {
   // the summed solves among them (mpse_pcg_sum_stats)
   enum PcgSumStat { PSS_SOLVES, PSS_ITERS, PSS_TERM_APPLIES, PSS_WAITS, PSS_DIAGS, PSS_COUNT };
   long long pcg_sum_stats[PSS_COUNT] = {0};
+  // mpse_pcg_batch (mpse_pcg_batch_stats; the order of include/mpsengine.h)
+  enum PcgBatchStat { PB_MEMBERS, PB_SINGLE, PB_SETS, PB_MATVEC_LAUNCHES, PB_WAITS, PB_COUNT };
+  long long pcg_batch_stats[PB_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 
@@ -372,6 +375,39 @@ int heff_small_batch_rt(mpse_ctx* ctx, int dtype, const mpse_heff* h, int B, con
 int heff_small_batch_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, int B, const BatchMember* mem,
                            const void* C0, void* parts0, int64_t n, double* dot_part0, int dot_cap, const int* skip0,
                            long long mstride);
+// One-launch two-layer matvec of small one-site centres (mpse_small2.hip), the matvec of mpse_pcg_batch.  Eligibility is
+// a rule on the member's own shape: every extent within these limits and the launch plan within the LDS budget.
+constexpr int SM2_WMAX = 8;            // MPO bond channels per layer (wl, wr)
+constexpr int SM2_DMAX = 16;           // physical dimension
+constexpr int SM2_BMAX = 64;           // bond dimensions Dl, Dr
+constexpr int SM2_LDS_MAX = 65536;     // bytes of LDS per workgroup (a second workgroup per compute unit stays possible)
+constexpr int SM2_NNZ_LDS = 1024;      // entries of the sparse W list kept in LDS (the rest is read from memory)
+struct Small2Plan {
+  int Dl, Dr, d, wl, wr;
+  int jh, nslice, G;                   // slice width of the ket bond of R, number of slices, K groups of the last step
+  int rows, pitch, nnz_lds;            // sparse W list: rows (x, y), capacity per row, entries held in LDS
+  int ptr_dbl, idx_dbl, csr_dbl;       // LDS doubles of the row pointers, the indices, the whole list (even)
+  int off_A, off_B;                    // LDS offsets (elements of the working type) behind the row of Lt
+  int lds;                             // dynamic LDS bytes
+};
+// one member of a launch set: operator parts, per-solve copies, vectors, partials and control block
+struct Pcg2Member {
+  const double *L, *R, *W;
+  double* Lt;                          // (Dl, wl, wl, Dl): [d][b][c][a] = L[a][b][c][d]
+  int *csr_ptr, *csr_idx;              // rows + 1 offsets; (u << 8) | v per entry
+  double* csr_val;
+  const double *mask, *diag, *b;
+  double *x, *y, *q, *r, *p;
+  double *part_bb, *part_pq, *part_bx, *part_rz0, *part_rz1;
+  void* ctl;                           // PcgCtl (mpse_pcg.hip); its first word is `done`
+  double shift;
+};
+// false: the shape does not take the one-launch two-layer matvec
+bool small2_plan(int dtype, int64_t Dl, int64_t d, int64_t Dr, int64_t wl, int64_t wr, Small2Plan* p);
+// per solve: transposed left environments and sparse W lists of B members in one launch
+int small2_prep(mpse_ctx* ctx, int dtype, const Small2Plan& p, int B, const Pcg2Member* mem);
+// one launch for B members; mode 0: y = Heff2 x, mode 1: q = mask * Heff2 p + shift * p with the partials of p^H q
+int small2_apply(mpse_ctx* ctx, int dtype, const Small2Plan& p, int B, const Pcg2Member* mem, int mode);
 // Fused 0-site matvec for large complex bond matrices (mpse_heff0.hip): number of parts it would deliver (0 = not
 // eligible), the attempt itself (needs a solve and MatvecReq::Parts::masked_ok), and the release of its per-solve data
 int heff0_fused_parts(const mpse_heff* h, int dtype);

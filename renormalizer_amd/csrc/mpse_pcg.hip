@@ -55,10 +55,9 @@ __device__ __forceinline__ double re_dotc(double2 a, double2 b) { return a.x * b
 // Entry: clears the control block, masks the start vector in place, partial sums of |mask * b|^2 and the number of
 // diagonal entries that are not positive (second slot of the pair).
 template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_pcg_prep(double* __restrict__ x, const double* __restrict__ b,
-                                                          const double* __restrict__ mask,
-                                                          const double* __restrict__ diag, long long n,
-                                                          double* __restrict__ part_bb, PcgCtl* ctl) {
+__device__ __forceinline__ void pcg_prep_body(double* __restrict__ x, const double* __restrict__ b,
+                                              const double* __restrict__ mask, const double* __restrict__ diag,
+                                              long long n, double* __restrict__ part_bb, PcgCtl* ctl) {
   if (blockIdx.x == 0 && threadIdx.x < PCG_CW) reinterpret_cast<double*>(ctl)[threadIdx.x] = 0.0;
   double bb = 0, bad = 0;
   const long long stride = (long long)gridDim.x * RED_THREADS;
@@ -75,18 +74,22 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_prep(double* __restrict__ x
     part_bb[2 * blockIdx.x + 1] = bad;
   }
 }
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_prep(double* __restrict__ x, const double* __restrict__ b,
+                                                          const double* __restrict__ mask,
+                                                          const double* __restrict__ diag, long long n,
+                                                          double* __restrict__ part_bb, PcgCtl* ctl) {
+  pcg_prep_body<CPLX>(x, b, mask, diag, n, part_bb, ctl);
+}
 
 // r = b - A x0 from y = Heff x0, p = z = r / diag; partial sums (r^H z, r^H r) and (b^H x, r^H x).  A right-hand side
 // that vanishes under the mask ends the solve here with x = 0; a diagonal entry that is not positive with MPSE_ERR_ARG.
 template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_pcg_start(const double* __restrict__ y, const double* __restrict__ b,
-                                                           const double* __restrict__ mask,
-                                                           const double* __restrict__ diag, double* __restrict__ x,
-                                                           double* __restrict__ r, double* __restrict__ p,
-                                                           double shift, long long n,
-                                                           const double* __restrict__ part_bb, int nb,
-                                                           double* __restrict__ part_rz, double* __restrict__ part_bx,
-                                                           PcgCtl* ctl) {
+__device__ __forceinline__ void pcg_start_body(const double* __restrict__ y, const double* __restrict__ b,
+                                               const double* __restrict__ mask, const double* __restrict__ diag,
+                                               double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
+                                               double shift, long long n, const double* __restrict__ part_bb, int nb,
+                                               double* __restrict__ part_rz, double* __restrict__ part_bx, PcgCtl* ctl) {
   double bb, bad;
   sum_partials(part_bb, nb, bb, bad);
   const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
@@ -123,6 +126,17 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_start(const double* __restr
     part_bx[2 * blockIdx.x] = bx;
     part_bx[2 * blockIdx.x + 1] = rx;
   }
+}
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_start(const double* __restrict__ y, const double* __restrict__ b,
+                                                           const double* __restrict__ mask,
+                                                           const double* __restrict__ diag, double* __restrict__ x,
+                                                           double* __restrict__ r, double* __restrict__ p,
+                                                           double shift, long long n,
+                                                           const double* __restrict__ part_bb, int nb,
+                                                           double* __restrict__ part_rz, double* __restrict__ part_bx,
+                                                           PcgCtl* ctl) {
+  pcg_start_body<CPLX>(y, b, mask, diag, x, r, p, shift, n, part_bb, nb, part_rz, part_bx, ctl);
 }
 
 // (a) q = mask * y + shift * p with y = Heff p; partial sums of p^H q (real for a Hermitian operator: the real part is kept)
@@ -198,16 +212,15 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_combine(const PcgTerms t, d
 // functional.  part_cur holds the (r^H z, r^H r) of the residual this step starts from, part_new receives the new ones
 // (another area: workgroups read all of part_cur while others already write).  A curvature p^H q that is not positive
 // (operator not positive definite, or NaN) ends the solve: every workgroup sees the same sum and leaves x alone.
+// (nbq: the number of p^H q partials - those of k_pcg_q, or one per workgroup of the one-launch two-layer matvec)
 template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_pcg_step(const double* __restrict__ p, const double* __restrict__ q,
-                                                          const double* __restrict__ b,
-                                                          const double* __restrict__ mask,
-                                                          const double* __restrict__ diag, double* __restrict__ x,
-                                                          double* __restrict__ r, long long n,
-                                                          const double* __restrict__ part_pq,
-                                                          const double* __restrict__ part_cur,
-                                                          double* __restrict__ part_new, double* __restrict__ part_bx,
-                                                          int nb, PcgCtl* ctl) {
+__device__ __forceinline__ void pcg_step_body(const double* __restrict__ p, const double* __restrict__ q,
+                                              const double* __restrict__ b, const double* __restrict__ mask,
+                                              const double* __restrict__ diag, double* __restrict__ x,
+                                              double* __restrict__ r, long long n, const double* __restrict__ part_pq,
+                                              int nbq, const double* __restrict__ part_cur,
+                                              double* __restrict__ part_new, double* __restrict__ part_bx, int nb,
+                                              PcgCtl* ctl) {
   // (a workgroup that starts after workgroup 0 has raised `done` for the curvature below leaves here instead of through
   // its own test of p^H q: the same outcome, x and r untouched)
   if (ctl->done) return;
@@ -230,7 +243,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_step(const double* __restri
   if (i0 < n) first = fetch(i0);
   asm volatile("" ::: "memory");
   double pq, rz_cur, t0, t1;
-  sum_partials(part_pq, nb, pq, t0);
+  sum_partials(part_pq, nbq, pq, t0);
   sum_partials(part_cur, nb, rz_cur, t1);
   if (!(pq > 0.0)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->done = 1, ctl->status = MPSE_ERR_ARG, ctl->why = PCG_WHY_CURVATURE;
@@ -259,18 +272,28 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_step(const double* __restri
     part_bx[2 * blockIdx.x + 1] = rx;
   }
 }
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_step(const double* __restrict__ p, const double* __restrict__ q,
+                                                          const double* __restrict__ b,
+                                                          const double* __restrict__ mask,
+                                                          const double* __restrict__ diag, double* __restrict__ x,
+                                                          double* __restrict__ r, long long n,
+                                                          const double* __restrict__ part_pq,
+                                                          const double* __restrict__ part_cur,
+                                                          double* __restrict__ part_new, double* __restrict__ part_bx,
+                                                          int nb, PcgCtl* ctl) {
+  pcg_step_body<CPLX>(p, q, b, mask, diag, x, r, n, part_pq, nb, part_cur, part_new, part_bx, nb, ctl);
+}
 
 // (c) after k iterations: beta = (r^H z)_new / (r^H z)_old, p = z + beta p (k == 0: p = z stands from k_pcg_start);
 // workgroup 0 decides - |r|^2 <= tol^2 |b|^2, then the iteration limit - and publishes the control block when the host
 // waits at this iteration (pub != null), also when the decision fell earlier.
 template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_pcg_dir(const double* __restrict__ r, const double* __restrict__ diag,
-                                                         double* __restrict__ p, long long n,
-                                                         const double* __restrict__ part_new,
-                                                         const double* __restrict__ part_old,
-                                                         const double* __restrict__ part_bx, int nb, double tol2, int k,
-                                                         int max_iter, PcgCtl* ctl, double* pub,
-                                                         volatile double* seq_slot, double seq) {
+__device__ __forceinline__ void pcg_dir_body(const double* __restrict__ r, const double* __restrict__ diag,
+                                             double* __restrict__ p, long long n, const double* __restrict__ part_new,
+                                             const double* __restrict__ part_old, const double* __restrict__ part_bx,
+                                             int nb, double tol2, int k, int max_iter, PcgCtl* ctl, double* pub,
+                                             volatile double* seq_slot, double seq) {
   const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
   // Workgroup 0 raises `done` inside this launch, possibly before other workgroups have started: those leave here and
   // skip their part of p = z + beta p.  That is harmless because p is never read again once `done` is set (every later
@@ -308,6 +331,58 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_dir(const double* __restric
       ctl->done = 1;
     }
     if (pub) pcg_publish(ctl, pub, seq_slot, seq);
+  }
+}
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_dir(const double* __restrict__ r, const double* __restrict__ diag,
+                                                         double* __restrict__ p, long long n,
+                                                         const double* __restrict__ part_new,
+                                                         const double* __restrict__ part_old,
+                                                         const double* __restrict__ part_bx, int nb, double tol2, int k,
+                                                         int max_iter, PcgCtl* ctl, double* pub,
+                                                         volatile double* seq_slot, double seq) {
+  pcg_dir_body<CPLX>(r, diag, p, n, part_new, part_old, part_bx, nb, tol2, k, max_iter, ctl, pub, seq_slot, seq);
+}
+
+// ---- batched forms (mpse_pcg_batch): member blockIdx.z of a launch set runs the bodies above on its own vectors,
+// partials and control block from the member table, with the grid its single launch would have: what a member computes
+// does not depend on the others
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_prep_b(const Pcg2Member* __restrict__ mem, long long n) {
+  const Pcg2Member mb = mem[blockIdx.z];
+  pcg_prep_body<CPLX>(mb.x, mb.b, mb.mask, mb.diag, n, mb.part_bb, static_cast<PcgCtl*>(mb.ctl));
+}
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_start_b(const Pcg2Member* __restrict__ mem, long long n, int nb) {
+  const Pcg2Member mb = mem[blockIdx.z];
+  pcg_start_body<CPLX>(mb.y, mb.b, mb.mask, mb.diag, mb.x, mb.r, mb.p, mb.shift, n, mb.part_bb, nb, mb.part_rz0,
+                       mb.part_bx, static_cast<PcgCtl*>(mb.ctl));
+}
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_step_b(const Pcg2Member* __restrict__ mem, long long n, int nbq,
+                                                            int nb, int k) {
+  const Pcg2Member mb = mem[blockIdx.z];
+  pcg_step_body<CPLX>(mb.p, mb.q, mb.b, mb.mask, mb.diag, mb.x, mb.r, n, mb.part_pq, nbq,
+                      (k - 1) & 1 ? mb.part_rz1 : mb.part_rz0, k & 1 ? mb.part_rz1 : mb.part_rz0, mb.part_bx, nb,
+                      static_cast<PcgCtl*>(mb.ctl));
+}
+template <bool CPLX>
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_dir_b(const Pcg2Member* __restrict__ mem, long long n, int nb,
+                                                           double tol2, int k, int max_iter) {
+  const Pcg2Member mb = mem[blockIdx.z];
+  pcg_dir_body<CPLX>(mb.r, mb.diag, mb.p, n, k & 1 ? mb.part_rz1 : mb.part_rz0, (k + 1) & 1 ? mb.part_rz1 : mb.part_rz0,
+                     mb.part_bx, nb, tol2, k, max_iter, static_cast<PcgCtl*>(mb.ctl), nullptr, nullptr, 0.0);
+}
+// the control blocks of all members to the pinned mirror, then the sequence number (one workgroup, after k_pcg_dir_b)
+__global__ __launch_bounds__(RED_THREADS) void k_pcg_publish_b(const Pcg2Member* __restrict__ mem, int B, double* pub,
+                                                               volatile double* seq_slot, double seq) {
+  for (int i = threadIdx.x; i < B * PCG_CW; i += RED_THREADS)
+    pub[i] = static_cast<const double*>(mem[i / PCG_CW].ctl)[i % PCG_CW];
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    *seq_slot = seq;
+    __threadfence_system();
   }
 }
 
@@ -525,7 +600,220 @@ static int pcg_report(mpse_ctx* ctx, const PcgCtl& hc, bool masked, double tol, 
   }
 }
 
+// ---- mpse_pcg_batch: launch sets of members with one shape that takes the one-launch two-layer matvec
+namespace {
+
+constexpr int PCGB_MAX = 32;         // members per launch set
+constexpr int PCGB_SLOT = 3700;      // pinned doubles [3700, 3956): the control blocks of a waited iteration (the slot of
+                                     // the batched Krylov solve, which never runs at the same time)
+static_assert(PCGB_SLOT + PCGB_MAX * PCG_CW < 3990, "batch slot clear of the QR status word");
+
+// the member's own shape decides: one-site, two layers, square, no ancilla, operands of the working type, real W
+bool pcg_batch_eligible(int dtype, const mpse_heff& h, int twolayer, Small2Plan* plan) {
+  if (!twolayer || h.nsite != 1) return false;
+  const mpse_dims& s = h.dims;
+  if ((s.Dl_bra > 0 && s.Dl_bra != s.Dl_ket) || (s.Dr_bra > 0 && s.Dr_bra != s.Dr_ket) || s.danc > 1) return false;
+  if (h.l_dtype != dtype || h.r_dtype != dtype || h.w_dtype != MPSE_F64) return false;
+  return small2_plan(dtype, s.Dl_ket, s.d0, s.Dr_ket, s.wl, s.wr, plan);
+}
+
+struct PcgSet {
+  Small2Plan plan;
+  std::vector<int> idx;      // member -> position in the caller's arrays
+};
+
+int pcg_batch_set(mpse_ctx* ctx, int dtype, const PcgSet& ps, const mpse_heff* hs, const double* shifts,
+                  const void* const* diags, const void* const* masks, const void* const* bs, void* const* xs, double tol,
+                  int max_iter, std::vector<PcgCtl>& hc) {
+  const int B = (int)ps.idx.size();
+  const Small2Plan& pl = ps.plan;
+  const bool cplx = dtype == MPSE_C128;
+  const size_t es = dtype_size(dtype);
+  const int64_t n = int64_t(pl.Dl) * pl.d * pl.Dr;
+  const int64_t nd = n * (cplx ? 2 : 1);
+  const int nb = red_blocks(nd), nbq = pl.Dl;
+  // per-member region of the slab (256-byte aligned sections): control block, partials (|b|^2; p^H q; b^H x; r^H z twice),
+  // y, q, r, p, the transposed left environment, the sparse W list
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t o_part = al(sizeof(PcgCtl));
+  const size_t o_vec = o_part + al(size_t(8 * nb + 2 * nbq) * sizeof(double));
+  const size_t vb = al(size_t(n) * es);
+  const size_t o_lt = o_vec + 4 * vb;
+  const size_t o_ptr = o_lt + al(size_t(pl.Dl) * pl.wl * pl.wl * pl.Dl * es);
+  const size_t cap = size_t(pl.rows) * pl.pitch;
+  const size_t o_idx = o_ptr + al(size_t(pl.rows + 1) * sizeof(int));
+  const size_t o_val = o_idx + al(cap * sizeof(int));
+  const size_t ms = o_val + al(cap * sizeof(double));
+  TmpBuf SLAB(ctx), MEM(ctx);
+  MPSE_TRY(SLAB.alloc(size_t(B) * ms));
+  MPSE_TRY(MEM.alloc(size_t(B) * sizeof(Pcg2Member)));
+  std::vector<Pcg2Member> mh(B);
+  for (int m = 0; m < B; ++m) {
+    const int i = ps.idx[m];
+    char* base = SLAB.as<char>() + size_t(m) * ms;
+    double* part = reinterpret_cast<double*>(base + o_part);
+    Pcg2Member& mb = mh[m];
+    mb.L = static_cast<const double*>(hs[i].L), mb.R = static_cast<const double*>(hs[i].R);
+    mb.W = static_cast<const double*>(hs[i].W0);
+    mb.Lt = reinterpret_cast<double*>(base + o_lt);
+    mb.csr_ptr = reinterpret_cast<int*>(base + o_ptr), mb.csr_idx = reinterpret_cast<int*>(base + o_idx);
+    mb.csr_val = reinterpret_cast<double*>(base + o_val);
+    mb.mask = masks ? static_cast<const double*>(masks[i]) : nullptr;
+    mb.diag = diags ? static_cast<const double*>(diags[i]) : nullptr;
+    mb.b = static_cast<const double*>(bs[i]);
+    mb.x = static_cast<double*>(xs[i]);
+    mb.y = reinterpret_cast<double*>(base + o_vec), mb.q = reinterpret_cast<double*>(base + o_vec + vb);
+    mb.r = reinterpret_cast<double*>(base + o_vec + 2 * vb), mb.p = reinterpret_cast<double*>(base + o_vec + 3 * vb);
+    mb.part_bb = part, mb.part_bx = part + 2 * nb, mb.part_rz0 = part + 4 * nb, mb.part_rz1 = part + 6 * nb;
+    mb.part_pq = part + 8 * nb;
+    mb.ctl = base;
+    mb.shift = shifts[i];
+    wsite_written(ctx, xs[i], size_t(n) * es);
+  }
+  MPSE_TRY(stage_h2d(ctx, MEM.p, mh.data(), mh.size() * sizeof(Pcg2Member)));
+  const Pcg2Member* mem = MEM.as<const Pcg2Member>();
+  const dim3 grid(nb, 1, B), block(RED_THREADS);
+  const long long nn = (long long)n;
+  const double tol2 = tol * tol;
+  if (max_iter <= 0) max_iter = int(10 * n);      // (n <= 64 * 16 * 64)
+
+#define PCGB_LAUNCH(kern, ...)                                                          \
+  do {                                                                                  \
+    if (cplx)                                                                           \
+      hipLaunchKernelGGL((kern<true>), grid, block, 0, ctx->stream, mem, __VA_ARGS__);  \
+    else                                                                                \
+      hipLaunchKernelGGL((kern<false>), grid, block, 0, ctx->stream, mem, __VA_ARGS__); \
+    MPSE_HIP(ctx, hipGetLastError());                                                   \
+  } while (0)
+
+  PCGB_LAUNCH(k_pcg_prep_b, nn);
+  MPSE_TRY(small2_prep(ctx, dtype, pl, B, mem));
+  MPSE_TRY(small2_apply(ctx, dtype, pl, B, mem, 0));
+  PCGB_LAUNCH(k_pcg_start_b, nn, nb);
+  ++ctx->pcg_batch_stats[mpse_ctx::PB_SETS];
+  for (int k = 0;; ++k) {
+    if (k > 0) {
+      MPSE_TRY(small2_apply(ctx, dtype, pl, B, mem, 1));
+      ++ctx->pcg_batch_stats[mpse_ctx::PB_MATVEC_LAUNCHES];
+      PCGB_LAUNCH(k_pcg_step_b, nn, nbq, nb, k);
+    }
+    PCGB_LAUNCH(k_pcg_dir_b, nn, nb, tol2, k, max_iter);
+    const bool wait_here = (k % PCG_K == PCG_K - 1) || k >= max_iter;
+    if (!wait_here) continue;
+    bool have = false;
+    if (ctx->pinned_dev) {
+      const double seq = double(++ctx->publish_seq);
+      hipLaunchKernelGGL(k_pcg_publish_b, dim3(1), block, 0, ctx->stream, mem, B, ctx->pinned_dev + PCGB_SLOT,
+                         (volatile double*)(ctx->pinned_dev + 4095), seq);
+      MPSE_HIP(ctx, hipGetLastError());
+      MPSE_TRY(publish_wait_seq(ctx, seq, static_cast<const double*>(mh[0].ctl), PCG_CW, PCGB_SLOT));
+      have = ctx->pinned[4095] == seq;
+    }
+    if (!have) {      // (no mapped view, or the number never arrived: plain copies)
+      MPSE_HIP(ctx, hipMemcpy2DAsync(ctx->pinned + PCGB_SLOT, sizeof(PcgCtl), SLAB.p, ms, sizeof(PcgCtl), size_t(B),
+                                     hipMemcpyDeviceToHost, ctx->stream));
+      MPSE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
+    memcpy(hc.data(), ctx->pinned + PCGB_SLOT, size_t(B) * sizeof(PcgCtl));
+    ++ctx->pcg_batch_stats[mpse_ctx::PB_WAITS];
+    bool all = true;
+    for (int m = 0; m < B; ++m) all = all && hc[m].done;
+    if (all) break;
+    if (k >= max_iter) return mpse_fail(ctx, MPSE_ERR_HIP, "pcg_batch: no decision at the iteration limit");
+  }
+#undef PCGB_LAUNCH
+  return MPSE_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+int mpse_pcg_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff* h, int twolayer, const double* shift_host,
+                   const void* const* diag_f64, const void* const* mask_f64, const void* const* b, void* const* x,
+                   double tol, int max_iter, int* status_host, int* iters_host, double* relres_host,
+                   double* lvalue_host) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (count < 0 || (count > 0 && (!h || !shift_host || !b || !x || !status_host)))
+    return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_batch: null argument");
+  if (dtype != MPSE_F64 && dtype != MPSE_C128) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_batch: unknown dtype");
+  if (!(tol >= 0.0)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_batch: tol must be >= 0");
+  if (count == 0) return MPSE_OK;
+  MPSE_BIND(ctx);
+  const size_t es = dtype_size(dtype);
+  // launch sets: eligible members of one shape, in the order of their first appearance, up to PCGB_MAX each
+  std::vector<PcgSet> sets, open;
+  std::vector<char> grouped(count, 0);
+  for (int i = 0; i < count; ++i) {
+    const mpse_heff& hi = h[i];
+    Small2Plan pl;
+    if (!b[i] || !x[i] || !hi.L || !hi.R || !hi.W0 || !std::isfinite(shift_host[i])) continue;   // (mpse_pcg refuses it)
+    if (!pcg_batch_eligible(dtype, hi, twolayer, &pl)) continue;
+    const size_t bytes = size_t(pl.Dl) * pl.d * pl.Dr * es;
+    const char *xb = static_cast<const char*>(x[i]), *bb = static_cast<const char*>(b[i]);
+    if (xb < bb + bytes && bb < xb + bytes) continue;
+    PcgSet* tgt = nullptr;
+    for (auto& o : open)
+      if (o.plan.Dl == pl.Dl && o.plan.d == pl.d && o.plan.Dr == pl.Dr && o.plan.wl == pl.wl && o.plan.wr == pl.wr) {
+        tgt = &o;
+        break;
+      }
+    if (tgt && (int)tgt->idx.size() == PCGB_MAX) {
+      sets.push_back(*tgt);
+      tgt->idx.clear();
+    }
+    if (!tgt) {
+      open.push_back(PcgSet{pl, {}});
+      tgt = &open.back();
+    }
+    tgt->idx.push_back(i);
+    grouped[i] = 1;
+  }
+  for (auto& o : open) sets.push_back(o);
+  for (const PcgSet& ps : sets) {
+    std::vector<PcgCtl> hc(ps.idx.size());
+    MPSE_TRY(pcg_batch_set(ctx, dtype, ps, h, shift_host, diag_f64, mask_f64, b, x, tol, max_iter, hc));
+    for (size_t m = 0; m < ps.idx.size(); ++m) {
+      const int i = ps.idx[m];
+      ++ctx->pcg_batch_stats[mpse_ctx::PB_MEMBERS];
+      if (iters_host) iters_host[i] = hc[m].iters;
+      if (relres_host) relres_host[i] = std::sqrt(hc[m].relres2);
+      if (lvalue_host) lvalue_host[i] = hc[m].lvalue;
+      status_host[i] = hc[m].status;
+    }
+  }
+  for (int i = 0; i < count; ++i) {
+    if (grouped[i]) continue;
+    ++ctx->pcg_batch_stats[mpse_ctx::PB_SINGLE];
+    int it = 0;
+    double rel = 0.0, lv = 0.0;
+    const int st = mpse_pcg(ctx, dtype, &h[i], twolayer, shift_host[i], diag_f64 ? diag_f64[i] : nullptr,
+                            mask_f64 ? mask_f64[i] : nullptr, b[i], x[i], tol, max_iter, &it, &rel, &lv);
+    if (st != MPSE_OK && st != MPSE_ERR_NOCONV && st != MPSE_ERR_ARG && st != MPSE_ERR_SHAPE) return st;
+    status_host[i] = st;
+    if (iters_host) iters_host[i] = it;
+    if (relres_host) relres_host[i] = rel;
+    if (lvalue_host) lvalue_host[i] = lv;
+  }
+  return MPSE_OK;
+}
+
+int mpse_pcg_batch_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  for (int i = 0; i < n; ++i) counts[i] = i < mpse_ctx::PB_COUNT ? ctx->pcg_batch_stats[i] : 0;
+  if (n > mpse_ctx::PB_COUNT) counts[mpse_ctx::PB_COUNT] = PCGB_MAX;
+  return MPSE_OK;
+}
+
+int mpse_pcg_batch_plan(int dtype, int64_t Dl, int64_t d, int64_t Dr, int64_t wl, int64_t wr, int64_t* info, int n) {
+  Small2Plan pl;
+  const bool ok = small2_plan(dtype, Dl, d, Dr, wl, wr, &pl);
+  const int64_t v[8] = {SM2_WMAX, SM2_DMAX, SM2_BMAX, SM2_LDS_MAX, ok ? pl.lds : 0, ok ? pl.jh : 0, ok ? pl.nslice : 0,
+                        SM2_NNZ_LDS};
+  for (int i = 0; i < n && info; ++i) info[i] = i < 8 ? v[i] : 0;
+  return ok ? 1 : 0;
+}
 
 int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const void* diag_f64,
              const void* mask_f64, const void* b, void* x, double tol, int max_iter, int* iters_host,

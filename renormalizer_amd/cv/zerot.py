@@ -12,6 +12,7 @@ a Python closure per matvec (zerot.py:231-290).  No centre vector, environment o
 sweep: of the solve the host reads the control block.  What it still does per centre is what ``optimize_mps`` does: the
 quantum-number mask is built on the host and uploaded, and ``_hdiag`` forms the per-site factor of the diagonal from a host
 copy of the centre's MPO sites."""
+import collections
 import logging
 
 import numpy as np
@@ -22,6 +23,8 @@ from ..utils import OptimizeConfig
 from .spectra_cv import SpectraCv
 
 logger = logging.getLogger("renormalizer_amd")
+
+CentreProblem = collections.namedtuple("CentreProblem", "hop b x diag mask shift tol cidx qnbigl qnbigr")
 
 
 class SpectraZtCV(SpectraCv):
@@ -84,7 +87,16 @@ class SpectraZtCV(SpectraCv):
 
     def optimize_cv(self, lr_group, isite, percent=0.0):
         """One centre: solve ((H - e0 - omega)^2 + eta^2) x = b in the projected space and put x into cv_mps
-        (zerot.py:130-302).  Returns the value of the functional L at x."""
+        (zerot.py:130-302).  Returns the value of the functional L at x.  The composition of the three parts below
+        with ``Engine.pcg``; ``cv.batch_run_lockstep`` puts ``Engine.pcg_batch`` over several objects between them."""
+        prob = self.centre_problem(lr_group, isite)
+        res = get_engine().pcg(prob.hop, prob.b, prob.x, diag=prob.diag, mask=prob.mask, shift=prob.shift, tol=prob.tol)
+        return self.centre_install(prob, res, percent)
+
+    def centre_problem(self, lr_group, isite):
+        """The centre system at ``isite``: moves the environments there and returns a ``CentreProblem`` (operator,
+        right-hand side, start vector, preconditioner diagonal, mask, shift, tolerance and what ``centre_install``
+        needs)."""
         from ..mps.hop_expr import hop_expr
         from ..mps.gs import _hdiag
         from ..mps.svd_qn import get_qn_mask
@@ -128,13 +140,17 @@ class SpectraZtCV(SpectraCv):
         x = (guess.to_complex() if cplx else guess).copy().reshape(xshape)
         if cplx:
             vec_b = vec_b.to_complex()
-        res = eng.pcg(hop, vec_b, x, diag=a_diag, mask=mask, shift=self.eta ** 2, tol=1.0e-5)
+        return CentreProblem(hop, vec_b, x, a_diag, mask, self.eta ** 2, 1.0e-5, cidx, qnbigl, qnbigr)
+
+    def centre_install(self, prob, res, percent=0.0):
+        """Puts the solution ``prob.x`` of the solve ``res`` (a ``PcgResult``) into cv_mps; returns the functional."""
+        cv = self.cv_mps
         # the reference's count (zerot.py:292, taken before the functional's own matvec at :296) is scipy's matvec of the
         # start residual b - A x0 plus one per iteration
         self.hop_time.append(res.iters + 1)
         if res.status != 0:
             logger.info("iteration solver not converged")
-        cv._update_mps(x, cidx, qnbigl, qnbigr, percent)
+        cv._update_mps(prob.x, prob.cidx, prob.qnbigl, prob.qnbigr, percent)
         if cv.compress_config.ofs is not None:
             raise NotImplementedError("OFS for correction vector not implemented")
         return float(res.lvalue)

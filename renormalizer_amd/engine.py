@@ -162,6 +162,11 @@ _SIGNATURES = {
     "mpse_pcg": [C.c_void_p, C.c_int, C.POINTER(mpse_heff), C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                  C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), _dblp, _dblp],
     "mpse_pcg_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_pcg_batch": [C.c_void_p, C.c_int, C.c_int, C.POINTER(mpse_heff), C.c_int, _dblp, C.POINTER(C.c_void_p),
+                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double, C.c_int,
+                       C.POINTER(C.c_int), C.POINTER(C.c_int), _dblp, _dblp],
+    "mpse_pcg_batch_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_pcg_batch_plan": [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i64p, C.c_int],
     "mpse_heff_apply_ft": [C.c_void_p, C.c_int, C.POINTER(mpse_heff_ft), C.c_void_p, C.c_void_p],
     "mpse_env_update_ft": [C.c_void_p, C.c_int, C.c_int, C.POINTER(mpse_heff_ft), C.c_void_p, C.c_int, C.c_void_p,
                            C.c_void_p],
@@ -524,6 +529,46 @@ class Engine:
         if check and st not in (0, 3):
             self._check(st)
         return PcgResult(int(st), it.value, rel.value, lv.value)
+
+    PCG_BATCH_STATS = ("batched_members", "single_members", "launch_sets", "matvec_launches", "host_waits",
+                       "set_limit")
+
+    def pcg_batch_stats(self):
+        """{name: count} of the ``pcg_batch`` calls of this context, cumulative (``mpse_pcg_batch_stats``; the names
+        follow the order of include/mpsengine.h).  ``set_limit`` is no count: the member limit per launch set."""
+        v = (C.c_int64 * len(self.PCG_BATCH_STATS))()
+        self._check(self.lib.mpse_pcg_batch_stats(self.ctx, v, len(v)))
+        return dict(zip(self.PCG_BATCH_STATS, (int(x) for x in v)))
+
+    def pcg_batch(self, hops, bs, xs, diags, masks, shifts, tol, max_iter=0):
+        """``pcg`` for several independent systems in one call (``mpse_pcg_batch``): lists of ``hop_expr`` closures (all
+        two-layer or all one-layer), right-hand sides, start vectors / solutions of one working dtype, preconditioner
+        diagonals and masks (the list or single entries may be None) and shifts.  Two-layer one-site members whose
+        shape passes ``small2_eligible`` are solved together, the others through ``mpse_pcg``; a member's result does
+        not depend on the others.  Returns one ``PcgResult`` per member; a member's status is its own (0, 3 = not
+        converged, 1 = refused), only a failure of the call as a whole raises."""
+        cnt = len(hops)
+        assert len(bs) == cnt and len(xs) == cnt and len(shifts) == cnt
+        if cnt == 0:
+            return []
+        diags = [None] * cnt if diags is None else list(diags)
+        masks = [None] * cnt if masks is None else list(masks)
+        assert len(diags) == cnt and len(masks) == cnt
+        code, two = xs[0].code, bool(hops[0].twolayer)
+        for hop, b, x, dg, mk in zip(hops, bs, xs, diags, masks):
+            n = int(np.prod(hop.cshape))
+            assert bool(hop.twolayer) == two and x.code == code and b.dtype == x.dtype
+            assert b.size == n and x.size == n, (b.shape, x.shape, hop.cshape)
+            assert dg is None or (dg.size == n and dg.dtype == np.float64)
+            assert mk is None or (mk.size == n and mk.dtype == np.float64)
+        harr = (mpse_heff * cnt)(*[hop.heff for hop in hops])
+        ptrs = lambda ts: (C.c_void_p * cnt)(*[None if t is None else t.ptr for t in ts])
+        sh = (C.c_double * cnt)(*[float(v) for v in shifts])
+        st, it = (C.c_int * cnt)(), (C.c_int * cnt)()
+        rel, lv = (C.c_double * cnt)(), (C.c_double * cnt)()
+        self._check(self.lib.mpse_pcg_batch(self.ctx, code, cnt, harr, int(two), sh, ptrs(diags), ptrs(masks), ptrs(bs),
+                                            ptrs(xs), float(tol), int(max_iter), st, it, rel, lv))
+        return [PcgResult(int(st[i]), int(it[i]), float(rel[i]), float(lv[i])) for i in range(cnt)]
 
     # -- two MPO layers on a two-leg centre: the terms of the finite-temperature correction-vector operator
     def ft_term(self, w1, w2, leg1, leg2, trans1, trans2, shape, L=None, R=None):
