@@ -1038,8 +1038,8 @@ int cholqr_run(mpse_ctx* ctx, double* ws, const QrBlk* blks, int nblk, const lon
     *ok = true;
     return MPSE_OK;
   }
-  MPSE_TRY(publish_and_wait(ctx, dstat, 1, 3990));
-  *ok = ctx->pinned[3990] == 0.0;
+  MPSE_TRY(publish_and_wait(ctx, dstat, 1, mpse_ctx::PIN_QR_STATUS));
+  *ok = ctx->pinned[mpse_ctx::PIN_QR_STATUS] == 0.0;
   return MPSE_OK;
 }
 

@@ -671,13 +671,14 @@ extern "C" int mpse_env_unit_channel(mpse_ctx* ctx, int dtype, const void* env, 
                        (int)D, (int)w, dev);
   MPSE_HIP(ctx, hipGetLastError());
   if (w <= 1024) {
-    MPSE_TRY(publish_and_wait(ctx, reinterpret_cast<const double*>(dev), (int)w, 32));
+    MPSE_TRY(publish_and_wait(ctx, reinterpret_cast<const double*>(dev), (int)w, mpse_ctx::PIN_ENV_UNIT));
   } else {
-    MPSE_HIP(ctx, hipMemcpyAsync(ctx->pinned + 32, dev, size_t(w) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MPSE_HIP(ctx, hipMemcpyAsync(ctx->pinned + mpse_ctx::PIN_ENV_UNIT, dev, size_t(w) * sizeof(double), hipMemcpyDeviceToHost,
+                                 ctx->stream));
     MPSE_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   for (int64_t b = 0; b < w; ++b)
-    if (ctx->pinned[32 + b] <= tol) {
+    if (ctx->pinned[mpse_ctx::PIN_ENV_UNIT + b] <= tol) {
       *unit_host = b + 1;
       break;
     }

@@ -269,7 +269,7 @@ int mpse_ctx_create(int device, mpse_ctx** out) {
     snprintf(ctx->dev_name, sizeof(ctx->dev_name), "%s (%s)", prop.name, prop.gcnArchName);
   }
   if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&ctx->pinned, 4096 * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&ctx->pinned, mpse_ctx::PIN_DOUBLES * sizeof(double)) != hipSuccess ||
       hipMalloc((void**)&ctx->dscratch, (size_t(1) << 16) * sizeof(double)) != hipSuccess ||
       hipMalloc((void**)&ctx->prof_ktiles, 4 * sizeof(unsigned long long)) != hipSuccess ||
       hipHostMalloc((void**)&ctx->stage, size_t(8) << 20) != hipSuccess) {
@@ -281,13 +281,16 @@ int mpse_ctx_create(int device, mpse_ctx** out) {
   (void)hipMemsetAsync(ctx->dscratch + (size_t(1) << 16) - 8, 0, 8 * sizeof(double), ctx->stream);
   (void)hipMemsetAsync(ctx->prof_ktiles, 0, 4 * sizeof(unsigned long long), ctx->stream);
   (void)hipStreamSynchronize(ctx->stream);
-  if (hipHostGetDevicePointer((void**)&ctx->pinned_dev, ctx->pinned, 0) != hipSuccess) ctx->pinned_dev = nullptr;
+  // MPSE_PINNED_MAP=0: no mapped view of the pinned buffer - every read-back takes the copy path
+  const char* pin_map = getenv("MPSE_PINNED_MAP");
+  if ((pin_map && pin_map[0] == '0') || hipHostGetDevicePointer((void**)&ctx->pinned_dev, ctx->pinned, 0) != hipSuccess)
+    ctx->pinned_dev = nullptr;
   {
     if (hipHostGetDevicePointer((void**)&ctx->stage_dev, ctx->stage, 0) != hipSuccess)
       ctx->stage_dev = nullptr;
     (void)hipGetLastError();
   }
-  ctx->pinned[4095] = 0.0;      // sequence slot of publish_and_wait
+  ctx->pinned[mpse_ctx::PIN_SEQ] = 0.0;
   ctx->stage_size = size_t(8) << 20;
   *out = ctx;
   return MPSE_OK;
@@ -532,7 +535,7 @@ __global__ void k_publish(const double* __restrict__ src, double* dst, int count
 }  // namespace
 
 int publish_wait_seq(mpse_ctx* ctx, double seq, const double* dsrc, int count, int slot) {
-  volatile double* flag = ctx->pinned + 4095;
+  volatile double* flag = ctx->pinned + mpse_ctx::PIN_SEQ;
   for (long long spins = 0; *flag != seq; ++spins) {
     if (spins > 2000000000LL || ((spins & 0xfffff) == 0xfffff && hipStreamQuery(ctx->stream) == hipSuccess && *flag != seq)) {
       // the kernel is gone but the number never arrived: fall back to the ordinary path (also surfaces errors)
@@ -545,16 +548,42 @@ int publish_wait_seq(mpse_ctx* ctx, double seq, const double* dsrc, int count, i
   return MPSE_OK;
 }
 
-int publish_and_wait(mpse_ctx* ctx, const double* dsrc, int count, int slot) {
-  if (count < 0 || count > 1024 || slot < 0 || slot + count > 4000) return mpse_fail(ctx, MPSE_ERR_ARG, "publish: range");
-  if (!ctx->pinned_dev) {  // no mapped view of the pinned buffer: plain copy + synchronise
-    MPSE_HIP(ctx, hipMemcpyAsync(ctx->pinned + slot, dsrc, size_t(count) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    MPSE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return MPSE_OK;
+PublishAt publish_target(mpse_ctx* ctx, bool wait_here, int slot) {
+  if (!wait_here || !ctx->pinned_dev) return PublishAt{nullptr, nullptr, 0.0};
+  return PublishAt{ctx->pinned_dev + slot, ctx->pinned_dev + mpse_ctx::PIN_SEQ, double(++ctx->publish_seq)};
+}
+
+// the waiting half: the values are at ctx->pinned + slot when it returns
+static int publish_wait(mpse_ctx* ctx, const PublishAt& at, const void* dsrc, size_t stride, int B, int W, int slot) {
+  if (at.seq != 0.0) {
+    MPSE_TRY(publish_wait_seq(ctx, at.seq, static_cast<const double*>(dsrc), W, slot));   // (rescues the first block itself)
+    if (B == 1 || ctx->pinned[mpse_ctx::PIN_SEQ] == at.seq) return MPSE_OK;
   }
-  const double seq = double(++ctx->publish_seq);
-  hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, ctx->stream, dsrc, ctx->pinned_dev + slot, count,
-                     (volatile double*)(ctx->pinned_dev + 4095), seq);
-  MPSE_HIP(ctx, hipGetLastError());
-  return publish_wait_seq(ctx, seq, dsrc, count, slot);
+  // no mapped view, or the number never arrived: plain copies
+  const size_t row = size_t(W) * sizeof(double);
+  if (B == 1)
+    MPSE_HIP(ctx, hipMemcpyAsync(ctx->pinned + slot, dsrc, row, hipMemcpyDeviceToHost, ctx->stream));
+  else
+    MPSE_HIP(ctx, hipMemcpy2DAsync(ctx->pinned + slot, row, dsrc, stride, row, size_t(B), hipMemcpyDeviceToHost, ctx->stream));
+  MPSE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MPSE_OK;
+}
+
+int publish_collect(mpse_ctx* ctx, const PublishAt& at, const void* dsrc, size_t stride, int B, int W, int slot,
+                    void* host_out) {
+  MPSE_TRY(publish_wait(ctx, at, dsrc, stride, B, W, slot));
+  if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
+  memcpy(host_out, ctx->pinned + slot, size_t(B) * W * sizeof(double));
+  return MPSE_OK;
+}
+
+int publish_and_wait(mpse_ctx* ctx, const double* dsrc, int count, int slot) {
+  if (count < 0 || count > 1024 || slot < 0 || slot + count > mpse_ctx::PIN_SLOTS_END)
+    return mpse_fail(ctx, MPSE_ERR_ARG, "publish: range");
+  const PublishAt at = publish_target(ctx, true, slot);
+  if (at.pub) {
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, ctx->stream, dsrc, at.pub, count, at.seq_slot, at.seq);
+    MPSE_HIP(ctx, hipGetLastError());
+  }
+  return publish_wait(ctx, at, dsrc, 0, 1, count, slot);
 }

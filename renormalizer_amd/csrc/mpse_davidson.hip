@@ -261,19 +261,15 @@ struct Dav {
   // vals[2 v ..] = <X_v, y>, v < nx  (device resident)
   int dots(const void* X, int nx, const void* y, double* dst) {
     if (nx <= 0) return MPSE_OK;
-    if (cplx)
-      hipLaunchKernelGGL((k_multi_dot<true>), dim3(nb, nx), dim3(RED_THREADS), 0, ctx->stream, (const double*)X,
-                         (long long)n, (const double*)y, (long long)n, part);
-    else
-      hipLaunchKernelGGL((k_multi_dot<false>), dim3(nb, nx), dim3(RED_THREADS), 0, ctx->stream, (const double*)X,
-                         (long long)n, (const double*)y, (long long)n, part);
+    MPSE_LAUNCH_TF(ctx, cplx, k_multi_dot, dim3(nb, nx), dim3(RED_THREADS), (const double*)X, (long long)n,
+                   (const double*)y, (long long)n, part);
     hipLaunchKernelGGL(k_multi_reduce, dim3(nx), dim3(RED_THREADS), 0, ctx->stream, (const double*)part, nb, dst);
     MPSE_HIP(ctx, hipGetLastError());
     return MPSE_OK;
   }
   int fetch(const double* dsrc, int count, std::vector<double>& out) {
-    MPSE_TRY(publish_and_wait(ctx, dsrc, count, 64));
-    out.assign(ctx->pinned + 64, ctx->pinned + 64 + count);
+    MPSE_TRY(publish_and_wait(ctx, dsrc, count, mpse_ctx::PIN_DAVIDSON));
+    out.assign(ctx->pinned + mpse_ctx::PIN_DAVIDSON, ctx->pinned + mpse_ctx::PIN_DAVIDSON + count);
     return MPSE_OK;
   }
   // column j of the subspace matrix: h[i][j] = <V_i, W_j>, i <= j  (one launch + one read-back)
@@ -302,12 +298,8 @@ struct Dav {
       c.re[i] = ev[(size_t)i * m + col].real();
       c.im[i] = ev[(size_t)i * m + col].imag();
     }
-    if (cplx)
-      hipLaunchKernelGGL((k_ritz<true>), dim3(nb), dim3(RED_THREADS), 0, ctx->stream, (double*)x, (double*)hx,
-                         (double*)r, (const double*)V, (const double*)W, (long long)n, m, c, e, part);
-    else
-      hipLaunchKernelGGL((k_ritz<false>), dim3(nb), dim3(RED_THREADS), 0, ctx->stream, (double*)x, (double*)hx,
-                         (double*)r, (const double*)V, (const double*)W, (long long)n, m, c, e, part);
+    MPSE_LAUNCH_TF(ctx, cplx, k_ritz, dim3(nb), dim3(RED_THREADS), (double*)x, (double*)hx, (double*)r, (const double*)V,
+                   (const double*)W, (long long)n, m, c, e, part);
     hipLaunchKernelGGL(k_multi_reduce, dim3(1), dim3(RED_THREADS), 0, ctx->stream, (const double*)part, nb, vals);
     MPSE_HIP(ctx, hipGetLastError());
     std::vector<double> g;
@@ -320,12 +312,8 @@ struct Dav {
   int orthonormalise(void* t, void* u, const void* X, const void* Y, int m, void* dst, void* dst2) {
     for (int pass = 0; pass < 2 && m > 0; ++pass) {
       MPSE_TRY(dots(X, m, t, vals));
-      if (cplx)
-        hipLaunchKernelGGL((k_project_out<true>), dim3(ew_blocks(n)), dim3(256), 0, ctx->stream, (double*)t,
-                           (const double*)X, (long long)n, m, (const double*)vals, (double*)u, (const double*)Y);
-      else
-        hipLaunchKernelGGL((k_project_out<false>), dim3(ew_blocks(n)), dim3(256), 0, ctx->stream, (double*)t,
-                           (const double*)X, (long long)n, m, (const double*)vals, (double*)u, (const double*)Y);
+      MPSE_LAUNCH_TF(ctx, cplx, k_project_out, dim3(ew_blocks(n)), dim3(256), (double*)t, (const double*)X, (long long)n, m,
+                     (const double*)vals, (double*)u, (const double*)Y);
     }
     MPSE_TRY(dots(t, 1, t, vals + 2 * DV_MAX));
     hipLaunchKernelGGL(k_scale_rsqrt, dim3(ew_blocks(n * (cplx ? 2 : 1))), dim3(256), 0, ctx->stream, (double*)dst,

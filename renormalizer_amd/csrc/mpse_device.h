@@ -132,9 +132,9 @@ __device__ __forceinline__ void block_allsum2(double& a, double& b) {
   b = y;
 }
 
-// ---- two-stage reductions over a vector (the Krylov solvers of mpse_vec.hip, the conjugate gradients of mpse_pcg.hip):
+// ---- two-stage reductions over a vector (the Krylov solvers of mpse_lanczos.hip, the conjugate gradients of mpse_pcg.hip):
 // per-block partials with a grid size that depends on n only and a fixed summation order, re-summed by their consumers
-// (the producers are kernels of the two files: k_dot_partial and the fused update passes)
+// (the producers are kernels of those files: k_dot_partial of mpse_vec_kernels.h and the fused update passes)
 namespace {
 
 constexpr int RED_MAX_BLOCKS = 512;  // two blocks per CU; consumers of the partials re-sum all of them per block

@@ -61,8 +61,23 @@ struct mpse_ctx {
   char* stage_dev = nullptr;   // the ring as the device sees it (mapped), null: copies go through the runtime
   size_t stage_size = 0, stage_pos = 0;
 
-  // small pinned staging buffer for scalar read-backs
-  double* pinned = nullptr;     // 4096 doubles
+  // Small pinned staging buffer for scalar read-backs, and its map (offsets in doubles).  The slots overlap; that is
+  // harmless because a reader copies its values out before the next enqueue on that context.
+  enum PinnedSlot {
+    PIN_SCALAR2 = 0,       // [0, 2): read_scalar2 (dot products, norms)
+    PIN_FLAG = 8,          // [8, 9): Lanczos closeness flag; block SVD: done words of nblk blocks, (nblk + 1) / 2 doubles
+    PIN_LZ_SCAL = 16,      // [16, 540): recurrence scalars of the synchronous Lanczos solve, up to 4 + 4 * 130 doubles
+    PIN_LZ_CTL = 24,       // [24, 28): LzCtl of the asynchronous Lanczos solve
+    PIN_ENV_UNIT = 32,        // [32, 32 + w): deviation from the unit per MPO channel of an environment, w <= 2048
+    PIN_PCG_CTL = 40,      // [40, 48): PcgCtl of mpse_pcg / mpse_pcg_sum
+    PIN_DAVIDSON = 64,     // [64, 64 + count): subspace products and norms of the Davidson solver, count <= 1024
+    PIN_BATCH_CTL = 3700,  // [3700, 3956): control blocks of a batched solve, 64 x LzCtl or 32 x PcgCtl (never both at once)
+    PIN_QR_STATUS = 3990,  // [3990, 3991): breakdown word of the Cholesky-QR
+    PIN_SLOTS_END = 4000,  // slots of publish_and_wait end here
+    PIN_DOUBLES = 4096,
+    PIN_SEQ = PIN_DOUBLES - 1   // the last double: sequence word of the published read-backs
+  };
+  double* pinned = nullptr;     // PIN_DOUBLES doubles
   double* pinned_dev = nullptr; // the same buffer as the device sees it (mapped, host coherent)
   unsigned long long publish_seq = 0;
   double* dscratch = nullptr;   // device scratch for reductions (1<<16 doubles); the last 8 hold flag words
@@ -237,6 +252,22 @@ struct ProfScope {
 
 #define MPSE_BIND(ctx) MPSE_TRY(mpse_bind(ctx))
 
+// One launch of kern<true> or kern<false> on the context stream, picked by a host bool (complex / real vectors, 16-byte
+// accesses), with one argument list.  MPSE_LAUNCH_TF leaves the error check to the call site (one check after a group
+// of launches); MPSE_LAUNCH_TF_CHK checks at once.
+#define MPSE_LAUNCH_TF(ctx, flag, kern, grid, block, ...)                           \
+  do {                                                                              \
+    if (flag)                                                                       \
+      hipLaunchKernelGGL((kern<true>), grid, block, 0, (ctx)->stream, __VA_ARGS__); \
+    else                                                                            \
+      hipLaunchKernelGGL((kern<false>), grid, block, 0, (ctx)->stream, __VA_ARGS__); \
+  } while (0)
+#define MPSE_LAUNCH_TF_CHK(ctx, ...)     \
+  do {                                   \
+    MPSE_LAUNCH_TF(ctx, __VA_ARGS__);    \
+    MPSE_HIP(ctx, hipGetLastError());    \
+  } while (0)
+
 // Entry points that may be recorded start with this: true -> the call was stored, return MPSE_OK.
 #define MPSE_RECORDING(ctx) ((ctx)->defer_recording >= 0)
 // runs and empties the armed list (no-op when none is armed); `status` of the solve it follows: a failed solve
@@ -262,7 +293,7 @@ static inline mpse_index idx2(int64_t hi_ext, int64_t lo_ext, int64_t s_hi, int6
   return mpse_index{hi_ext * lo_ext, lo_ext > 0 ? lo_ext : 1, s_hi, s_lo};
 }
 
-// What a solver fixes for the length of one solve (the Lanczos drivers of mpse_vec.hip, Davidson), handed by pointer to
+// What a solver fixes for the length of one solve (the Lanczos drivers of mpse_lanczos.hip, Davidson), handed by pointer to
 // every matvec of it; null outside a solve.  The per-solve caches of the context (occ_cache, perm_cache, small_rt, f0)
 // are kept only while a solve runs: its end drops them.
 struct SolveScope {
@@ -349,7 +380,7 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
                    MatvecReq* mv, bool* taken);
 void heff_small_drop_cache(mpse_ctx* ctx);
 
-// Batched small-centre Krylov solves (mpse_expm_lanczos_batch, mpse_vec.hip): what differs between the members of one
+// Batched small-centre Krylov solves (mpse_expm_lanczos_batch, mpse_lanczos.hip): what differs between the members of one
 // launch set beyond their slab (vectors, scalars, partials and control block at member-0 addresses + m * mstride bytes)
 struct BatchMember {
   const void* L;    // environments and MPO site of the member's effective Hamiltonian
@@ -462,11 +493,25 @@ int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype
 // Low-latency read-back of a few device doubles: a one-wave kernel copies them into the mapped pinned buffer
 // and then publishes a sequence number; the host spins on that number instead of going through a copy-engine
 // transfer plus hipStreamSynchronize (the gap the GPU idles after every convergence check shrinks from ~25 us to
-// the launch latency).  count <= 1024; the values land at ctx->pinned + slot.
+// the launch latency).  count <= 1024; the values land at ctx->pinned + slot, below PIN_SLOTS_END.
 int publish_and_wait(mpse_ctx* ctx, const double* dsrc, int count, int slot);
 // The waiting half alone, for a kernel that publishes by itself (writes `count` doubles at pinned_dev + slot, then the
-// sequence number `seq` = double(++ctx->publish_seq) at pinned_dev + 4095, each followed by __threadfence_system()).
+// sequence number `seq` at pinned_dev + PIN_SEQ, each followed by __threadfence_system()).
 int publish_wait_seq(mpse_ctx* ctx, double seq, const double* dsrc, int count, int slot);
+// The wait path of the solvers whose deciding kernel publishes its control block(s).  publish_target says where to:
+// `wait_here` = the host waits at this launch; all null / zero when it does not or when there is no mapped view (the
+// kernel then publishes nothing).  publish_collect, after the launch: waits for the sequence number - or, when none was
+// handed out or it never arrives, copies the B blocks of W doubles, `stride` bytes apart at dsrc, to the slot (B == 1: a
+// plain copy, else a 2-D copy) - drains the profiler queue and copies the blocks from the slot to `host_out`.
+// (hidden: the dynamic symbol table of the library stays what it was)
+struct PublishAt {
+  double* pub;
+  volatile double* seq_slot;
+  double seq;
+};
+__attribute__((visibility("hidden"))) PublishAt publish_target(mpse_ctx* ctx, bool wait_here, int slot);
+__attribute__((visibility("hidden"))) int publish_collect(mpse_ctx* ctx, const PublishAt& at, const void* dsrc, size_t stride,
+                                                          int B, int W, int slot, void* host_out);
 
 // reductions (mpse_vec.hip): results land in ctx->pinned after a stream sync
 int dotc_sync(mpse_ctx* ctx, int dtype, const void* x, const void* y, int64_t n, double* re, double* im);

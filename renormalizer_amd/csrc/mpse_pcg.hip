@@ -24,7 +24,6 @@ namespace {
 
 constexpr int PCG_K = 4;        // the host reads the pinned control block every PCG_K iterations: at most PCG_K - 1
                                 // matvecs are enqueued past the decision
-constexpr int PCG_SLOT = 40;    // pinned doubles [40, 48): the mirror of the control block
 
 enum { PCG_WHY_NONE = 0, PCG_WHY_TOL = 1, PCG_WHY_MAXITER = 2, PCG_WHY_CURVATURE = 3, PCG_WHY_DIAG = 4, PCG_WHY_ZERO_B = 5 };
 
@@ -432,18 +431,6 @@ int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double s
   const long long nn = (long long)n;
   const double tol2 = tol * tol;
   memset(hc, 0, sizeof(*hc));
-  // the host reads the control block that the k_pcg_dir launched last published (seq != 0) or fetches it itself
-  auto wait_here_for = [&](double seq) -> int {
-    if (seq != 0.0)
-      MPSE_TRY(publish_wait_seq(ctx, seq, reinterpret_cast<const double*>(ctl), PCG_CW, PCG_SLOT));
-    else
-      MPSE_TRY(publish_and_wait(ctx, reinterpret_cast<const double*>(ctl), PCG_CW, PCG_SLOT));
-    if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
-    memcpy(hc, ctx->pinned + PCG_SLOT, sizeof(PcgCtl));
-    ++ctx->pcg_stats[mpse_ctx::PS_WAITS];
-    if (nterms > 0) ++ctx->pcg_sum_stats[mpse_ctx::PSS_WAITS];
-    return MPSE_OK;
-  };
 
   hipLaunchKernelGGL(k_pcg_prep<CPLX>, grid, block, 0, ctx->stream, x, b, mask, diag, nn, part_bb, ctl);
   MPSE_HIP(ctx, hipGetLastError());
@@ -473,25 +460,26 @@ int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double s
       MPSE_HIP(ctx, hipGetLastError());
     }
     const bool wait_here = (k % PCG_K == PCG_K - 1) || k >= max_iter;
-    const bool self_pub = wait_here && ctx->pinned_dev != nullptr;
-    const double seq = self_pub ? double(++ctx->publish_seq) : 0.0;
+    const PublishAt at = publish_target(ctx, wait_here, mpse_ctx::PIN_PCG_CTL);
     hipLaunchKernelGGL(k_pcg_dir<CPLX>, grid, block, 0, ctx->stream, (const double*)r, diag, p, nn,
                        (const double*)part_rz[k & 1], (const double*)part_rz[(k + 1) & 1], (const double*)part_bx, nb,
-                       tol2, k, max_iter, ctl, self_pub ? ctx->pinned_dev + PCG_SLOT : (double*)nullptr,
-                       (volatile double*)(self_pub ? ctx->pinned_dev + 4095 : nullptr), seq);
+                       tol2, k, max_iter, ctl, at.pub, at.seq_slot, at.seq);
     MPSE_HIP(ctx, hipGetLastError());
     if (wait_here) {
-      MPSE_TRY(wait_here_for(seq));
+      // the control block that this k_pcg_dir published, or a copy of it
+      MPSE_TRY(publish_collect(ctx, at, ctl, 0, 1, PCG_CW, mpse_ctx::PIN_PCG_CTL, hc));
+      ++ctx->pcg_stats[mpse_ctx::PS_WAITS];
+      if (nterms > 0) ++ctx->pcg_sum_stats[mpse_ctx::PSS_WAITS];
       if (hc->done) break;
       if (k >= max_iter) return mpse_fail(ctx, MPSE_ERR_HIP, "pcg: no decision at the iteration limit");
     }
   }
   return MPSE_OK;
 }
-
-}  // namespace
-
-namespace {
+template <class... A>
+int pcg_run_dtype(mpse_ctx* ctx, int dtype, A... a) {
+  return dtype == MPSE_C128 ? pcg_run<true>(ctx, dtype, a...) : pcg_run<false>(ctx, dtype, a...);
+}
 
 // ---- preconditioner of the summed solve: the diagonal of each term from the environment diagonals and a per-site factor
 // element of an MPO site W (wl, d, d, wr) that takes leg value `in` to `out` under the layer's transposition flag
@@ -604,9 +592,7 @@ static int pcg_report(mpse_ctx* ctx, const PcgCtl& hc, bool masked, double tol, 
 namespace {
 
 constexpr int PCGB_MAX = 32;         // members per launch set
-constexpr int PCGB_SLOT = 3700;      // pinned doubles [3700, 3956): the control blocks of a waited iteration (the slot of
-                                     // the batched Krylov solve, which never runs at the same time)
-static_assert(PCGB_SLOT + PCGB_MAX * PCG_CW < 3990, "batch slot clear of the QR status word");
+static_assert(mpse_ctx::PIN_BATCH_CTL + PCGB_MAX * PCG_CW < mpse_ctx::PIN_QR_STATUS, "batch slot clear of the QR status word");
 
 // the member's own shape decides: one-site, two layers, square, no ancilla, operands of the working type, real W
 bool pcg_batch_eligible(int dtype, const mpse_heff& h, int twolayer, Small2Plan* plan) {
@@ -677,52 +663,32 @@ int pcg_batch_set(mpse_ctx* ctx, int dtype, const PcgSet& ps, const mpse_heff* h
   const double tol2 = tol * tol;
   if (max_iter <= 0) max_iter = int(10 * n);      // (n <= 64 * 16 * 64)
 
-#define PCGB_LAUNCH(kern, ...)                                                          \
-  do {                                                                                  \
-    if (cplx)                                                                           \
-      hipLaunchKernelGGL((kern<true>), grid, block, 0, ctx->stream, mem, __VA_ARGS__);  \
-    else                                                                                \
-      hipLaunchKernelGGL((kern<false>), grid, block, 0, ctx->stream, mem, __VA_ARGS__); \
-    MPSE_HIP(ctx, hipGetLastError());                                                   \
-  } while (0)
-
-  PCGB_LAUNCH(k_pcg_prep_b, nn);
+  MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_prep_b, grid, block, mem, nn);
   MPSE_TRY(small2_prep(ctx, dtype, pl, B, mem));
   MPSE_TRY(small2_apply(ctx, dtype, pl, B, mem, 0));
-  PCGB_LAUNCH(k_pcg_start_b, nn, nb);
+  MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_start_b, grid, block, mem, nn, nb);
   ++ctx->pcg_batch_stats[mpse_ctx::PB_SETS];
   for (int k = 0;; ++k) {
     if (k > 0) {
       MPSE_TRY(small2_apply(ctx, dtype, pl, B, mem, 1));
       ++ctx->pcg_batch_stats[mpse_ctx::PB_MATVEC_LAUNCHES];
-      PCGB_LAUNCH(k_pcg_step_b, nn, nbq, nb, k);
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_step_b, grid, block, mem, nn, nbq, nb, k);
     }
-    PCGB_LAUNCH(k_pcg_dir_b, nn, nb, tol2, k, max_iter);
+    MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_dir_b, grid, block, mem, nn, nb, tol2, k, max_iter);
     const bool wait_here = (k % PCG_K == PCG_K - 1) || k >= max_iter;
     if (!wait_here) continue;
-    bool have = false;
-    if (ctx->pinned_dev) {
-      const double seq = double(++ctx->publish_seq);
-      hipLaunchKernelGGL(k_pcg_publish_b, dim3(1), block, 0, ctx->stream, mem, B, ctx->pinned_dev + PCGB_SLOT,
-                         (volatile double*)(ctx->pinned_dev + 4095), seq);
+    const PublishAt at = publish_target(ctx, true, mpse_ctx::PIN_BATCH_CTL);
+    if (at.pub) {
+      hipLaunchKernelGGL(k_pcg_publish_b, dim3(1), block, 0, ctx->stream, mem, B, at.pub, at.seq_slot, at.seq);
       MPSE_HIP(ctx, hipGetLastError());
-      MPSE_TRY(publish_wait_seq(ctx, seq, static_cast<const double*>(mh[0].ctl), PCG_CW, PCGB_SLOT));
-      have = ctx->pinned[4095] == seq;
     }
-    if (!have) {      // (no mapped view, or the number never arrived: plain copies)
-      MPSE_HIP(ctx, hipMemcpy2DAsync(ctx->pinned + PCGB_SLOT, sizeof(PcgCtl), SLAB.p, ms, sizeof(PcgCtl), size_t(B),
-                                     hipMemcpyDeviceToHost, ctx->stream));
-      MPSE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (ctx->prof_pending.size() > 2048) prof_drain(ctx);
-    memcpy(hc.data(), ctx->pinned + PCGB_SLOT, size_t(B) * sizeof(PcgCtl));
+    MPSE_TRY(publish_collect(ctx, at, SLAB.p, ms, B, PCG_CW, mpse_ctx::PIN_BATCH_CTL, hc.data()));
     ++ctx->pcg_batch_stats[mpse_ctx::PB_WAITS];
     bool all = true;
     for (int m = 0; m < B; ++m) all = all && hc[m].done;
     if (all) break;
     if (k >= max_iter) return mpse_fail(ctx, MPSE_ERR_HIP, "pcg_batch: no decision at the iteration limit");
   }
-#undef PCGB_LAUNCH
   return MPSE_OK;
 }
 
@@ -842,11 +808,8 @@ int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double 
 
   PcgCtl hc;
   const double *diag = static_cast<const double*>(diag_f64), *mask = static_cast<const double*>(mask_f64);
-  const int st = dtype == MPSE_C128
-                     ? pcg_run<true>(ctx, dtype, h, twolayer, shift, diag, mask, static_cast<const double*>(b),
-                                     static_cast<double*>(x), tol, max_iter, n, &hc)
-                     : pcg_run<false>(ctx, dtype, h, twolayer, shift, diag, mask, static_cast<const double*>(b),
-                                      static_cast<double*>(x), tol, max_iter, n, &hc);
+  const int st = pcg_run_dtype(ctx, dtype, h, twolayer, shift, diag, mask, static_cast<const double*>(b),
+                               static_cast<double*>(x), tol, max_iter, n, &hc);
   if (st != MPSE_OK) return st;      // (allocation or runtime failure: no solve is counted)
   if (twolayer) ++ctx->pcg_stats[mpse_ctx::PS_TWOLAYER];
   return pcg_report(ctx, hc, mask_f64 != nullptr, tol, iters_host, relres_host, lvalue_host);
@@ -887,11 +850,8 @@ int mpse_pcg_sum(mpse_ctx* ctx, int dtype, int nterms, const mpse_heff_ft* terms
 
   PcgCtl hc;
   const double *diag = static_cast<const double*>(diag_f64), *mask = static_cast<const double*>(mask_f64);
-  const int st = dtype == MPSE_C128
-                     ? pcg_run<true>(ctx, dtype, nullptr, 0, shift, diag, mask, static_cast<const double*>(b),
-                                     static_cast<double*>(x), tol, max_iter, n, &hc, nterms, terms, weights_host)
-                     : pcg_run<false>(ctx, dtype, nullptr, 0, shift, diag, mask, static_cast<const double*>(b),
-                                      static_cast<double*>(x), tol, max_iter, n, &hc, nterms, terms, weights_host);
+  const int st = pcg_run_dtype(ctx, dtype, nullptr, 0, shift, diag, mask, static_cast<const double*>(b),
+                               static_cast<double*>(x), tol, max_iter, n, &hc, nterms, terms, weights_host);
   if (st != MPSE_OK) return st;
   ++ctx->pcg_sum_stats[mpse_ctx::PSS_SOLVES];
   ctx->pcg_sum_stats[mpse_ctx::PSS_ITERS] += hc.iters;

@@ -564,12 +564,8 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
       dst = rt_tmp.p;
     }
     const int nb = env_transpose_blocks(Dr, wr);
-    if (cplx)
-      hipLaunchKernelGGL((k_env_transpose<true>), dim3(nb), dim3(SM_THREADS), 0, ctx->stream, (double*)dst,
-                         (const double*)h->R, (int)Dr, (int)wr, skip);
-    else
-      hipLaunchKernelGGL((k_env_transpose<false>), dim3(nb), dim3(SM_THREADS), 0, ctx->stream, (double*)dst,
-                         (const double*)h->R, (int)Dr, (int)wr, skip);
+    MPSE_LAUNCH_TF(ctx, cplx, k_env_transpose, dim3(nb), dim3(SM_THREADS), (double*)dst, (const double*)h->R, (int)Dr,
+                   (int)wr, skip);
     rt = static_cast<const double*>(dst);
   }
 
@@ -613,13 +609,8 @@ int heff_small_batch_rt(mpse_ctx* ctx, int dtype, const mpse_heff* h, int B, con
                         const int* skip0, long long mstride) {
   const int64_t Dr = h->dims.Dr_ket, wr = h->dims.wr;
   const dim3 grid((unsigned)env_transpose_blocks(Dr, wr), 1, (unsigned)B);
-  if (dtype == MPSE_C128)
-    hipLaunchKernelGGL((k_env_transpose_b<true>), grid, dim3(SM_THREADS), 0, ctx->stream, mem, (int)Dr, (int)wr, skip0,
-                       mstride);
-  else
-    hipLaunchKernelGGL((k_env_transpose_b<false>), grid, dim3(SM_THREADS), 0, ctx->stream, mem, (int)Dr, (int)wr, skip0,
-                       mstride);
-  MPSE_HIP(ctx, hipGetLastError());
+  MPSE_LAUNCH_TF_CHK(ctx, dtype == MPSE_C128, k_env_transpose_b, grid, dim3(SM_THREADS), mem, (int)Dr, (int)wr, skip0,
+                     mstride);
   return MPSE_OK;
 }
 

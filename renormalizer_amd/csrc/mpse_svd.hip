@@ -1034,8 +1034,8 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
       MPSE_HIP(ctx, hipGetLastError());
       // one read-back per sweep for all blocks
       if (nblk <= 2000) {
-        MPSE_TRY(publish_and_wait(ctx, reinterpret_cast<const double*>(done), (nblk + 1) / 2, 8));
-        memcpy(hdone.data(), ctx->pinned + 8, size_t(nblk) * sizeof(int));
+        MPSE_TRY(publish_and_wait(ctx, reinterpret_cast<const double*>(done), (nblk + 1) / 2, mpse_ctx::PIN_FLAG));
+        memcpy(hdone.data(), ctx->pinned + mpse_ctx::PIN_FLAG, size_t(nblk) * sizeof(int));
       } else {
         MPSE_TRY(mpse_memcpy_d2h(ctx, hdone.data(), done, size_t(nblk) * sizeof(int)));
       }

@@ -1,4 +1,4 @@
-"""mpse_expm_lanczos (mpse_vec.hip) against exact exponentials, on every path of the solve.
+"""mpse_expm_lanczos (mpse_lanczos.hip) against exact exponentials, on every path of the solve.
 
 The operators are Kronecker sums (tests/kron_problems.py): exp(dt H) C is exact in float64 from the eigendecompositions
 of the small factors, at any centre size.  Each case asserts the deltas of ``mpse_expm_lanczos_path_stats`` for the
