@@ -501,6 +501,39 @@ int mpse_site_factor_ft(mpse_ctx* ctx, const mpse_heff_ft* h, void* S_f64);
 int mpse_diag_ft(mpse_ctx* ctx, const mpse_heff_ft* h, const void* S_f64, double weight, double shift, int accumulate,
                  void* diag_f64);
 
+/* ------------------------------------------------------ overlap of two chains */
+
+/* <bra|ket> of two different matrix product states (or density operators) in one call, replaces the per-site
+ * tensordot pair of mps/mp.py:933-956 (MatrixProduct.dot):
+ *   E_0 = 1,  E_{i+1}[b', k'] = sum_{b, sigma, k} op(B_i)[b, sigma, b'] E_i[b, k] K_i[k, sigma, k'],  result E_N[0, 0]
+ *   bra[i], ket[i]   : device site tensors, contiguous (D_l, p, D_r), each MPSE_F64 or MPSE_C128 (bra_dtype[i] /
+ *                      ket_dtype[i]; any mixture); an MpDm site (D_l, d_up, d_down, D_r) passes p = d_up * d_down
+ *   dims             : nsite rows (Db_l, Dk_l, p, Db_r, Dk_r), host
+ *   conj_bra != 0    : op = complex conjugate (the bra buffers hold the state itself); 0: they hold the conjugate already
+ *   out_re_im_host   : two doubles
+ * Rows with an extent < 1, neighbours whose bonds differ, or a first / last bond != 1: MPSE_ERR_SHAPE before any
+ * device work.  Chains that pass mpse_mps_overlap_plan run as ONE launch (k_overlap_chain: one workgroup walks the
+ * sites, E and one sigma slice of T = E . K[:, sigma, :] in LDS, working dtype complex as soon as any site is); every
+ * other chain as the 2 nsite products of the reference enqueued back to back through the contraction kernel, with two
+ * pooled temporaries.  No atomics, no host read between sites, a fixed summation order: the same inputs give the same
+ * bits on every call (the two paths sum in different orders and agree to rounding).  MPSE_OVERLAP_CHAIN=0 in the
+ * environment sends every chain through the enqueued products (for measurements).  Synchronous. */
+int mpse_mps_overlap(mpse_ctx* ctx, int nsite, const void* const* bra, const int* bra_dtype, const void* const* ket,
+                     const int* ket_dtype, const int64_t* dims /* nsite x 5 */, int conj_bra, double* out_re_im_host);
+/* counts[i], i < n, cumulative:  0 chains taken by the chain kernel, 1 chains taken by the enqueued path, 2 sites
+ * walked (both paths).  A refused call counts nothing.  Diagnostics for tests; no device work. */
+int mpse_mps_overlap_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims table alone: returns 1 when the chain kernel takes the chain, else 0 (also for a table
+ * mpse_mps_overlap refuses).  Eligible: every bond of either side <= info[0], every p <= 65536, and E (rows padded to
+ * an odd length against bank conflicts) plus the largest T slice within info[1] bytes of LDS in the working dtype
+ * (complex when any_complex != 0).  info[i], i < n (may be NULL):
+ *    0  the bond limit: the largest power of two D with a complex D x D E and T slice inside info[1]
+ *    1  LDS bytes a workgroup may use (the 160 KiB of a gfx950 compute unit)
+ *    2  LDS bytes of this chain's launch (0: not eligible)    3  its elements of E    4  its elements of T
+ *    5  threads of the workgroup    6  the largest bond of the table (0: refused)    7  1 when the table is a chain
+ * No context, no device work. */
+int mpse_mps_overlap_plan(int nsite, const int64_t* dims, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

@@ -180,6 +180,9 @@ struct mpse_ctx {
   // mpse_pcg_batch (mpse_pcg_batch_stats; the order of include/mpsengine.h)
   enum PcgBatchStat { PB_MEMBERS, PB_SINGLE, PB_SETS, PB_MATVEC_LAUNCHES, PB_WAITS, PB_COUNT };
   long long pcg_batch_stats[PB_COUNT] = {0};
+  // mpse_mps_overlap (mpse_mps_overlap_stats; the order of include/mpsengine.h)
+  enum OverlapStat { OV_CHAIN, OV_ENQUEUED, OV_SITES, OV_COUNT };
+  long long overlap_stats[OV_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

@@ -175,6 +175,10 @@ _SIGNATURES = {
     "mpse_pcg_sum_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_site_factor_ft": [C.c_void_p, C.POINTER(mpse_heff_ft), C.c_void_p],
     "mpse_diag_ft": [C.c_void_p, C.POINTER(mpse_heff_ft), C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p],
+    "mpse_mps_overlap": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                         C.POINTER(C.c_int), _i64p, C.c_int, _dblp],
+    "mpse_mps_overlap_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_overlap_plan": [C.c_int, _i64p, C.c_int, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -204,6 +208,21 @@ def load_library(path=LIB_PATH):
     lib.mpse_version.argtypes = []
     lib.mpse_version.restype = C.c_char_p
     return lib
+
+
+OVERLAP_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid")
+
+
+def mps_overlap_plan(dims, any_complex, lib=None):
+    """Which path ``Engine.mps_overlap`` takes for a chain, from its ``dims`` rows (Db_l, Dk_l, p, Db_r, Dk_r) alone
+    (``mpse_mps_overlap_plan``; needs the built library, no GPU).  Returns (chain kernel?, {info name: value})."""
+    lib = lib or load_library()
+    rows = [[int(x) for x in r] for r in dims]
+    assert all(len(r) == 5 for r in rows), "dims rows are (Db_l, Dk_l, p, Db_r, Dk_r)"
+    flat = (C.c_int64 * max(5 * len(rows), 1))(*[x for r in rows for x in r])
+    info = (C.c_int64 * len(OVERLAP_PLAN_INFO))()
+    ok = lib.mpse_mps_overlap_plan(len(rows), flat, int(bool(any_complex)), info, len(info))
+    return bool(ok), dict(zip(OVERLAP_PLAN_INFO, (int(v) for v in info)))
 
 
 class _Recording:
@@ -646,6 +665,36 @@ class Engine:
         if check and st not in (0, 3):
             self._check(st)
         return PcgResult(int(st), it.value, rel.value, lv.value)
+
+    # -- overlap of two chains
+    OVERLAP_STATS = ("chain_kernel", "enqueued", "sites")
+
+    def mps_overlap_stats(self):
+        """{name: count} of the ``mps_overlap`` calls of this context, cumulative (``mpse_mps_overlap_stats``): chains
+        taken by the chain kernel, chains taken by the enqueued products, sites walked."""
+        v = (C.c_int64 * len(self.OVERLAP_STATS))()
+        self._check(self.lib.mpse_mps_overlap_stats(self.ctx, v, len(v)))
+        return dict(zip(self.OVERLAP_STATS, (int(x) for x in v)))
+
+    def mps_overlap(self, bra_sites, ket_sites, conj_bra):
+        """<bra|ket> of two chains of device site tensors (D_l, p.., D_r) in one engine call (``mpse_mps_overlap``);
+        every leg between the bonds is summed, so MpDm sites pass as they are.  ``conj_bra``: conjugate the bra inside
+        the contraction.  Real and complex sites may be mixed.  Returns a complex."""
+        n = len(bra_sites)
+        if n != len(ket_sites) or n == 0:
+            raise ValueError(f"mps_overlap: {n} bra sites, {len(ket_sites)} ket sites")
+        dims = (C.c_int64 * (5 * n))()
+        for i, (b, k) in enumerate(zip(bra_sites, ket_sites)):
+            pb, pk = b.size // (b.shape[0] * b.shape[-1]), k.size // (k.shape[0] * k.shape[-1])
+            if pb != pk:
+                raise ValueError(f"mps_overlap: site {i} has physical extents {b.shape[1:-1]} and {k.shape[1:-1]}")
+            dims[5 * i:5 * i + 5] = [b.shape[0], k.shape[0], pb, b.shape[-1], k.shape[-1]]
+        out = (C.c_double * 2)()
+        self._check(self.lib.mpse_mps_overlap(
+            self.ctx, n, (C.c_void_p * n)(*[t.ptr for t in bra_sites]), (C.c_int * n)(*[t.code for t in bra_sites]),
+            (C.c_void_p * n)(*[t.ptr for t in ket_sites]), (C.c_int * n)(*[t.code for t in ket_sites]), dims,
+            int(bool(conj_bra)), out))
+        return complex(out[0], out[1])
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""

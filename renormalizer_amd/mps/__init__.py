@@ -1,6 +1,6 @@
 from .backend import backend
 from .mpo import Mpo
-from .mps import Mps
+from .mps import BraKetPair, Mps
 from .batch import evolve_batch
 from .mpdm import MpDm
 from .thermalprop import thermal_state

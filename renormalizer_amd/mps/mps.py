@@ -390,6 +390,14 @@ class Mps:
             e = eng.matmul(b.reshape(-1, b.shape[-1]), t, trans_a=True, conj_a=not self_is_conj)
         return complex(e.to_host()[0, 0])
 
+    def overlap(self, other: "Mps", self_is_conj=True) -> complex:
+        """The value of ``dot`` as ONE engine call (``Engine.mps_overlap`` -> ``mpse_mps_overlap``): the chain is walked
+        inside the engine, by a single launch where every bond fits its LDS budget, and the host reads once.  For the
+        overlap taken after every step of a correlation function; ``dot`` itself stays as it is (its values are pinned
+        bit for bit).  The two sum in different orders and agree to rounding."""
+        assert len(self) == len(other)
+        return get_engine().mps_overlap(self._mp, other._mp, conj_bra=not self_is_conj)
+
     @property
     def mp_norm(self) -> float:
         """mps/mp.py:354-372"""
@@ -1845,6 +1853,40 @@ def _evolve_prop_and_compress_tdrk(self, mpo, evolve_dt) -> "Mps":
 
 Mps._evolve_prop_and_compress_tdrk4 = _evolve_prop_and_compress_tdrk4
 Mps._evolve_prop_and_compress_tdrk = _evolve_prop_and_compress_tdrk
+
+
+class BraKetPair:
+    """A bra and a ket state evolved side by side and their overlap ``ft`` = <bra|ket> (with ``mpo``: <bra|mpo|ket>),
+    the value a correlation-function job records per step (mps/mps.py:2061-2088).  The overlap goes through
+    ``Mps.overlap`` (one engine call) with the bra conjugated inside the contraction; the two ``coeff`` factors enter
+    as in the reference: conj(bra.coeff) * ket.coeff.  ``ft`` may be injected (a value computed elsewhere)."""
+
+    def __init__(self, bra_mps, ket_mps, mpo=None, ft=None):
+        self.bra_mps = bra_mps
+        self.ket_mps = ket_mps
+        self.mpo = mpo
+        self.ft = self.calc_ft() if ft is None else ft
+
+    def calc_ft(self):
+        if self.mpo is None:
+            dot = self.bra_mps.overlap(self.ket_mps, self_is_conj=False)
+        else:
+            dot = self.ket_mps.expectation(self.mpo, self.bra_mps.conj())
+        return complex(dot * np.conjugate(self.bra_mps.coeff) * self.ket_mps.coeff)
+
+    def __str__(self):
+        if np.iscomplexobj(self.ft):
+            sign = "+" if 0 <= self.ft.imag else ""        # a negative imaginary part brings its own sign
+            ft_str = "%g%s%gj" % (self.ft.real, sign, self.ft.imag)
+        else:
+            ft_str = "%g" % self.ft
+        return "bra: %s, ket: %s, ft: %s" % (self.bra_mps, self.ket_mps, ft_str)
+
+    def __iter__(self):
+        return iter((self.bra_mps, self.ket_mps))
+
+    def __getitem__(self, i):
+        return (self.bra_mps, self.ket_mps)[i]
 
 
 def _min_abs(t1, t2):
