@@ -32,6 +32,7 @@
 
 #include "mpse_device.h"
 #include "mpse_internal.h"
+#include "mpse_plans.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
@@ -1231,11 +1232,161 @@ __global__ __launch_bounds__(256) void k_transpose_inner(double* out, const doub
   }
 }
 
+// ---- pieces shared by the launchers (gemm_impl, occ_mask_get, gemm_grouped)
+inline int n_cu_of(const mpse_ctx* ctx) { return ctx->n_cu > 0 ? ctx->n_cu : 256; }
+
+// stride of the index as it moves through memory, for "which index of an operand is the contiguous one"
+long long fastest(const IdxMap& m) { return m.ext <= 1 ? (long long)1 << 60 : (m.s_lo < 0 ? -m.s_lo : m.s_lo); }
+
+// the fast kernel addresses its operands as uniform base + 32-bit lane offset: non-negative strides, spans < 4 GB
+bool span_ok(const IdxMap& m, const IdxMap& k, bool cplx) {
+  if (m.s_hi < 0 || m.s_lo < 0 || k.s_hi < 0 || k.s_lo < 0) return false;
+  auto span = [](const IdxMap& x) {
+    if (x.ext <= 1) return 0.0;
+    if (x.lo == 0x7fffffff) return double(x.ext - 1) * double(x.s_lo);
+    return double((x.ext - 1) / x.lo) * double(x.s_hi) + double(x.lo - 1) * double(x.s_lo);
+  };
+  return (span(m) + span(k) + 1.0) * (cplx ? 16.0 : 8.0) < 4.0e9;
+}
+bool fast_ok(const GemmArgs& g, bool ca, bool cb) { return span_ok(g.mA, g.kA, ca) && span_ok(g.nB, g.kB, cb); }
+
+// The six index maps of a product with what follows from them: extents, tiles, staging orientation.  false: an extent
+// is out of range.
+// Workgroup tile: 64 x 64.  (A 32 x 32 one-wave tile for products whose 64 x 64 tiles cannot fill the chip lost to
+// split-K by 17 % on the headline run - one wave walking the whole K is a longer latency chain than many workgroups
+// walking two K tiles each plus a reduction pass - and was removed.)
+bool fill_maps(GemmArgs& g, const mpse_index& ma, const mpse_index& ka, const mpse_index& kb, const mpse_index& nb,
+               const mpse_index& mc, const mpse_index& nc) {
+  if (!to_map(ma, &g.mA) || !to_map(ka, &g.kA) || !to_map(kb, &g.kB) || !to_map(nb, &g.nB) || !to_map(mc, &g.mC) ||
+      !to_map(nc, &g.nC))
+    return false;
+  g.M = g.mA.ext, g.N = g.nB.ext, g.K = g.kA.ext;
+  g.tiles_m = g.mtiles_m = (g.M + BM - 1) / BM;
+  g.tiles_n = g.mtiles_n = (g.N + BN - 1) / BN;
+  g.a_kfast = fastest(g.kA) <= fastest(g.mA);
+  g.b_kfast = fastest(g.kB) <= fastest(g.nB);
+  return true;
+}
+
+// ---- occupancy masks: flags of the 64 x 16 tiles of one operand (`batch` matrices sb elements apart, rows through
+// rm, K through km), [batch][tile][nkw * 8] bytes
+mpse_ctx::OccKey occ_key(const void* p, const IdxMap& rm, const IdxMap& km, long long sb, long long batch, bool cplx) {
+  mpse_ctx::OccKey k;
+  memset(&k, 0, sizeof(k));
+  k.ptr = p;
+  k.r_ext = rm.ext, k.r_lo = rm.lo, k.r_shi = rm.s_hi, k.r_slo = rm.s_lo;
+  k.k_ext = km.ext, k.k_lo = km.lo, k.k_shi = km.s_hi, k.k_slo = km.s_lo;
+  k.sb = sb, k.nrows = rm.ext, k.tiles = (rm.ext + BM - 1) / BM, k.nkw = ((km.ext + BK - 1) / BK + 7) / 8;
+  k.batch = (int)batch, k.K = km.ext, k.cplx = cplx ? 1 : 0;
+  return k;
+}
+size_t occ_bytes(const mpse_ctx::OccKey& k) { return size_t(k.batch) * k.tiles * k.nkw * 8; }
+
+struct OccMask {
+  void* mask = nullptr;
+  bool scan = false;     // the flags are still to be written (k_tile_occ)
+  bool stable = true;    // the mask (or its absence) outlives the call: cached or the solve's
+};
+// Where the mask of an operand comes from.  Inside a Krylov solve the environments do not change: the mask of an
+// operand inside them (`keep` = SolveScope::in_env) is looked up in occ_cache and on a miss stored there until the
+// solve ends.  Any other operand takes the mask the caller already has (`given`, null = none) or, to be scanned, `tmp`
+// in a temporary of the caller.
+int occ_mask_source(mpse_ctx* ctx, bool keep, const mpse_ctx::OccKey& key, const void* given, void* tmp, OccMask* m) {
+  m->stable = keep || given;
+  if (keep)
+    for (const auto& e : ctx->occ_cache)
+      if (memcmp(&e.key, &key, sizeof(key)) == 0) {
+        m->mask = e.mask;
+        return MPSE_OK;
+      }
+  m->scan = !given;
+  if (given) {
+    m->mask = const_cast<void*>(given);
+  } else if (keep) {
+    MPSE_TRY(mpse_malloc(ctx, occ_bytes(key), &m->mask));
+    ctx->occ_cache.push_back({key, m->mask});
+  } else {
+    m->mask = tmp;
+  }
+  return MPSE_OK;
+}
+OccOperand occ_operand(const mpse_ctx::OccKey& k, const IdxMap& rm, const IdxMap& km, int kfast, const OccMask& m) {
+  return OccOperand{static_cast<const double*>(k.ptr), rm, km, k.nrows, m.scan ? k.tiles : 0, k.cplx, kfast, k.sb,
+                    static_cast<unsigned char*>(m.mask)};
+}
+
+// ---- launch order (k_tile_order).  keep: the masks it is computed from are the running solve's - the order is looked
+// up in perm_cache (key: every field but perm) and on a miss stored there like the masks; otherwise it goes to `tmp`.
+// *sort: the order is still to be computed.
+int perm_source(mpse_ctx* ctx, bool keep, mpse_ctx::PermEntry key, size_t bytes, TmpBuf& tmp, int** perm, bool* sort) {
+  *sort = false;
+  if (keep)
+    for (const auto& e : ctx->perm_cache)
+      if (e.amask == key.amask && e.bmask == key.bmask && e.tiles_m == key.tiles_m && e.tiles_n == key.tiles_n &&
+          e.nkt == key.nkt) {
+        *perm = static_cast<int*>(e.perm);
+        return MPSE_OK;
+      }
+  *sort = true;
+  if (keep) {
+    MPSE_TRY(mpse_malloc(ctx, bytes, &key.perm));
+    ctx->perm_cache.push_back(key);
+    *perm = static_cast<int*>(key.perm);
+  } else {
+    MPSE_TRY(tmp.alloc(bytes));
+    *perm = tmp.as<int>();
+  }
+  return MPSE_OK;
+}
+
+// ---- the one place where k_gemm and k_splitk_reduce are instantiated and launched: for every operand type pair the
+// fast kernel with eight (`wide`) and four waves and the general kernel; for a complex second operand the two grouped
+// forms of the fast kernel.  A split product whose slices are not left to its consumer is followed by its reduction
+// (rgrid.x != 0).
+void launch_gemm(mpse_ctx* ctx, const GemmArgs& g, long long nwg, bool ca, bool cb, bool fast, bool wide, bool grouped,
+                 dim3 rgrid = dim3(0), int batch = 1) {
+  using Kern = void (*)(const GemmArgs);
+  static const Kern plain[4][3] = {   // [complex operands first][eight waves, four waves, general]
+      {k_gemm<true, true, true, 2, 1>, k_gemm<true, true, true, 2>, k_gemm<true, true, false, 2>},
+      {k_gemm<true, false, true, 2, 1>, k_gemm<true, false, true, 2>, k_gemm<true, false, false, 2>},
+      {k_gemm<false, true, true, 2, 1>, k_gemm<false, true, true, 2>, k_gemm<false, true, false, 2>},
+      {k_gemm<false, false, true, 2, 1>, k_gemm<false, false, true, 2>, k_gemm<false, false, false, 2>}};
+  static void (*const reduce[2])(const GemmArgs, int) = {k_splitk_reduce<true>, k_splitk_reduce<false>};
+  static const Kern groups[2][2] = {   // [complex first operand first][eight waves, four waves]
+      {k_gemm<true, true, true, 2, 1, true>, k_gemm<true, true, true, 2, 2, true>},
+      {k_gemm<false, true, true, 2, 1, true>, k_gemm<false, true, true, 2, 2, true>}};
+  const int form = fast && wide ? 0 : fast ? 1 : 2;
+  const Kern k = grouped ? groups[ca ? 0 : 1][form] : plain[(ca ? 0 : 2) + (cb ? 0 : 1)][form];
+  hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(form == 0 ? 512 : 256), 0, ctx->stream, g);
+  if (rgrid.x) hipLaunchKernelGGL(reduce[(ca || cb) ? 0 : 1], rgrid, dim3(256), 0, ctx->stream, g, batch);
+}
+
+// the path counters of mpse_gemm_path_stats
+void count_paths(long long* gp, const mpse_plan::GemmPlan& p, bool batched) {
+  const bool masked = p.fast && p.masks;   // (the general kernel visits every K tile)
+  ++gp[mpse_ctx::GP_LAUNCH];
+  gp[mpse_ctx::GP_GENERAL] += !p.fast;
+  gp[mpse_ctx::GP_WIDE] += p.wide;
+  gp[mpse_ctx::GP_SPLIT_B1] += p.ksplit > 1 && !batched;
+  gp[mpse_ctx::GP_SPLIT_BN] += p.ksplit > 1 && batched;
+  gp[mpse_ctx::GP_DIE1] += p.die_group == 1;
+  gp[mpse_ctx::GP_DIE2] += p.die_group == 2;
+  gp[mpse_ctx::GP_SKEW] += !p.order && !p.die_group;
+  gp[mpse_ctx::GP_ORDER] += p.order;
+  gp[mpse_ctx::GP_MASK] += masked;
+  gp[mpse_ctx::GP_MASK_GLOBAL] += masked && p.nkw > 64;
+}
+void count_paths(long long* gp, const GroupedDesc& d) {
+  ++gp[mpse_ctx::GP_GROUPED];
+  gp[mpse_ctx::GP_GROUPED_SPLIT2] += d.split2;
+}
+
 }  // namespace
 
 // sc: the solve the product runs in, rq: what run_plan asks of it beyond the descriptor (both may be null)
 static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, const void* B, void* C, int skip_zero,
                      const SolveScope* sc, ProductReq* rq) {
+  // ---- check
   if (!ctx || !d) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if ((d->dtype_a != MPSE_F64 && d->dtype_a != MPSE_C128) || (d->dtype_b != MPSE_F64 && d->dtype_b != MPSE_C128))
@@ -1246,62 +1397,32 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
                      (long long)d->k_a.ext, (long long)d->k_b.ext);
   if (d->m_a.ext == 0 || d->n_b.ext == 0 || d->batch <= 0) return MPSE_OK;
   if (!A || !B || !C) return mpse_fail(ctx, MPSE_ERR_ARG, "mpse_gemm: null operand");
-  GemmArgs g;
+  GemmArgs g = {};
   g.A = (const double*)A;
   g.B = (const double*)B;
   g.C = (double*)C;
-  if (!to_map(d->m_a, &g.mA) || !to_map(d->k_a, &g.kA) || !to_map(d->k_b, &g.kB) || !to_map(d->n_b, &g.nB) ||
-      !to_map(d->m_c, &g.mC) || !to_map(d->n_c, &g.nC))
+  if (!fill_maps(g, d->m_a, d->k_a, d->k_b, d->n_b, d->m_c, d->n_c))
     return mpse_fail(ctx, MPSE_ERR_SHAPE, "mpse_gemm: extent out of range");
   g.sbA = d->sb_a;
   g.sbB = d->sb_b;
   g.sbC = d->sb_c;
-  g.M = g.mA.ext;
-  g.N = g.nB.ext;
-  g.K = g.kA.ext;
-  g.mtiles_m = (g.M + BM - 1) / BM;
-  g.mtiles_n = (g.N + BN - 1) / BN;
-  // workgroup tile: 64 x 64.  (A 32 x 32 one-wave tile for products whose 64 x 64 tiles cannot fill the chip lost to
-  // split-K by 17 % on the headline run - one wave walking the whole K is a longer latency chain than many workgroups
-  // walking two K tiles each plus a reduction pass - and was removed.)
-  g.tiles_m = g.mtiles_m;
-  g.tiles_n = g.mtiles_n;
-  auto fast = [](const IdxMap& m) { return m.ext <= 1 ? (long long)1 << 60 : (m.s_lo < 0 ? -m.s_lo : m.s_lo); };
-  g.a_kfast = fast(g.kA) <= fast(g.mA);
-  g.b_kfast = fast(g.kB) <= fast(g.nB);
-  g.conjA = d->conj_a && d->dtype_a == MPSE_C128;
-  g.conjB = d->conj_b && d->dtype_b == MPSE_C128;
+  const bool ca = d->dtype_a == MPSE_C128, cb = d->dtype_b == MPSE_C128;
+  g.conjA = d->conj_a && ca;
+  g.conjB = d->conj_b && cb;
   g.alpha_re = d->alpha_re;
   g.alpha_im = d->alpha_im;
   g.beta_re = d->beta_re;
   g.beta_im = d->beta_im;
   g.use_beta = (d->beta_re != 0.0 || d->beta_im != 0.0);
   // beta source of the caller (ProductReq::cin)
-  g.Cin = nullptr;
   if (rq && rq->cin) {
     if (d->batch != 1 || !g.use_beta || !to_map(rq->cin_m, &g.mCin) || !to_map(rq->cin_n, &g.nCin) ||
         g.mCin.ext != g.mC.ext || g.nCin.ext != g.nC.ext)
       return mpse_fail(ctx, MPSE_ERR_ARG, "mpse_gemm: beta source needs batch == 1, beta != 0 and the extents of C");
     g.Cin = static_cast<const double*>(rq->cin);
   }
-  const int* skip = sc ? sc->skip : nullptr;
-  const bool ca = d->dtype_a == MPSE_C128, cb = d->dtype_b == MPSE_C128;
-  // split-K when the output tiles alone cannot fill the 256 CUs (skinny results with long K)
-  const long long base_blocks = (long long)g.tiles_m * g.tiles_n * d->batch;
-  const int nkt_all = (g.K + BK - 1) / BK;
-  g.ksplit = 1;
-  g.kt_per_split = nkt_all > 0 ? nkt_all : 1;
-  g.ws = nullptr;
-  g.amask = g.bmask = nullptr;
-  g.nkw = 0;
-  g.skip = skip;
+  g.skip = sc ? sc->skip : nullptr;
   g.skew = 1;
-  g.perm = nullptr;
-  g.gg.ngrp = 0;
-  g.slice_fast = 0;
-  g.die_group = 0;
-  g.dot_y = nullptr;
-  g.dot_part = nullptr;
   if (!ctx->gemm_trace_checked) {
     ctx->gemm_trace_checked = true;
     if (getenv("MPSE_GEMM_TRACE")) {
@@ -1313,62 +1434,34 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
     }
   }
   g.trace = gemm_trace_ptr(ctx);
-  TmpBuf WSB(ctx), MSK(ctx);
-  bool leave_slices = false;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-  const int tiles_limit = n_cu;
-  const long long wg_target = n_cu;   // one workgroup per CU (policy sweeps of the headline run)
-  if (base_blocks < tiles_limit && nkt_all >= 4) {
-    // fewer output tiles than CUs: slice K until ~1 workgroup per CU exists (2 per CU: equal to 1.7 % slower on the
-    // headline run depending on the box - the reduction pass reads twice the slices; 3 per CU: -3 %; 0.5 per CU: -7 %).  (One tile per CU runs as fast
-    // unsplit as split in two + reduction pass since the K loop prefetches fragments: measured, 4096x256 C-step.)
-    int want = (int)((wg_target + base_blocks - 1) / base_blocks);
-    int maxs = nkt_all / 2;                                           // at least two k-tiles per slice
-    int S = want < maxs ? want : maxs;
-    if (S > 1) {
-      g.kt_per_split = (nkt_all + S - 1) / S;
-      g.ksplit = (nkt_all + g.kt_per_split - 1) / g.kt_per_split;
-      // (Leaving the slices to the consumer of a matvec result - the Lanczos update adding them while it reads -
-      // instead of the reduction launch measured 1.4 % slower on the headline run: every slice's workgroups then load
-      // the dot partner, and the update kernel streams 16 slices with a fraction of the reduction kernel's blocks.)
-      const size_t esz = (ca || cb) ? 16 : 8;
-      const size_t ws_bytes = size_t(d->batch) * g.ksplit * size_t(g.M) * size_t(g.N) * esz;
-      // slices for a consumer that adds them itself (ProductReq::slices): plain product into a compact result
-      const bool compact = is_single(g.mC) && is_single(g.nC) && g.mC.s_lo == g.N && (g.nC.s_lo == 1 || g.N == 1);
-      if (rq && rq->slices && !rq->dot && d->batch == 1 && compact && !g.use_beta && d->alpha_re == 1.0 &&
-          d->alpha_im == 0.0 && ws_bytes <= rq->slices_cap) {
-        g.ws = static_cast<double*>(rq->slices);
-        rq->slices_used = g.ksplit;
-        leave_slices = true;
-      } else {
-        MPSE_TRY(WSB.alloc(ws_bytes));
-        g.ws = WSB.as<double>();
-      }
-    }
-  }
-  g.slice_fast = g.ksplit > 1 && d->batch == 1;
-  long long nblk = base_blocks * g.ksplit;
-  if (nblk > 0x7fffffffLL) return mpse_fail(ctx, MPSE_ERR_SHAPE, "mpse_gemm: grid too large");
 
-  // dot request of the caller (ProductReq::dot: run_plan passes it to the step that completes the result)
+  // ---- plan
+  // dot request of the caller (ProductReq::dot: run_plan passes it to the step that completes the result); slices
+  // for a consumer that adds them itself (ProductReq::slices): plain product into a compact result
   MatvecReq::Dot* dot = rq ? rq->dot : nullptr;
-  long long rgx = (g.N + 255) / 256 > 64 ? 64 : (g.N + 255) / 256;
-  long long rgy = (long long)g.M * d->batch > 32768 ? 32768 : (long long)g.M * d->batch;
-  if (dot && d->batch == 1) {
-    long long producers = base_blocks;
-    if (g.ksplit > 1) {
-      const long long cap_y = dot->cap / rgx;
-      if (cap_y >= 1 && rgy > cap_y) rgy = cap_y;
-      producers = rgx * rgy;
-    }
-    if (producers >= 1 && producers <= dot->cap) {
-      g.dot_y = static_cast<const double*>(dot->y);
-      g.dot_part = dot->part;
-      dot->nb_out = (int)producers;
-    }
+  const bool compact = is_single(g.mC) && is_single(g.nC) && g.mC.s_lo == g.N && (g.nC.s_lo == 1 || g.N == 1);
+  const bool slices = rq && rq->slices && compact && d->alpha_re == 1.0 && d->alpha_im == 0.0;
+  const mpse_plan::GemmPlan p = mpse_plan::launch_plan(
+      {g.M, g.N, g.K, d->batch, n_cu_of(ctx), ca, cb, skip_zero, is_single(g.kA) && is_single(g.kB), fast_ok(g, ca, cb),
+       dot != nullptr, dot ? dot->cap : 0, slices, slices ? rq->slices_cap : 0, g.use_beta != 0});
+  if (p.nwg > 0x7fffffffLL) return mpse_fail(ctx, MPSE_ERR_SHAPE, "mpse_gemm: grid too large");
+  g.ksplit = p.ksplit;
+  g.kt_per_split = p.kt_per_split;
+  g.slice_fast = g.ksplit > 1 && d->batch == 1;
+  g.die_group = p.die_group;
+  TmpBuf WSB(ctx), MSK(ctx), PERM(ctx);
+  if (p.leave_slices) {
+    g.ws = static_cast<double*>(rq->slices);
+    rq->slices_used = g.ksplit;
+  } else if (g.ksplit > 1) {
+    MPSE_TRY(WSB.alloc(p.ws_bytes));
+    g.ws = WSB.as<double>();
   }
-
-  dim3 grid((unsigned)nblk), block(256);
+  if (p.dot_producers) {
+    g.dot_y = static_cast<const double*>(dot->y);
+    g.dot_part = dot->part;
+    dot->nb_out = (int)p.dot_producers;
+  }
   mpse_ctx::ProfRec rec;
   const int variant = (ca ? 1 : 0) + (cb ? 2 : 0);
   const double mnk = double(g.M) * double(g.N) * double(g.K) * double(d->batch);
@@ -1379,176 +1472,54 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
                           double(g.M) * g.N * ((ca || cb) ? 16 : 8) * (g.use_beta ? 2 : 1)),
       &rec);
   g.kt_counter = prof_this && ctx->prof_ktiles ? ctx->prof_ktiles + variant : nullptr;
-  bool mask_a_stable = true, mask_b_stable = true;   // the mask (or its absence) outlives this call: cached or the solve's
-  if (skip_zero && is_single(g.kA) && is_single(g.kB) && nkt_all >= 2 && d->batch <= 16384) {
-    // tile occupancy of both operands (one small scan launch), then only K tiles with data on both sides are visited
-    g.nkw = (nkt_all + 7) / 8;
-    const size_t wa = size_t(d->batch) * g.mtiles_m * g.nkw, wb = size_t(d->batch) * g.mtiles_n * g.nkw;
-    // skip_zero bit 0: scan A, bit 1: scan B (an operand that is as large as the product itself is not worth a pass)
-    const bool sa = skip_zero & 1, sb_ = skip_zero & 2;
-    // Inside a Krylov solve the environments do not change: their masks are computed once and kept (SolveScope)
-    auto cacheable = [&](const void* p) { return sc && sc->in_env(p); };
-    auto make_key = [&](const void* p, const IdxMap& rm, const IdxMap& km, long long sb, int nrows, int tiles, int cplx) {
-      mpse_ctx::OccKey k;
-      memset(&k, 0, sizeof(k));
-      k.ptr = p;
-      k.r_ext = rm.ext, k.r_lo = rm.lo, k.r_shi = rm.s_hi, k.r_slo = rm.s_lo;
-      k.k_ext = km.ext, k.k_lo = km.lo, k.k_shi = km.s_hi, k.k_slo = km.s_lo;
-      k.sb = sb, k.nrows = nrows, k.tiles = tiles, k.nkw = g.nkw, k.batch = (int)d->batch, k.K = g.K, k.cplx = cplx;
-      return k;
-    };
-    auto find = [&](const mpse_ctx::OccKey& k) -> void* {
-      for (const auto& e : ctx->occ_cache)
-        if (memcmp(&e.key, &k, sizeof(k)) == 0) return e.mask;
-      return nullptr;
-    };
-    unsigned long long *am = nullptr, *bmk = nullptr;
-    bool scan_a = sa, scan_b = sb_, b_structural = false;
-    mpse_ctx::OccKey ka, kb;
-    const bool ca_ok = sa && cacheable(g.A), cb_ok = sb_ && cacheable(g.B);
-    if (ca_ok) {
-      ka = make_key(g.A, g.mA, g.kA, g.sbA, g.M, g.mtiles_m, ca ? 1 : 0);
-      if (void* hit = find(ka)) am = static_cast<unsigned long long*>(hit), scan_a = false;
-    }
-    if (cb_ok) {
-      kb = make_key(g.B, g.nB, g.kB, g.sbB, g.N, g.mtiles_n, cb ? 1 : 0);
-      if (void* hit = find(kb)) bmk = static_cast<unsigned long long*>(hit), scan_b = false;
-    }
+
+  // ---- masks: tile occupancy of the operands the hint names (bit 0: A, bit 1: B - an operand that is as large as the
+  // product itself is not worth a pass), then only K tiles with data on both sides are visited
+  OccMask ma, mb;
+  if (p.masks) {
+    g.nkw = p.nkw;
+    const bool sa = skip_zero & 1, sb = skip_zero & 2;
+    const mpse_ctx::OccKey ka = occ_key(g.A, g.mA, g.kA, g.sbA, d->batch, ca);
+    const mpse_ctx::OccKey kb = occ_key(g.B, g.nB, g.kB, g.sbB, d->batch, cb);
+    const bool keep_a = sa && sc && sc->in_env(g.A), keep_b = sb && sc && sc->in_env(g.B);
     // B is a Krylov vector of a solve whose caller supplied the structural mask of the centre tensor: no scan
-    if (scan_b && sc && sc->in_krylov(g.B) && d->batch == 1 &&
-        (long long)(wb * sizeof(unsigned long long)) == sc->cmask.bytes) {
-      bmk = static_cast<unsigned long long*>(const_cast<void*>(sc->cmask.ptr));
-      scan_b = false;
-      b_structural = true;
-    }
-    mask_a_stable = !sa || ca_ok;
-    mask_b_stable = !sb_ || cb_ok || b_structural;
-    // storage: cached masks live until the solve ends, the others in a temporary of this call
-    size_t tmp_words = 0;
-    if (scan_a && !ca_ok) tmp_words += wa;
-    if (scan_b && !cb_ok) tmp_words += wb;
-    if (tmp_words) MPSE_TRY(MSK.alloc(tmp_words * sizeof(unsigned long long)));
-    unsigned long long* tmp = MSK.as<unsigned long long>();
-    if (scan_a) {
-      if (ca_ok) {
-        void* pm = nullptr;
-        MPSE_TRY(mpse_malloc(ctx, wa * sizeof(unsigned long long), &pm));
-        ctx->occ_cache.push_back({ka, pm});
-        am = static_cast<unsigned long long*>(pm);
-      } else {
-        am = tmp;
-        tmp += wa;
-      }
-    }
-    if (scan_b) {
-      if (cb_ok) {
-        void* pm = nullptr;
-        MPSE_TRY(mpse_malloc(ctx, wb * sizeof(unsigned long long), &pm));
-        ctx->occ_cache.push_back({kb, pm});
-        bmk = static_cast<unsigned long long*>(pm);
-      } else {
-        bmk = tmp;
-      }
-    }
+    const void* centre = (sb && sc && sc->in_krylov(g.B) && d->batch == 1 && (long long)occ_bytes(kb) == sc->cmask.bytes)
+                             ? sc->cmask.ptr : nullptr;
+    // (one temporary for the masks that are not kept)
+    const size_t tmp_a = sa && !keep_a ? occ_bytes(ka) : 0, tmp_b = sb && !keep_b && !centre ? occ_bytes(kb) : 0;
+    if (tmp_a + tmp_b) MPSE_TRY(MSK.alloc(tmp_a + tmp_b));
+    if (sa) MPSE_TRY(occ_mask_source(ctx, keep_a, ka, nullptr, MSK.p, &ma));
+    if (sb) MPSE_TRY(occ_mask_source(ctx, keep_b, kb, centre, MSK.as<char>() + tmp_a, &mb));
     // (flag bytes past the last k tile stay unwritten: next_kt never looks beyond kt_end)
-    if (scan_a || scan_b) {
-      OccOperand oa{g.A, g.mA, g.kA, g.M, scan_a ? g.mtiles_m : 0, ca ? 1 : 0, g.a_kfast, g.sbA, reinterpret_cast<unsigned char*>(am)};
-      OccOperand ob{g.B, g.nB, g.kB, g.N, scan_b ? g.mtiles_n : 0, cb ? 1 : 0, g.b_kfast, g.sbB, reinterpret_cast<unsigned char*>(bmk)};
-      const int tmax = (scan_a ? g.mtiles_m : 0) > (scan_b ? g.mtiles_n : 0) ? (scan_a ? g.mtiles_m : 0) : (scan_b ? g.mtiles_n : 0);
-      const dim3 og((nkt_all + 3) / 4, tmax, (unsigned)(2 * d->batch));
-      hipLaunchKernelGGL(k_tile_occ, og, dim3(256), 0, ctx->stream, oa, ob, g.K, g.nkw, (int)d->batch, skip);
+    if (ma.scan || mb.scan) {
+      const OccOperand oa = occ_operand(ka, g.mA, g.kA, g.a_kfast, ma), ob = occ_operand(kb, g.nB, g.kB, g.b_kfast, mb);
+      const dim3 og((p.nkt + 3) / 4, oa.tiles > ob.tiles ? oa.tiles : ob.tiles, (unsigned)(2 * d->batch));
+      hipLaunchKernelGGL(k_tile_occ, og, dim3(256), 0, ctx->stream, oa, ob, g.K, g.nkw, (int)d->batch, g.skip);
     }
-    g.amask = sa ? am : nullptr;
-    g.bmask = sb_ ? bmk : nullptr;
+    g.amask = static_cast<const unsigned long long*>(ma.mask);
+    g.bmask = static_cast<const unsigned long long*>(mb.mask);
   }
-  TmpBuf PERM(ctx);
-  const long long ntile_all = (long long)g.tiles_m * g.tiles_n;
-  if (d->batch == 1 && (g.amask || g.bmask) && ntile_all * g.ksplit > 2 * n_cu && ntile_all <= 2048) {
+
+  // ---- order
+  if (p.order) {
     // inside a Krylov solve both masks are the solve's (cached environment mask, structural centre mask): one sort
     // serves every matvec of the solve
-    const bool keep = sc && sc->occ_cache && mask_a_stable && mask_b_stable;
+    const bool keep = sc && sc->occ_cache && ma.stable && mb.stable;
     int* pp = nullptr;
-    if (keep)
-      for (const auto& e : ctx->perm_cache)
-        if (e.amask == g.amask && e.bmask == g.bmask && e.tiles_m == g.tiles_m && e.tiles_n == g.tiles_n && e.nkt == nkt_all)
-          pp = static_cast<int*>(e.perm);
-    if (!pp) {
-      if (keep) {
-        void* pm = nullptr;
-        MPSE_TRY(mpse_malloc(ctx, size_t(ntile_all) * sizeof(int), &pm));
-        ctx->perm_cache.push_back({g.amask, g.bmask, g.tiles_m, g.tiles_n, nkt_all, pm});
-        pp = static_cast<int*>(pm);
-      } else {
-        MPSE_TRY(PERM.alloc(size_t(ntile_all) * sizeof(int)));
-        pp = PERM.as<int>();
-      }
-      hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, ctx->stream, g.amask, g.bmask, g.nkw, nkt_all, g.tiles_m,
-                         g.tiles_n, 1, pp, skip, GemmGroups(), (unsigned char*)nullptr, 0);
-    }
+    bool sort = false;
+    MPSE_TRY(perm_source(ctx, keep, {g.amask, g.bmask, g.tiles_m, g.tiles_n, p.nkt, nullptr},
+                         size_t(g.tiles_m) * g.tiles_n * sizeof(int), PERM, &pp, &sort));
+    if (sort)
+      hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, ctx->stream, g.amask, g.bmask, g.nkw, p.nkt, g.tiles_m,
+                         g.tiles_n, 1, pp, g.skip, GemmGroups(), (unsigned char*)nullptr, 0);
     g.perm = pp;
   }
-  // the fast kernel addresses its operands as uniform base + 32-bit lane offset: non-negative strides, spans < 4 GB
-  auto span_ok = [](const IdxMap& m, const IdxMap& k, bool cplx) {
-    if (m.s_hi < 0 || m.s_lo < 0 || k.s_hi < 0 || k.s_lo < 0) return false;
-    auto span = [](const IdxMap& x) {
-      if (x.ext <= 1) return 0.0;
-      if (x.lo == 0x7fffffff) return double(x.ext - 1) * double(x.s_lo);
-      return double((x.ext - 1) / x.lo) * double(x.s_hi) + double(x.lo - 1) * double(x.s_lo);
-    };
-    return (span(m) + span(k) + 1.0) * (cplx ? 16.0 : 8.0) < 4.0e9;
-  };
-  const bool ks = is_single(g.kA) && is_single(g.kB) && span_ok(g.mA, g.kA, ca) && span_ok(g.nB, g.kB, cb);
-  if (!g.perm && g.ksplit == 1 && d->batch == 1 && (long long)g.tiles_m * g.tiles_n >= 64) {
-    const double size_a = double(g.M) * (ca ? 2 : 1), size_b = double(g.N) * (cb ? 2 : 1);   // per unit of K
-    if (size_a >= size_b && g.tiles_m % 8 == 0)
-      g.die_group = 1;
-    else if (g.tiles_n % 8 == 0)
-      g.die_group = 2;
-    else if (g.tiles_m % 8 == 0)
-      g.die_group = 1;
-  }
-#define MPSE_LAUNCH(CA_, CB_)                                                                         \
-  do {                                                                                                \
-    if (ks && wide)                                                                                   \
-      hipLaunchKernelGGL((k_gemm<CA_, CB_, true, 2, 1>), grid, dim3(512), 0, ctx->stream, g);         \
-    else if (ks)                                                                                      \
-      hipLaunchKernelGGL((k_gemm<CA_, CB_, true, 2>), grid, block, 0, ctx->stream, g);                \
-    else                                                                                              \
-      hipLaunchKernelGGL((k_gemm<CA_, CB_, false, 2>), grid, block, 0, ctx->stream, g);               \
-  } while (0)
-  // one workgroup per compute unit (or fewer): eight waves on the tile instead of four
-  const bool wide = nblk <= n_cu && nkt_all >= 2;
-  {
-    long long* gp = ctx->gemm_paths;
-    const bool masked = ks && (g.amask || g.bmask);   // (the general kernel visits every K tile)
-    ++gp[mpse_ctx::GP_LAUNCH];
-    gp[mpse_ctx::GP_GENERAL] += !ks;
-    gp[mpse_ctx::GP_WIDE] += ks && wide;
-    gp[mpse_ctx::GP_SPLIT_B1] += g.ksplit > 1 && d->batch == 1;
-    gp[mpse_ctx::GP_SPLIT_BN] += g.ksplit > 1 && d->batch > 1;
-    gp[mpse_ctx::GP_DIE1] += g.die_group == 1;
-    gp[mpse_ctx::GP_DIE2] += g.die_group == 2;
-    gp[mpse_ctx::GP_SKEW] += g.skew && !g.perm && !g.die_group;
-    gp[mpse_ctx::GP_ORDER] += g.perm != nullptr;
-    gp[mpse_ctx::GP_MASK] += masked;
-    gp[mpse_ctx::GP_MASK_GLOBAL] += masked && g.nkw > 64;
-  }
-  if (ca && cb)
-    MPSE_LAUNCH(true, true);
-  else if (ca)
-    MPSE_LAUNCH(true, false);
-  else if (cb)
-    MPSE_LAUNCH(false, true);
-  else
-    MPSE_LAUNCH(false, false);
-#undef MPSE_LAUNCH
-  if (g.ksplit > 1 && !leave_slices) {
-    const dim3 rgrid((unsigned)rgx, (unsigned)rgy);
-    if (ca || cb)
-      hipLaunchKernelGGL((k_splitk_reduce<true>), rgrid, dim3(256), 0, ctx->stream, g, (int)d->batch);
-    else
-      hipLaunchKernelGGL((k_splitk_reduce<false>), rgrid, dim3(256), 0, ctx->stream, g, (int)d->batch);
-  }
+
+  // ---- launch
+  count_paths(ctx->gemm_paths, p, d->batch > 1);
+  const bool reduce = g.ksplit > 1 && !p.leave_slices;
+  launch_gemm(ctx, g, p.nwg, ca, cb, p.fast, p.wide, false, reduce ? dim3((unsigned)p.rgx, (unsigned)p.rgy) : dim3(0),
+              (int)d->batch);
   if (prof_this) prof_end(ctx, rec);
   MPSE_HIP(ctx, hipGetLastError());
   return MPSE_OK;
@@ -1563,77 +1534,42 @@ int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype
   IdxMap rm, km;
   if (!to_map(r, &rm) || !to_map(k, &km) || !is_single(km))
     return mpse_fail(ctx, MPSE_ERR_SHAPE, "occupancy scan: K index must be single level");
-  const int K = km.ext, nrows = rm.ext, nkt = (K + BK - 1) / BK, nkw = (nkt + 7) / 8, tiles = (nrows + BM - 1) / BM;
-  const bool cplx = dtype == MPSE_C128;
-  auto fastest = [](const IdxMap& m) { return m.ext <= 1 ? (long long)1 << 60 : (m.s_lo < 0 ? -m.s_lo : m.s_lo); };
-  const int kfast = fastest(km) <= fastest(rm);
-  mpse_ctx::OccKey key;
-  memset(&key, 0, sizeof(key));
-  key.ptr = ptr;
-  key.r_ext = rm.ext, key.r_lo = rm.lo, key.r_shi = rm.s_hi, key.r_slo = rm.s_lo;
-  key.k_ext = km.ext, key.k_lo = km.lo, key.k_shi = km.s_hi, key.k_slo = km.s_lo;
-  key.sb = 0, key.nrows = nrows, key.tiles = tiles, key.nkw = nkw, key.batch = 1, key.K = K, key.cplx = cplx ? 1 : 0;
-  const bool cacheable = sc && sc->in_env(ptr);
-  *pitch = nkw * 8;
-  *stable = cacheable;
-  if (cacheable)
-    for (const auto& e : ctx->occ_cache)
-      if (memcmp(&e.key, &key, sizeof(key)) == 0) {
-        *flags = static_cast<const unsigned char*>(e.mask);
-        return MPSE_OK;
-      }
-  void* pm = nullptr;
-  const size_t bytes = size_t(tiles) * nkw * 8;
-  if (cacheable) {
-    MPSE_TRY(mpse_malloc(ctx, bytes, &pm));
-    ctx->occ_cache.push_back({key, pm});
-  } else {
-    MPSE_TRY(tmp.alloc(bytes));
-    pm = tmp.p;
+  const mpse_ctx::OccKey key = occ_key(ptr, rm, km, 0, 1, dtype == MPSE_C128);
+  const bool keep = sc && sc->in_env(ptr);
+  OccMask m;
+  if (!keep) MPSE_TRY(tmp.alloc(occ_bytes(key)));
+  MPSE_TRY(occ_mask_source(ctx, keep, key, nullptr, tmp.p, &m));
+  if (m.scan) {
+    const OccOperand oa = occ_operand(key, rm, km, fastest(km) <= fastest(rm), m);
+    OccOperand ob = oa;
+    ob.tiles = 0;
+    hipLaunchKernelGGL(k_tile_occ, dim3(((key.K + BK - 1) / BK + 3) / 4, key.tiles, 2), dim3(256), 0, ctx->stream, oa, ob,
+                       key.K, key.nkw, 1, sc ? sc->skip : nullptr);
+    MPSE_HIP(ctx, hipGetLastError());
   }
-  OccOperand oa{static_cast<const double*>(ptr), rm, km, nrows, tiles, cplx ? 1 : 0, kfast, 0, static_cast<unsigned char*>(pm)};
-  OccOperand ob = oa;
-  ob.tiles = 0;
-  hipLaunchKernelGGL(k_tile_occ, dim3((nkt + 3) / 4, tiles, 2), dim3(256), 0, ctx->stream, oa, ob, K, nkw, 1,
-                     sc ? sc->skip : nullptr);
-  MPSE_HIP(ctx, hipGetLastError());
-  *flags = static_cast<const unsigned char*>(pm);
+  *flags = static_cast<const unsigned char*>(m.mask);
+  *pitch = key.nkw * 8;
+  *stable = m.stable;
   return MPSE_OK;
 }
 
 // Grouped launch of the contraction kernel (mpse_internal.h GroupedDesc; folded one-site matvec of mpse_plans.h).
 // dot: the caller's dot request when this launch completes a matvec result (one group only), else null.
 int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, MatvecReq::Dot* dot) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
+  // ---- check
+  GemmArgs g = {};
   if (d.ngrp < 1 || d.ngrp > GMAX_GRP) return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: 1 .. %d groups", GMAX_GRP);
-  if (!to_map(d.ma, &g.mA) || !to_map(d.ka, &g.kA) || !to_map(d.kb, &g.kB) || !to_map(d.nb, &g.nB) ||
-      !to_map(d.mc, &g.mC) || !to_map(d.nc, &g.nC))
+  if (!fill_maps(g, d.ma, d.ka, d.kb, d.nb, d.mc, d.nc))
     return mpse_fail(ctx, MPSE_ERR_SHAPE, "grouped product: extent out of range");
-  g.M = g.mA.ext, g.N = g.nB.ext, g.K = g.kA.ext;
   if (g.M != g.mC.ext || g.N != g.nC.ext || g.K != g.kB.ext) return mpse_fail(ctx, MPSE_ERR_SHAPE, "grouped product: extents disagree");
   if (g.M == 0 || g.N == 0) return MPSE_OK;
   const bool ca = d.dta == MPSE_C128, cb = d.dtb == MPSE_C128;
-  auto span_ok = [](const IdxMap& m, const IdxMap& k, bool cplx) {
-    if (m.s_hi < 0 || m.s_lo < 0 || k.s_hi < 0 || k.s_lo < 0) return false;
-    auto span = [](const IdxMap& x) {
-      if (x.ext <= 1) return 0.0;
-      if (x.lo == 0x7fffffff) return double(x.ext - 1) * double(x.s_lo);
-      return double((x.ext - 1) / x.lo) * double(x.s_hi) + double(x.lo - 1) * double(x.s_lo);
-    };
-    return (span(m) + span(k) + 1.0) * (cplx ? 16.0 : 8.0) < 4.0e9;
-  };
-  if (!is_single(g.kA) || !is_single(g.kB) || !span_ok(g.mA, g.kA, ca) || !span_ok(g.nB, g.kB, cb) || g.K % BK != 0 ||
-      g.K < BK || (d.ngrp > 1 && g.M % BM != 0) || !cb)
+  if (!is_single(g.kA) || !is_single(g.kB) || !fast_ok(g, ca, cb) || g.K % BK != 0 || g.K < BK ||
+      (d.ngrp > 1 && g.M % BM != 0) || !cb)
     return mpse_fail(ctx, MPSE_ERR_SHAPE, "grouped product: needs single-level K indices, K a multiple of %d, group "
                      "heights a multiple of %d and a complex second operand", BK, BM);
-  g.mtiles_m = (g.M + BM - 1) / BM;
-  g.mtiles_n = (g.N + BN - 1) / BN;
-  g.tiles_m = g.mtiles_m * d.ngrp;
-  g.tiles_n = g.mtiles_n;
-  auto fast = [](const IdxMap& m) { return m.ext <= 1 ? (long long)1 << 60 : (m.s_lo < 0 ? -m.s_lo : m.s_lo); };
-  g.a_kfast = fast(g.kA) <= fast(g.mA);
-  g.b_kfast = fast(g.kB) <= fast(g.nB);
+  if (d.split2 && (d.ngrp != 1 || !d.c2 || g.M % BM != 0))
+    return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: halved tiles need one group, whole tile rows and a second result");
   g.alpha_re = 1.0, g.beta_re = 1.0;
   g.ksplit = 1;
   g.skip = sc ? sc->skip : nullptr;
@@ -1644,10 +1580,9 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, Matv
   gg.am_pitch = d.am_pitch, gg.bm_pitch = d.bm_pitch;
   gg.split2 = d.split2 ? 1 : 0;
   gg.C2 = static_cast<double*>(d.c2);
-  gg.cpd = (ctx->n_cu > 0 ? ctx->n_cu : 256) / 8;
-  if (d.split2 && (d.ngrp != 1 || !d.c2 || g.M % BM != 0))
-    return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: halved tiles need one group, whole tile rows and a second result");
+  gg.cpd = n_cu_of(ctx) / 8;
   int max_seg = 0;
+  double segs = 0;
   bool any_mask = false, any_beta = false;
   for (int i = 0; i < d.ngrp; ++i) {
     const GroupedGrp& s = d.grp[i];
@@ -1663,85 +1598,55 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, Matv
       any_mask = any_mask || s.seg[q].am || s.seg[q].bm;
     }
     max_seg = s.nseg > max_seg ? s.nseg : max_seg;
+    segs += s.nseg;
   }
   g.A = gg.g[0].seg[0].A, g.B = gg.g[0].seg[0].B, g.C = gg.g[0].C;
   g.use_beta = any_beta;
+
+  // ---- plan
   const int nkt_max = max_seg * gg.nkt_seg;
-  g.nkw = (any_mask && (nkt_max + 7) / 8 <= 64) ? (nkt_max + 7) / 8 : 0;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-  const long long ntile = (long long)g.tiles_m * g.tiles_n;
+  const mpse_plan::GroupedPlan p = mpse_plan::grouped_plan(g.M, g.N, d.ngrp, nkt_max, any_mask, d.split2, ca, n_cu_of(ctx));
+  const long long ntile = (long long)p.tiles_m * p.tiles_n;
   if (ntile > 0x7fffffffLL) return mpse_fail(ctx, MPSE_ERR_SHAPE, "grouped product: grid too large");
-  const long long nwg = ntile * (d.split2 ? 2 : 1);
-  if (dot && d.ngrp == 1 && nwg >= 1 && nwg <= dot->cap) {
+  g.tiles_m = p.tiles_m;
+  g.nkw = p.nkw;
+  g.die_group = p.die_group;
+  if (dot && d.ngrp == 1 && p.nwg >= 1 && p.nwg <= dot->cap) {
     g.dot_y = static_cast<const double*>(dot->y);
     g.dot_part = dot->part;
-    dot->nb_out = (int)nwg;
+    dot->nb_out = (int)p.nwg;
   }
   mpse_ctx::ProfRec rec;
   const int variant = (ca ? 1 : 0) + (cb ? 2 : 0);
-  double segs = 0;
-  for (int i = 0; i < d.ngrp; ++i) segs += d.grp[i].nseg;
   const double mnk = double(g.M) * double(g.N) * double(g.K) * segs;
   const bool prof_this = prof_begin(ctx, variant, mnk * ((ca && cb) ? 8.0 : 4.0),
                                     segs * (double(g.M) * g.K * (ca ? 16 : 8) + double(g.K) * g.N * 16.0) +
                                         double(d.ngrp) * double(g.M) * g.N * 16.0 * (any_beta ? 2 : 1),
                                     &rec);
   g.kt_counter = prof_this && ctx->prof_ktiles ? ctx->prof_ktiles + variant : nullptr;
+
+  // ---- order (the masks are the segments' own)
   TmpBuf PERM(ctx);
-  // launch order by weight: products with more tiles than slots (heaviest first, die aware), and halved products (their
-  // position -> (tile, half) map pairs heavy and light halves per compute unit through it; plain sorted order)
-  if (g.nkw > 0 && (ntile > 2 * n_cu || d.split2) && ntile <= 2048) {
-    int* pp = nullptr;
-    const void *ka = gg.g[0].seg[0].am, *kb = gg.g[0].seg[0].bm;
-    const int nkt_key = nkt_max + 1000 * d.ngrp;       // (grouped entries never collide with plain ones)
-    const bool keep = sc && sc->occ_cache && d.masks_stable;
-    if (keep)
-      for (const auto& e : ctx->perm_cache)
-        if (e.amask == ka && e.bmask == kb && e.tiles_m == g.tiles_m && e.tiles_n == g.tiles_n && e.nkt == nkt_key)
-          pp = static_cast<int*>(e.perm);
-    // (one buffer: the launch order, then the assembled flags of every tile - 8-byte aligned)
+  if (p.order) {
+    // (one buffer: the launch order, then the assembled flags of every tile - 8-byte aligned; grouped entries of the
+    // cache never collide with plain ones)
     const size_t perm_bytes = (size_t(ntile) * sizeof(int) + 7) & ~size_t(7), flag_pitch = size_t(g.nkw) * 8;
-    if (!pp) {
-      if (keep) {
-        void* pm = nullptr;
-        MPSE_TRY(mpse_malloc(ctx, perm_bytes + size_t(ntile) * flag_pitch, &pm));
-        ctx->perm_cache.push_back({ka, kb, g.tiles_m, g.tiles_n, nkt_key, pm});
-        pp = static_cast<int*>(pm);
-      } else {
-        MPSE_TRY(PERM.alloc(perm_bytes + size_t(ntile) * flag_pitch));
-        pp = PERM.as<int>();
-      }
+    int* pp = nullptr;
+    bool sort = false;
+    MPSE_TRY(perm_source(ctx, sc && sc->occ_cache && d.masks_stable,
+                         {gg.g[0].seg[0].am, gg.g[0].seg[0].bm, g.tiles_m, g.tiles_n, nkt_max + 1000 * d.ngrp, nullptr},
+                         perm_bytes + size_t(ntile) * flag_pitch, PERM, &pp, &sort));
+    if (sort)
       hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long*)nullptr,
                          (const unsigned long long*)nullptr, 0, nkt_max, g.tiles_m, g.tiles_n, d.split2 ? 0 : 1, pp,
                          g.skip, gg, reinterpret_cast<unsigned char*>(pp) + perm_bytes, (int)flag_pitch);
-    }
     g.perm = pp;
     g.gg.flags = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(pp) + perm_bytes);
   }
-  if (!g.perm && ntile >= 64) {
-    const double size_a = double(g.M) * d.ngrp * (ca ? 2 : 1), size_b = double(g.N) * 2;
-    if (size_a >= size_b && g.tiles_m % 8 == 0)
-      g.die_group = 1;
-    else if (g.tiles_n % 8 == 0)
-      g.die_group = 2;
-    else if (g.tiles_m % 8 == 0)
-      g.die_group = 1;
-  }
-  const dim3 grid((unsigned)nwg);
-  const bool wide = nwg <= n_cu;
-  ++ctx->gemm_paths[mpse_ctx::GP_GROUPED];
-  ctx->gemm_paths[mpse_ctx::GP_GROUPED_SPLIT2] += gg.split2 != 0;
-  if (ca) {
-    if (wide)
-      hipLaunchKernelGGL((k_gemm<true, true, true, 2, 1, true>), grid, dim3(512), 0, ctx->stream, g);
-    else
-      hipLaunchKernelGGL((k_gemm<true, true, true, 2, 2, true>), grid, dim3(256), 0, ctx->stream, g);
-  } else {
-    if (wide)
-      hipLaunchKernelGGL((k_gemm<false, true, true, 2, 1, true>), grid, dim3(512), 0, ctx->stream, g);
-    else
-      hipLaunchKernelGGL((k_gemm<false, true, true, 2, 2, true>), grid, dim3(256), 0, ctx->stream, g);
-  }
+
+  // ---- launch
+  count_paths(ctx->gemm_paths, d);
+  launch_gemm(ctx, g, p.nwg, ca, cb, true, p.wide, true);
   if (prof_this) prof_end(ctx, rec);
   MPSE_HIP(ctx, hipGetLastError());
   return MPSE_OK;

@@ -1082,4 +1082,119 @@ inline Plan plan_env_ft(int dtype, int domain, const mpse_heff_ft& h, int env_dt
   return p;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Launch plans of the contraction kernel (mpse_gemm.hip): everything its launchers decide from sizes and flags alone -
+// pure integer arithmetic, so the policy is checked on a CPU (tests/test_gemm_plan_host.py).  64 x 64 output tiles,
+// K tiles of 16.
+
+// Unsplit products without a sorted order, from 64 tiles on: a die owns whole tile rows (1) or tile columns (2) of
+// the larger operand (size_a, size_b: doubles per unit of K), where their number divides among the eight dies; 0: off
+inline int die_group_rule(long long ntile, int tiles_m, int tiles_n, double size_a, double size_b) {
+  if (ntile < 64) return 0;
+  if (size_a >= size_b && tiles_m % 8 == 0) return 1;
+  if (tiles_n % 8 == 0) return 2;
+  return tiles_m % 8 == 0 ? 1 : 0;
+}
+// A launch order by weight (k_tile_order) pays for block-sparse products with more workgroups than two per compute
+// unit (`always`: halved tiles are paired through it whatever their number); the sort holds 2048 tiles.
+inline bool order_pays(long long ntile, long long nwg, int n_cu, bool always = false) {
+  return (always || nwg > 2LL * n_cu) && ntile <= 2048;
+}
+
+struct GemmShape {         // a plain product as launch_plan sees it; M, N, batch > 0
+  long long M, N, K, batch;
+  int n_cu;
+  bool ca, cb;             // complex operands
+  int skip_hint;           // bit 0 / bit 1: skip the structurally zero tiles of A / B
+  bool k_single;           // both K maps are single level
+  bool fast_ok;            // non-negative strides and operand spans below 4 GB (what the fast kernel addresses)
+  bool dot;                // the caller wants sum conj(C) . y as partials, with room for dot_cap of them
+  long long dot_cap;
+  bool slices;             // the caller offers to add the K slices itself (compact result, alpha = 1), slices_cap bytes
+  unsigned long long slices_cap;
+  bool use_beta;
+};
+struct GemmPlan {
+  int tiles_m, tiles_n, nkt;
+  int ksplit, kt_per_split;    // K slices (1 = none), K tiles per slice
+  unsigned long long ws_bytes; // partial sums of a split product
+  bool leave_slices;           // ... stay in the caller's buffer: no reduction launch
+  long long nwg;               // workgroups
+  bool fast, wide;             // single-level kernel; its eight-wave form
+  bool masks;                  // occupancy masks are used, nkw 64-bit words of 8 flags per tile row
+  int nkw;
+  bool order;                  // launch order by weight
+  int die_group;
+  long long rgx, rgy;          // reduction grid of a split product
+  long long dot_producers;     // workgroups that store a dot partial; 0: the request is not taken
+};
+inline GemmPlan launch_plan(const GemmShape& s) {
+  GemmPlan p{};
+  p.tiles_m = int((s.M + 63) / 64), p.tiles_n = int((s.N + 63) / 64), p.nkt = int((s.K + 15) / 16);
+  const long long ntile = (long long)p.tiles_m * p.tiles_n, base = ntile * s.batch;
+  p.ksplit = 1;
+  p.kt_per_split = p.nkt > 0 ? p.nkt : 1;
+  // split-K when the output tiles alone cannot fill the compute units (skinny results with long K)
+  if (base < s.n_cu && p.nkt >= 4) {
+    // fewer output tiles than CUs: slice K until ~1 workgroup per CU exists (policy sweeps of the headline run,
+    // DESIGN.md 4.1.  2 per CU: equal to 1.7 % slower depending on the box - the reduction pass reads twice the
+    // slices; 3 per CU: -3 %; 0.5 per CU: -7 %).  (One tile per CU runs as fast unsplit as split in two + reduction
+    // pass since the K loop prefetches fragments: measured, 4096x256 C-step.)
+    const long long want = (s.n_cu + base - 1) / base, maxs = p.nkt / 2;   // at least two K tiles per slice
+    const int S = int(want < maxs ? want : maxs);
+    if (S > 1) {
+      p.kt_per_split = (p.nkt + S - 1) / S;
+      p.ksplit = (p.nkt + p.kt_per_split - 1) / p.kt_per_split;
+      p.ws_bytes = (unsigned long long)s.batch * p.ksplit * s.M * s.N * ((s.ca || s.cb) ? 16 : 8);
+      // (Leaving the slices to the consumer of a matvec result - the Lanczos update adding them while it reads -
+      // instead of the reduction launch measured 1.4 % slower on the headline run: every slice's workgroups then load
+      // the dot partner, and the update kernel streams 16 slices with a fraction of the reduction kernel's blocks.)
+      p.leave_slices = s.slices && !s.dot && s.batch == 1 && !s.use_beta && p.ws_bytes <= s.slices_cap;
+    }
+  }
+  p.nwg = base * p.ksplit;
+  p.rgx = (s.N + 255) / 256 > 64 ? 64 : (s.N + 255) / 256;
+  p.rgy = s.M * s.batch > 32768 ? 32768 : s.M * s.batch;
+  if (s.dot && s.batch == 1) {
+    // the kernel that stores the final values forms the partials: the product's workgroups, or the reduction's
+    long long producers = base;
+    if (p.ksplit > 1) {
+      const long long cap_y = s.dot_cap / p.rgx;
+      if (cap_y >= 1 && p.rgy > cap_y) p.rgy = cap_y;
+      producers = p.rgx * p.rgy;
+    }
+    if (producers >= 1 && producers <= s.dot_cap) p.dot_producers = producers;
+  }
+  p.masks = (s.skip_hint & 3) && s.k_single && p.nkt >= 2 && s.batch <= 16384;
+  p.nkw = p.masks ? (p.nkt + 7) / 8 : 0;
+  p.order = s.batch == 1 && p.masks && order_pays(ntile, ntile * p.ksplit, s.n_cu);
+  if (!p.order && p.ksplit == 1 && s.batch == 1)
+    p.die_group = die_group_rule(ntile, p.tiles_m, p.tiles_n, double(s.M) * (s.ca ? 2 : 1), double(s.N) * (s.cb ? 2 : 1));
+  p.fast = s.k_single && s.fast_ok;
+  // one workgroup per compute unit (or fewer): eight waves on the tile instead of four
+  p.wide = p.fast && p.nwg <= s.n_cu && p.nkt >= 2;
+  return p;
+}
+
+// Grouped launch: ngrp groups of M rows each, complex second operand, nkt_max = K tiles of the longest group.
+struct GroupedPlan {
+  int tiles_m, tiles_n, nkw, die_group;
+  bool order, wide;
+  long long nwg;
+};
+inline GroupedPlan grouped_plan(long long M, long long N, int ngrp, int nkt_max, bool any_mask, bool split2, bool ca,
+                                int n_cu) {
+  GroupedPlan p{};
+  p.tiles_m = int((M + 63) / 64) * ngrp, p.tiles_n = int((N + 63) / 64);
+  const long long ntile = (long long)p.tiles_m * p.tiles_n;
+  p.nwg = ntile * (split2 ? 2 : 1);
+  p.nkw = (any_mask && (nkt_max + 7) / 8 <= 64) ? (nkt_max + 7) / 8 : 0;   // (a tile's flag words must fit its LDS copy)
+  // products with more tiles than slots (heaviest first, die aware), and halved products (their position -> (tile,
+  // half) map pairs heavy and light halves per compute unit through the order; plain sorted order)
+  p.order = p.nkw > 0 && order_pays(ntile, ntile, n_cu, split2);
+  if (!p.order) p.die_group = die_group_rule(ntile, p.tiles_m, p.tiles_n, double(M) * ngrp * (ca ? 2 : 1), double(N) * 2);
+  p.wide = p.nwg <= n_cu;
+  return p;
+}
+
 }  // namespace mpse_plan

@@ -216,3 +216,21 @@ extern "C" void emu_set_fold_min(long long macs, long long align, long long spli
   fold_split2_min_kt() = split2_min_kt;
 }
 extern "C" void emu_set_beta_source(int on) { beta_source_flag() = on != 0; }
+
+// The launch plans of the contraction kernel as flat integer records (tests/test_gemm_plan_host.py).
+// in: M, N, K, batch, n_cu, ca, cb, skip_hint, k_single, fast_ok, dot, dot_cap, slices, slices_cap, use_beta
+// out: tiles_m, tiles_n, nkt, ksplit, kt_per_split, ws_bytes, leave_slices, nwg, fast, wide, masks, nkw, order, die_group,
+//      rgx, rgy, dot_producers
+extern "C" void emu_gemm_launch_plan(const long long* in, long long* out) {
+  const GemmPlan p = launch_plan({in[0], in[1], in[2], in[3], (int)in[4], in[5] != 0, in[6] != 0, (int)in[7], in[8] != 0,
+                                  in[9] != 0, in[10] != 0, in[11], in[12] != 0, (unsigned long long)in[13], in[14] != 0});
+  const long long r[17] = {p.tiles_m, p.tiles_n, p.nkt, p.ksplit, p.kt_per_split, (long long)p.ws_bytes, p.leave_slices,
+                           p.nwg, p.fast, p.wide, p.masks, p.nkw, p.order, p.die_group, p.rgx, p.rgy, p.dot_producers};
+  memcpy(out, r, sizeof(r));
+}
+// in: M, N, ngrp, nkt_max, any_mask, split2, ca, n_cu;  out: tiles_m, tiles_n, nkw, die_group, order, wide, nwg
+extern "C" void emu_gemm_grouped_plan(const long long* in, long long* out) {
+  const GroupedPlan p = grouped_plan(in[0], in[1], (int)in[2], (int)in[3], in[4] != 0, in[5] != 0, in[6] != 0, (int)in[7]);
+  const long long r[7] = {p.tiles_m, p.tiles_n, p.nkw, p.die_group, p.order, p.wide, p.nwg};
+  memcpy(out, r, sizeof(r));
+}

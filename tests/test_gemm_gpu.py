@@ -14,12 +14,13 @@ Operands live in flat buffers whose unused elements are NaN (a misaddressed read
 elements of C hold a sentinel that must survive the call.
 """
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 from renormalizer_amd import engine as E
+
+from gemm_policy import CASES, _shape_preconditions, expected_paths   # (tests/gemm_policy.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -100,17 +101,6 @@ def _delta(before, after):
     return {k: after[k] - before[k] for k in after if after[k] != before[k]}
 
 
-def _ksplit(base, nkt, n_cu):
-    """K slices of a product with `base` output tiles (the split rule of gemm_impl), 1 = unsplit"""
-    if base >= n_cu or nkt < 4:
-        return 1
-    s = min(-(-n_cu // base), nkt // 2)
-    if s <= 1:
-        return 1
-    per = -(-nkt // s)
-    return -(-nkt // per)
-
-
 # ------------------------------------------------------------------------------------------------ operand layouts
 def layout(kind, M, N, K, batch):
     """index maps (m_a, k_a, k_b, n_b, m_c, n_c) and batch strides of the named storage"""
@@ -129,90 +119,6 @@ def layout(kind, M, N, K, batch):
     if kind == "reversed":    # A and B read backwards from their last element
         return (one(M, -K), one(K, -1), one(K, -N), one(N, -1), one(M, N), one(N, 1)), (-M * K, -K * N, M * N)
     raise ValueError(kind)
-
-
-# ------------------------------------------------------------------------------------------------ the table
-def _four_wave_dims(n_cu):
-    tn = n_cu // 18 + 1
-    tn += tn % 8 == 0
-    return 64 * 18 - 52, 64 * tn - 60, 24, 1          # 18 x tn tiles > n_cu, neither side a multiple of 8
-
-
-def _tile_order_dims(n_cu):
-    t = max(25, math.isqrt(2 * n_cu) + 1)
-    t += t % 8 == 0
-    assert t * t <= 2048
-    return 64 * t, 64 * t, 64, 1                      # t * t tiles: above 2 n_cu, at most 2048
-
-
-# name: (dims(n_cu) -> (M, N, K, batch), layout, block sparse, skip hints, alpha, beta)
-CASES = {
-    "eight_wave": (lambda n: (300, 200, 40, 1), "rowmajor", False, (0,), 1, 0),
-    "four_wave": (_four_wave_dims, "rowmajor", False, (0,), 2, -1),
-    "split_b1": (lambda n: (100, 90, 3000, 1), "rowmajor", False, (0,), 2 - 1j, 3 + 2j),
-    "split_batched": (lambda n: (70, 130, 2000, 3), "gaps", False, (0,), -1 + 1j, 0.5),
-    "die_group1": (lambda n: (2048, 300, 32, 1), "rowmajor", True, (0, 1, 2, 3), 1, 1),
-    "die_group1_ragged": (lambda n: (2000, 300, 32, 1), "rowmajor", True, (0, 1, 2, 3), 0.25, -2),
-    "die_group2": (lambda n: (300, 2000, 32, 1), "rowmajor", True, (0, 1, 2, 3), 1j, 1),
-    "die_group1_fallback": (lambda n: (512, 1100, 8, 1), "rowmajor", False, (0,), 1, 2),
-    "tile_order": (_tile_order_dims, "rowmajor", True, (0, 1, 2, 3), 2 + 1j, -1j),
-    "masks_global": (lambda n: (100, 90, 9000, 1), "rowmajor", True, (0, 3), 1, -1),
-    "masks_transposed": (lambda n: (300, 200, 520, 1), "trans", True, (0, 1, 2, 3), -2, 1 + 1j),
-    "general_twolevel": (lambda n: (300, 301, 299, 1), "twolevel", False, (0,), 1 - 1j, 2),
-    "general_reversed": (lambda n: (200, 150, 100, 1), "reversed", False, (0,), 3, 0.5j),
-    "general_reversed_unsplit": (_four_wave_dims, "reversed", False, (0,), 1, 1),
-    "general_span": (lambda n: (70, 50, 3, 1), "span", False, (0,), 1 + 2j, -1),
-}
-
-
-def expected_paths(name, n_cu, M, N, K, batch, hint):
-    """the counter deltas of one launch of case `name`"""
-    tiles = -(-M // 64) * -(-N // 64)
-    nkt = -(-K // 16)
-    ks = _ksplit(tiles * batch, nkt, n_cu)
-    wide = tiles * batch * ks <= n_cu and nkt >= 2
-    masks = hint != 0
-    e = {"launches": 1}
-    if name == "eight_wave":
-        e.update(eight_wave=1, skew=1)
-    elif name == "four_wave":
-        e.update(skew=1)
-    elif name == "split_b1":
-        e.update(split_b1=1, skew=1, eight_wave=int(wide))
-    elif name == "split_batched":
-        e.update(split_batched=1, skew=1, eight_wave=int(wide))
-    elif name in ("die_group1", "die_group1_ragged", "die_group2"):
-        e.update({"die_group2" if name == "die_group2" else "die_group1": 1, "eight_wave": int(wide),
-                  "masks": int(masks)})
-    elif name == "die_group1_fallback":
-        e.update(die_group1=1)
-    elif name == "tile_order":
-        e.update(tile_order=1, masks=1) if masks else e.update(skew=1)
-    elif name in ("masks_global", "masks_transposed"):
-        e.update(split_b1=1, skew=1, eight_wave=int(wide), masks=int(masks))
-        if name == "masks_global":
-            e.update(masks_global=int(masks))
-    elif name in ("general_twolevel", "general_reversed"):
-        e.update(general=1, split_b1=1, skew=1)
-    elif name in ("general_reversed_unsplit", "general_span"):
-        e.update(general=1, skew=1)
-    return {k: v for k, v in e.items() if v}
-
-
-def _shape_preconditions(name, n_cu, M, N, K, batch):
-    """the shape reaches its row of the table for this n_cu (a failure here means the table needs new sizes)"""
-    tm, tn, nkt = -(-M // 64), -(-N // 64), -(-K // 16)
-    ks = _ksplit(tm * tn * batch, nkt, n_cu)
-    if name.startswith("split") or name.startswith("masks") or name in ("general_twolevel", "general_reversed"):
-        assert ks > 1
-    if name == "split_batched":
-        assert batch > 1
-    if name.startswith("die_group") or name in ("four_wave", "tile_order", "general_reversed_unsplit"):
-        assert ks == 1 and tm * tn >= 64
-    if name == "four_wave":
-        assert tm * tn > n_cu and tm % 8 and tn % 8
-    if name == "masks_global":
-        assert -(-nkt // 8) > 64
 
 
 # ------------------------------------------------------------------------------------------------ data
