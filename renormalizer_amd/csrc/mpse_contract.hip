@@ -358,6 +358,7 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
         hipLaunchKernelGGL((k_wmix<true>), grid, dim3(256), lds, ctx->stream, g);
       else
         hipLaunchKernelGGL((k_wmix<false>), grid, dim3(256), lds, ctx->stream, g);
+      ++ctx->gemm_paths[mpse_ctx::GP_WMIX];
       MPSE_HIP(ctx, hipGetLastError());
       continue;
     }
@@ -402,6 +403,18 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
         o.C = (char*)const_cast<void*>(bufs[g.cbuf]) + size_t(g.c_off) * es;
         o.nseg = g.nseg;
         o.beta = g.beta;
+        if (g.nmix > 0) {       // the beta term formed in the epilogue from the blocks of the MPO site
+          if (gd.nmix > 0 || !bufs[g.wbuf]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: bad epilogue mix");
+          gd.nmix = g.nmix, gd.mix_grp = i;
+          gd.mix_w = bufs[g.wbuf];
+          gd.mix_d = (int)g.mix_d, gd.mix_wr = (int)g.mix_wr, gd.mix_ld = g.mix_ld;
+          for (int t = 0; t < g.nmix; ++t) {
+            const EpiTerm& m = g.mix[t];
+            if (!bufs[m.src]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
+            gd.mix[t].src = (const char*)bufs[m.src] + size_t(m.src_off) * es;
+            gd.mix[t].b = m.b, gd.mix[t].f = m.f, gd.mix[t].delta = m.delta;
+          }
+        }
         for (int q = 0; q < g.nseg; ++q) {
           const GSegPlan& sg = g.seg[q];
           if (!bufs[sg.abuf] || !bufs[sg.bbuf]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
@@ -495,7 +508,7 @@ int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void
   // tells it whether the second part holds anything
   MatvecReq::Parts* pr = mv && mv->parts.ptr ? &mv->parts : nullptr;
   const bool two_ok = pr && pr->cap_elems >= 2 * pr->n;
-  Plan p = plan_heff(dtype, *h, static_cast<const WSiteInfo*>(wi_keep.get()), two_ok);
+  Plan p = plan_heff(dtype, *h, static_cast<const WSiteInfo*>(wi_keep.get()), two_ok, fold_epi());
   if (pr) pr->used = 0;
   const void* bufs[B_COUNT] = {nullptr};
   bufs[B_L] = h->L;

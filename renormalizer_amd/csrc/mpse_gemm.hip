@@ -58,7 +58,11 @@ struct IdxMap {
 // - the K loop runs over the segments one after the other.  All pairs share the index maps of GemmArgs (M = rows of
 // one group, K = length of one segment).  am / bm: byte flags of the 64 x 16 tiles of the segment's operands (row of
 // tile t at t * pitch), null = all occupied.
-constexpr int GMAX_GRP = 8, GMAX_SEG = 4;
+constexpr int GMAX_GRP = 8, GMAX_SEG = 4, GMAX_MIX = 8;
+struct GMix {             // epilogue mix term (GroupedMixTerm)
+  const double* src;
+  int b, f, delta, pad;
+};
 struct GSeg {
   const double* A;
   const double* B;
@@ -86,6 +90,13 @@ struct GemmGroups {
   // optional: the flags of every tile's concatenated K range, assembled once (k_tile_order, kept with the launch order
   // for the solve): nkw words per tile, tile = (group's tile row, tile column) in launch-independent order
   const unsigned long long* flags;
+  // epilogue mix (complex x complex; mpse_internal.h GroupedDesc): group mix_grp takes as its beta term
+  //   sum_t W[b_t, x, x + delta_t, f_t] src_t[row + delta_t, column],  x = row mod mix_d (64 % mix_d == 0)
+  // - a plane of the folded one-site matvec that is only ever accumulated onto, formed where it is consumed
+  int nmix, mix_grp, mix_d, mix_wr;
+  long long mix_ld;
+  const double* mix_w;
+  GMix mix[GMAX_MIX];
 };
 
 struct GemmArgs {
@@ -832,6 +843,63 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   constexpr bool PRE = CA && CB;
   double2 pre_c[PRE ? WI : 1][2][4], pre_y[PRE ? WI : 1][2][4];
   const bool need_c = GRP ? (gp.use_beta != 0 && half == 0) : g.use_beta != 0, need_y = g.dot_y != nullptr;
+  // Epilogue mix: the beta term of this group is a sum of band-diagonal taps on up to GMAX_MIX tensors laid out like C
+  // (rows (a, x), x = row mod d; the tile's 64 rows hold whole runs of x, so row + delta stays inside the tile where the
+  // weight is not zero).  Weights per (term, tile row) are put into the LDS the K loop has left, out of range = 0.
+  // A zero weight SELECTS zero - never multiplies: a source may hold anything where its own product was not asked for.
+  // Loads are unconditional at clamped addresses.  One term at a time, its loads in flight together: the terms of a
+  // sub-tile all at once would not fit the registers next to the accumulators.
+  bool mix_on = false;
+  if constexpr (GRP && PRE) mix_on = need_c && g.gg.nmix > 0 && grp == g.gg.mix_grp;   // workgroup-uniform
+  if constexpr (GRP && PRE) {
+    if (mix_on) {
+      const int d = g.gg.mix_d;
+      __syncthreads();                   // every wave has read its last fragments: the panels are free
+      for (int x = tid; x < g.gg.nmix * BM; x += NT) {
+        const GMix& m = g.gg.mix[x / BM];
+        const int sg = (x % BM) % d, e = sg + m.delta;
+        double w = 0.0;
+        if (e >= 0 && e < d) w = g.gg.mix_w[(((long long)m.b * d + sg) * d + e) * g.gg.mix_wr + m.f];
+        smem[x] = w;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < WI; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pre_c[i][j][r] = make_double2(0.0, 0.0);
+      for (int t = 0; t < g.gg.nmix; ++t) {
+        const double* src = g.gg.mix[t].src;
+        const int delta = g.gg.mix[t].delta;
+        double2 v[WI][2][4];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int gj = min(tn * TBN + wn * 32 + j * 16 + (lane & 15), g.N - 1);
+#pragma unroll
+          for (int i = 0; i < WI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int gi = tm * TBM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r + delta;
+              const int gc = min(max(gi, 0), g.M - 1);
+              v[i][j][r] = *reinterpret_cast<const double2*>(src + ((long long)gc * g.gg.mix_ld + gj) * 2);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < WI; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double w = smem[t * BM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              // (one fused multiply-add per tap, taps in the order of the elementwise pass: the same bits as k_wmix)
+              pre_c[i][j][r].x = w != 0.0 ? fma(w, v[i][j][r].x, pre_c[i][j][r].x) : pre_c[i][j][r].x;
+              pre_c[i][j][r].y = w != 0.0 ? fma(w, v[i][j][r].y, pre_c[i][j][r].y) : pre_c[i][j][r].y;
+            }
+          }
+      }
+    }
+  }
   if (PRE && (need_c || need_y)) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -844,7 +912,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
         for (int r = 0; r < 4; ++r) {
           const int gi = min(tm * TBM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r, g.M - 1);
           const long long co = idx_off(g.mC, gi) + coffn;
-          if (need_c) {
+          if (need_c && !mix_on) {
             const double* pin = g.Cin ? g.Cin + (idx_off(g.mCin, gi) + cinn) * EC : C + co * EC;
             if constexpr (CC)
               pre_c[i][j][r] = *reinterpret_cast<const double2*>(pin);
@@ -1379,6 +1447,7 @@ void count_paths(long long* gp, const mpse_plan::GemmPlan& p, bool batched) {
 void count_paths(long long* gp, const GroupedDesc& d) {
   ++gp[mpse_ctx::GP_GROUPED];
   gp[mpse_ctx::GP_GROUPED_SPLIT2] += d.split2;
+  gp[mpse_ctx::GP_GROUPED_MIX] += d.nmix > 0;
 }
 
 }  // namespace
@@ -1553,6 +1622,17 @@ int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype
   return MPSE_OK;
 }
 
+// compulsory reads of an epilogue mix beyond the one beta term already counted: its distinct sources
+static double mix_sources(const GroupedDesc& d) {
+  int n = 0;
+  for (int t = 0; t < d.nmix; ++t) {
+    bool seen = false;
+    for (int u = 0; u < t; ++u) seen = seen || d.mix[u].src == d.mix[t].src;
+    n += seen ? 0 : 1;
+  }
+  return n > 1 ? double(n - 1) : 0.0;
+}
+
 // Grouped launch of the contraction kernel (mpse_internal.h GroupedDesc; folded one-site matvec of mpse_plans.h).
 // dot: the caller's dot request when this launch completes a matvec result (one group only), else null.
 int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, MatvecReq::Dot* dot) {
@@ -1602,6 +1682,19 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, Matv
   }
   g.A = gg.g[0].seg[0].A, g.B = gg.g[0].seg[0].B, g.C = gg.g[0].C;
   g.use_beta = any_beta;
+  if (d.nmix > 0) {
+    // (the sources are read through 32-bit row numbers of C's own row space; the rows of a tile keep their a)
+    if (!ca || d.nmix > GMAX_MIX || d.mix_grp < 0 || d.mix_grp >= d.ngrp || d.grp[d.mix_grp].beta != 1.0 || !d.mix_w ||
+        d.mix_d < 1 || BM % d.mix_d != 0 || g.M % BM != 0 || d.mix_wr < 1 || d.mix_ld < g.N)
+      return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: bad epilogue mix");
+    gg.nmix = d.nmix, gg.mix_grp = d.mix_grp, gg.mix_d = d.mix_d, gg.mix_wr = d.mix_wr, gg.mix_ld = d.mix_ld;
+    gg.mix_w = static_cast<const double*>(d.mix_w);
+    for (int t = 0; t < d.nmix; ++t) {
+      if (!d.mix[t].src || d.mix[t].delta <= -d.mix_d || d.mix[t].delta >= d.mix_d)
+        return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: bad epilogue mix term");
+      gg.mix[t] = GMix{static_cast<const double*>(d.mix[t].src), d.mix[t].b, d.mix[t].f, d.mix[t].delta, 0};
+    }
+  }
 
   // ---- plan
   const int nkt_max = max_seg * gg.nkt_seg;
@@ -1621,7 +1714,8 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, Matv
   const double mnk = double(g.M) * double(g.N) * double(g.K) * segs;
   const bool prof_this = prof_begin(ctx, variant, mnk * ((ca && cb) ? 8.0 : 4.0),
                                     segs * (double(g.M) * g.K * (ca ? 16 : 8) + double(g.K) * g.N * 16.0) +
-                                        double(d.ngrp) * double(g.M) * g.N * 16.0 * (any_beta ? 2 : 1),
+                                        double(d.ngrp) * double(g.M) * g.N * 16.0 * (any_beta ? 2 : 1) +
+                                        mix_sources(d) * double(g.M) * g.N * 16.0,
                                     &rec);
   g.kt_counter = prof_this && ctx->prof_ktiles ? ctx->prof_ktiles + variant : nullptr;
 

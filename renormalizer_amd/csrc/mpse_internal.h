@@ -148,7 +148,7 @@ struct mpse_ctx {
   // launch decisions of the contraction kernel (mpse_gemm_path_stats; the order of include/mpsengine.h)
   enum GemmPath {
     GP_LAUNCH, GP_GENERAL, GP_WIDE, GP_SPLIT_B1, GP_SPLIT_BN, GP_DIE1, GP_DIE2, GP_SKEW, GP_ORDER, GP_MASK,
-    GP_MASK_GLOBAL, GP_GROUPED, GP_GROUPED_SPLIT2, GP_COUNT
+    GP_MASK_GLOBAL, GP_GROUPED, GP_GROUPED_SPLIT2, GP_GROUPED_MIX, GP_WMIX, GP_COUNT
   };
   long long gemm_paths[GP_COUNT] = {0};
   // mpse_block_qr: decompositions that took the Cholesky-QR path / that fell back from it to Householder
@@ -471,6 +471,10 @@ struct GroupedSeg {
   const unsigned char* am = nullptr;
   const unsigned char* bm = nullptr;
 };
+struct GroupedMixTerm {       // one diagonal of one block of an MPO site applied to a tensor laid out like C's rows
+  const void* src = nullptr;  // (complex128, rows (a, x) at stride ld, columns contiguous)
+  int b = 0, f = 0, delta = 0;
+};
 struct GroupedGrp {
   GroupedSeg seg[4];
   void* C = nullptr;
@@ -488,6 +492,14 @@ struct GroupedDesc {
   // goes to C, the second to c2 (laid out like C): the consumer adds them
   bool split2 = false;
   void* c2 = nullptr;
+  // epilogue mix (mpse_plans.h EpiTerm; complex x complex only): the beta term of group mix_grp (beta = 1) is
+  //   sum_t W[b_t, x, x + delta_t, f_t] src_t[(a, x + delta_t), j]   for output row (a, x), x = row mod d, 64 % d == 0
+  // instead of C itself.  W: the real site (., d, d, wr) on the device.
+  int nmix = 0, mix_grp = 0;
+  GroupedMixTerm mix[8];
+  const void* mix_w = nullptr;
+  int mix_d = 0, mix_wr = 0;
+  long long mix_ld = 0;
 };
 int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, MatvecReq::Dot* dot);
 int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,

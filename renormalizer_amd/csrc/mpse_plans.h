@@ -45,6 +45,12 @@ enum Kind { K_GEMM = 0, K_COPY = 1, K_WMIX = 2, K_GGEMM = 3 };
 //     out (+)= sum_{f != ru} P_f . R[:,f,:]^T is one more: one group whose K loop runs over the channels (segments).
 // Every channel keeps its own product, so the quantum-number zero blocks of L[:,b,:] stay whole empty tiles.
 constexpr int G_MAXGRP = 8, G_MAXSEG = 4, WM_MAXDST = 4, WM_MAXTERM = 4;
+// Epilogue mix: the plane of R's unit channel (f = ru) is never an operand of the products with R - it is what they
+// accumulate onto.  Where its blocks are bands of half-width <= EPI_MAXBAND, the first product with R forms it in its
+// epilogue instead of reading it back from `out`: a term = one diagonal of one block,
+//   mix[(a, x), k] = sum_terms W[b, x, x + delta, f] src[(a, x + delta), k],
+// and a 64-row output tile holds whole runs of x (64 % d == 0), so the taps never leave the tile's rows of a.
+constexpr int EPI_MAXTERM = 8, EPI_MAXBAND = 2;
 
 struct WBlock {
   int b, f;
@@ -98,12 +104,23 @@ struct GSegPlan {
   int bm_kind = BM_NONE;  // BM_SCAN: from scan_b, K tiles from bm_kt0 on; BM_CENTRE: B is the centre tensor (structural
   int64_t bm_kt0 = 0;     // mask of the solve)
 };
+struct EpiTerm {
+  int src = 0;            // tensor (rows (a, x), columns k) the diagonal is applied to: the centre, a temporary or `out`
+  int64_t src_off = 0;
+  int b = 0, f = 0;       // block W[b, :, :, f] of the site in wbuf ...
+  int delta = 0;          // ... and its diagonal e = x + delta
+};
 struct GGroupPlan {
   int nseg = 0;
   GSegPlan seg[G_MAXSEG];
   int cbuf = 0;
   int64_t c_off = 0;
   double beta = 0.0;
+  // epilogue mix (nmix > 0; beta == 1): the beta term is the sum of these terms instead of C itself
+  int nmix = 0;
+  EpiTerm mix[EPI_MAXTERM];
+  int wbuf = B_W0;
+  int64_t mix_d = 0, mix_wr = 0, mix_ld = 0;   // site (., d, d, wr); row stride of the sources
   // split2 (single-group steps): two workgroups per output tile, each over half of the tile's occupied K tiles; the
   // first half (+ beta C) is stored to C, the second to B_OUT2, laid out like C: the caller of the plan adds the two
   bool split2 = false;
@@ -267,12 +284,14 @@ inline void push_w(Plan& p, int wbuf, int w_dtype, int tin, int tout, int t_dtyp
 // differ from the ket-side bonds (columns of L / R, bonds of C): that is the projection of H C onto another
 // state's bond spaces used by the variational compression (mps/mp.py:513-650); the Krylov / Davidson drivers
 // require them equal.
-inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, bool two_results);
+inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, bool two_results, bool mix_epilogue);
 
 // `wi`: block structure of the MPO site where the caller knows it (mpse_mpo_site_hint): large one-site centres then
 // take the folded plan.  `two_results`: the caller accepts the result as the sum of B_OUT and B_OUT2 (Plan::two_results
-// says whether the plan made use of it).
-inline Plan plan_heff(int dtype, const mpse_heff& h, const WSiteInfo* wi = nullptr, bool two_results = false) {
+// says whether the plan made use of it).  `mix_epilogue`: the folded plan may form the plane of R's unit channel in the
+// epilogue of the first product with R (EpiTerm); the caller's executor must understand GGroupPlan::nmix.
+inline Plan plan_heff(int dtype, const mpse_heff& h, const WSiteInfo* wi = nullptr, bool two_results = false,
+                      bool mix_epilogue = false) {
   Plan p;
   const mpse_dims& s = h.dims;
   const int64_t Dl = s.Dl_ket, Dr = s.Dr_ket, wl = s.wl, wr = s.wr;
@@ -291,7 +310,7 @@ inline Plan plan_heff(int dtype, const mpse_heff& h, const WSiteInfo* wi = nullp
   }
   if (h.nsite == 1) {
     if (wi) {
-      Plan f = plan_heff1_fold(dtype, h, *wi, two_results);
+      Plan f = plan_heff1_fold(dtype, h, *wi, two_results, mix_epilogue);
       if (!f.error) return f;
     }
     // abc,bdef,lfk,cek->adl (hop_expr.py:75-79); ancilla cegk->adgl (87-91)
@@ -356,6 +375,13 @@ inline bool& fold_split2() {
   }();
   return v;
 }
+inline bool& fold_epi() {
+  static bool v = [] {
+    const char* e = getenv("MPSE_WFOLD_EPI");  // MPSE_WFOLD_EPI=0: every mixed plane through the elementwise pass
+    return !(e && e[0] == '0');
+  }();
+  return v;
+}
 inline int64_t& fold_split2_min_kt() {   // fewest K tiles of a product worth halving (test hook)
   static int64_t v = 8;
   return v;
@@ -366,7 +392,8 @@ inline int64_t& fold_align() {   // bra-bond multiple the device needs (a 64-row
 }
 
 // Folded one-site matvec (see above); p.error is set when the site does not qualify and the caller takes plan_heff.
-inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, bool two_results = false) {
+inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, bool two_results = false,
+                            bool mix_epilogue = false) {
   Plan p;
   const mpse_dims& s = h.dims;
   const int64_t Dl = s.Dl_ket, Dr = s.Dr_ket, wl = s.wl, wr = s.wr, d = s.d0;
@@ -387,13 +414,55 @@ inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, 
   const int64_t N = d * Dr, plane = Dlb * N;
   std::vector<std::vector<const WBlock*>> by_f(wr), by_b(wl);
   for (const WBlock& k : wi.blocks) by_f[k.f].push_back(&k), by_b[k.b].push_back(&k);
+  // Epilogue mix: the plane f = ru, where it is a sum of narrow bands and a product with R follows to carry it.  One
+  // identity block whose channel b feeds nothing else is written straight into `out` by the product with L (nothing
+  // else writes `out` before the products with R) and read back as a term of its own.
+  bool epi = false;
+  int64_t epi_direct_b = -1;
+  std::vector<std::pair<const WBlock*, int>> epi_diag;    // (block, delta)
+  if (mix_epilogue && ru >= 0 && !by_f[ru].empty() && d > 0 && 64 % d == 0) {
+    bool sum = true, follows = false;
+    {
+      const WBlock* k = by_f[ru][0];
+      if (by_f[ru].size() == 1 && k->ident && k->b != lu && by_b[k->b].size() == 1) sum = false;   // already direct
+    }
+    for (int64_t f = 0; f < wr; ++f)
+      if (f != ru && !by_f[f].empty()) follows = true;
+    bool narrow = true;
+    for (const WBlock* k : by_f[ru]) {
+      if (k->ident) {
+        epi_diag.push_back({k, 0});
+        continue;
+      }
+      bool diag[2 * EPI_MAXBAND + 1] = {false};
+      for (int64_t x = 0; x < d; ++x)
+        for (int64_t e = 0; e < d; ++e)
+          if (wi.w[((k->b * d + x) * d + e) * wr + k->f] != 0.0) {
+            if (std::abs(e - x) > EPI_MAXBAND)
+              narrow = false;
+            else
+              diag[e - x + EPI_MAXBAND] = true;
+          }
+      for (int q = 0; q <= 2 * EPI_MAXBAND; ++q)
+        if (diag[q]) epi_diag.push_back({k, q - EPI_MAXBAND});
+    }
+    epi = sum && follows && narrow && (int)epi_diag.size() <= EPI_MAXTERM;
+    if (epi)
+      for (const WBlock* k : by_f[ru])
+        if (k->ident && k->b != lu && by_b[k->b].size() == 1) {
+          epi_direct_b = k->b;
+          break;
+        }
+  }
   // where the product of channel b goes: straight into the plane of its channel f, or into a temporary
   std::vector<int64_t> direct_f(wl, -1), tmp_of(wl, -1);
   int64_t ntmp = 0, ngemm = 0;
   for (int64_t b = 0; b < wl; ++b) {
     if (b == lu || by_b[b].empty()) continue;
     ++ngemm;
-    if (by_b[b].size() == 1 && by_b[b][0]->ident && by_f[by_b[b][0]->f].size() == 1)
+    if (b == epi_direct_b)
+      direct_f[b] = ru;
+    else if (by_b[b].size() == 1 && by_b[b][0]->ident && by_f[by_b[b][0]->f].size() == 1)
       direct_f[b] = by_b[b][0]->f;
     else
       tmp_of[b] = ntmp++;
@@ -459,6 +528,7 @@ inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, 
   const int64_t nchunk = (d + WM_CHUNK - 1) / WM_CHUNK;
   for (int64_t f = 0; f < wr; ++f) {
     if (!present[f] || alias[f]) continue;
+    if (epi && f == ru) continue;        // formed by the first product with R
     bool is_direct = false;
     for (const WBlock* k : by_f[f])
       if (k->b != lu && direct_f[k->b] == f) is_direct = true;
@@ -532,6 +602,19 @@ inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, 
     g.beta = out_init ? 1.0 : 0.0;
     if (split2) g.split2 = true, p.two_results = true;
     for (size_t j = i; j < csegs.size() && j < i + G_MAXSEG; ++j) g.seg[g.nseg++] = csegs[j];
+    if (epi && i == 0) {
+      g.wbuf = B_W0, g.mix_d = d, g.mix_wr = wr, g.mix_ld = Dr;
+      for (const auto& kd : epi_diag) {
+        EpiTerm& t = g.mix[g.nmix++];
+        t.b = kd.first->b, t.f = kd.first->f, t.delta = kd.second;
+        if (kd.first->b == lu)
+          t.src = B_C, t.src_off = 0;
+        else if (kd.first->b == epi_direct_b)
+          t.src = B_OUT, t.src_off = 0;
+        else
+          t.src = B_T1, t.src_off = tmp_of[kd.first->b] * plane;
+      }
+    }
     st.groups.push_back(g);
     p.steps.push_back(st);
     out_init = true;

@@ -718,6 +718,15 @@ class Engine:
         self._check(self.lib.mpse_gemm_path_stats(self.ctx, v, len(v)))
         return dict(zip(self.GEMM_PATHS, (int(x) for x in v)))
 
+    def wfold_path_stats(self):
+        """{"grouped_mix": grouped launches that formed their beta term in the epilogue from blocks of the MPO site,
+        "wmix": launches of the elementwise MPO pass by the contraction plans}, cumulative (counters 13 and 14 of
+        ``mpse_gemm_path_stats``)."""
+        n = len(self.GEMM_PATHS)
+        v = (C.c_int64 * (n + 2))()
+        self._check(self.lib.mpse_gemm_path_stats(self.ctx, v, n + 2))
+        return {"grouped_mix": int(v[n]), "wmix": int(v[n + 1])}
+
     def block_qr_optimistic(self, on):
         """Optimistic mode of the Cholesky-QR path (``mpse_block_qr_optimistic``): breakdowns are not read back per
         decomposition but raise a sticky flag - ``block_qr_check()`` at the end of a step that can be repeated."""
