@@ -536,6 +536,50 @@ int mpse_mps_overlap_stats(mpse_ctx* ctx, int64_t* counts, int n);
  * No context, no device work. */
 int mpse_mps_overlap_plan(int nsite, const int64_t* dims, int any_complex, int64_t* info, int n);
 
+/* ------------------------------------------- <bra| O |ket> of two chains and an MPO */
+
+/* <bra| O |ket> of two different matrix product states (or density operators) with a matrix product operator between
+ * them in one call, replaces the Environ walk behind mps/mp.py expectation(mpo, self_conj):
+ *   E_0 = 1 (1 x 1 x 1),
+ *   E_{i+1}[b', g', k'] = sum_{b, g, k, s', s, a} op(B_i[b, s', a, b']) W_i[g, s', s, g'] E_i[b, g, k] K_i[k, s, a, k'],
+ *   result E_N[0, 0, 0]
+ *   bra[i], ket[i]   : device site tensors, contiguous (D_l, d, danc, D_r); a is the ancilla leg of a density-operator
+ *                      site (danc = 1 for an MPS), each MPSE_F64 or MPSE_C128 (any mixture per site and per side)
+ *   W[i]             : device MPO site (wl, d, d, wr), MPSE_F64 or MPSE_C128 (w_dtype[i]); its FIRST physical leg meets
+ *                      the bra, as in mpse_env_update and Mpo.apply
+ *   dims             : nsite rows (Db_l, Dk_l, wl, d, danc, Db_r, Dk_r, wr), host
+ *   conj_bra != 0    : op = complex conjugate (the bra buffers hold the state itself); 0: they hold the conjugate already
+ *   out_re_im_host   : two doubles
+ * Rows with an extent < 1, neighbours whose bonds or MPO bonds differ, or a first / last bond or MPO bond != 1:
+ * MPSE_ERR_SHAPE before any device work.  Null pointers and unknown dtypes: MPSE_ERR_ARG.  Chains that pass
+ * mpse_mps_sandwich_plan run as ONE launch (k_sandwich_chain: one workgroup walks the sites, E and one (s, a) slice of
+ * T = E . K[:, s, a, :] in LDS, the new E in registers, W read through the scalar path with its zero entries skipped,
+ * working dtype complex as soon as any tensor is); every other chain as the environment-update plan of
+ * mpse_env_update (left domain, env_unit = 0) site after site on two pooled environments.  No atomics, no host read
+ * between sites, a fixed summation order: the same inputs give the same bits on every call (the two paths sum in
+ * different orders and agree to rounding).  MPSE_SANDWICH_CHAIN=0 in the environment sends every chain through the
+ * enqueued updates, =1 every chain whose launch fits through the kernel whatever its work (both for measurements).
+ * Synchronous; refused while a deferred list is being recorded. */
+int mpse_mps_sandwich(mpse_ctx* ctx, int nsite, const void* const* bra, const int* bra_dtype, const void* const* ket,
+                      const int* ket_dtype, const void* const* W, const int* w_dtype, const int64_t* dims /* nsite x 8 */,
+                      int conj_bra, double* out_re_im_host);
+/* counts[i], i < n, cumulative:  0 chains taken by the chain kernel, 1 chains taken by the enqueued path, 2 sites
+ * walked (both paths).  A refused call counts nothing.  Diagnostics for tests; no device work. */
+int mpse_mps_sandwich_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims table alone: returns 1 when the chain kernel takes the chain, else 0 (also for a table
+ * mpse_mps_sandwich refuses).  Eligible: E (Db x w rows of Dk elements, padded to an odd length against bank
+ * conflicts; the largest over the bonds) plus the largest T slice (Db_l wl Dk_r elements) within info[0] bytes of LDS
+ * in the working dtype (complex when any_complex != 0); wr * ceil(Db_r Dk_r / info[4]) <= info[5] accumulators per
+ * thread at every site; and the dense multiply-add count of the heaviest site,
+ * d danc (Db_l wl Dk_l Dk_r + d wl Db_l Db_r Dk_r), at most info[7].  info[i], i < n (may be NULL):
+ *    0  LDS bytes a workgroup may use (the 160 KiB of a gfx950 compute unit)
+ *    1  LDS bytes of this chain's launch (0: not eligible)    2  its elements of E    3  its elements of T
+ *    4  threads of the workgroup    5  accumulators a thread has    6  accumulators the heaviest site needs
+ *    7  the work bound (measured, profiles/sandwich.md)    8  multiply-adds of the heaviest site
+ *    9  1 when the table is a chain    10  bytes of a working element (8 or 16)
+ * No context, no device work. */
+int mpse_mps_sandwich_plan(int nsite, const int64_t* dims, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

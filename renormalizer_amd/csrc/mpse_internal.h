@@ -183,6 +183,9 @@ struct mpse_ctx {
   // mpse_mps_overlap (mpse_mps_overlap_stats; the order of include/mpsengine.h)
   enum OverlapStat { OV_CHAIN, OV_ENQUEUED, OV_SITES, OV_COUNT };
   long long overlap_stats[OV_COUNT] = {0};
+  // mpse_mps_sandwich (mpse_mps_sandwich_stats; the order of include/mpsengine.h)
+  enum SandwichStat { SW_CHAIN, SW_ENQUEUED, SW_SITES, SW_COUNT };
+  long long sandwich_stats[SW_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

@@ -179,6 +179,10 @@ _SIGNATURES = {
                          C.POINTER(C.c_int), _i64p, C.c_int, _dblp],
     "mpse_mps_overlap_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_mps_overlap_plan": [C.c_int, _i64p, C.c_int, _i64p, C.c_int],
+    "mpse_mps_sandwich": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                          C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p, C.c_int, _dblp],
+    "mpse_mps_sandwich_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_sandwich_plan": [C.c_int, _i64p, C.c_int, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -223,6 +227,23 @@ def mps_overlap_plan(dims, any_complex, lib=None):
     info = (C.c_int64 * len(OVERLAP_PLAN_INFO))()
     ok = lib.mpse_mps_overlap_plan(len(rows), flat, int(bool(any_complex)), info, len(info))
     return bool(ok), dict(zip(OVERLAP_PLAN_INFO, (int(v) for v in info)))
+
+
+SANDWICH_PLAN_INFO = ("lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "acc_per_thread", "acc_needed",
+                      "work_max", "work", "valid", "elem_bytes", "channel_limit")
+
+
+def mps_sandwich_plan(dims, any_complex, lib=None):
+    """Which path ``Engine.mps_sandwich`` takes for a chain, from its ``dims`` rows (Db_l, Dk_l, wl, d, danc, Db_r,
+    Dk_r, wr) alone (``mpse_mps_sandwich_plan``; needs the built library, no GPU).  Returns (chain kernel?, {info name:
+    value})."""
+    lib = lib or load_library()
+    rows = [[int(x) for x in r] for r in dims]
+    assert all(len(r) == 8 for r in rows), "dims rows are (Db_l, Dk_l, wl, d, danc, Db_r, Dk_r, wr)"
+    flat = (C.c_int64 * max(8 * len(rows), 1))(*[x for r in rows for x in r])
+    info = (C.c_int64 * len(SANDWICH_PLAN_INFO))()
+    ok = lib.mpse_mps_sandwich_plan(len(rows), flat, int(bool(any_complex)), info, len(info))
+    return bool(ok), dict(zip(SANDWICH_PLAN_INFO, (int(v) for v in info)))
 
 
 class _Recording:
@@ -693,6 +714,48 @@ class Engine:
         self._check(self.lib.mpse_mps_overlap(
             self.ctx, n, (C.c_void_p * n)(*[t.ptr for t in bra_sites]), (C.c_int * n)(*[t.code for t in bra_sites]),
             (C.c_void_p * n)(*[t.ptr for t in ket_sites]), (C.c_int * n)(*[t.code for t in ket_sites]), dims,
+            int(bool(conj_bra)), out))
+        return complex(out[0], out[1])
+
+    # -- <bra| O |ket> of two chains and an MPO
+    SANDWICH_STATS = ("chain_kernel", "enqueued", "sites")
+
+    def mps_sandwich_stats(self):
+        """{name: count} of the ``mps_sandwich`` calls of this context, cumulative (``mpse_mps_sandwich_stats``): chains
+        taken by the chain kernel, chains taken by the enqueued environment updates, sites walked."""
+        v = (C.c_int64 * len(self.SANDWICH_STATS))()
+        self._check(self.lib.mpse_mps_sandwich_stats(self.ctx, v, len(v)))
+        return dict(zip(self.SANDWICH_STATS, (int(x) for x in v)))
+
+    @staticmethod
+    def sandwich_dims(bra_sites, w_sites, ket_sites):
+        """The ``dims`` rows (Db_l, Dk_l, wl, d, danc, Db_r, Dk_r, wr) of a chain of site tensors (D_l, d[, danc], D_r)
+        and MPO sites (wl, d, d, wr); ValueError when the three do not describe the same sites."""
+        n = len(bra_sites)
+        if n == 0 or n != len(ket_sites) or n != len(w_sites):
+            raise ValueError(f"mps_sandwich: {n} bra sites, {len(w_sites)} MPO sites, {len(ket_sites)} ket sites")
+        rows = []
+        for i, (b, w, k) in enumerate(zip(bra_sites, w_sites, ket_sites)):
+            if b.ndim not in (3, 4) or k.ndim != b.ndim or w.ndim != 4 or tuple(b.shape[1:-1]) != tuple(k.shape[1:-1]) \
+                    or w.shape[1] != b.shape[1] or w.shape[2] != b.shape[1]:
+                raise ValueError(f"mps_sandwich: site {i} has shapes {b.shape}, {w.shape}, {k.shape}")
+            rows.append([b.shape[0], k.shape[0], w.shape[0], b.shape[1], b.shape[2] if b.ndim == 4 else 1, b.shape[-1],
+                         k.shape[-1], w.shape[3]])
+        return rows
+
+    def mps_sandwich(self, bra_sites, w_sites, ket_sites, conj_bra):
+        """<bra| O |ket> of two chains of device site tensors (D_l, d[, danc], D_r) and the device sites (wl, d, d, wr)
+        of an MPO in one engine call (``mpse_mps_sandwich``); the first physical leg of an MPO site meets the bra, the
+        ancilla leg of density-operator sites is traced.  ``conj_bra``: conjugate the bra inside the contraction.  Real
+        and complex tensors may be mixed.  Returns a complex."""
+        rows = self.sandwich_dims(bra_sites, w_sites, ket_sites)
+        n = len(rows)
+        dims = (C.c_int64 * (8 * n))(*[int(x) for r in rows for x in r])
+        out = (C.c_double * 2)()
+        self._check(self.lib.mpse_mps_sandwich(
+            self.ctx, n, (C.c_void_p * n)(*[t.ptr for t in bra_sites]), (C.c_int * n)(*[t.code for t in bra_sites]),
+            (C.c_void_p * n)(*[t.ptr for t in ket_sites]), (C.c_int * n)(*[t.code for t in ket_sites]),
+            (C.c_void_p * n)(*[t.ptr for t in w_sites]), (C.c_int * n)(*[t.code for t in w_sites]), dims,
             int(bool(conj_bra)), out))
         return complex(out[0], out[1])
 

@@ -398,6 +398,21 @@ class Mps:
         assert len(self) == len(other)
         return get_engine().mps_overlap(self._mp, other._mp, conj_bra=not self_is_conj)
 
+    def matrix_element(self, mpo, ket: "Mps", self_is_conj=True) -> complex:
+        """<self| mpo |ket> as ONE engine call (``Engine.mps_sandwich`` -> ``mpse_mps_sandwich``), with ``self`` the bra
+        exactly as in ``overlap``: it holds the already-conjugated bra unless ``self_is_conj=False``, which conjugates
+        inside the contraction.  The value of ``ket.expectation(mpo, self)`` resp. ``ket.expectation(mpo, self.conj())``
+        without the conjugated copy, the ``Environ`` and the per-site calls; ``expectation`` itself stays as it is (its
+        values are pinned bit for bit), the two sum in different orders and agree to rounding.  The ``coeff`` factors
+        are not included.  Works for ``Mps`` and ``MpDm`` (the ancilla leg is traced)."""
+        if isinstance(mpo, (Op, OpSum)):
+            mpo = Mpo(self.model, mpo)
+        assert len(self) == len(ket) == len(mpo)
+        eng = get_engine()
+        w_sites = [mpo.device(i, eng) if hasattr(mpo, "device") else eng.asdevice(np.asarray(mpo[i]))
+                   for i in range(len(self))]
+        return eng.mps_sandwich(self._mp, w_sites, ket._mp, conj_bra=not self_is_conj)
+
     @property
     def mp_norm(self) -> float:
         """mps/mp.py:354-372"""
