@@ -580,6 +580,54 @@ int mpse_mps_sandwich_stats(mpse_ctx* ctx, int64_t* counts, int n);
  * No context, no device work. */
 int mpse_mps_sandwich_plan(int nsite, const int64_t* dims, int any_complex, int64_t* info, int n);
 
+/* ------------------------------- matrix of two-point functions of one-site operators */
+
+/* C[k, l] = <psi| X_k Y_l |psi> for k < l and C[k, k] = <psi| Z_k |psi> of one-site operators on the selected sites
+ * sel[0] < sel[1] < .. of ONE chain, the bra being the conjugate of the state itself, in one call; replaces the
+ * n (n + 1) / 2 MPO expectations of mps/mps.py:1657-1687 (calc_edof_rdm):
+ *   sites[i]    : device site tensors, contiguous (D_l, d, danc, D_r); a is the ancilla leg of a density-operator site,
+ *                 which is traced (danc = 1 for an MPS); each MPSE_F64 or MPSE_C128 (dtype[i]; any mixture)
+ *   dims        : nsite rows (D_l, d, danc, D_r), host
+ *   sel         : nsel site indices, strictly ascending, host
+ *   X, Y, Z     : host; for every selected site in turn a d x d matrix of complex pairs (2 d d doubles): X_k opens,
+ *                 Y_k closes, Z_k is the operator of the diagonal entry.  The FIRST index of a matrix meets the bra, as
+ *                 W[g, s', s, g'] does in mpse_env_update
+ *   out_host    : nsel x nsel complex pairs, row k column l; the lower triangle is left zero
+ * Rows with an extent < 1, neighbours whose bonds differ, a first / last bond != 1, or a selection that is not strictly
+ * ascending inside [0, nsite): MPSE_ERR_SHAPE before any device work.  Null pointers, an empty selection and unknown
+ * dtypes: MPSE_ERR_ARG.  Chains that pass mpse_mps_corr_plan (bonds up to a measured limit) run as TWO launches on the context stream with no host
+ * read between them: k_corr_right (one workgroup walks from the right with the identity environment in LDS and leaves
+ * the environments closed with Y_l and with Z_l at every selected site l in pooled memory) and k_corr_rows (workgroup k
+ * walks from the left, opens with X_k at sel[k] and closes at every later selected site); no flag, spin wait or atomic
+ * between workgroups.  Every other chain runs the same two passes as products of the contraction kernel, the open rows
+ * as one stack that grows by a row per selected site, all temporaries pooled (MPSE_ERR_OOM when they do not fit; the
+ * context stays usable).  The working dtype is complex as soon as any site or local matrix is.  A fixed summation
+ * order: the same inputs give the same bits on every call (the two paths sum in different orders and agree to
+ * rounding).  MPSE_CORR_CHAIN=0 in the environment sends every chain through the enqueued products, =1 every chain
+ * whose launches fit through the kernels, above the measured bond limit as well (both for measurements).  Synchronous;
+ * refused while a deferred list is being recorded. */
+int mpse_mps_corr(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype, const int64_t* dims /* nsite x 4 */,
+                  int nsel, const int* sel, const double* X, const double* Y, const double* Z, double* out_host);
+/* counts[i], i < n, cumulative:  0 calls taken by the chain kernels, 1 calls taken by the enqueued path, 2 sites walked
+ * (nsite per call), 3 matrix entries produced (nsel (nsel + 1) / 2 per call).  A refused call counts nothing.
+ * Diagnostics for tests; no device work. */
+int mpse_mps_corr_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims table and the number of selected sites alone: returns 1 when the chain kernels take the
+ * call, else 0 (also for a table mpse_mps_corr refuses).  The launches FIT when every bond <= info[10], d * danc <=
+ * info[9], 1 <= nsel <= info[8], and the environment plus the largest T slice (rows padded to an odd length against bank
+ * conflicts) plus 16 reduction words lie within info[1] bytes of LDS in the working dtype (complex when any_complex !=
+ * 0).  The kernels TAKE a call that fits when every bond is also <= info[0], the measured limit up to which they are
+ * faster than the enqueued products (profiles/corr_matrix.md).  info[i], i < n (may be NULL):
+ *    0  the bond limit of the rule (measured)
+ *    1  LDS bytes a workgroup may use (the 160 KiB of a gfx950 compute unit)
+ *    2  LDS bytes of either launch (0: not taken)    3  its elements of E (0: does not fit)    4  its elements of T
+ *    5  threads of a workgroup    6  the largest bond of the table (0: refused)    7  1 when the table is a chain
+ *    8  the grid cap: the largest nsel the chain kernels take    9  the largest d * danc they take
+ *   10  the bond limit of the LDS: the largest power of two D with a complex D x D environment and T slice inside info[1]
+ *   11  LDS bytes of either launch when it fits, whatever info[0] says (0: does not fit)
+ * No context, no device work. */
+int mpse_mps_corr_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

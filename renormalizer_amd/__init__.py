@@ -27,6 +27,9 @@ def __getattr__(name):
     if name in ("MpDm", "thermal_state", "BraKetPair"):
         from . import mps as _mps
         return getattr(_mps, name)
+    if name in ("ChargeDiffusionDynamics", "InitElectron", "EDGE_THRESHOLD", "calc_r_square"):
+        from . import transport as _transport
+        return getattr(_transport, name)
     if name == "backend":
         from .mps.backend import backend
         return backend

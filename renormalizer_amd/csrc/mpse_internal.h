@@ -186,6 +186,9 @@ struct mpse_ctx {
   // mpse_mps_sandwich (mpse_mps_sandwich_stats; the order of include/mpsengine.h)
   enum SandwichStat { SW_CHAIN, SW_ENQUEUED, SW_SITES, SW_COUNT };
   long long sandwich_stats[SW_COUNT] = {0};
+  // mpse_mps_corr (mpse_mps_corr_stats; the order of include/mpsengine.h)
+  enum CorrStat { CR_CHAIN, CR_ENQUEUED, CR_SITES, CR_ENTRIES, CR_COUNT };
+  long long corr_stats[CR_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

@@ -183,6 +183,10 @@ _SIGNATURES = {
                           C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p, C.c_int, _dblp],
     "mpse_mps_sandwich_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_mps_sandwich_plan": [C.c_int, _i64p, C.c_int, _i64p, C.c_int],
+    "mpse_mps_corr": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p, C.c_int, C.POINTER(C.c_int),
+                      _dblp, _dblp, _dblp, _dblp],
+    "mpse_mps_corr_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_corr_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -244,6 +248,23 @@ def mps_sandwich_plan(dims, any_complex, lib=None):
     info = (C.c_int64 * len(SANDWICH_PLAN_INFO))()
     ok = lib.mpse_mps_sandwich_plan(len(rows), flat, int(bool(any_complex)), info, len(info))
     return bool(ok), dict(zip(SANDWICH_PLAN_INFO, (int(v) for v in info)))
+
+
+CORR_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid",
+                  "nsel_limit", "p_limit", "bond_fit_limit", "lds_fit_bytes")
+
+
+def mps_corr_plan(dims, nsel, any_complex, lib=None):
+    """Which path ``Engine.mps_corr`` takes for a chain, from its ``dims`` rows (D_l, d, danc, D_r) and the number of
+    selected sites alone (``mpse_mps_corr_plan``; needs the built library, no GPU).  Returns (chain kernels?, {info
+    name: value})."""
+    lib = lib or load_library()
+    rows = [[int(x) for x in r] for r in dims]
+    assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
+    flat = (C.c_int64 * max(4 * len(rows), 1))(*[x for r in rows for x in r])
+    info = (C.c_int64 * len(CORR_PLAN_INFO))()
+    ok = lib.mpse_mps_corr_plan(len(rows), flat, int(nsel), int(bool(any_complex)), info, len(info))
+    return bool(ok), dict(zip(CORR_PLAN_INFO, (int(v) for v in info)))
 
 
 class _Recording:
@@ -758,6 +779,54 @@ class Engine:
             (C.c_void_p * n)(*[t.ptr for t in w_sites]), (C.c_int * n)(*[t.code for t in w_sites]), dims,
             int(bool(conj_bra)), out))
         return complex(out[0], out[1])
+
+    # -- matrix of two-point functions of one-site operators
+    CORR_STATS = ("chain_kernel", "enqueued", "sites", "entries")
+
+    def mps_corr_stats(self):
+        """{name: count} of the ``mps_corr`` calls of this context, cumulative (``mpse_mps_corr_stats``): calls taken by
+        the chain kernels, calls taken by the enqueued products, sites walked, matrix entries produced."""
+        v = (C.c_int64 * len(self.CORR_STATS))()
+        self._check(self.lib.mpse_mps_corr_stats(self.ctx, v, len(v)))
+        return dict(zip(self.CORR_STATS, (int(x) for x in v)))
+
+    @staticmethod
+    def corr_dims(sites):
+        """The ``dims`` rows (D_l, d, danc, D_r) of a chain of site tensors (D_l, d[, danc], D_r)"""
+        rows = []
+        for i, t in enumerate(sites):
+            if t.ndim not in (3, 4):
+                raise ValueError(f"mps_corr: site {i} has shape {t.shape}")
+            rows.append([t.shape[0], t.shape[1], t.shape[2] if t.ndim == 4 else 1, t.shape[-1]])
+        return rows
+
+    def mps_corr(self, sites, sel, x_mats, y_mats, z_mats):
+        """C[k, l] = <psi| X_k Y_l |psi> (k < l), C[k, k] = <psi| Z_k |psi> for one-site operators on the sites ``sel``
+        (strictly ascending) of a chain of device site tensors (D_l, d[, danc], D_r), in one engine call
+        (``mpse_mps_corr``).  ``x_mats`` / ``y_mats`` / ``z_mats``: one (d, d) host matrix per selected site, first
+        index on the bra side; the ancilla leg of density-operator sites is traced.  Returns an (nsel, nsel) complex
+        array whose lower triangle is zero."""
+        rows = self.corr_dims(sites)
+        n, nsel = len(rows), len(sel)
+        if n == 0 or nsel == 0 or not (len(x_mats) == len(y_mats) == len(z_mats) == nsel):
+            raise ValueError(f"mps_corr: {n} sites, {nsel} selected, {len(x_mats)}/{len(y_mats)}/{len(z_mats)} matrices")
+        packed = []
+        for mats in (x_mats, y_mats, z_mats):
+            flat = []
+            for k, m in zip(sel, mats):
+                m = np.ascontiguousarray(m, dtype=np.complex128)
+                d = rows[k][1] if 0 <= int(k) < n else m.shape[0]
+                if m.shape != (d, d):
+                    raise ValueError(f"mps_corr: a local matrix of site {k} has shape {m.shape}, the site has d = {d}")
+                flat.append(m.reshape(-1))
+            packed.append(np.ascontiguousarray(np.concatenate(flat)).view(np.float64))
+        dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
+        out = np.zeros((nsel, nsel), dtype=np.complex128)
+        self._check(self.lib.mpse_mps_corr(
+            self.ctx, n, (C.c_void_p * n)(*[t.ptr for t in sites]), (C.c_int * n)(*[t.code for t in sites]), dims, nsel,
+            (C.c_int * nsel)(*[int(k) for k in sel]), packed[0].ctypes.data_as(_dblp), packed[1].ctypes.data_as(_dblp),
+            packed[2].ctypes.data_as(_dblp), out.ctypes.data_as(_dblp)))
+        return out
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""

@@ -690,6 +690,75 @@ class Mps:
                 k += 1
         return rho
 
+    def _local_matrix(self, symbol, dof):
+        """(site index, d x d matrix) of the one-site operator ``Op(symbol, dof)``: the single non-trivial site tensor
+        of its ``Mpo`` (first index on the bra side), times the scalars the builder may have left on the identity
+        sites.  Cached on the model."""
+        key = ("local_matrix", symbol, dof)
+        if key not in self.model.mpos:
+            mpo = Mpo(self.model, Op(symbol, dof))
+            idx = self.model.dof_to_siteidx[dof]
+            factor = 1.0
+            for i in range(len(mpo)):
+                w = np.asarray(mpo[i])
+                if w.shape[0] != 1 or w.shape[3] != 1:
+                    raise ValueError(f"Op({symbol!r}, {dof!r}) is not a one-site operator: MPO bonds {mpo.bond_dims}")
+                if i == idx:
+                    continue
+                if not np.array_equal(w[0, :, :, 0], w[0, 0, 0, 0] * np.eye(w.shape[1])):
+                    raise ValueError(f"Op({symbol!r}, {dof!r}) acts on site {i} besides its own site {idx}")
+                factor = factor * w[0, 0, 0, 0]
+            self.model.mpos[key] = (idx, np.asarray(mpo[idx])[0, :, :, 0] * factor)
+        return self.model.mpos[key]
+
+    def correlation_matrix(self, op_a, op_b, dofs, hermitian=False) -> np.ndarray:
+        """M[i, j] = <psi| op_a(dof_i) op_b(dof_j) |psi> for all pairs of ``dofs``, the diagonal with the local product
+        op_a . op_b, as ONE engine call per triangle (``Engine.mps_corr`` -> ``mpse_mps_corr``): a state opened with
+        op_a at one site is carried to the right and closed with op_b at every later requested site, instead of one
+        operator window per pair.  ``hermitian=True`` says M is Hermitian (op_b = op_a^+): the lower triangle is the
+        conjugate of the upper one; otherwise a second call with the roles of the two operators exchanged fills it
+        (operators on different sites commute).  Works for ``Mps`` and ``MpDm`` (the ancilla leg is traced); the
+        ``coeff`` factor is not included, as in ``expectations``.  When two requested dofs share a site (``HolsteinModel``
+        scheme 4) the entries are ``expectations`` of the pair operators instead."""
+        dofs = list(dofs)
+        n = len(dofs)
+        site_of = [self.model.dof_to_siteidx[d] for d in dofs]
+        if len(set(site_of)) < n:
+            pairs = [(i, j) for i in range(n) for j in (range(i, n) if hermitian else range(n))]
+            key = ("correlation_matrix", op_a, op_b, tuple(dofs), bool(hermitian))
+            if key not in self.model.mpos:
+                self.model.mpos[key] = [Mpo(self.model, Op(op_a, dofs[i]) * Op(op_b, dofs[j])) for i, j in pairs]
+            vals = np.atleast_1d(self.expectations(self.model.mpos[key]))
+            out = np.zeros((n, n), dtype=np.complex128)
+            for (i, j), v in zip(pairs, vals):
+                out[i, j] = v
+                if hermitian:
+                    out[j, i] = np.conj(v)
+            return out
+        order = sorted(range(n), key=lambda i: site_of[i])
+        sel = [site_of[i] for i in order]
+        a_mats = [self._local_matrix(op_a, dofs[i])[1] for i in order]
+        b_mats = [self._local_matrix(op_b, dofs[i])[1] for i in order]
+        ab_mats = [a @ b for a, b in zip(a_mats, b_mats)]
+        eng = get_engine()
+        upper = eng.mps_corr(self._mp, sel, a_mats, b_mats, ab_mats)
+        if hermitian:
+            full = upper + np.triu(upper, 1).conj().T
+        else:
+            # <op_a(i) op_b(j)> for site_i > site_j = <op_b(j) op_a(i)>: open with op_b, close with op_a
+            lower = eng.mps_corr(self._mp, sel, b_mats, a_mats, ab_mats)
+            full = upper + np.triu(lower, 1).T
+        out = np.zeros((n, n), dtype=np.complex128)
+        out[np.ix_(order, order)] = full
+        return out
+
+    def edof_rdm(self) -> np.ndarray:
+        """rho_ij = <a_i^dagger a_j> over the electronic degrees of freedom: the value of ``calc_edof_rdm()`` from one
+        walk over the chain inside the engine (``correlation_matrix``) instead of n_e (n_e + 1) / 2 operator windows
+        with a host read each.  ``calc_edof_rdm`` itself stays as it is (its values are pinned); the two sum in
+        different orders and agree to rounding."""
+        return self.correlation_matrix(r"a^\dagger", "a", self.model.e_dofs, hermitian=True)
+
     def calc_bond_singular_values(self) -> np.ndarray:
         """mps/mps.py:1759-1773: singular values at every bond (rows padded with zeros), on a copy"""
         mps = self.copy()

@@ -2,7 +2,12 @@
 
 ``TransportKubo`` is the Green-Kubo mobility: the current-current correlation function of a thermal state, one
 ``<bra| j |ket>`` of two density operators per recorded step (``Mps.matrix_element``, one engine call,
-``mpse_mps_sandwich``).  ``ChargeDiffusionDynamics`` and the spectral-function driver are not provided."""
+``mpse_mps_sandwich``).  ``ChargeDiffusionDynamics`` is the real-time diffusion of an electron created on the centre
+molecule, at zero or finite temperature; with ``rdm=True`` it records the reduced density matrix of the electron after
+every step, which is ``Mps.edof_rdm()``: one walk over the chain inside the engine (``mpse_mps_corr``).  The
+spectral-function driver is not provided."""
+from .dynamics import EDGE_THRESHOLD, ChargeDiffusionDynamics, InitElectron, calc_r_square
 from .kubo import TransportKubo, current_operators
 
-__all__ = ["TransportKubo", "current_operators"]
+__all__ = ["TransportKubo", "current_operators", "ChargeDiffusionDynamics", "InitElectron", "EDGE_THRESHOLD",
+           "calc_r_square"]
