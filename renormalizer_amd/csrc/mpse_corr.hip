@@ -9,23 +9,19 @@
 //   enqueued   the same two passes as products of the contraction kernel; the open rows are one stack of environments
 //              that grows by a row per selected site - every other chain
 // The host reads once, at the end.  A fixed summation order: the same inputs give the same bits.
-#include "mpse_internal.h"
+#include "mpse_chain.h"
 
 namespace {
 
-constexpr int CR_THREADS = 1024;          // one workgroup, 16 waves: the largest a launch may have
-constexpr int CR_WAVES = CR_THREADS / 64;
+constexpr int CR_WAVES = CHAIN_THREADS / 64;
 constexpr int CR_OUT_PER_THREAD = 4;      // entries of a new environment a thread accumulates in registers
-constexpr int64_t CR_LDS_MAX = 160 * 1024;   // LDS of a gfx950 compute unit; one workgroup may use all of it
-// rows of E / R and of the slice T are padded to an odd number of elements, as in k_overlap_chain: the threads of a wave
-// that work on different rows read a column, and an even pitch would put a column on few banks
-constexpr int64_t cr_pitch(int64_t d) { return d | 1; }
-constexpr int64_t cr_lds_bytes(int64_t D, int64_t es) { return (2 * D * cr_pitch(D) + CR_WAVES) * es; }
+// rows of E / R and of the slice T are padded (chain_pitch)
+constexpr int64_t cr_lds_bytes(int64_t D, int64_t es) { return (2 * D * chain_pitch(D) + CR_WAVES) * es; }
 constexpr int64_t cr_bond_limit() {
   // the largest power-of-two bond D whose complex environment and T slice (both D rows, padded) and the reduction
   // words fit, and whose environment has one entry per accumulator of the workgroup
   int64_t D = 1;
-  while (cr_lds_bytes(2 * D, 16) <= CR_LDS_MAX && 4 * D * D <= int64_t(CR_THREADS) * CR_OUT_PER_THREAD) D *= 2;
+  while (cr_lds_bytes(2 * D, 16) <= CHAIN_LDS_MAX && 4 * D * D <= int64_t(CHAIN_THREADS) * CR_OUT_PER_THREAD) D *= 2;
   return D;
 }
 constexpr int64_t CR_BOND_FIT = cr_bond_limit();
@@ -35,7 +31,7 @@ static_assert(CR_BOND_FIT == 64, "2 x 64 x 65 complex128 + 16 = 130 KB of 160 KB
 // behind at 64).  Chains between this and CR_BOND_FIT take the kernels only under MPSE_CORR_CHAIN=1.
 constexpr int64_t CR_BOND_MAX = 16;
 static_assert(CR_BOND_MAX <= CR_BOND_FIT, "the measured limit lies inside what fits");
-constexpr int64_t CR_P_MAX = 1 << 16;     // site offsets stay inside 32 bits: 64 * 65536 * 64 = 2^28 elements
+// d danc <= CHAIN_EXT_MAX keeps the site offsets inside 32 bits: 64 * 65536 * 64 = 2^28 elements
 constexpr int64_t CR_NSEL_MAX = 256;      // grid cap of k_corr_rows: one workgroup per compute unit of the chip
 
 struct CrSite {   // one row of the descriptor table (40 bytes, uploaded once per call)
@@ -57,82 +53,35 @@ struct CrPlan {
   int64_t lds;           // bytes of either launch, working dtype
 };
 
-// false: the table is not a chain (extent < 1, neighbours that do not match, an open end)
-bool corr_plan(int nsite, const int64_t* dims, int nsel, bool cplx, CrPlan* pl) {
-  *pl = CrPlan{false, false, 0, 0, 0, 0};
-  if (nsite < 1 || !dims) return false;
+bool corr_table_ok(int nsite, const int64_t* dims) { return chain_table_ok(nsite, dims, 4, {0}, {3}); }
+
+// the sizing of a table that is a chain
+CrPlan corr_plan(int nsite, const int64_t* dims, int nsel, bool cplx) {
+  CrPlan pl{false, false, 0, 0, 0, 0};
   bool fits = true;
   for (int i = 0; i < nsite; ++i) {
     const int64_t* d = dims + 4 * i;
-    for (int j = 0; j < 4; ++j)
-      if (d[j] < 1) return false;
-    if (i == 0 && d[0] != 1) return false;
-    if (i == nsite - 1 && d[3] != 1) return false;
-    if (i + 1 < nsite && d[3] != d[4]) return false;
-    for (int j : {0, 3}) pl->max_bond = d[j] > pl->max_bond ? d[j] : pl->max_bond;
-    if (pl->max_bond > CR_BOND_FIT || d[1] > CR_P_MAX || d[2] > CR_P_MAX || d[1] * d[2] > CR_P_MAX) {
+    for (int j : {0, 3}) pl.max_bond = d[j] > pl.max_bond ? d[j] : pl.max_bond;
+    if (pl.max_bond > CR_BOND_FIT || d[1] > CHAIN_EXT_MAX || d[2] > CHAIN_EXT_MAX ||
+        d[1] * d[2] > CHAIN_EXT_MAX) {
       fits = false;
       continue;
     }
-    const int64_t e_l = d[0] * cr_pitch(d[0]), e_r = d[3] * cr_pitch(d[3]), t = d[0] * cr_pitch(d[3]);
-    pl->e_elems = e_l > pl->e_elems ? e_l : pl->e_elems;
-    pl->e_elems = e_r > pl->e_elems ? e_r : pl->e_elems;
-    pl->t_elems = t > pl->t_elems ? t : pl->t_elems;
+    const int64_t e_l = d[0] * chain_pitch(d[0]), e_r = d[3] * chain_pitch(d[3]), t = d[0] * chain_pitch(d[3]);
+    pl.e_elems = e_l > pl.e_elems ? e_l : pl.e_elems;
+    pl.e_elems = e_r > pl.e_elems ? e_r : pl.e_elems;
+    pl.t_elems = t > pl.t_elems ? t : pl.t_elems;
   }
   if (!fits || nsel < 1 || nsel > CR_NSEL_MAX) {
-    pl->e_elems = pl->t_elems = 0;
-    return true;
+    pl.e_elems = pl.t_elems = 0;
+    return pl;
   }
-  pl->lds = (pl->e_elems + pl->t_elems + CR_WAVES) * (cplx ? 16 : 8);
-  pl->fit = pl->lds <= CR_LDS_MAX;
-  if (!pl->fit) pl->lds = pl->e_elems = pl->t_elems = 0;
-  pl->chain = pl->fit && pl->max_bond <= CR_BOND_MAX;
-  return true;
+  pl.lds = (pl.e_elems + pl.t_elems + CR_WAVES) * (cplx ? 16 : 8);
+  pl.fit = pl.lds <= CHAIN_LDS_MAX;
+  if (!pl.fit) pl.lds = pl.e_elems = pl.t_elems = 0;
+  pl.chain = pl.fit && pl.max_bond <= CR_BOND_MAX;
+  return pl;
 }
-
-// working element of the chain kernels
-template <bool CPLX>
-struct CrEl;
-template <>
-struct CrEl<false> {
-  using T = double;
-  __device__ static T zero() { return 0.0; }
-  __device__ static T one() { return 1.0; }
-  __device__ static T ld(const void* p, int /*cplx*/, int i) { return static_cast<const double*>(p)[i]; }
-  __device__ static T ldm(const double* m, int i) { return m[2 * i]; }   // local matrices are complex pairs
-  __device__ static bool nz(T a) { return a != 0.0; }
-  __device__ static T cj(T a) { return a; }
-  __device__ static void add(T& acc, T a) { acc += a; }
-  __device__ static void fma(T& acc, T a, T b) { acc += a * b; }
-  __device__ static T shfl_down(T a, int off) { return __shfl_down(a, off, 64); }
-  __device__ static double re(T a) { return a; }
-  __device__ static double im(T) { return 0.0; }
-};
-template <>
-struct CrEl<true> {
-  using T = double2;
-  __device__ static T zero() { return make_double2(0.0, 0.0); }
-  __device__ static T one() { return make_double2(1.0, 0.0); }
-  __device__ static T ld(const void* p, int cplx, int i) {
-    return cplx ? static_cast<const double2*>(p)[i] : make_double2(static_cast<const double*>(p)[i], 0.0);
-  }
-  __device__ static T ldm(const double* m, int i) { return make_double2(m[2 * i], m[2 * i + 1]); }
-  __device__ static bool nz(T a) { return a.x != 0.0 || a.y != 0.0; }
-  __device__ static T cj(T a) { return make_double2(a.x, -a.y); }
-  __device__ static void add(T& acc, T a) {
-    acc.x += a.x;
-    acc.y += a.y;
-  }
-  __device__ static void fma(T& acc, T a, T b) {
-    acc.x += a.x * b.x - a.y * b.y;
-    acc.y += a.x * b.y + a.y * b.x;
-  }
-  __device__ static T shfl_down(T a, int off) {
-    return make_double2(__shfl_down(a.x, off, 64), __shfl_down(a.y, off, 64));
-  }
-  __device__ static double re(T a) { return a.x; }
-  __device__ static double im(T a) { return a.y; }
-};
 
 // R_N = 1.  Per site from the right, per (sigma, a) in ascending order:
 //   T[c, b'] = sum_c' A[c, sigma, a, c'] R[b', c']                                          (into LDS)
@@ -140,12 +89,13 @@ struct CrEl<true> {
 // and at a selected site, for every sigma' whose Y[sigma', sigma] or Z[sigma', sigma] is not zero,
 //   S = sum_b' conj(A[b, sigma', a, b']) T[c, b'],  G[b, c] += Y[sigma', sigma] S,  Gd[b, c] += Z[sigma', sigma] S.
 // R' replaces R in LDS after the last (sigma, a); G and Gd go to gbuf.  A thread owns the entries (b, c) = tid + j *
-// CR_THREADS, c fastest: A[b, ..] is one address per b group, the reads of T run down a column of padded rows.  The walk
-// ends at the first selected site.
+// CHAIN_THREADS, c fastest: A[b, ..] is one address per b group, the reads of T run down a column of padded rows.  The
+// walk ends at the first selected site.
 template <bool CPLX>
-__global__ __launch_bounds__(CR_THREADS) void k_corr_right(const CrSite* __restrict__ sites, int nsite, int first,
-                                                           int e_elems, const double* __restrict__ mats, void* gbuf) {
-  using El = CrEl<CPLX>;
+__global__ __launch_bounds__(CHAIN_THREADS) void k_corr_right(const CrSite* __restrict__ sites, int nsite, int first,
+                                                              int e_elems, const double* __restrict__ mats,
+                                                              void* gbuf) {
+  using El = ChainEl<CPLX>;
   using T = typename El::T;
   extern __shared__ __attribute__((aligned(16))) double cr_lds[];
   T* R = reinterpret_cast<T*>(cr_lds);
@@ -168,7 +118,7 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_right(const CrSite* __restr
     for (int j = 0; j < CR_OUT_PER_THREAD; ++j) acc_r[j] = acc_g[j] = acc_d[j] = El::zero();
     for (int sa = 0; sa < p; ++sa) {
       const int sg = sa / danc, a = sa - sg * danc;
-      for (int o = tid; o < nT; o += CR_THREADS) {
+      for (int o = tid; o < nT; o += CHAIN_THREADS) {
         const int c = o / Dr, bp = o - c * Dr;
         const T* r_row = R + bp * pr;
         const int a0 = c * row + sa * Dr;
@@ -180,7 +130,7 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_right(const CrSite* __restr
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < CR_OUT_PER_THREAD; ++j) {
-        const int o = tid + j * CR_THREADS;
+        const int o = tid + j * CHAIN_THREADS;
         if (o < nE) {
           const int b = o / Dl, c = o - b * Dl;
           const T* t_row = Ts + c * pr;
@@ -210,7 +160,7 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_right(const CrSite* __restr
     }
 #pragma unroll
     for (int j = 0; j < CR_OUT_PER_THREAD; ++j) {
-      const int o = tid + j * CR_THREADS;
+      const int o = tid + j * CHAIN_THREADS;
       if (o < nE) {
         const int b = o / Dl, c = o - b * Dl;
         R[b * pn + c] = acc_r[j];
@@ -227,8 +177,9 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_right(const CrSite* __restr
 // sum of v over the workgroup in a fixed order: down the lanes of each wave, then a tree over the waves through LDS;
 // the value is valid in thread 0
 template <bool CPLX>
-__device__ typename CrEl<CPLX>::T cr_block_sum(typename CrEl<CPLX>::T v, typename CrEl<CPLX>::T* red, int tid) {
-  using El = CrEl<CPLX>;
+__device__ typename ChainEl<CPLX>::T cr_block_sum(typename ChainEl<CPLX>::T v, typename ChainEl<CPLX>::T* red,
+                                                  int tid) {
+  using El = ChainEl<CPLX>;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) El::add(v, El::shfl_down(v, off));
   if ((tid & 63) == 0) red[tid >> 6] = v;
@@ -250,10 +201,10 @@ __device__ typename CrEl<CPLX>::T cr_block_sum(typename CrEl<CPLX>::T v, typenam
 // with O = X_k at site sel[k] (its non-zero entries) and the identity elsewhere.  Threads take (b', c') with c'
 // fastest, as in k_overlap_chain.
 template <bool CPLX>
-__global__ __launch_bounds__(CR_THREADS) void k_corr_rows(const CrSite* __restrict__ sites, int last, int nsel,
-                                                          int e_elems, int t_elems, const double* __restrict__ mats,
-                                                          const void* __restrict__ gbuf, double* __restrict__ out) {
-  using El = CrEl<CPLX>;
+__global__ __launch_bounds__(CHAIN_THREADS) void k_corr_rows(const CrSite* __restrict__ sites, int last, int nsel,
+                                                             int e_elems, int t_elems, const double* __restrict__ mats,
+                                                             const void* __restrict__ gbuf, double* __restrict__ out) {
+  using El = ChainEl<CPLX>;
   using T = typename El::T;
   extern __shared__ __attribute__((aligned(16))) double cr_lds[];
   T* E = reinterpret_cast<T*>(cr_lds);
@@ -274,7 +225,7 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_rows(const CrSite* __restri
     if (l >= k) {
       const T* g = G + s.goff + (l == k ? Dl * Dl : 0);
       T part = El::zero();
-      for (int o = tid; o < Dl * Dl; o += CR_THREADS) {
+      for (int o = tid; o < Dl * Dl; o += CHAIN_THREADS) {
         const int b = o / Dl, c = o - b * Dl;
         El::fma(part, E[b * pe + c], g[o]);
       }
@@ -292,7 +243,7 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_rows(const CrSite* __restri
     for (int j = 0; j < CR_OUT_PER_THREAD; ++j) acc[j] = El::zero();
     for (int sa = 0; sa < p; ++sa) {
       const int sg = sa / danc, a = sa - sg * danc;
-      for (int o = tid; o < nT; o += CR_THREADS) {
+      for (int o = tid; o < nT; o += CHAIN_THREADS) {
         const int b = o / Dr, cc = o - b * Dr;
         const T* e_row = E + b * pe;
         const int a0 = sa * Dr + cc;
@@ -304,7 +255,7 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_rows(const CrSite* __restri
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < CR_OUT_PER_THREAD; ++j) {
-        const int o = tid + j * CR_THREADS;
+        const int o = tid + j * CHAIN_THREADS;
         if (o < nE) {
           const int bb = o / Dr, cc = o - bb * Dr;
           for (int sp = open ? 0 : sg; sp < (open ? d : sg + 1); ++sp) {
@@ -328,7 +279,7 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_rows(const CrSite* __restri
     }
 #pragma unroll
     for (int j = 0; j < CR_OUT_PER_THREAD; ++j) {
-      const int o = tid + j * CR_THREADS;
+      const int o = tid + j * CHAIN_THREADS;
       if (o < nE) {
         const int bb = o / Dr, cc = o - bb * Dr;
         E[bb * pe_new + cc] = acc[j];
@@ -336,18 +287,6 @@ __global__ __launch_bounds__(CR_THREADS) void k_corr_rows(const CrSite* __restri
     }
     __syncthreads();
   }
-}
-
-int corr_lds_attr(mpse_ctx* ctx) {
-  static std::mutex mu;
-  static bool done = false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (done) return MPSE_OK;
-  for (const void* f : {reinterpret_cast<const void*>(&k_corr_right<true>), reinterpret_cast<const void*>(&k_corr_right<false>),
-                        reinterpret_cast<const void*>(&k_corr_rows<true>), reinterpret_cast<const void*>(&k_corr_rows<false>)})
-    MPSE_HIP(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LDS_MAX));
-  done = true;
-  return MPSE_OK;
 }
 
 struct CrArgs {
@@ -396,36 +335,26 @@ int corr_chain(mpse_ctx* ctx, const CrArgs& a, bool cplx, const CrPlan& pl, doub
       ++k;
     }
   }
-  MPSE_TRY(corr_lds_attr(ctx));
+  MPSE_TRY(chain_lds_attr(ctx, {CHAIN_KERNELS(k_corr_right), CHAIN_KERNELS(k_corr_rows)}, CHAIN_LDS_MAX));
   const size_t es = cplx ? 16 : 8, n_out = (size_t)a.nsel * a.nsel * 2;
   TmpBuf tab(ctx), mbuf(ctx), gbuf(ctx), res(ctx);
-  MPSE_TRY(tab.alloc(rows.size() * sizeof(CrSite)));
+  MPSE_TRY(chain_stage_rows(ctx, tab, rows));
   MPSE_TRY(mbuf.alloc(mats.size() * sizeof(double)));
   MPSE_TRY(gbuf.alloc((size_t)g_elems * es));
   MPSE_TRY(res.alloc(n_out * sizeof(double)));
-  MPSE_TRY(stage_h2d(ctx, tab.p, rows.data(), rows.size() * sizeof(CrSite)));
   MPSE_TRY(stage_h2d(ctx, mbuf.p, mats.data(), mats.size() * sizeof(double)));
   MPSE_TRY(device_zero(ctx, res.p, n_out * sizeof(double)));
   const int first = a.sel[0], last = a.sel[a.nsel - 1];
-  if (cplx) {
-    hipLaunchKernelGGL((k_corr_right<true>), dim3(1), dim3(CR_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const CrSite>(), a.nsite, first, (int)pl.e_elems, mbuf.as<const double>(), gbuf.p);
-    hipLaunchKernelGGL((k_corr_rows<true>), dim3((unsigned)a.nsel), dim3(CR_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const CrSite>(), last, a.nsel, (int)pl.e_elems, (int)pl.t_elems, mbuf.as<const double>(),
-                       (const void*)gbuf.p, res.as<double>());
-  } else {
-    hipLaunchKernelGGL((k_corr_right<false>), dim3(1), dim3(CR_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const CrSite>(), a.nsite, first, (int)pl.e_elems, mbuf.as<const double>(), gbuf.p);
-    hipLaunchKernelGGL((k_corr_rows<false>), dim3((unsigned)a.nsel), dim3(CR_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const CrSite>(), last, a.nsel, (int)pl.e_elems, (int)pl.t_elems, mbuf.as<const double>(),
-                       (const void*)gbuf.p, res.as<double>());
-  }
+  CHAIN_LAUNCH(ctx, cplx, k_corr_right, 1, pl.lds, tab.as<const CrSite>(), a.nsite, first, (int)pl.e_elems,
+               mbuf.as<const double>(), gbuf.p);
+  CHAIN_LAUNCH(ctx, cplx, k_corr_rows, a.nsel, pl.lds, tab.as<const CrSite>(), last, a.nsel, (int)pl.e_elems,
+               (int)pl.t_elems, mbuf.as<const double>(), (const void*)gbuf.p, res.as<double>());
   MPSE_HIP(ctx, hipGetLastError());
   return mpse_memcpy_d2h(ctx, out_host, res.p, n_out * sizeof(double));
 }
 
 // Both passes as products of the contraction kernel, in one dtype: complex as soon as any site or local matrix is (real
-// sites are widened into pooled copies first, as in sandwich_enqueued).
+// sites are widened into pooled copies first, widen_site).
 //   right pass, site i from the last one down to sel[0], R (D_r, D_r) = [b', c']:
 //     Y1[(c, s, a), b'] = sum_c' A[(c, s, a), c'] R[b', c']
 //     R'[b, c] = sum_(s, a, b') conj(A[b, (s, a, b')]) Y1[c, (s, a, b')]
@@ -464,9 +393,7 @@ int corr_enqueued(mpse_ctx* ctx, const CrArgs& a, bool cplx, double* out_host) {
     const int64_t* d = a.dims + 4 * i;
     const int64_t n = d[0] * d[1] * d[2] * d[3];
     wide.emplace_back(new TmpBuf(ctx));
-    MPSE_TRY(wide.back()->alloc((size_t)n * 16));
-    MPSE_TRY(mpse_cast_f64_to_c128(ctx, wide.back()->p, a.sites[i], n));
-    site[i] = wide.back()->p;
+    MPSE_TRY(widen_site(ctx, *wide.back(), &site[i], n, n));
   }
   TmpBuf mbuf(ctx), gbuf(ctx), res(ctx), r0(ctx), r1(ctx), y1(ctx), y2(ctx);
   MPSE_TRY(mbuf.alloc(mats.size() * sizeof(double)));
@@ -568,19 +495,17 @@ int corr_enqueued(mpse_ctx* ctx, const CrArgs& a, bool cplx, double* out_host) {
 extern "C" {
 
 int mpse_mps_corr_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n) {
-  CrPlan pl;
-  const bool valid = corr_plan(nsite, dims, nsel, any_complex != 0, &pl);
-  const int64_t v[12] = {CR_BOND_MAX, CR_LDS_MAX, pl.chain ? pl.lds : 0, pl.fit ? pl.e_elems : 0,
-                         pl.fit ? pl.t_elems : 0, CR_THREADS, valid ? pl.max_bond : 0, valid ? 1 : 0,
-                         CR_NSEL_MAX, CR_P_MAX, CR_BOND_FIT, pl.fit ? pl.lds : 0};
-  for (int i = 0; i < n && info; ++i) info[i] = i < 12 ? v[i] : 0;
-  return valid && pl.chain ? 1 : 0;
+  const bool valid = corr_table_ok(nsite, dims);
+  const CrPlan pl = valid ? corr_plan(nsite, dims, nsel, any_complex != 0) : CrPlan{false, false, 0, 0, 0, 0};
+  const int64_t v[12] = {CR_BOND_MAX, CHAIN_LDS_MAX, pl.chain ? pl.lds : 0, pl.fit ? pl.e_elems : 0,
+                         pl.fit ? pl.t_elems : 0, CHAIN_THREADS, pl.max_bond, valid ? 1 : 0,
+                         CR_NSEL_MAX, CHAIN_EXT_MAX, CR_BOND_FIT, pl.fit ? pl.lds : 0};
+  plan_info_out(info, n, v, 12);
+  return pl.chain ? 1 : 0;
 }
 
 int mpse_mps_corr_stats(mpse_ctx* ctx, int64_t* counts, int n) {
-  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
-  for (int i = 0; i < n; ++i) counts[i] = i < mpse_ctx::CR_COUNT ? ctx->corr_stats[i] : 0;
-  return MPSE_OK;
+  return stats_out(ctx, &mpse_ctx::corr_stats, counts, n);
 }
 
 int mpse_mps_corr(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype, const int64_t* dims, int nsel,
@@ -589,17 +514,11 @@ int mpse_mps_corr(mpse_ctx* ctx, int nsite, const void* const* sites, const int*
   if (nsite < 1 || !sites || !dtype || !dims || nsel < 1 || !sel || !X || !Y || !Z || !out_host)
     return mpse_fail(ctx, MPSE_ERR_ARG, "mps_corr: null argument, no sites or no selection");
   bool cplx = false;
-  for (int i = 0; i < nsite; ++i) {
-    if (!sites[i]) return mpse_fail(ctx, MPSE_ERR_ARG, "mps_corr: null site %d", i);
-    if (dtype[i] != MPSE_F64 && dtype[i] != MPSE_C128)
-      return mpse_fail(ctx, MPSE_ERR_ARG, "mps_corr: unknown dtype at site %d", i);
-    cplx = cplx || dtype[i] == MPSE_C128;
-  }
+  MPSE_TRY(chain_scan_sites(ctx, "mps_corr", nsite, {sites}, {dtype}, &cplx));
   for (int k = 0; k < nsel; ++k)
     if (sel[k] < 0 || sel[k] >= nsite || (k > 0 && sel[k] <= sel[k - 1]))
       return mpse_fail(ctx, MPSE_ERR_SHAPE, "mps_corr: the selection is not strictly ascending inside [0, %d)", nsite);
-  CrPlan pl;
-  if (!corr_plan(nsite, dims, nsel, false, &pl))
+  if (!corr_table_ok(nsite, dims))
     return mpse_fail(ctx, MPSE_ERR_SHAPE,
                      "mps_corr: dims is not a chain (extents >= 1, matching neighbours, first and last bond 1)");
   if (MPSE_RECORDING(ctx))
@@ -607,13 +526,13 @@ int mpse_mps_corr(mpse_ctx* ctx, int nsite, const void* const* sites, const int*
   int64_t n_mat = 0;
   for (int k = 0; k < nsel; ++k) n_mat += dims[4 * sel[k] + 1] * dims[4 * sel[k] + 1];
   for (int64_t e = 0; e < n_mat && !cplx; ++e) cplx = X[2 * e + 1] != 0.0 || Y[2 * e + 1] != 0.0 || Z[2 * e + 1] != 0.0;
-  corr_plan(nsite, dims, nsel, cplx, &pl);
+  CrPlan pl = corr_plan(nsite, dims, nsel, cplx);
   MPSE_BIND(ctx);
   // MPSE_CORR_CHAIN=0 sends every chain through the enqueued products; =1 sends every chain whose launches fit through
   // the kernels, above the measured bond limit as well (measurements of that limit: tools/corr_bench.py)
-  const char* env = getenv("MPSE_CORR_CHAIN");
-  if (env && env[0] == '0') pl.chain = false;
-  if (env && env[0] == '1') pl.chain = pl.fit;
+  const char env = chain_env_switch("MPSE_CORR_CHAIN");
+  if (env == '0') pl.chain = false;
+  if (env == '1') pl.chain = pl.fit;
   const CrArgs args{nsite, sites, dtype, dims, nsel, sel, X, Y, Z};
   std::vector<double> res((size_t)nsel * nsel * 2, 0.0);
   if (pl.chain)

@@ -261,16 +261,26 @@ struct ProfScope {
 
 #define MPSE_BIND(ctx) MPSE_TRY(mpse_bind(ctx))
 
+// Body of a *_stats export: counts[i], i < n, are the counters `src` of the context, zeros behind them
+template <int COUNT>
+static inline int stats_out(const mpse_ctx* ctx, long long (mpse_ctx::*src)[COUNT], int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  for (int i = 0; i < n; ++i) counts[i] = i < COUNT ? (ctx->*src)[i] : 0;
+  return MPSE_OK;
+}
+
 // One launch of kern<true> or kern<false> on the context stream, picked by a host bool (complex / real vectors, 16-byte
 // accesses), with one argument list.  MPSE_LAUNCH_TF leaves the error check to the call site (one check after a group
-// of launches); MPSE_LAUNCH_TF_CHK checks at once.
-#define MPSE_LAUNCH_TF(ctx, flag, kern, grid, block, ...)                           \
-  do {                                                                              \
-    if (flag)                                                                       \
-      hipLaunchKernelGGL((kern<true>), grid, block, 0, (ctx)->stream, __VA_ARGS__); \
-    else                                                                            \
-      hipLaunchKernelGGL((kern<false>), grid, block, 0, (ctx)->stream, __VA_ARGS__); \
+// of launches); MPSE_LAUNCH_TF_CHK checks at once; MPSE_LAUNCH_TF_LDS is MPSE_LAUNCH_TF with `lds` bytes of dynamic LDS.
+#define MPSE_LAUNCH_TF_LDS(ctx, flag, kern, grid, block, lds, ...)                      \
+  do {                                                                                  \
+    if (flag)                                                                           \
+      hipLaunchKernelGGL((kern<true>), grid, block, lds, (ctx)->stream, __VA_ARGS__);   \
+    else                                                                                \
+      hipLaunchKernelGGL((kern<false>), grid, block, lds, (ctx)->stream, __VA_ARGS__);  \
   } while (0)
+#define MPSE_LAUNCH_TF(ctx, flag, kern, grid, block, ...) \
+  MPSE_LAUNCH_TF_LDS(ctx, flag, kern, grid, block, 0, __VA_ARGS__)
 #define MPSE_LAUNCH_TF_CHK(ctx, ...)     \
   do {                                   \
     MPSE_LAUNCH_TF(ctx, __VA_ARGS__);    \

@@ -5,28 +5,22 @@
 //   enqueued         2 N products through the contraction kernel, enqueued back to back from here with two pooled
 //                    temporaries (the products of Mps.dot, without its host round trips) - every other chain
 // Either way the host reads once, at the end.  No atomics, a fixed summation order: the same inputs give the same bits.
-#include "mpse_internal.h"
+#include "mpse_chain.h"
 
 namespace {
 
-constexpr int OV_THREADS = 1024;          // one workgroup, 16 waves: the largest a launch may have
 constexpr int OV_OUT_PER_THREAD = 4;      // entries of the new E a thread accumulates in registers over sigma
-constexpr int64_t OV_LDS_MAX = 160 * 1024;   // LDS of a gfx950 compute unit; one workgroup may use all of it
-// rows of E are padded to an odd number of elements: the threads of a wave that work on different rows b of
-// T[b, k'] = sum_k E[b, k] K[k, k'] read E[b, k] for one k at a time, a column, and an even pitch would put a column
-// on few banks
-constexpr int64_t ov_pitch(int64_t d) { return d | 1; }
-constexpr int64_t ov_lds_bytes(int64_t D, int64_t es) { return (D * ov_pitch(D) + D * D) * es; }
+constexpr int64_t ov_lds_bytes(int64_t D, int64_t es) { return (D * chain_pitch(D) + D * D) * es; }
 constexpr int64_t ov_bond_limit() {
   // the largest power-of-two bond D whose complex E (D x D, padded) and T slice (D x D) fit, and whose E has one entry
   // per accumulator of the workgroup
   int64_t D = 1;
-  while (ov_lds_bytes(2 * D, 16) <= OV_LDS_MAX && 4 * D * D <= int64_t(OV_THREADS) * OV_OUT_PER_THREAD) D *= 2;
+  while (ov_lds_bytes(2 * D, 16) <= CHAIN_LDS_MAX && 4 * D * D <= int64_t(CHAIN_THREADS) * OV_OUT_PER_THREAD) D *= 2;
   return D;
 }
 constexpr int64_t OV_BOND_MAX = ov_bond_limit();
 static_assert(OV_BOND_MAX == 64, "64 x 65 + 64 x 64 complex128 = 129 KB of 160 KB; 128 would need 516 KB");
-constexpr int64_t OV_P_MAX = 1 << 16;     // site offsets stay inside 32 bits: 64 * 65536 * 64 = 2^28 elements
+// p <= CHAIN_EXT_MAX keeps the site offsets inside 32 bits: 64 * 65536 * 64 = 2^28 elements
 
 struct OvSite {   // one row of the descriptor table (48 bytes, uploaded once per call)
   const void* bra;
@@ -45,65 +39,30 @@ struct OvPlan {
   int64_t lds;           // bytes, working dtype
 };
 
-// false: the table is not a chain (extent < 1, neighbours that do not match, an open end)
-bool overlap_plan(int nsite, const int64_t* dims, bool cplx, OvPlan* pl) {
-  *pl = OvPlan{false, 0, 0, 0, 0};
-  if (nsite < 1 || !dims) return false;
+bool overlap_table_ok(int nsite, const int64_t* dims) { return chain_table_ok(nsite, dims, 5, {0, 1}, {3, 4}); }
+
+// the sizing of a table that is a chain
+OvPlan overlap_plan(int nsite, const int64_t* dims, bool cplx) {
+  OvPlan pl{false, 0, 0, 0, 0};
   bool fits = true;
   for (int i = 0; i < nsite; ++i) {
     const int64_t* d = dims + 5 * i;
-    for (int j = 0; j < 5; ++j)
-      if (d[j] < 1) return false;
-    if (i == 0 && (d[0] != 1 || d[1] != 1)) return false;
-    if (i == nsite - 1 && (d[3] != 1 || d[4] != 1)) return false;
-    if (i + 1 < nsite && (d[3] != d[5] || d[4] != d[6])) return false;
-    for (int j : {0, 1, 3, 4}) pl->max_bond = d[j] > pl->max_bond ? d[j] : pl->max_bond;
-    if (pl->max_bond > OV_BOND_MAX || d[2] > OV_P_MAX) {
+    for (int j : {0, 1, 3, 4}) pl.max_bond = d[j] > pl.max_bond ? d[j] : pl.max_bond;
+    if (pl.max_bond > OV_BOND_MAX || d[2] > CHAIN_EXT_MAX) {
       fits = false;
       continue;
     }
-    const int64_t e_l = d[0] * ov_pitch(d[1]), e_r = d[3] * ov_pitch(d[4]), t = d[0] * d[4];
-    pl->e_elems = e_l > pl->e_elems ? e_l : pl->e_elems;
-    pl->e_elems = e_r > pl->e_elems ? e_r : pl->e_elems;
-    pl->t_elems = t > pl->t_elems ? t : pl->t_elems;
+    const int64_t e_l = d[0] * chain_pitch(d[1]), e_r = d[3] * chain_pitch(d[4]), t = d[0] * d[4];
+    pl.e_elems = e_l > pl.e_elems ? e_l : pl.e_elems;
+    pl.e_elems = e_r > pl.e_elems ? e_r : pl.e_elems;
+    pl.t_elems = t > pl.t_elems ? t : pl.t_elems;
   }
-  if (!fits) return true;
-  pl->lds = (pl->e_elems + pl->t_elems) * (cplx ? 16 : 8);
-  pl->chain = pl->lds <= OV_LDS_MAX;
-  if (!pl->chain) pl->lds = 0;
-  return true;
+  if (!fits) return pl;
+  pl.lds = (pl.e_elems + pl.t_elems) * (cplx ? 16 : 8);
+  pl.chain = pl.lds <= CHAIN_LDS_MAX;
+  if (!pl.chain) pl.lds = 0;
+  return pl;
 }
-
-// working element of the chain kernel
-template <bool CPLX>
-struct OvEl;
-template <>
-struct OvEl<false> {
-  using T = double;
-  __device__ static T zero() { return 0.0; }
-  __device__ static T one() { return 1.0; }
-  __device__ static T ld(const void* p, int /*cplx*/, int i) { return static_cast<const double*>(p)[i]; }
-  __device__ static T cj(T a) { return a; }
-  __device__ static void fma(T& acc, T a, T b) { acc += a * b; }
-  __device__ static double re(T a) { return a; }
-  __device__ static double im(T) { return 0.0; }
-};
-template <>
-struct OvEl<true> {
-  using T = double2;
-  __device__ static T zero() { return make_double2(0.0, 0.0); }
-  __device__ static T one() { return make_double2(1.0, 0.0); }
-  __device__ static T ld(const void* p, int cplx, int i) {
-    return cplx ? static_cast<const double2*>(p)[i] : make_double2(static_cast<const double*>(p)[i], 0.0);
-  }
-  __device__ static T cj(T a) { return make_double2(a.x, -a.y); }
-  __device__ static void fma(T& acc, T a, T b) {
-    acc.x += a.x * b.x - a.y * b.y;
-    acc.y += a.x * b.y + a.y * b.x;
-  }
-  __device__ static double re(T a) { return a.x; }
-  __device__ static double im(T a) { return a.y; }
-};
 
 // E_0 = 1;  per site, per sigma in ascending order:  T[b, k'] = sum_k E[b, k] K[k, sigma, k']  (into LDS), then
 // E'[b', k'] += sum_b op(B[b, sigma, b']) T[b, k']  (registers of the thread that owns (b', k')); E' replaces E in LDS
@@ -111,10 +70,10 @@ struct OvEl<true> {
 // B[b, sigma, b'] is one address per b' group.  The result E_N[0, 0] goes to out[0..1] and, when pub is set, to the
 // mapped host buffer followed by the sequence number (publish_collect).
 template <bool CPLX>
-__global__ __launch_bounds__(OV_THREADS) void k_overlap_chain(const OvSite* __restrict__ sites, int nsite, int conj_bra,
-                                                              int e_elems, double* out, double* pub,
-                                                              volatile double* seq_slot, double seq) {
-  using El = OvEl<CPLX>;
+__global__ __launch_bounds__(CHAIN_THREADS) void k_overlap_chain(const OvSite* __restrict__ sites, int nsite,
+                                                                 int conj_bra, int e_elems, double* out, double* pub,
+                                                                 volatile double* seq_slot, double seq) {
+  using El = ChainEl<CPLX>;
   using T = typename El::T;
   extern __shared__ __attribute__((aligned(16))) double ov_lds[];
   T* E = reinterpret_cast<T*>(ov_lds);
@@ -133,7 +92,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_overlap_chain(const OvSite* __re
 #pragma unroll
     for (int j = 0; j < OV_OUT_PER_THREAD; ++j) acc[j] = El::zero();
     for (int sg = 0; sg < p; ++sg) {
-      for (int o = tid; o < nT; o += OV_THREADS) {
+      for (int o = tid; o < nT; o += CHAIN_THREADS) {
         const int b = o / Dkr, kk = o - b * Dkr;
         const T* e_row = E + b * pe;
         const int k0 = sg * Dkr + kk;
@@ -145,7 +104,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_overlap_chain(const OvSite* __re
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < OV_OUT_PER_THREAD; ++j) {
-        const int o = tid + j * OV_THREADS;
+        const int o = tid + j * CHAIN_THREADS;
         if (o < nE) {
           const int bb = o / Dkr, kk = o - bb * Dkr;
           const int b0 = sg * Dbr + bb;
@@ -163,7 +122,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_overlap_chain(const OvSite* __re
     }
 #pragma unroll
     for (int j = 0; j < OV_OUT_PER_THREAD; ++j) {
-      const int o = tid + j * OV_THREADS;
+      const int o = tid + j * CHAIN_THREADS;
       if (o < nE) {
         const int bb = o / Dkr, kk = o - bb * Dkr;
         E[bb * pe_new + kk] = acc[j];
@@ -171,31 +130,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_overlap_chain(const OvSite* __re
     }
     __syncthreads();
   }
-  if (tid == 0) {
-    const double re = El::re(E[0]), im = El::im(E[0]);
-    out[0] = re;
-    out[1] = im;
-    if (pub) {
-      pub[0] = re;
-      pub[1] = im;
-      __threadfence_system();
-      *seq_slot = seq;
-      __threadfence_system();
-    }
-  }
-}
-
-int chain_lds_attr(mpse_ctx* ctx) {
-  static std::mutex mu;
-  static bool done = false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (done) return MPSE_OK;
-  MPSE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_overlap_chain<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)OV_LDS_MAX));
-  MPSE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_overlap_chain<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)OV_LDS_MAX));
-  done = true;
-  return MPSE_OK;
+  if (tid == 0) chain_publish2(out, pub, seq_slot, seq, El::re(E[0]), El::im(E[0]));
 }
 
 int overlap_chain(mpse_ctx* ctx, int nsite, const void* const* bra, const int* bra_dtype, const void* const* ket,
@@ -206,22 +141,11 @@ int overlap_chain(mpse_ctx* ctx, int nsite, const void* const* bra, const int* b
     rows[i] = OvSite{bra[i], ket[i], (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4],
                      bra_dtype[i] == MPSE_C128, ket_dtype[i] == MPSE_C128, 0};
   }
-  MPSE_TRY(chain_lds_attr(ctx));
-  TmpBuf tab(ctx), res(ctx);
-  MPSE_TRY(tab.alloc(rows.size() * sizeof(OvSite)));
-  MPSE_TRY(res.alloc(2 * sizeof(double)));
-  MPSE_TRY(stage_h2d(ctx, tab.p, rows.data(), rows.size() * sizeof(OvSite)));
-  const PublishAt at = publish_target(ctx, true, mpse_ctx::PIN_SCALAR2);
-  if (cplx)
-    hipLaunchKernelGGL((k_overlap_chain<true>), dim3(1), dim3(OV_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const OvSite>(), nsite, conj_bra, (int)pl.e_elems, res.as<double>(), at.pub, at.seq_slot,
-                       at.seq);
-  else
-    hipLaunchKernelGGL((k_overlap_chain<false>), dim3(1), dim3(OV_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const OvSite>(), nsite, conj_bra, (int)pl.e_elems, res.as<double>(), at.pub, at.seq_slot,
-                       at.seq);
-  MPSE_HIP(ctx, hipGetLastError());
-  return publish_collect(ctx, at, res.p, 0, 1, 2, mpse_ctx::PIN_SCALAR2, out2);
+  MPSE_TRY(chain_lds_attr(ctx, {CHAIN_KERNELS(k_overlap_chain)}, CHAIN_LDS_MAX));
+  return chain_scalar_launch(ctx, rows, [&](const OvSite* tab, double* res, const PublishAt& at) {
+    CHAIN_LAUNCH(ctx, cplx, k_overlap_chain, 1, pl.lds, tab, nsite, conj_bra, (int)pl.e_elems, res, at.pub, at.seq_slot,
+                 at.seq);
+  }, out2);
 }
 
 // the two products per site of Mps.dot, enqueued from here: T = E . K as (Db_l, p Dk_r), E' = op(B)^T . T with B as
@@ -251,11 +175,7 @@ int overlap_enqueued(mpse_ctx* ctx, int nsite, const void* const* bra, const int
                        idx1(Dkr, 1), idx1(Dbr, Dkr), idx1(Dkr, 1), 1, 0, 0, 0, bra[i], tbuf.p, ebuf.p));
     e_dt = (t_dt == MPSE_C128 || bra_dtype[i] == MPSE_C128) ? MPSE_C128 : MPSE_F64;
   }
-  // E_N is 1 x 1; the word behind a real one is inside the buffer and not used
-  MPSE_TRY(publish_and_wait(ctx, ebuf.as<double>(), 2, mpse_ctx::PIN_SCALAR2));
-  out2[0] = ctx->pinned[mpse_ctx::PIN_SCALAR2];
-  out2[1] = e_dt == MPSE_C128 ? ctx->pinned[mpse_ctx::PIN_SCALAR2 + 1] : 0.0;
-  return MPSE_OK;
+  return chain_scalar_result(ctx, ebuf.p, e_dt == MPSE_C128, out2);   // E_N is 1 x 1
 }
 
 }  // namespace
@@ -263,18 +183,16 @@ int overlap_enqueued(mpse_ctx* ctx, int nsite, const void* const* bra, const int
 extern "C" {
 
 int mpse_mps_overlap_plan(int nsite, const int64_t* dims, int any_complex, int64_t* info, int n) {
-  OvPlan pl;
-  const bool valid = overlap_plan(nsite, dims, any_complex != 0, &pl);
-  const int64_t v[8] = {OV_BOND_MAX, OV_LDS_MAX, pl.chain ? pl.lds : 0, pl.chain ? pl.e_elems : 0,
-                        pl.chain ? pl.t_elems : 0, OV_THREADS, valid ? pl.max_bond : 0, valid ? 1 : 0};
-  for (int i = 0; i < n && info; ++i) info[i] = i < 8 ? v[i] : 0;
-  return valid && pl.chain ? 1 : 0;
+  const bool valid = overlap_table_ok(nsite, dims);
+  const OvPlan pl = valid ? overlap_plan(nsite, dims, any_complex != 0) : OvPlan{false, 0, 0, 0, 0};
+  const int64_t v[8] = {OV_BOND_MAX, CHAIN_LDS_MAX, pl.lds, pl.chain ? pl.e_elems : 0, pl.chain ? pl.t_elems : 0,
+                        CHAIN_THREADS, pl.max_bond, valid ? 1 : 0};
+  plan_info_out(info, n, v, 8);
+  return pl.chain ? 1 : 0;
 }
 
 int mpse_mps_overlap_stats(mpse_ctx* ctx, int64_t* counts, int n) {
-  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
-  for (int i = 0; i < n; ++i) counts[i] = i < mpse_ctx::OV_COUNT ? ctx->overlap_stats[i] : 0;
-  return MPSE_OK;
+  return stats_out(ctx, &mpse_ctx::overlap_stats, counts, n);
 }
 
 int mpse_mps_overlap(mpse_ctx* ctx, int nsite, const void* const* bra, const int* bra_dtype, const void* const* ket,
@@ -283,21 +201,16 @@ int mpse_mps_overlap(mpse_ctx* ctx, int nsite, const void* const* bra, const int
   if (nsite < 1 || !bra || !bra_dtype || !ket || !ket_dtype || !dims || !out_re_im_host)
     return mpse_fail(ctx, MPSE_ERR_ARG, "mps_overlap: null argument or no sites");
   bool cplx = false;
-  for (int i = 0; i < nsite; ++i) {
-    if (!bra[i] || !ket[i]) return mpse_fail(ctx, MPSE_ERR_ARG, "mps_overlap: null site %d", i);
-    for (int dt : {bra_dtype[i], ket_dtype[i]}) {
-      if (dt != MPSE_F64 && dt != MPSE_C128) return mpse_fail(ctx, MPSE_ERR_ARG, "mps_overlap: unknown dtype at site %d", i);
-      cplx = cplx || dt == MPSE_C128;
-    }
-  }
-  OvPlan pl;
-  if (!overlap_plan(nsite, dims, cplx, &pl))
+  MPSE_TRY(chain_scan_sites(ctx, "mps_overlap", nsite, {bra, ket}, {bra_dtype, ket_dtype}, &cplx));
+  if (!overlap_table_ok(nsite, dims))
     return mpse_fail(ctx, MPSE_ERR_SHAPE,
                      "mps_overlap: dims is not a chain (extents >= 1, matching neighbours, first and last bond 1)");
+  // No refusal while a deferred list is recorded, unlike mpse_mps_sandwich and mpse_mps_corr: the enqueued path goes
+  // through gemm_call, which does not record, so the call runs at once on either path
+  OvPlan pl = overlap_plan(nsite, dims, cplx);
   MPSE_BIND(ctx);
   // MPSE_OVERLAP_CHAIN=0 sends every chain through the enqueued products (measurements: tools/overlap_bench.py)
-  const char* env = getenv("MPSE_OVERLAP_CHAIN");
-  if (env && env[0] == '0') pl.chain = false;
+  if (chain_env_switch("MPSE_OVERLAP_CHAIN") == '0') pl.chain = false;
   double res[2] = {0.0, 0.0};
   if (pl.chain)
     MPSE_TRY(overlap_chain(ctx, nsite, bra, bra_dtype, ket, ket_dtype, dims, cplx, conj_bra, pl, res));

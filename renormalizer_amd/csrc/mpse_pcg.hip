@@ -766,8 +766,7 @@ int mpse_pcg_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff* h, int 
 }
 
 int mpse_pcg_batch_stats(mpse_ctx* ctx, int64_t* counts, int n) {
-  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
-  for (int i = 0; i < n; ++i) counts[i] = i < mpse_ctx::PB_COUNT ? ctx->pcg_batch_stats[i] : 0;
+  MPSE_TRY(stats_out(ctx, &mpse_ctx::pcg_batch_stats, counts, n));
   if (n > mpse_ctx::PB_COUNT) counts[mpse_ctx::PB_COUNT] = PCGB_MAX;
   return MPSE_OK;
 }
@@ -859,9 +858,7 @@ int mpse_pcg_sum(mpse_ctx* ctx, int dtype, int nterms, const mpse_heff_ft* terms
 }
 
 int mpse_pcg_sum_stats(mpse_ctx* ctx, int64_t* counts, int n) {
-  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
-  for (int i = 0; i < n; ++i) counts[i] = i < mpse_ctx::PSS_COUNT ? ctx->pcg_sum_stats[i] : 0;
-  return MPSE_OK;
+  return stats_out(ctx, &mpse_ctx::pcg_sum_stats, counts, n);
 }
 
 int mpse_site_factor_ft(mpse_ctx* ctx, const mpse_heff_ft* h, void* S_f64) {

@@ -6,26 +6,20 @@
 //   enqueued          the environment-update plan of mpse_env_update (left domain, no unit channel) site after site on
 //                     two pooled environments, enqueued back to back from here
 // Either way the host reads once, at the end.  No atomics, a fixed summation order: the same inputs give the same bits.
-#include "mpse_internal.h"
+#include "mpse_chain.h"
 
 namespace {
 
-constexpr int SW_THREADS = 1024;             // one workgroup, 16 waves: the largest a launch may have
 // entries of the new E a thread accumulates in registers over (sigma, a): SW_PLANES entries (b', k') of the plane
 // Dbr x Dkr, each in all of the up to SW_CHANNELS outgoing MPO channels g'
 constexpr int SW_PLANES = 2;
 constexpr int SW_CHANNELS = 8;
 constexpr int SW_ACC = SW_PLANES * SW_CHANNELS;
-constexpr int64_t SW_LDS_MAX = 160 * 1024;   // LDS of a gfx950 compute unit; one workgroup may use all of it
-constexpr int64_t SW_EXT_MAX = 1 << 16;      // extents above this never take the chain kernel (32-bit offsets)
 constexpr int64_t SW_SITE_ELEMS_MAX = 1ll << 30;   // elements of one site tensor: offsets stay inside 32 bits
 // Multiply-adds (of the working type) of the heaviest site above which the enqueued products are faster than one
 // workgroup although the chain still fits: measured with tools/sandwich_bench.py, profiles/sandwich.md
 constexpr int64_t SW_WORK_MAX = 1ll << 62;
 constexpr int64_t SW_WORK_CLAMP = INT64_MAX;   // what the work of an absurd table is reported as
-// rows of E are padded to an odd number of elements, as in k_overlap_chain: the threads of a wave that form different
-// rows of T read a column of E, and an even pitch would put a column on few banks
-constexpr int64_t sw_pitch(int64_t d) { return d | 1; }
 
 struct SwSite {   // one row of the descriptor table (72 bytes, uploaded once per call)
   const void* bra;
@@ -48,111 +42,65 @@ struct SwPlan {
   int64_t work;       // multiply-adds of the heaviest site, dense: d danc (Dbl wl Dkl Dkr + d wl Dbl Dbr Dkr)
 };
 
-// false: the table is not a chain (extent < 1, neighbours that do not match, an open end)
-bool sandwich_plan(int nsite, const int64_t* dims, bool cplx, SwPlan* pl) {
-  *pl = SwPlan{false, 0, 0, 0, 0, 0, 0, 0};
-  if (nsite < 1 || !dims) return false;
+bool sandwich_table_ok(int nsite, const int64_t* dims) { return chain_table_ok(nsite, dims, 8, {0, 1, 2}, {5, 6, 7}); }
+
+// the sizing of a table that is a chain
+SwPlan sandwich_plan(int nsite, const int64_t* dims, bool cplx) {
+  SwPlan pl{false, 0, 0, 0, 0, 0, 0, 0};
   bool fits = true, bonds_ok = true;
   for (int i = 0; i < nsite; ++i) {
     const int64_t* s = dims + 8 * i;
-    for (int j = 0; j < 8; ++j)
-      if (s[j] < 1) return false;
-    if (i == 0 && (s[0] != 1 || s[1] != 1 || s[2] != 1)) return false;
-    if (i == nsite - 1 && (s[5] != 1 || s[6] != 1 || s[7] != 1)) return false;
-    if (i + 1 < nsite && (s[5] != s[8] || s[6] != s[9] || s[7] != s[10])) return false;
     const int64_t Dbl = s[0], Dkl = s[1], wl = s[2], d = s[3], danc = s[4], Dbr = s[5], Dkr = s[6], wr = s[7];
     const double work = double(d) * double(danc) *
                         (double(Dbl) * double(wl) * double(Dkl) * double(Dkr) +
                          double(d) * double(wl) * double(Dbl) * double(Dbr) * double(Dkr));
     const int64_t wk = work >= 9.0e18 ? SW_WORK_CLAMP : int64_t(work);
-    pl->work = wk > pl->work ? wk : pl->work;
+    pl.work = wk > pl.work ? wk : pl.work;
     // what the launch needs depends on the bonds alone; the physical extents only have to keep offsets inside 32 bits
     bool small = true;
-    for (int j : {0, 1, 2, 5, 6, 7}) small = small && s[j] <= SW_EXT_MAX;
+    for (int j : {0, 1, 2, 5, 6, 7}) small = small && s[j] <= CHAIN_EXT_MAX;
     if (!small) {
       bonds_ok = false;
       continue;
     }
     const double site_max = double(SW_SITE_ELEMS_MAX);
-    if (d > SW_EXT_MAX || danc > SW_EXT_MAX || double(Dbl) * d * danc * Dbr > site_max ||
+    if (d > CHAIN_EXT_MAX || danc > CHAIN_EXT_MAX || double(Dbl) * d * danc * Dbr > site_max ||
         double(Dkl) * d * danc * Dkr > site_max || double(wl) * d * d * wr > site_max)
       fits = false;
-    const int64_t e_l = Dbl * wl * sw_pitch(Dkl), e_r = Dbr * wr * sw_pitch(Dkr), t = Dbl * wl * Dkr;
-    const int64_t acc = SW_CHANNELS * ((Dbr * Dkr + SW_THREADS - 1) / SW_THREADS);
-    pl->w_max = wr > pl->w_max ? wr : pl->w_max;
-    pl->e_elems = e_l > pl->e_elems ? e_l : pl->e_elems;
-    pl->e_elems = e_r > pl->e_elems ? e_r : pl->e_elems;
-    pl->t_elems = t > pl->t_elems ? t : pl->t_elems;
-    pl->acc = acc > pl->acc ? acc : pl->acc;
+    const int64_t e_l = Dbl * wl * chain_pitch(Dkl), e_r = Dbr * wr * chain_pitch(Dkr), t = Dbl * wl * Dkr;
+    const int64_t acc = SW_CHANNELS * ((Dbr * Dkr + CHAIN_THREADS - 1) / CHAIN_THREADS);
+    pl.w_max = wr > pl.w_max ? wr : pl.w_max;
+    pl.e_elems = e_l > pl.e_elems ? e_l : pl.e_elems;
+    pl.e_elems = e_r > pl.e_elems ? e_r : pl.e_elems;
+    pl.t_elems = t > pl.t_elems ? t : pl.t_elems;
+    pl.acc = acc > pl.acc ? acc : pl.acc;
   }
   if (!bonds_ok) {
-    pl->e_elems = pl->t_elems = pl->acc = 0;
-    return true;
+    pl.e_elems = pl.t_elems = pl.acc = 0;
+    return pl;
   }
-  const int64_t lds = (pl->e_elems + pl->t_elems) * (cplx ? 16 : 8);
-  pl->lds_fit = fits && lds <= SW_LDS_MAX && pl->acc <= SW_ACC && pl->w_max <= SW_CHANNELS ? lds : 0;
-  pl->chain = pl->lds_fit > 0 && pl->work <= SW_WORK_MAX;
-  pl->lds = pl->chain ? lds : 0;
-  return true;
+  const int64_t lds = (pl.e_elems + pl.t_elems) * (cplx ? 16 : 8);
+  pl.lds_fit = fits && lds <= CHAIN_LDS_MAX && pl.acc <= SW_ACC && pl.w_max <= SW_CHANNELS ? lds : 0;
+  pl.chain = pl.lds_fit > 0 && pl.work <= SW_WORK_MAX;
+  pl.lds = pl.chain ? lds : 0;
+  return pl;
 }
-
-// W is small and read at addresses that are the same for the whole workgroup: through the constant address space the
-// loads are scalar, and the branch on a zero entry is taken by the wave, not by its lanes
-using cdouble_p = const __attribute__((address_space(4))) double*;
-
-// working element of the chain kernel
-template <bool CPLX>
-struct SwEl;
-template <>
-struct SwEl<false> {
-  using T = double;
-  __device__ static T zero() { return 0.0; }
-  __device__ static T one() { return 1.0; }
-  __device__ static T ld(const void* p, int /*cplx*/, int i) { return static_cast<const double*>(p)[i]; }
-  __device__ static T ldc(const void* p, int /*cplx*/, int i) { return ((cdouble_p)p)[i]; }
-  __device__ static bool nz(T a) { return a != 0.0; }
-  __device__ static T cj(T a) { return a; }
-  __device__ static void fma(T& acc, T a, T b) { acc += a * b; }
-  __device__ static double re(T a) { return a; }
-  __device__ static double im(T) { return 0.0; }
-};
-template <>
-struct SwEl<true> {
-  using T = double2;
-  __device__ static T zero() { return make_double2(0.0, 0.0); }
-  __device__ static T one() { return make_double2(1.0, 0.0); }
-  __device__ static T ld(const void* p, int cplx, int i) {
-    return cplx ? static_cast<const double2*>(p)[i] : make_double2(static_cast<const double*>(p)[i], 0.0);
-  }
-  __device__ static T ldc(const void* p, int cplx, int i) {
-    cdouble_p q = (cdouble_p)p;
-    return cplx ? make_double2(q[2 * i], q[2 * i + 1]) : make_double2(q[i], 0.0);
-  }
-  __device__ static bool nz(T a) { return a.x != 0.0 || a.y != 0.0; }
-  __device__ static T cj(T a) { return make_double2(a.x, -a.y); }
-  __device__ static void fma(T& acc, T a, T b) {
-    acc.x += a.x * b.x - a.y * b.y;
-    acc.y += a.x * b.y + a.y * b.x;
-  }
-  __device__ static double re(T a) { return a.x; }
-  __device__ static double im(T a) { return a.y; }
-};
 
 // E_0 = 1 (1 x 1 x 1).  Per site and per (sigma, a) in ascending order:
 //   T[b, g, k'] = sum_k E[b, g, k] K[k, sigma, a, k']                                     (into LDS)
 //   for every (sigma', g) whose row W[g, sigma', sigma, :] holds a non-zero entry:
 //     S[b', k']       = sum_b op(B[b, sigma', a, b']) T[b, g, k']                          (register of the owner)
 //     E'[b', g', k'] += W[g, sigma', sigma, g'] S[b', k']   for the non-zero entries g'    (registers of the owner)
-// E' replaces E in LDS after the last (sigma, a).  A thread owns the entries (b', k') = tid + jj * SW_THREADS, jj <
+// E' replaces E in LDS after the last (sigma, a).  A thread owns the entries (b', k') = tid + jj * CHAIN_THREADS, jj <
 // SW_PLANES, of every channel g' < SW_CHANNELS: SW_ACC accumulators, all indexed statically (sandwich_plan).  (b', k')
 // runs with k' fastest: the reads of K are contiguous, those of T conflict free, B[b, sigma', a, b'] is one address per
 // b' group.  The result E_N[0, 0, 0] goes to out[0..1] and, when pub is set, to the mapped host buffer followed by the
 // sequence number (publish_collect).
 template <bool CPLX>
-__global__ __launch_bounds__(SW_THREADS) void k_sandwich_chain(const SwSite* __restrict__ sites, int nsite,
-                                                               int conj_bra, int e_elems, double* out, double* pub,
-                                                               volatile double* seq_slot, double seq) {
-  using El = SwEl<CPLX>;
+__global__ __launch_bounds__(CHAIN_THREADS) void k_sandwich_chain(const SwSite* __restrict__ sites, int nsite,
+                                                                  int conj_bra, int e_elems, double* out, double* pub,
+                                                                  volatile double* seq_slot, double seq) {
+  using El = ChainEl<CPLX>;
   using T = typename El::T;
   extern __shared__ __attribute__((aligned(16))) double sw_lds[];
   T* E = reinterpret_cast<T*>(sw_lds);
@@ -175,7 +123,7 @@ __global__ __launch_bounds__(SW_THREADS) void k_sandwich_chain(const SwSite* __r
       for (int gp = 0; gp < SW_CHANNELS; ++gp) acc[jj][gp] = El::zero();
     for (int sa = 0; sa < p; ++sa) {
       const int sg = sa / danc, a = sa - sg * danc;
-      for (int o = tid; o < nT; o += SW_THREADS) {
+      for (int o = tid; o < nT; o += CHAIN_THREADS) {
         const int r = o / Dkr, kk = o - r * Dkr;
         const T* e_row = E + r * pe;
         const int k0 = sa * Dkr + kk;
@@ -194,8 +142,8 @@ __global__ __launch_bounds__(SW_THREADS) void k_sandwich_chain(const SwSite* __r
           const int b_base = (sp * danc + a) * Dbr;
 #pragma unroll
           for (int jj = 0; jj < SW_PLANES; ++jj) {
-            const int o = tid + jj * SW_THREADS;
-            if (jj * SW_THREADS >= P) break;
+            const int o = tid + jj * CHAIN_THREADS;
+            if (jj * CHAIN_THREADS >= P) break;
             T S = El::zero();
             if (o < P) {
               const int bb = o / Dkr, kk = o - bb * Dkr;
@@ -222,7 +170,7 @@ __global__ __launch_bounds__(SW_THREADS) void k_sandwich_chain(const SwSite* __r
     }
 #pragma unroll
     for (int jj = 0; jj < SW_PLANES; ++jj) {
-      const int o = tid + jj * SW_THREADS;
+      const int o = tid + jj * CHAIN_THREADS;
       if (o < P) {
         const int bb = o / Dkr, kk = o - bb * Dkr;
         T* e_new = E + bb * wr * pe_new + kk;
@@ -233,31 +181,7 @@ __global__ __launch_bounds__(SW_THREADS) void k_sandwich_chain(const SwSite* __r
     }
     __syncthreads();
   }
-  if (tid == 0) {
-    const double re = El::re(E[0]), im = El::im(E[0]);
-    out[0] = re;
-    out[1] = im;
-    if (pub) {
-      pub[0] = re;
-      pub[1] = im;
-      __threadfence_system();
-      *seq_slot = seq;
-      __threadfence_system();
-    }
-  }
-}
-
-int sandwich_lds_attr(mpse_ctx* ctx) {
-  static std::mutex mu;
-  static bool done = false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (done) return MPSE_OK;
-  MPSE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sandwich_chain<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)SW_LDS_MAX));
-  MPSE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sandwich_chain<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)SW_LDS_MAX));
-  done = true;
-  return MPSE_OK;
+  if (tid == 0) chain_publish2(out, pub, seq_slot, seq, El::re(E[0]), El::im(E[0]));
 }
 
 struct SwArgs {
@@ -280,22 +204,11 @@ int sandwich_chain(mpse_ctx* ctx, const SwArgs& a, bool cplx, const SwPlan& pl, 
                      (int)s[6], (int)s[7], a.bra_dtype[i] == MPSE_C128, a.ket_dtype[i] == MPSE_C128,
                      a.w_dtype[i] == MPSE_C128, 0};
   }
-  MPSE_TRY(sandwich_lds_attr(ctx));
-  TmpBuf tab(ctx), res(ctx);
-  MPSE_TRY(tab.alloc(rows.size() * sizeof(SwSite)));
-  MPSE_TRY(res.alloc(2 * sizeof(double)));
-  MPSE_TRY(stage_h2d(ctx, tab.p, rows.data(), rows.size() * sizeof(SwSite)));
-  const PublishAt at = publish_target(ctx, true, mpse_ctx::PIN_SCALAR2);
-  if (cplx)
-    hipLaunchKernelGGL((k_sandwich_chain<true>), dim3(1), dim3(SW_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const SwSite>(), a.nsite, a.conj_bra, (int)pl.e_elems, res.as<double>(), at.pub,
-                       at.seq_slot, at.seq);
-  else
-    hipLaunchKernelGGL((k_sandwich_chain<false>), dim3(1), dim3(SW_THREADS), (size_t)pl.lds, ctx->stream,
-                       tab.as<const SwSite>(), a.nsite, a.conj_bra, (int)pl.e_elems, res.as<double>(), at.pub,
-                       at.seq_slot, at.seq);
-  MPSE_HIP(ctx, hipGetLastError());
-  return publish_collect(ctx, at, res.p, 0, 1, 2, mpse_ctx::PIN_SCALAR2, out2);
+  MPSE_TRY(chain_lds_attr(ctx, {CHAIN_KERNELS(k_sandwich_chain)}, CHAIN_LDS_MAX));
+  return chain_scalar_launch(ctx, rows, [&](const SwSite* tab, double* res, const PublishAt& at) {
+    CHAIN_LAUNCH(ctx, cplx, k_sandwich_chain, 1, pl.lds, tab, a.nsite, a.conj_bra, (int)pl.e_elems, res, at.pub,
+                 at.seq_slot, at.seq);
+  }, out2);
 }
 
 // mpse_env_update (left domain, env_unit = 0) per site on two pooled environments.  The update works in one dtype per
@@ -325,16 +238,8 @@ int sandwich_enqueued(mpse_ctx* ctx, const SwArgs& a, double* out2) {
     const int dt = cx ? MPSE_C128 : MPSE_F64;
     const void* bra = a.bra[i];
     const void* ket = a.ket[i];
-    if (cx && a.bra_dtype[i] != MPSE_C128) {
-      if (!cb.p) MPSE_TRY(cb.alloc((size_t)site_max * 16));
-      MPSE_TRY(mpse_cast_f64_to_c128(ctx, cb.p, bra, s[0] * s[3] * s[4] * s[5]));
-      bra = cb.p;
-    }
-    if (cx && a.ket_dtype[i] != MPSE_C128) {
-      if (!ck.p) MPSE_TRY(ck.alloc((size_t)site_max * 16));
-      MPSE_TRY(mpse_cast_f64_to_c128(ctx, ck.p, ket, s[1] * s[3] * s[4] * s[6]));
-      ket = ck.p;
-    }
+    if (cx && a.bra_dtype[i] != MPSE_C128) MPSE_TRY(widen_site(ctx, cb, &bra, s[0] * s[3] * s[4] * s[5], site_max));
+    if (cx && a.ket_dtype[i] != MPSE_C128) MPSE_TRY(widen_site(ctx, ck, &ket, s[1] * s[3] * s[4] * s[6], site_max));
     mpse_dims dm{};
     dm.Dl_bra = s[0], dm.Dl_ket = s[1], dm.Dr_bra = s[5], dm.Dr_ket = s[6];
     dm.d0 = s[3], dm.d1 = 1, dm.danc = s[4];
@@ -346,11 +251,7 @@ int sandwich_enqueued(mpse_ctx* ctx, const SwArgs& a, double* out2) {
     env = nxt, nxt = t;
     e_dt = dt;
   }
-  // E_N is 1 x 1 x 1; the word behind a real one is inside the buffer and not used
-  MPSE_TRY(publish_and_wait(ctx, static_cast<const double*>(env), 2, mpse_ctx::PIN_SCALAR2));
-  out2[0] = ctx->pinned[mpse_ctx::PIN_SCALAR2];
-  out2[1] = e_dt == MPSE_C128 ? ctx->pinned[mpse_ctx::PIN_SCALAR2 + 1] : 0.0;
-  return MPSE_OK;
+  return chain_scalar_result(ctx, env, e_dt == MPSE_C128, out2);   // E_N is 1 x 1 x 1
 }
 
 }  // namespace
@@ -358,18 +259,16 @@ int sandwich_enqueued(mpse_ctx* ctx, const SwArgs& a, double* out2) {
 extern "C" {
 
 int mpse_mps_sandwich_plan(int nsite, const int64_t* dims, int any_complex, int64_t* info, int n) {
-  SwPlan pl;
-  const bool valid = sandwich_plan(nsite, dims, any_complex != 0, &pl);
-  const int64_t v[12] = {SW_LDS_MAX, pl.lds,      pl.e_elems,  pl.t_elems,      SW_THREADS,     SW_ACC,
-                         pl.acc,     SW_WORK_MAX, pl.work,     valid ? 1 : 0,   any_complex ? 16 : 8, SW_CHANNELS};
-  for (int i = 0; i < n && info; ++i) info[i] = i < 12 ? v[i] : 0;
-  return valid && pl.chain ? 1 : 0;
+  const bool valid = sandwich_table_ok(nsite, dims);
+  const SwPlan pl = valid ? sandwich_plan(nsite, dims, any_complex != 0) : SwPlan{false, 0, 0, 0, 0, 0, 0, 0};
+  const int64_t v[12] = {CHAIN_LDS_MAX, pl.lds,      pl.e_elems, pl.t_elems,    CHAIN_THREADS,        SW_ACC,
+                         pl.acc,        SW_WORK_MAX, pl.work,    valid ? 1 : 0, any_complex ? 16 : 8, SW_CHANNELS};
+  plan_info_out(info, n, v, 12);
+  return pl.chain ? 1 : 0;
 }
 
 int mpse_mps_sandwich_stats(mpse_ctx* ctx, int64_t* counts, int n) {
-  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
-  for (int i = 0; i < n; ++i) counts[i] = i < mpse_ctx::SW_COUNT ? ctx->sandwich_stats[i] : 0;
-  return MPSE_OK;
+  return stats_out(ctx, &mpse_ctx::sandwich_stats, counts, n);
 }
 
 int mpse_mps_sandwich(mpse_ctx* ctx, int nsite, const void* const* bra, const int* bra_dtype, const void* const* ket,
@@ -379,26 +278,19 @@ int mpse_mps_sandwich(mpse_ctx* ctx, int nsite, const void* const* bra, const in
   if (nsite < 1 || !bra || !bra_dtype || !ket || !ket_dtype || !W || !w_dtype || !dims || !out_re_im_host)
     return mpse_fail(ctx, MPSE_ERR_ARG, "mps_sandwich: null argument or no sites");
   bool cplx = false;
-  for (int i = 0; i < nsite; ++i) {
-    if (!bra[i] || !ket[i] || !W[i]) return mpse_fail(ctx, MPSE_ERR_ARG, "mps_sandwich: null site %d", i);
-    for (int dt : {bra_dtype[i], ket_dtype[i], w_dtype[i]}) {
-      if (dt != MPSE_F64 && dt != MPSE_C128)
-        return mpse_fail(ctx, MPSE_ERR_ARG, "mps_sandwich: unknown dtype at site %d", i);
-      cplx = cplx || dt == MPSE_C128;
-    }
-  }
-  SwPlan pl;
-  if (!sandwich_plan(nsite, dims, cplx, &pl))
+  MPSE_TRY(chain_scan_sites(ctx, "mps_sandwich", nsite, {bra, ket, W}, {bra_dtype, ket_dtype, w_dtype}, &cplx));
+  if (!sandwich_table_ok(nsite, dims))
     return mpse_fail(ctx, MPSE_ERR_SHAPE,
                      "mps_sandwich: dims is not a chain (extents >= 1, matching neighbours, first and last bonds 1)");
   if (MPSE_RECORDING(ctx))
     return mpse_fail(ctx, MPSE_ERR_ARG, "mps_sandwich: synchronous, not available while a deferred list is recorded");
+  SwPlan pl = sandwich_plan(nsite, dims, cplx);
   MPSE_BIND(ctx);
   // MPSE_SANDWICH_CHAIN=0 sends every chain through the enqueued updates; =1 sends every chain that fits the launch
   // through the kernel, over the work bound as well (measurements of that bound: tools/sandwich_bench.py)
-  const char* env = getenv("MPSE_SANDWICH_CHAIN");
-  if (env && env[0] == '0') pl.chain = false;
-  if (env && env[0] == '1' && pl.lds_fit > 0) pl.chain = true, pl.lds = pl.lds_fit;
+  const char env = chain_env_switch("MPSE_SANDWICH_CHAIN");
+  if (env == '0') pl.chain = false;
+  if (env == '1' && pl.lds_fit > 0) pl.chain = true, pl.lds = pl.lds_fit;
   const SwArgs args{nsite, bra, bra_dtype, ket, ket_dtype, W, w_dtype, dims, conj_bra};
   double res[2] = {0.0, 0.0};
   if (pl.chain)

@@ -218,6 +218,15 @@ def load_library(path=LIB_PATH):
     return lib
 
 
+def _chain_plan(lib_fn, rows, row_len, info_names, *extra):
+    """(chain kernel?, {info name: value}) of one of the ``mpse_mps_*_plan`` exports for ``rows`` of ``row_len`` extents;
+    ``extra``: the integer arguments between the table and the info array"""
+    flat = (C.c_int64 * max(row_len * len(rows), 1))(*[x for r in rows for x in r])
+    info = (C.c_int64 * len(info_names))()
+    ok = lib_fn(len(rows), flat, *extra, info, len(info))
+    return bool(ok), dict(zip(info_names, (int(v) for v in info)))
+
+
 OVERLAP_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid")
 
 
@@ -227,10 +236,7 @@ def mps_overlap_plan(dims, any_complex, lib=None):
     lib = lib or load_library()
     rows = [[int(x) for x in r] for r in dims]
     assert all(len(r) == 5 for r in rows), "dims rows are (Db_l, Dk_l, p, Db_r, Dk_r)"
-    flat = (C.c_int64 * max(5 * len(rows), 1))(*[x for r in rows for x in r])
-    info = (C.c_int64 * len(OVERLAP_PLAN_INFO))()
-    ok = lib.mpse_mps_overlap_plan(len(rows), flat, int(bool(any_complex)), info, len(info))
-    return bool(ok), dict(zip(OVERLAP_PLAN_INFO, (int(v) for v in info)))
+    return _chain_plan(lib.mpse_mps_overlap_plan, rows, 5, OVERLAP_PLAN_INFO, int(bool(any_complex)))
 
 
 SANDWICH_PLAN_INFO = ("lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "acc_per_thread", "acc_needed",
@@ -244,10 +250,7 @@ def mps_sandwich_plan(dims, any_complex, lib=None):
     lib = lib or load_library()
     rows = [[int(x) for x in r] for r in dims]
     assert all(len(r) == 8 for r in rows), "dims rows are (Db_l, Dk_l, wl, d, danc, Db_r, Dk_r, wr)"
-    flat = (C.c_int64 * max(8 * len(rows), 1))(*[x for r in rows for x in r])
-    info = (C.c_int64 * len(SANDWICH_PLAN_INFO))()
-    ok = lib.mpse_mps_sandwich_plan(len(rows), flat, int(bool(any_complex)), info, len(info))
-    return bool(ok), dict(zip(SANDWICH_PLAN_INFO, (int(v) for v in info)))
+    return _chain_plan(lib.mpse_mps_sandwich_plan, rows, 8, SANDWICH_PLAN_INFO, int(bool(any_complex)))
 
 
 CORR_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid",
@@ -261,10 +264,13 @@ def mps_corr_plan(dims, nsel, any_complex, lib=None):
     lib = lib or load_library()
     rows = [[int(x) for x in r] for r in dims]
     assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
-    flat = (C.c_int64 * max(4 * len(rows), 1))(*[x for r in rows for x in r])
-    info = (C.c_int64 * len(CORR_PLAN_INFO))()
-    ok = lib.mpse_mps_corr_plan(len(rows), flat, int(nsel), int(bool(any_complex)), info, len(info))
-    return bool(ok), dict(zip(CORR_PLAN_INFO, (int(v) for v in info)))
+    return _chain_plan(lib.mpse_mps_corr_plan, rows, 4, CORR_PLAN_INFO, int(nsel), int(bool(any_complex)))
+
+
+def _site_args(sites):
+    """(pointer array, dtype-code array) of a list of device site tensors, as the chain calls take them"""
+    n = len(sites)
+    return (C.c_void_p * n)(*[t.ptr for t in sites]), (C.c_int * n)(*[t.code for t in sites])
 
 
 class _Recording:
@@ -543,6 +549,12 @@ class Engine:
     def prof_reset(self):
         self._check(self.lib.mpse_prof_reset(self.ctx))
 
+    def _stats_dict(self, fn, names):
+        """{name: count} of one of the ``*_stats`` exports that fill an array of counters in the order of ``names``"""
+        v = (C.c_int64 * len(names))()
+        self._check(fn(self.ctx, v, len(v)))
+        return dict(zip(names, (int(x) for x in v)))
+
     def lanczos_batch_stats(self):
         """(members solved by the batched Krylov kernels, members of mpse_expm_lanczos_batch calls that took the single
         solve), cumulative"""
@@ -557,9 +569,7 @@ class Engine:
     def lanczos_path_stats(self):
         """{path: count}: how the Lanczos solves of this context ran, cumulative (``mpse_expm_lanczos_path_stats``;
         the names follow the order of include/mpsengine.h)."""
-        v = (C.c_int64 * len(self.LANCZOS_PATHS))()
-        self._check(self.lib.mpse_expm_lanczos_path_stats(self.ctx, v, len(v)))
-        return dict(zip(self.LANCZOS_PATHS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_expm_lanczos_path_stats, self.LANCZOS_PATHS)
 
     PCG_STATS = ("solves", "iterations", "matvecs", "host_waits", "end_tol", "end_max_iter", "end_curvature",
                  "twolayer", "masked", "wait_interval")
@@ -568,9 +578,7 @@ class Engine:
         """{name: count}: what the conjugate-gradient solves of this context did, cumulative (``mpse_pcg_stats``; the
         names follow the order of include/mpsengine.h).  ``wait_interval`` is no count: the engine's number of
         iterations between two host reads of the control block."""
-        v = (C.c_int64 * len(self.PCG_STATS))()
-        self._check(self.lib.mpse_pcg_stats(self.ctx, v, len(v)))
-        return dict(zip(self.PCG_STATS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_pcg_stats, self.PCG_STATS)
 
     def pcg(self, hop, b, x, diag=None, mask=None, shift=0.0, tol=1e-5, max_iter=0, check=True):
         """Solve ``(mask * hop + shift) x = b`` by preconditioned conjugate gradients inside the engine (``mpse_pcg``).
@@ -597,9 +605,7 @@ class Engine:
     def pcg_batch_stats(self):
         """{name: count} of the ``pcg_batch`` calls of this context, cumulative (``mpse_pcg_batch_stats``; the names
         follow the order of include/mpsengine.h).  ``set_limit`` is no count: the member limit per launch set."""
-        v = (C.c_int64 * len(self.PCG_BATCH_STATS))()
-        self._check(self.lib.mpse_pcg_batch_stats(self.ctx, v, len(v)))
-        return dict(zip(self.PCG_BATCH_STATS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_pcg_batch_stats, self.PCG_BATCH_STATS)
 
     def pcg_batch(self, hops, bs, xs, diags, masks, shifts, tol, max_iter=0):
         """``pcg`` for several independent systems in one call (``mpse_pcg_batch``): lists of ``hop_expr`` closures (all
@@ -686,9 +692,7 @@ class Engine:
 
     def pcg_sum_stats(self):
         """{name: count} of the summed conjugate-gradient solves (``mpse_pcg_sum_stats``), cumulative."""
-        v = (C.c_int64 * len(self.PCG_SUM_STATS))()
-        self._check(self.lib.mpse_pcg_sum_stats(self.ctx, v, len(v)))
-        return dict(zip(self.PCG_SUM_STATS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_pcg_sum_stats, self.PCG_SUM_STATS)
 
     def pcg_sum(self, terms, weights, b, x, diag=None, mask=None, shift=0.0, tol=1e-5, max_iter=0, check=True):
         """Solve ``(mask * sum_t weights[t] * terms[t] + shift) x = b`` (``mpse_pcg_sum``); arguments and result as
@@ -714,9 +718,7 @@ class Engine:
     def mps_overlap_stats(self):
         """{name: count} of the ``mps_overlap`` calls of this context, cumulative (``mpse_mps_overlap_stats``): chains
         taken by the chain kernel, chains taken by the enqueued products, sites walked."""
-        v = (C.c_int64 * len(self.OVERLAP_STATS))()
-        self._check(self.lib.mpse_mps_overlap_stats(self.ctx, v, len(v)))
-        return dict(zip(self.OVERLAP_STATS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_mps_overlap_stats, self.OVERLAP_STATS)
 
     def mps_overlap(self, bra_sites, ket_sites, conj_bra):
         """<bra|ket> of two chains of device site tensors (D_l, p.., D_r) in one engine call (``mpse_mps_overlap``);
@@ -733,9 +735,7 @@ class Engine:
             dims[5 * i:5 * i + 5] = [b.shape[0], k.shape[0], pb, b.shape[-1], k.shape[-1]]
         out = (C.c_double * 2)()
         self._check(self.lib.mpse_mps_overlap(
-            self.ctx, n, (C.c_void_p * n)(*[t.ptr for t in bra_sites]), (C.c_int * n)(*[t.code for t in bra_sites]),
-            (C.c_void_p * n)(*[t.ptr for t in ket_sites]), (C.c_int * n)(*[t.code for t in ket_sites]), dims,
-            int(bool(conj_bra)), out))
+            self.ctx, n, *_site_args(bra_sites), *_site_args(ket_sites), dims, int(bool(conj_bra)), out))
         return complex(out[0], out[1])
 
     # -- <bra| O |ket> of two chains and an MPO
@@ -744,9 +744,7 @@ class Engine:
     def mps_sandwich_stats(self):
         """{name: count} of the ``mps_sandwich`` calls of this context, cumulative (``mpse_mps_sandwich_stats``): chains
         taken by the chain kernel, chains taken by the enqueued environment updates, sites walked."""
-        v = (C.c_int64 * len(self.SANDWICH_STATS))()
-        self._check(self.lib.mpse_mps_sandwich_stats(self.ctx, v, len(v)))
-        return dict(zip(self.SANDWICH_STATS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_mps_sandwich_stats, self.SANDWICH_STATS)
 
     @staticmethod
     def sandwich_dims(bra_sites, w_sites, ket_sites):
@@ -774,10 +772,8 @@ class Engine:
         dims = (C.c_int64 * (8 * n))(*[int(x) for r in rows for x in r])
         out = (C.c_double * 2)()
         self._check(self.lib.mpse_mps_sandwich(
-            self.ctx, n, (C.c_void_p * n)(*[t.ptr for t in bra_sites]), (C.c_int * n)(*[t.code for t in bra_sites]),
-            (C.c_void_p * n)(*[t.ptr for t in ket_sites]), (C.c_int * n)(*[t.code for t in ket_sites]),
-            (C.c_void_p * n)(*[t.ptr for t in w_sites]), (C.c_int * n)(*[t.code for t in w_sites]), dims,
-            int(bool(conj_bra)), out))
+            self.ctx, n, *_site_args(bra_sites), *_site_args(ket_sites), *_site_args(w_sites), dims, int(bool(conj_bra)),
+            out))
         return complex(out[0], out[1])
 
     # -- matrix of two-point functions of one-site operators
@@ -786,9 +782,7 @@ class Engine:
     def mps_corr_stats(self):
         """{name: count} of the ``mps_corr`` calls of this context, cumulative (``mpse_mps_corr_stats``): calls taken by
         the chain kernels, calls taken by the enqueued products, sites walked, matrix entries produced."""
-        v = (C.c_int64 * len(self.CORR_STATS))()
-        self._check(self.lib.mpse_mps_corr_stats(self.ctx, v, len(v)))
-        return dict(zip(self.CORR_STATS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_mps_corr_stats, self.CORR_STATS)
 
     @staticmethod
     def corr_dims(sites):
@@ -823,9 +817,8 @@ class Engine:
         dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
         out = np.zeros((nsel, nsel), dtype=np.complex128)
         self._check(self.lib.mpse_mps_corr(
-            self.ctx, n, (C.c_void_p * n)(*[t.ptr for t in sites]), (C.c_int * n)(*[t.code for t in sites]), dims, nsel,
-            (C.c_int * nsel)(*[int(k) for k in sel]), packed[0].ctypes.data_as(_dblp), packed[1].ctypes.data_as(_dblp),
-            packed[2].ctypes.data_as(_dblp), out.ctypes.data_as(_dblp)))
+            self.ctx, n, *_site_args(sites), dims, nsel, (C.c_int * nsel)(*[int(k) for k in sel]),
+            *[p.ctypes.data_as(_dblp) for p in packed], out.ctypes.data_as(_dblp)))
         return out
 
     def block_qr_stats(self):
@@ -846,9 +839,7 @@ class Engine:
     def gemm_path_stats(self):
         """{path: count}: how the contraction kernel was launched by this context, cumulative
         (``mpse_gemm_path_stats``; the names follow the order of include/mpsengine.h)."""
-        v = (C.c_int64 * len(self.GEMM_PATHS))()
-        self._check(self.lib.mpse_gemm_path_stats(self.ctx, v, len(v)))
-        return dict(zip(self.GEMM_PATHS, (int(x) for x in v)))
+        return self._stats_dict(self.lib.mpse_gemm_path_stats, self.GEMM_PATHS)
 
     def wfold_path_stats(self):
         """{"grouped_mix": grouped launches that formed their beta term in the epilogue from blocks of the MPO site,

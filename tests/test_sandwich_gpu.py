@@ -15,30 +15,11 @@ import sys
 import numpy as np
 import pytest
 
+from chain_problems import _chain, _dev, _mpo, took_path   # (tests/chain_problems.py)
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rand(rng, shape, cplx):
-    a = rng.standard_normal(shape)
-    return a + 1j * rng.standard_normal(shape) if cplx else a
-
-
-def _flags(c, n):
-    return [c] * n if isinstance(c, bool) else list(c)
-
-
-def _chain(rng, bonds, ds, cplx, danc=None):
-    """site tensors (bonds[i], ds[i][, danc[i]], bonds[i + 1]); cplx: one flag or one per site"""
-    fl = _flags(cplx, len(ds))
-    return [_rand(rng, (bonds[i], d) + (() if danc is None else (danc[i],)) + (bonds[i + 1],), fl[i])
-            for i, d in enumerate(ds)]
-
-
-def _mpo(rng, wb, ds, cplx):
-    fl = _flags(cplx, len(ds))
-    return [_rand(rng, (wb[i], d, d, wb[i + 1]), fl[i]) for i, d in enumerate(ds)]
 
 
 def _host_sandwich(bra, w, ket, conj_bra):
@@ -64,18 +45,10 @@ def _tol(bra, w, ket):
     return 4.0 * 2.0 ** -53 * n * _scale(bra, w, ket)
 
 
-def _dev(eng, arrays):
-    return [eng.asdevice(np.ascontiguousarray(a)) for a in arrays]
-
-
 def _run(eng, bra, w, ket, conj_bra, path):
     """one call on the path the case means to take (asserted through the stats); returns the value"""
-    s0 = eng.mps_sandwich_stats()
-    got = eng.mps_sandwich(_dev(eng, bra), _dev(eng, w), _dev(eng, ket), conj_bra)
-    s1 = eng.mps_sandwich_stats()
-    other = "enqueued" if path == "chain_kernel" else "chain_kernel"
-    assert s1[path] - s0[path] == 1 and s1[other] == s0[other] and s1["sites"] - s0["sites"] == len(bra), (path, s0, s1)
-    return got
+    return took_path(eng.mps_sandwich_stats,
+                     lambda: eng.mps_sandwich(_dev(eng, bra), _dev(eng, w), _dev(eng, ket), conj_bra), path, len(bra))[0]
 
 
 def _check(eng, bra, w, ket, conj_bra, path, label=""):
@@ -114,6 +87,21 @@ def test_rectangular_chain(eng, kind):
     bra, ket, w = _chain(rng, BRA5, D5, bra_c), _chain(rng, KET5, D5, ket_c), _mpo(rng, W5, D5, w_c)
     for conj_bra in (False, True):
         _check(eng, bra, w, ket, conj_bra, "chain_kernel", f"{kind} conj_bra={conj_bra}")
+
+
+def test_mixed_chain_through_the_enqueued_updates(eng, monkeypatch):
+    """the mixed chain of test_rectangular_chain with the kernel switched off (the switch is read per call): the real
+    bra and the real ket sites next to complex operands are widened into pooled complex copies on the way"""
+    rng = np.random.default_rng(22)
+    bra, ket = _chain(rng, BRA5, D5, False), _chain(rng, KET5, D5, [False, False, True, True, False])
+    w = _mpo(rng, W5, D5, [False, True, False, False, False])
+    for conj_bra in (False, True):
+        kernel = _run(eng, bra, w, ket, conj_bra, "chain_kernel")
+        monkeypatch.setenv("MPSE_SANDWICH_CHAIN", "0")
+        enq = _check(eng, bra, w, ket, conj_bra, "enqueued", f"mixed enqueued conj_bra={conj_bra}")
+        monkeypatch.delenv("MPSE_SANDWICH_CHAIN")
+        print(f"|chain - enqueued| / scale = {abs(kernel - enq) / _scale(bra, w, ket):.2e}")
+        assert abs(kernel - enq) <= 2 * _tol(bra, w, ket)
 
 
 def test_conjugation_differs_on_complex_data(eng):
