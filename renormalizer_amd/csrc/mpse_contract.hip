@@ -257,7 +257,7 @@ int copy_call(mpse_ctx* ctx, int dtype, const void* src, void* dst, mpse_index m
 
 // sc: the solve the plan runs in, mv: the requests of the matvec it computes (both may be null)
 static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in[B_COUNT],
-                    const SolveScope* sc = nullptr, MatvecReq* mv = nullptr) {
+                    SolveScope* sc = nullptr, MatvecReq* mv = nullptr) {
   if (p.error) return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s", p.error);
   const int* skip = sc ? sc->skip : nullptr;
   MatvecReq::Dot* dot = mv && mv->dot.y ? &mv->dot : nullptr;
@@ -483,7 +483,7 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
   return MPSE_OK;
 }
 
-int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc,
                MatvecReq* mv) {
   if (!ctx || !h || !C || !out || !h->L || !h->R) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
@@ -610,7 +610,7 @@ extern "C" int mpse_env_update_multi(mpse_ctx* ctx, int dtype, int domain, const
   return run_plan(ctx, dtype, p, bufs);
 }
 
-int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc) {
+int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc) {
   if (!ctx || !h || !C || !out || !h->L || !h->R || !h->W0) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (dtype != MPSE_C128 && (h->l_dtype == MPSE_C128 || h->r_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
@@ -631,7 +631,7 @@ extern "C" int mpse_heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, co
 }
 
 // ---- two layers on a two-leg centre (finite-temperature correction vector): plans of mpse_plans.h
-int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out, const SolveScope* sc) {
+int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out, SolveScope* sc) {
   if (!ctx || !h || !C || !out || !h->L || !h->R || !h->W1 || !h->W2) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (dtype != MPSE_C128 && (h->l_dtype == MPSE_C128 || h->r_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))

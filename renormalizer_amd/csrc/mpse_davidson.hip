@@ -233,7 +233,7 @@ struct Dav {
   int dtype;
   bool cplx;
   const mpse_heff* h;
-  const SolveScope* scope;
+  SolveScope* scope;
   int twolayer;
   const void* mask;
   int64_t n;

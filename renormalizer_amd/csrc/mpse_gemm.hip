@@ -1338,8 +1338,8 @@ bool fill_maps(GemmArgs& g, const mpse_index& ma, const mpse_index& ka, const mp
 
 // ---- occupancy masks: flags of the 64 x 16 tiles of one operand (`batch` matrices sb elements apart, rows through
 // rm, K through km), [batch][tile][nkw * 8] bytes
-mpse_ctx::OccKey occ_key(const void* p, const IdxMap& rm, const IdxMap& km, long long sb, long long batch, bool cplx) {
-  mpse_ctx::OccKey k;
+SolveScope::OccKey occ_key(const void* p, const IdxMap& rm, const IdxMap& km, long long sb, long long batch, bool cplx) {
+  SolveScope::OccKey k;
   memset(&k, 0, sizeof(k));
   k.ptr = p;
   k.r_ext = rm.ext, k.r_lo = rm.lo, k.r_shi = rm.s_hi, k.r_slo = rm.s_lo;
@@ -1348,7 +1348,7 @@ mpse_ctx::OccKey occ_key(const void* p, const IdxMap& rm, const IdxMap& km, long
   k.batch = (int)batch, k.K = km.ext, k.cplx = cplx ? 1 : 0;
   return k;
 }
-size_t occ_bytes(const mpse_ctx::OccKey& k) { return size_t(k.batch) * k.tiles * k.nkw * 8; }
+size_t occ_bytes(const SolveScope::OccKey& k) { return size_t(k.batch) * k.tiles * k.nkw * 8; }
 
 struct OccMask {
   void* mask = nullptr;
@@ -1356,13 +1356,14 @@ struct OccMask {
   bool stable = true;    // the mask (or its absence) outlives the call: cached or the solve's
 };
 // Where the mask of an operand comes from.  Inside a Krylov solve the environments do not change: the mask of an
-// operand inside them (`keep` = SolveScope::in_env) is looked up in occ_cache and on a miss stored there until the
-// solve ends.  Any other operand takes the mask the caller already has (`given`, null = none) or, to be scanned, `tmp`
-// in a temporary of the caller.
-int occ_mask_source(mpse_ctx* ctx, bool keep, const mpse_ctx::OccKey& key, const void* given, void* tmp, OccMask* m) {
+// operand inside them (`keep` = the solve's scope where SolveScope::in_env, else null) is looked up in the scope's
+// occ_cache and on a miss stored there until the scope ends.  Any other operand takes the mask the caller already has
+// (`given`, null = none) or, to be scanned, `tmp` in a temporary of the caller.
+int occ_mask_source(mpse_ctx* ctx, SolveScope* keep, const SolveScope::OccKey& key, const void* given, void* tmp,
+                    OccMask* m) {
   m->stable = keep || given;
   if (keep)
-    for (const auto& e : ctx->occ_cache)
+    for (const auto& e : keep->occ_cache)
       if (memcmp(&e.key, &key, sizeof(key)) == 0) {
         m->mask = e.mask;
         return MPSE_OK;
@@ -1372,24 +1373,25 @@ int occ_mask_source(mpse_ctx* ctx, bool keep, const mpse_ctx::OccKey& key, const
     m->mask = const_cast<void*>(given);
   } else if (keep) {
     MPSE_TRY(mpse_malloc(ctx, occ_bytes(key), &m->mask));
-    ctx->occ_cache.push_back({key, m->mask});
+    keep->occ_cache.push_back({key, m->mask});
   } else {
     m->mask = tmp;
   }
   return MPSE_OK;
 }
-OccOperand occ_operand(const mpse_ctx::OccKey& k, const IdxMap& rm, const IdxMap& km, int kfast, const OccMask& m) {
+OccOperand occ_operand(const SolveScope::OccKey& k, const IdxMap& rm, const IdxMap& km, int kfast, const OccMask& m) {
   return OccOperand{static_cast<const double*>(k.ptr), rm, km, k.nrows, m.scan ? k.tiles : 0, k.cplx, kfast, k.sb,
                     static_cast<unsigned char*>(m.mask)};
 }
 
-// ---- launch order (k_tile_order).  keep: the masks it is computed from are the running solve's - the order is looked
-// up in perm_cache (key: every field but perm) and on a miss stored there like the masks; otherwise it goes to `tmp`.
-// *sort: the order is still to be computed.
-int perm_source(mpse_ctx* ctx, bool keep, mpse_ctx::PermEntry key, size_t bytes, TmpBuf& tmp, int** perm, bool* sort) {
+// ---- launch order (k_tile_order).  keep: the scope of the solve whose masks it is computed from, else null - the
+// order is looked up in the scope's perm_cache (key: every field but perm) and on a miss stored there like the masks;
+// otherwise it goes to `tmp`.  *sort: the order is still to be computed.
+int perm_source(mpse_ctx* ctx, SolveScope* keep, SolveScope::PermEntry key, size_t bytes, TmpBuf& tmp, int** perm,
+                bool* sort) {
   *sort = false;
   if (keep)
-    for (const auto& e : ctx->perm_cache)
+    for (const auto& e : keep->perm_cache)
       if (e.amask == key.amask && e.bmask == key.bmask && e.tiles_m == key.tiles_m && e.tiles_n == key.tiles_n &&
           e.nkt == key.nkt) {
         *perm = static_cast<int*>(e.perm);
@@ -1398,7 +1400,7 @@ int perm_source(mpse_ctx* ctx, bool keep, mpse_ctx::PermEntry key, size_t bytes,
   *sort = true;
   if (keep) {
     MPSE_TRY(mpse_malloc(ctx, bytes, &key.perm));
-    ctx->perm_cache.push_back(key);
+    keep->perm_cache.push_back(key);
     *perm = static_cast<int*>(key.perm);
   } else {
     MPSE_TRY(tmp.alloc(bytes));
@@ -1454,7 +1456,7 @@ void count_paths(long long* gp, const GroupedDesc& d) {
 
 // sc: the solve the product runs in, rq: what run_plan asks of it beyond the descriptor (both may be null)
 static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, const void* B, void* C, int skip_zero,
-                     const SolveScope* sc, ProductReq* rq) {
+                     SolveScope* sc, ProductReq* rq) {
   // ---- check
   if (!ctx || !d) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
@@ -1548,9 +1550,10 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
   if (p.masks) {
     g.nkw = p.nkw;
     const bool sa = skip_zero & 1, sb = skip_zero & 2;
-    const mpse_ctx::OccKey ka = occ_key(g.A, g.mA, g.kA, g.sbA, d->batch, ca);
-    const mpse_ctx::OccKey kb = occ_key(g.B, g.nB, g.kB, g.sbB, d->batch, cb);
-    const bool keep_a = sa && sc && sc->in_env(g.A), keep_b = sb && sc && sc->in_env(g.B);
+    const SolveScope::OccKey ka = occ_key(g.A, g.mA, g.kA, g.sbA, d->batch, ca);
+    const SolveScope::OccKey kb = occ_key(g.B, g.nB, g.kB, g.sbB, d->batch, cb);
+    SolveScope* const keep_a = sa && sc && sc->in_env(g.A) ? sc : nullptr;
+    SolveScope* const keep_b = sb && sc && sc->in_env(g.B) ? sc : nullptr;
     // B is a Krylov vector of a solve whose caller supplied the structural mask of the centre tensor: no scan
     const void* centre = (sb && sc && sc->in_krylov(g.B) && d->batch == 1 && (long long)occ_bytes(kb) == sc->cmask.bytes)
                              ? sc->cmask.ptr : nullptr;
@@ -1573,7 +1576,7 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
   if (p.order) {
     // inside a Krylov solve both masks are the solve's (cached environment mask, structural centre mask): one sort
     // serves every matvec of the solve
-    const bool keep = sc && sc->occ_cache && ma.stable && mb.stable;
+    SolveScope* const keep = sc && sc->keeps_env_masks && ma.stable && mb.stable ? sc : nullptr;
     int* pp = nullptr;
     bool sort = false;
     MPSE_TRY(perm_source(ctx, keep, {g.amask, g.bmask, g.tiles_m, g.tiles_n, p.nkt, nullptr},
@@ -1596,15 +1599,15 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
 
 // ------------------------------------------------------------------------------------------------------------------
 // Tile-occupancy flags of one operand (rows through `r`, K through `k`, both from `ptr`): from the cache of the
-// running Krylov solve, else scanned now - into the cache when the operand lies inside the solve's environment
+// Krylov solve's scope, else scanned now - into that cache when the operand lies inside the solve's environment
 // ranges, into `tmp` otherwise.  flags[t * pitch + kt], 64 rows per tile t.
-int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,
+int occ_mask_get(mpse_ctx* ctx, SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,
                  TmpBuf& tmp, const unsigned char** flags, int* pitch, bool* stable) {
   IdxMap rm, km;
   if (!to_map(r, &rm) || !to_map(k, &km) || !is_single(km))
     return mpse_fail(ctx, MPSE_ERR_SHAPE, "occupancy scan: K index must be single level");
-  const mpse_ctx::OccKey key = occ_key(ptr, rm, km, 0, 1, dtype == MPSE_C128);
-  const bool keep = sc && sc->in_env(ptr);
+  const SolveScope::OccKey key = occ_key(ptr, rm, km, 0, 1, dtype == MPSE_C128);
+  SolveScope* const keep = sc && sc->in_env(ptr) ? sc : nullptr;
   OccMask m;
   if (!keep) MPSE_TRY(tmp.alloc(occ_bytes(key)));
   MPSE_TRY(occ_mask_source(ctx, keep, key, nullptr, tmp.p, &m));
@@ -1635,7 +1638,7 @@ static double mix_sources(const GroupedDesc& d) {
 
 // Grouped launch of the contraction kernel (mpse_internal.h GroupedDesc; folded one-site matvec of mpse_plans.h).
 // dot: the caller's dot request when this launch completes a matvec result (one group only), else null.
-int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, MatvecReq::Dot* dot) {
+int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq::Dot* dot) {
   // ---- check
   GemmArgs g = {};
   if (d.ngrp < 1 || d.ngrp > GMAX_GRP) return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: 1 .. %d groups", GMAX_GRP);
@@ -1727,7 +1730,7 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, Matv
     const size_t perm_bytes = (size_t(ntile) * sizeof(int) + 7) & ~size_t(7), flag_pitch = size_t(g.nkw) * 8;
     int* pp = nullptr;
     bool sort = false;
-    MPSE_TRY(perm_source(ctx, sc && sc->occ_cache && d.masks_stable,
+    MPSE_TRY(perm_source(ctx, sc && sc->keeps_env_masks && d.masks_stable ? sc : nullptr,
                          {gg.g[0].seg[0].am, gg.g[0].seg[0].bm, g.tiles_m, g.tiles_n, nkt_max + 1000 * d.ngrp, nullptr},
                          perm_bytes + size_t(ntile) * flag_pitch, PERM, &pp, &sort));
     if (sort)
@@ -1763,7 +1766,7 @@ extern "C" int mpse_gemm_path_stats(mpse_ctx* ctx, int64_t* counts, int n) {
 
 int gemm_call(mpse_ctx* ctx, int dta, int dtb, int conja, int conjb, mpse_index ma, mpse_index ka, mpse_index kb,
               mpse_index nb, mpse_index mc, mpse_index nc, int64_t batch, int64_t sba, int64_t sbb, int64_t sbc,
-              const void* A, const void* B, void* C, double alpha, double beta, int skip_zero, const SolveScope* sc,
+              const void* A, const void* B, void* C, double alpha, double beta, int skip_zero, SolveScope* sc,
               ProductReq* rq) {
   mpse_gemm_desc d;
   d.dtype_a = dta;

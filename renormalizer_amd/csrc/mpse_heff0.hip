@@ -643,16 +643,11 @@ int heff0_fused_parts(const mpse_heff* h, int dtype) {
   return (int)nparts;
 }
 
-void heff0_drop_cache(mpse_ctx* ctx) {
-  if (ctx->f0.buf) mpse_free(ctx, ctx->f0.buf);
-  ctx->f0 = mpse_ctx::F0Cache();
-}
-
 // Runs the fused matvec inside a solve when the caller offered masked parts (MatvecReq::Parts::masked_ok) with room
 // for all of them.  w_host: the MPO site (wl, d, d, wr) of a one-site centre as the host knows it
 // (mpse_mpo_site_hint), else null.
 int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, const double* w_host,
-                    const SolveScope* sc, MatvecReq* mv, bool* taken) {
+                    SolveScope* sc, MatvecReq* mv, bool* taken) {
   *taken = false;
   const int nparts = heff0_fused_parts(h, dtype);
   if (nparts == 0 || !mv || !mv->parts.ptr || !mv->parts.masked_ok) return MPSE_OK;
@@ -712,7 +707,7 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
     }
   if (!sc) return MPSE_OK;     // (outside a solve nothing would own the flags and the mask until the consumer has run)
   const int* skip = sc->skip;
-  mpse_ctx::F0Cache& fc = ctx->f0;
+  SolveScope::F0Cache& fc = sc->f0;
   char* base = nullptr;
   const bool hit = fc.buf && fc.L == h->L && fc.R == h->R && fc.W == h->W0 && fc.cmask == (const void*)FC && fc.Dl == Dl &&
                    fc.Dr == Dr && fc.w == wr && fc.nsite == h->nsite;
@@ -727,7 +722,8 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
     base = static_cast<char*>(fc.buf);
   } else {
     void* p = nullptr;
-    heff0_drop_cache(ctx);
+    if (fc.buf) mpse_free(ctx, fc.buf);
+    fc = SolveScope::F0Cache();
     MPSE_TRY(mpse_malloc(ctx, tot_bytes, &p));
     fc.buf = p, fc.L = h->L, fc.R = h->R, fc.W = h->W0, fc.cmask = FC, fc.Dl = Dl, fc.Dr = Dr, fc.w = wr, fc.nsite = h->nsite;
     base = static_cast<char*>(p);

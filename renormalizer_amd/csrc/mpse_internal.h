@@ -82,18 +82,6 @@ struct mpse_ctx {
   unsigned long long publish_seq = 0;
   double* dscratch = nullptr;   // device scratch for reductions (1<<16 doubles); the last 8 hold flag words
   unsigned int flag_gen = 0;    // generation stamp of the Lanczos convergence flag (no per-check memset)
-  // Tile-occupancy masks of operands that stay constant over one Krylov solve (the two environments): computed by
-  // the first matvec, reused by the others.  Kept only for operands inside the environment ranges of the running
-  // Lanczos solve (SolveScope), and dropped at its end.
-  struct OccKey {
-    const void* ptr;
-    long long r_ext, r_lo, r_shi, r_slo, k_ext, k_lo, k_shi, k_slo, sb;
-    int nrows, tiles, nkw, batch, K, cplx;
-  };
-  struct OccEntry {
-    OccKey key;
-    void* mask;
-  };
   // Krylov dimension of the last solve per problem class (number of sites, vector length): how far to run ahead
   std::unordered_map<unsigned long long, int> lz_hint;
   // Block structure of MPO sites the caller has described (mpse_mpo_site_hint), by device pointer: large one-site
@@ -114,8 +102,9 @@ struct mpse_ctx {
   bool defer_hold = false;                  // guarded by pool_mu
   std::vector<void*> defer_frees;           // guarded by pool_mu
   // Tile-occupancy mask of the centre tensor as operand B of the first products of a matvec, supplied by the caller
-  // (mpse_expm_centre_mask: the structural pattern of the quantum numbers, the same for every Krylov vector) for the
-  // next solve, which takes it over (SolveScope::cmask)
+  // (mpse_expm_centre_mask: the structural pattern of the quantum numbers, the same for every Krylov vector).  It waits
+  // here for the next mpse_expm_lanczos, which takes it out on entry and hands it down as an argument to the scope of
+  // its solve (SolveScope::cmask); nothing else reads it.
   struct CMask {
     const void* ptr = nullptr;
     long long bytes = 0;
@@ -124,26 +113,6 @@ struct mpse_ctx {
   // record (grid, K tiles multiplied, s_memtime stamps of its phases); mpse_prof_get writes the file.
   unsigned long long* gemm_trace = nullptr;   // [1 + GEMM_TRACE_CAP * GEMM_TRACE_WORDS] words: counter, then records
   bool gemm_trace_checked = false;
-  std::vector<OccEntry> occ_cache;
-  // launch orders of block-sparse products (k_tile_order), kept like the masks they were computed from
-  struct PermEntry {
-    const void *amask, *bmask;
-    int tiles_m, tiles_n, nkt;
-    void* perm;
-  };
-  std::vector<PermEntry> perm_cache;
-  // Transposed right environment of the small-centre matvec (mpse_small.hip), kept for the running solve like the masks
-  struct SmallRt {
-    const void* src = nullptr;
-    void* rt = nullptr;
-    size_t bytes = 0;
-  } small_rt;
-  // Per-solve data of the fused 0-site matvec (mpse_heff0.hip): transposed right environment, tile flags, part mask
-  struct F0Cache {
-    void* buf = nullptr;
-    const void *L = nullptr, *R = nullptr, *W = nullptr, *cmask = nullptr;
-    int Dl = 0, Dr = 0, w = 0, nsite = -1;
-  } f0;
   long long f0_launches[2] = {0, 0};   // fused matvec launches: bond matrices, two-level sites
   // launch decisions of the contraction kernel (mpse_gemm_path_stats; the order of include/mpsengine.h)
   enum GemmPath {
@@ -312,32 +281,72 @@ static inline mpse_index idx2(int64_t hi_ext, int64_t lo_ext, int64_t s_hi, int6
   return mpse_index{hi_ext * lo_ext, lo_ext > 0 ? lo_ext : 1, s_hi, s_lo};
 }
 
-// What a solver fixes for the length of one solve (the Lanczos drivers of mpse_lanczos.hip, Davidson), handed by pointer to
-// every matvec of it; null outside a solve.  The per-solve caches of the context (occ_cache, perm_cache, small_rt, f0)
-// are kept only while a solve runs: its end drops them.
+// What a solver fixes and keeps for the length of one solve (the Lanczos drivers of mpse_lanczos.hip, Davidson, PCG),
+// handed by pointer to every matvec of it; null outside a solve.  The scope owns the device data that the matvecs of its
+// solve compute once and share - masks, launch orders, the transposed right environment, the data of the fused matvec:
+// a matvec fills them through the pointer it was given, and the end of the scope frees exactly these and nothing else.
+// The context keeps none of it, so scopes do not see each other's data.
 struct SolveScope {
   mpse_ctx* ctx;
   // device word that turns every contraction launch into a no-op once it is non-zero: the asynchronous Lanczos solve,
   // whose iterations are enqueued ahead of the convergence decision
   const int* skip = nullptr;
   // Lanczos: the environments [env_lo, env_hi), constant over the solve - the tile-occupancy masks of operands inside
-  // them are scanned once and kept, and so are the launch orders built on such masks
-  bool occ_cache = false;
+  // them are scanned once and kept (occ_cache), and so are the launch orders built on such masks (perm_cache)
+  bool keeps_env_masks = false;
   const char* env_lo[2] = {nullptr, nullptr};
   const char* env_hi[2] = {nullptr, nullptr};
-  // the caller's structural mask of the centre (taken over from mpse_ctx::cmask_pending): it describes the operands
-  // inside the Krylov basis [krylov_lo, krylov_hi)
+  // the caller's structural mask of the centre (mpse_expm_centre_mask, handed down by mpse_expm_lanczos): it describes
+  // the operands inside the Krylov basis [krylov_lo, krylov_hi)
   mpse_ctx::CMask cmask;
   const char* krylov_lo = nullptr;
   const char* krylov_hi = nullptr;
 
+  // Tile-occupancy masks of the operands inside the environment ranges: computed by the first matvec, reused by the
+  // others (mpse_gemm.hip)
+  struct OccKey {
+    const void* ptr;
+    long long r_ext, r_lo, r_shi, r_slo, k_ext, k_lo, k_shi, k_slo, sb;
+    int nrows, tiles, nkw, batch, K, cplx;
+  };
+  struct OccEntry {
+    OccKey key;
+    void* mask;
+  };
+  std::vector<OccEntry> occ_cache;
+  // launch orders of block-sparse products (k_tile_order), kept like the masks they were computed from
+  struct PermEntry {
+    const void *amask, *bmask;
+    int tiles_m, tiles_n, nkt;
+    void* perm;
+  };
+  std::vector<PermEntry> perm_cache;
+  // Transposed right environment of the small-centre matvec (mpse_small.hip); another R replaces it
+  struct SmallRt {
+    const void* src = nullptr;
+    void* rt = nullptr;
+    size_t bytes = 0;
+  } small_rt;
+  // Data of the fused 0-site matvec (mpse_heff0.hip): transposed right environment, tile flags, part mask; other
+  // operands replace it
+  struct F0Cache {
+    void* buf = nullptr;
+    const void *L = nullptr, *R = nullptr, *W = nullptr, *cmask = nullptr;
+    int Dl = 0, Dr = 0, w = 0, nsite = -1;
+  } f0;
+
   explicit SolveScope(mpse_ctx* c) : ctx(c) {}
   SolveScope(const SolveScope&) = delete;
   SolveScope& operator=(const SolveScope&) = delete;
-  ~SolveScope();
+  ~SolveScope() {
+    for (auto& e : occ_cache) mpse_free(ctx, e.mask);
+    for (auto& e : perm_cache) mpse_free(ctx, e.perm);
+    if (f0.buf) mpse_free(ctx, f0.buf);
+    if (small_rt.rt) mpse_free(ctx, small_rt.rt);
+  }
   bool in_env(const void* p) const {
     const char* c = static_cast<const char*>(p);
-    return occ_cache && ((c >= env_lo[0] && c < env_hi[0]) || (c >= env_lo[1] && c < env_hi[1]));
+    return keeps_env_masks && ((c >= env_lo[0] && c < env_hi[0]) || (c >= env_lo[1] && c < env_hi[1]));
   }
   bool in_krylov(const void* p) const {
     const char* c = static_cast<const char*>(p);
@@ -388,16 +397,15 @@ struct ProductReq {
 };
 
 // The matvec behind mpse_heff_apply, for a caller inside a solve (sc) and / or with requests (mv); both may be null
-int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc,
                MatvecReq* mv);
 // The two-layer matvec behind mpse_heff_apply2, for a caller inside a solve (sc may be null)
-int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc);
+int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc);
 // One term of the finite-temperature correction-vector operator (mpse_heff_apply_ft), inside a solve (sc may be null)
-int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out, const SolveScope* sc);
+int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out, SolveScope* sc);
 // One-launch matvec of small 0- / 1-site centres (mpse_small.hip); *taken says whether it ran (else: the plans)
-int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc,
                    MatvecReq* mv, bool* taken);
-void heff_small_drop_cache(mpse_ctx* ctx);
 
 // Batched small-centre Krylov solves (mpse_expm_lanczos_batch, mpse_lanczos.hip): what differs between the members of one
 // launch set beyond their slab (vectors, scalars, partials and control block at member-0 addresses + m * mstride bytes)
@@ -459,24 +467,16 @@ int small2_prep(mpse_ctx* ctx, int dtype, const Small2Plan& p, int B, const Pcg2
 // one launch for B members; mode 0: y = Heff2 x, mode 1: q = mask * Heff2 p + shift * p with the partials of p^H q
 int small2_apply(mpse_ctx* ctx, int dtype, const Small2Plan& p, int B, const Pcg2Member* mem, int mode);
 // Fused 0-site matvec for large complex bond matrices (mpse_heff0.hip): number of parts it would deliver (0 = not
-// eligible), the attempt itself (needs a solve and MatvecReq::Parts::masked_ok), and the release of its per-solve data
+// eligible) and the attempt itself (needs a solve, which keeps its data, and MatvecReq::Parts::masked_ok)
 int heff0_fused_parts(const mpse_heff* h, int dtype);
 int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, const double* w_host,
-                    const SolveScope* sc, MatvecReq* mv, bool* taken);
-void heff0_drop_cache(mpse_ctx* ctx);
-inline SolveScope::~SolveScope() {
-  for (auto& e : ctx->occ_cache) mpse_free(ctx, e.mask);
-  ctx->occ_cache.clear();
-  for (auto& e : ctx->perm_cache) mpse_free(ctx, e.perm);
-  ctx->perm_cache.clear();
-  heff_small_drop_cache(ctx);
-}
+                    SolveScope* sc, MatvecReq* mv, bool* taken);
 
 // convenience wrapper over mpse_gemm used by the contraction entry points
 int gemm_call(mpse_ctx* ctx, int dta, int dtb, int conja, int conjb, mpse_index ma, mpse_index ka,
               mpse_index kb, mpse_index nb, mpse_index mc, mpse_index nc, int64_t batch, int64_t sba,
               int64_t sbb, int64_t sbc, const void* A, const void* B, void* C, double alpha = 1.0,
-              double beta = 0.0, int skip_zero = 0, const SolveScope* sc = nullptr, ProductReq* rq = nullptr);
+              double beta = 0.0, int skip_zero = 0, SolveScope* sc = nullptr, ProductReq* rq = nullptr);
 
 // Grouped launch of the contraction kernel (mpse_gemm.hip): up to 8 groups of equal height dividing the tile rows, each
 // with its own result C (same index maps) and up to 4 (A, B) operand pairs whose products are summed (+ beta C, beta 0
@@ -517,8 +517,8 @@ struct GroupedDesc {
   int mix_d = 0, mix_wr = 0;
   long long mix_ld = 0;
 };
-int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, const SolveScope* sc, MatvecReq::Dot* dot);
-int occ_mask_get(mpse_ctx* ctx, const SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,
+int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq::Dot* dot);
+int occ_mask_get(mpse_ctx* ctx, SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,
                  TmpBuf& tmp, const unsigned char** flags, int* pitch, bool* stable);
 
 // Low-latency read-back of a few device doubles: a one-wave kernel copies them into the mapped pinned buffer

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <complex>
 #include <cstdlib>
+#include <utility>
 
 #include "mpse_internal.h"
 #include "mpse_vec_kernels.h"
@@ -787,14 +788,15 @@ void keep_env_masks(SolveScope& sc, const mpse_heff* h) {
   const size_t rb = size_t(s.Dr_ket) * s.wr * s.Dr_ket * (h->r_dtype == MPSE_C128 ? 16 : 8);
   sc.env_lo[0] = static_cast<const char*>(h->L), sc.env_hi[0] = sc.env_lo[0] + lb;
   sc.env_lo[1] = static_cast<const char*>(h->R), sc.env_hi[1] = sc.env_lo[1] + rb;
-  sc.occ_cache = true;
+  sc.keeps_env_masks = true;
 }
 
 constexpr int LZ_FALLBACK = -77;   // internal: the asynchronous solve hands the problem to the synchronous one
 constexpr int LZ_BADSTART = -78;   // internal: |C|^2 outside [LZ_N2_MIN, LZ_N2_MAX) (expm_lanczos_solve decides)
 
+// cmask: the caller's structural mask of the centre (empty: none); it describes the Krylov vectors of this solve
 int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::complex<double> dt, const void* Cin, void* out,
-                       double rtol, double atol, int max_dim, int* nvec, int64_t n) {
+                       double rtol, double atol, int max_dim, int* nvec, int64_t n, mpse_ctx::CMask cmask) {
   const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
   const int64_t nd = n * (cplx ? 2 : 1);
@@ -829,8 +831,7 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
   SolveScope scope(ctx);
   scope.skip = done;
   keep_env_masks(scope, h);
-  scope.cmask = ctx->cmask_pending;   // the caller's structural mask applies to the Krylov vectors of THIS solve only
-  ctx->cmask_pending = mpse_ctx::CMask();
+  scope.cmask = cmask;
 
   // the structural mask of the centre also serves the vector kernels of this solve (square operators on complex vectors
   // whose rows are whole multiples of 64 elements)
@@ -850,24 +851,21 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
       vm_kw = (int)(nkw * 8);
     }
   }
-  auto bracket = [&](double bytes, auto&& launch) {
-    mpse_ctx::ProfRec rec;
-    const bool pt = prof_begin(ctx, 4, 0.0, bytes, &rec);
-    launch();
-    if (pt) prof_end(ctx, rec);
-  };
+  // (the vector launches are bracketed for the profiler: variant 4, algorithmic bytes)
   auto dot_partials = [&](const void* x, const void* y, double* dst) {
-    bracket(2.0 * vbytes, [&] {
-      MPSE_LAUNCH_TF(ctx, cplx, k_dot_partial, dim3(nb), dim3(RED_THREADS), (const double*)x, (const double*)y, (long long)n,
-                     dst, done);
-    });
+    ProfScope ps(ctx, 4, 0.0, 2.0 * vbytes);
+    MPSE_LAUNCH_TF(ctx, cplx, k_dot_partial, dim3(nb), dim3(RED_THREADS), (const double*)x, (const double*)y, (long long)n,
+                   dst, done);
+    ps.end();
   };
   // U_0 = C itself (the Krylov basis is kept unnormalised, k_lanczos_update_u); |C|^2 partials feed the first step
   double* part_b2[2] = {ctx->dscratch + 4 * RED_MAX_BLOCKS, ctx->dscratch + 8 * RED_MAX_BLOCKS};
-  bracket(3.0 * vbytes, [&] {
+  {
+    ProfScope ps(ctx, 4, 0.0, 3.0 * vbytes);
     MPSE_LAUNCH_TF(ctx, cplx, k_lz_start, dim3(nb), dim3(RED_THREADS), (double*)vec(0), (const double*)Cin, (long long)n,
                    part_b2[0], ctl);
-  });
+    ps.end();
+  }
   MPSE_HIP(ctx, hipGetLastError());
 
   unsigned int* dflag = reinterpret_cast<unsigned int*>(ctx->dscratch + (size_t(1) << 16) - 8);
@@ -928,12 +926,14 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
     if (two || pmask) ++ctx->lz_paths[mpse_ctx::LP_PARTS];
     if (!pmask && vmask) ++ctx->lz_paths[mpse_ctx::LP_VMASK];
     if (!vec16) ++ctx->lz_paths[mpse_ctx::LP_UNVEC];
-    bracket((j > 0 ? 4.0 : 3.0) * vbytes + (nparts - 1) * vbytes, [&] {
+    {
+      ProfScope ps(ctx, 4, 0.0, (j > 0 ? 4.0 : 3.0) * vbytes + (nparts - 1) * vbytes);
       MPSE_LAUNCH_TF(ctx, vec16, k_lanczos_update_u, dim3(nb), dim3(RED_THREADS), (double*)vec(j + 1), W.as<const double>(),
                      nparts, (long long)nd, (const double*)vec(j), j > 0 ? (const double*)vec(j - 1) : (const double*)nullptr,
                      (long long)nd, (const double*)part_a, a_nb, scal + 4 + 4 * j, (const double*)cur_part, nb, cur_out,
                      prev2, new_part, done, pmask, prow, ptiles, pmask ? nullptr : vmask, vm_row, vm_kw);
-    });
+      ps.end();
+    }
     const LzSchedule::Step step = sch.at(j, prev != nullptr);
     const bool merged = step.merged, last = step.last;
     if (step.check) {
@@ -982,20 +982,14 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
   return MPSE_OK;
 }
 
-// One attempt at C as it is: the asynchronous solve where it applies, behind it the synchronous one.  LZ_BADSTART: |C|^2
-// is outside what the recurrence takes (expm_lanczos_solve decides); the arguments are checked there.
-int lanczos_attempt(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin, void* out,
-                    double rtol, double atol, int max_dim, int* nvec, int64_t n, bool async_first) {
+// The synchronous solve: the host reads the recurrence scalars at every check and forms the coefficients itself.  It
+// starts from Cin and takes no structural centre mask.
+int expm_lanczos_sync(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::complex<double> dt, const void* Cin, void* out,
+                      double rtol, double atol, int max_dim, int* nvec, int64_t n) {
   const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
-  if (async_first && lanczos_async_enabled() && n > 256) {
-    const int st = expm_lanczos_async(ctx, dtype, h, std::complex<double>(dt_re, dt_im), Cin, out, rtol, atol, max_dim,
-                                      nvec, n);
-    if (st != LZ_FALLBACK) return st;
-  }
   ++ctx->lz_paths[mpse_ctx::LP_SYNC];
   const int64_t nd = n * (cplx ? 2 : 1);  // doubles per vector
-  const std::complex<double> dt(dt_re, dt_im);
   const double tiny = 100.0 * double(n) * 2.220446049250313e-16;
 
   int cap = 16;
@@ -1014,17 +1008,10 @@ int lanczos_attempt(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, 
   // optional HIP-event sampling of the HBM-bound vector kernels (mpse_prof_*, variant 4): algorithmic bytes
   const double vbytes = double(n) * double(es);
   auto dot_partials = [&](const void* x, const void* y, double* dst_partial) {
-    mpse_ctx::ProfRec rec;
-    const bool pt = prof_begin(ctx, 4, 0.0, 2.0 * vbytes, &rec);
-    struct End {
-      mpse_ctx* c;
-      const mpse_ctx::ProfRec* r;
-      ~End() {
-        if (r) prof_end(c, *r);
-      }
-    } end{ctx, pt ? &rec : nullptr};
+    ProfScope ps(ctx, 4, 0.0, 2.0 * vbytes);
     MPSE_LAUNCH_TF(ctx, cplx, k_dot_partial, dim3(nb), dim3(RED_THREADS), (const double*)x, (const double*)y, (long long)n,
                    dst_partial, (const int*)nullptr);
+    ps.end();
   };
 
   // v0 = C / |C|
@@ -1095,12 +1082,11 @@ int lanczos_attempt(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, 
       return MPSE_OK;
     }
     if (!vec16) ++ctx->lz_paths[mpse_ctx::LP_UNVEC];
-    mpse_ctx::ProfRec urec;
-    const bool upt = prof_begin(ctx, 4, 0.0, (j > 0 ? 4.0 : 3.0) * vbytes, &urec);
+    ProfScope ups(ctx, 4, 0.0, (j > 0 ? 4.0 : 3.0) * vbytes);
     MPSE_LAUNCH_TF(ctx, vec16, k_lanczos_update, dim3(nb), dim3(RED_THREADS), W.as<double>(), (const double*)vec(j),
                    j > 0 ? (const double*)vec(j - 1) : (const double*)nullptr, (long long)nd, (const double*)part_a, nb,
                    scal + 4 + 4 * j, (const double*)(scal + 6 + 4 * (j > 0 ? j - 1 : 0)), part_b, (const int*)nullptr);
-    if (upt) prof_end(ctx, urec);
+    ups.end();
     // beta_j^2: needed by the host at a check and by the next update; k_scale_into_dev stores it when it runs
     // (every path that continues), the returning paths below read it through k_reduce_final
     const bool check = (j > 3 && j % 2 == 0);                      // krylov.py:76-81
@@ -1174,20 +1160,32 @@ int lanczos_attempt(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, 
       std::swap(V.p, V2.p);
       cap = ncap;
     }
-    mpse_ctx::ProfRec srec;
-    const bool spt = prof_begin(ctx, 4, 0.0, 2.0 * vbytes, &srec);
+    ProfScope sps(ctx, 4, 0.0, 2.0 * vbytes);
     MPSE_LAUNCH_TF(ctx, vec16, k_scale_into_dev, dim3(nb), dim3(RED_THREADS), (double*)vec(j + 1), W.as<const double>(),
                    (long long)nd, (const double*)part_b, nb, scal + 6 + 4 * j, (const int*)nullptr);
-    if (spt) prof_end(ctx, srec);
+    sps.end();
   }
+}
+
+// One attempt at C as it is: the asynchronous solve where it applies, behind it the synchronous one.  LZ_BADSTART: |C|^2
+// is outside what the recurrence takes (expm_lanczos_solve decides); the arguments are checked there.
+int lanczos_attempt(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin, void* out,
+                    double rtol, double atol, int max_dim, int* nvec, int64_t n, bool async_first, mpse_ctx::CMask cmask) {
+  const std::complex<double> dt(dt_re, dt_im);
+  if (async_first && lanczos_async_enabled() && n > 256) {
+    const int st = expm_lanczos_async(ctx, dtype, h, dt, Cin, out, rtol, atol, max_dim, nvec, n, cmask);
+    if (st != LZ_FALLBACK) return st;
+  }
+  return expm_lanczos_sync(ctx, dtype, h, dt, Cin, out, rtol, atol, max_dim, nvec, n);
 }
 
 // The solve behind mpse_expm_lanczos and the members of a batch that run alone.  A start vector whose |C|^2 the recurrence
 // cannot take as it is (LZ_BADSTART) is zero or not finite - an error - or a nonzero C whose squared norm is subnormal or
 // beyond 1e300.  That one is solved as 2^e C, its largest element in [1, 2), with atol scaled alike, and the result scaled
 // back by 2^-e: the same stopping decisions, exact scalings.  Rare, and outside every iteration: C goes through the host once.
+// cmask: the caller's structural mask of the centre for this solve (empty: none) - both attempts receive it.
 int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin, void* out,
-                       double rtol, double atol, int max_dim, int* nvec, bool async_first = true) {
+                       double rtol, double atol, int max_dim, int* nvec, mpse_ctx::CMask cmask, bool async_first = true) {
   const bool cplx = dtype == MPSE_C128;
   if (!cplx && dt_im != 0.0)
     return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: complex time step needs a complex128 centre tensor");
@@ -1206,8 +1204,7 @@ int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_r
     if (o0 != c0 && o0 < c0 + bytes && c0 < o0 + bytes)
       return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: out overlaps C without being C");
   }
-  const mpse_ctx::CMask cmask = ctx->cmask_pending;   // (the first attempt takes it over)
-  int st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, n, async_first);
+  int st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, n, async_first, cmask);
   if (st != LZ_BADSTART) return st;
   const int64_t nd = n * (cplx ? 2 : 1);
   std::vector<double> hv(static_cast<size_t>(nd));
@@ -1224,8 +1221,7 @@ int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_r
   MPSE_TRY(S.alloc(size_t(nd) * sizeof(double)));
   MPSE_TRY(mpse_memcpy_h2d(ctx, S.p, hv.data(), size_t(nd) * sizeof(double)));
   ++ctx->lz_paths[mpse_ctx::LP_RESCALE];
-  ctx->cmask_pending = cmask;
-  st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, S.p, out, rtol, std::ldexp(atol, e), max_dim, nvec, n, true);
+  st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, S.p, out, rtol, std::ldexp(atol, e), max_dim, nvec, n, true, cmask);
   if (st == LZ_BADSTART) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: start vector out of range after scaling");
   if (st == MPSE_OK || st == MPSE_ERR_NOCONV) {   // (NOCONV leaves its last estimate in out as well)
     hipLaunchKernelGGL((k_scal<false>), dim3(ew_blocks(nd)), dim3(256), 0, ctx->stream, (double*)out, (long long)nd,
@@ -1392,10 +1388,9 @@ int expm_lanczos_batch_set(mpse_ctx* ctx, int dtype, const BatchSet& bs, const m
   for (int m = 0; m < B; ++m) {
     if (!single[m]) continue;
     const int i = bs.idx[m];
-    ctx->cmask_pending = mpse_ctx::CMask();
     int nv = 0;
     const int st = expm_lanczos_solve(ctx, dtype, &hs[i], dt.real(), dt.imag(), member_ptr(vec(0), m, mstride), outs[i],
-                                      rtol, atol, max_dim, &nv, hc[m].bad != 0);
+                                      rtol, atol, max_dim, &nv, mpse_ctx::CMask(), hc[m].bad != 0);
     if (nvec) nvec[i] = nv;
     st_out[i] = st;
     if (st != MPSE_OK) msg[i] = ctx->err;
@@ -1424,8 +1419,9 @@ int mpse_expm_lanczos(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re
   MPSE_BIND(ctx);
   // calls recorded by the caller for the time the result exists (QR of the new centre, environment update, absorption
   // of a bond factor) are issued here, before control goes back to the host language
-  const int st = expm_lanczos_solve(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec);
-  ctx->cmask_pending = mpse_ctx::CMask();   // a mask is good for the solve it was set for, whatever path that took
+  // a mask is good for the one solve it was set for, whatever path that takes: it leaves the context here
+  const mpse_ctx::CMask cmask = std::exchange(ctx->cmask_pending, mpse_ctx::CMask());
+  const int st = expm_lanczos_solve(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, cmask);
   return defer_replay(ctx, st);
 }
 
@@ -1438,7 +1434,6 @@ int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff
   MPSE_BIND(ctx);
   const int md = (max_dim <= 0 || max_dim > 128) ? 128 : max_dim;
   const bool cplx = dtype == MPSE_C128;
-  const mpse_ctx::CMask saved_mask = ctx->cmask_pending;   // (left for the next mpse_expm_lanczos)
   std::vector<int> st(count, MPSE_OK);
   std::vector<std::string> msg(count);
   std::vector<char> grouped(count, 0);
@@ -1501,18 +1496,16 @@ int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff
   for (int i = 0; i < count; ++i) {
     if (grouped[i]) continue;
     ++ctx->lz_batch_single;
-    ctx->cmask_pending = mpse_ctx::CMask();
     if (!C[i] || !out[i]) {
       st[i] = mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: null vector");
       msg[i] = ctx->err;
       continue;
     }
     int nv = 0;
-    st[i] = expm_lanczos_solve(ctx, dtype, &h[i], dt_re, dt_im, C[i], out[i], rtol, atol, max_dim, &nv);
+    st[i] = expm_lanczos_solve(ctx, dtype, &h[i], dt_re, dt_im, C[i], out[i], rtol, atol, max_dim, &nv, mpse_ctx::CMask());
     if (nvec) nvec[i] = nv;
     if (st[i] != MPSE_OK) msg[i] = ctx->err;
   }
-  ctx->cmask_pending = saved_mask;
   int status = MPSE_OK;
   for (int i = 0; i < count; ++i)
     if (st[i] != MPSE_OK) {

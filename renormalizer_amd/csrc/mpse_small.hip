@@ -526,13 +526,7 @@ MatvecReq::Parts lanczos_parts(int64_t n) {
 
 }  // namespace
 
-void heff_small_drop_cache(mpse_ctx* ctx) {
-  heff0_drop_cache(ctx);       // (the fused 0-site matvec keeps its per-solve data for the same span)
-  if (ctx->small_rt.rt) mpse_free(ctx, ctx->small_rt.rt);
-  ctx->small_rt = mpse_ctx::SmallRt();
-}
-
-int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, const SolveScope* sc,
+int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc,
                    MatvecReq* mv, bool* taken) {
   *taken = false;
   const MatvecReq::Parts pr = mv ? mv->parts : MatvecReq::Parts();
@@ -543,22 +537,20 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
   const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
 
-  // transposed right environment: once per solve (the cache lives as long as the solve's SolveScope)
+  // transposed right environment: once per solve (the solve's SolveScope keeps it; another R replaces it)
   const size_t rbytes = size_t(Dr) * wr * Dr * es;
   TmpBuf rt_tmp(ctx);
   const double* rt = nullptr;
-  const bool keep = sc != nullptr;
   const int* skip = sc ? sc->skip : nullptr;
-  if (keep && ctx->small_rt.src == h->R && ctx->small_rt.bytes == rbytes && ctx->small_rt.rt) {
-    rt = static_cast<const double*>(ctx->small_rt.rt);
+  if (sc && sc->small_rt.src == h->R && sc->small_rt.bytes == rbytes && sc->small_rt.rt) {
+    rt = static_cast<const double*>(sc->small_rt.rt);
   } else {
     void* dst = nullptr;
-    if (keep) {
-      heff_small_drop_cache(ctx);
+    if (sc) {
+      if (sc->small_rt.rt) mpse_free(ctx, sc->small_rt.rt);
+      sc->small_rt = SolveScope::SmallRt();
       MPSE_TRY(mpse_malloc(ctx, rbytes, &dst));
-      ctx->small_rt.rt = dst;
-      ctx->small_rt.src = h->R;
-      ctx->small_rt.bytes = rbytes;
+      sc->small_rt = SolveScope::SmallRt{h->R, dst, rbytes};
     } else {
       MPSE_TRY(rt_tmp.alloc(rbytes));
       dst = rt_tmp.p;

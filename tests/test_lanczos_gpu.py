@@ -426,6 +426,56 @@ def test_centre_mask_vmask(eng):
         assert np.abs(o[~allowed]).max() <= 1e-12 * np.abs(o).max()
 
 
+def test_centre_mask_lifetime(eng):
+    """a centre mask serves exactly the one mpse_expm_lanczos that follows it (the problem of test_centre_mask_vmask):
+    the second solve after it runs without; a batch between the mask and its solve neither uses nor drops it; a solve
+    that is refused on its arguments uses it up"""
+    Dl, d, Dr = 32, 4, 64
+    chl, chs, chr_ = np.arange(Dl) // 16, np.arange(d), np.arange(Dr) // 32
+    k = kron_problem(130, (Dl, d, Dr), True, charges=[chl, chs, chr_])
+    allowed = ((chl[:, None, None] + chs[None, :, None] + chr_[None, None, :]) == 1).reshape(Dl, d * Dr)
+    hop = _hop(k)                                           # (no cmask attribute: _solve sets no mask by itself)
+    cmask = centre_tile_mask(eng, (chl[:, None] + chs[None, :]).reshape(-1, 1), chr_[:, None], np.array([1]), k.shape)
+    assert cmask is not None
+    c = _rand(np.random.default_rng(15), (Dl, d * Dr), True) * allowed
+    dt = -0.3j
+    ex = k.expm(dt, c.ravel())
+
+    def set_mask():
+        eng._check(eng.lib.mpse_expm_centre_mask(eng.ctx, cmask.ptr, cmask.nbytes))
+
+    def solve(masked):
+        st, out, nv, dd = _solve(eng, hop, eng.asdevice(c.reshape(k.shape)), dt, 1e-10)
+        assert st == 0 and dd.get("async_done") == 1, (st, dd)
+        assert (dd.get("update_vmask", 0) > 0) == masked, dd
+        assert np.linalg.norm(out - ex) <= 1e-9 * np.linalg.norm(ex)
+
+    # consumed once
+    set_mask()
+    solve(True)
+    solve(False)
+    # survives a batch, whose members do not use it
+    set_mask()
+    devs = [eng.asdevice(c.reshape(k.shape)) for _ in range(2)]
+    st, outs, nvs, dd, (nb, ns) = _batch(eng, [hop, hop], devs, dt, 1e-10)
+    assert st == 0 and nb + ns == 2 and "update_vmask" not in dd, (st, nb, ns, dd)
+    for o in outs:
+        assert np.linalg.norm(o - ex) <= 1e-9 * np.linalg.norm(ex)
+    solve(True)
+    solve(False)
+    # cleared by a solve that is refused before any launch: out overlaps C without being C
+    set_mask()
+    buf = eng.asdevice(np.concatenate([c.ravel(), np.zeros(k.n)]))
+    nvc = C.c_int()
+    s0, g0 = eng.lanczos_path_stats(), eng.gemm_path_stats()
+    st = eng.lib.mpse_expm_lanczos(eng.ctx, buf.code, C.byref(hop.heff), dt.real, dt.imag, buf.ptr, buf.ptr + 16 * 64,
+                                   1e-10, 0.0, 0, C.byref(nvc))
+    assert st == E.MPSE_ERR_ARG
+    assert eng.lanczos_path_stats() == s0 and eng.gemm_path_stats() == g0
+    assert np.array_equal(buf.to_host()[:k.n], c.ravel())
+    solve(False)
+
+
 # =============================================================================================== 5. run-ahead hint
 
 def test_run_ahead_hint_changes_waits_only(eng):
