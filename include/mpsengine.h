@@ -239,7 +239,9 @@ int mpse_env_update_multi(mpse_ctx* ctx, int dtype, int domain, const mpse_dims*
 
 /* Finds an MPO-bond channel b of a square environment env (D, w, D) with max|env[:, b, :] - 1| <= tol: the
  * channel in which no operator has acted yet is the identity matrix when the sites behind it are canonical
- * (the reference contracts it like any other, mps/lib.py:200-205).  *unit_host = b + 1, or 0 if there is none.
+ * (the reference contracts it like any other, mps/lib.py:200-205).  *unit_host = b + 1 for the first such channel, or 0
+ * if there is none; a channel that holds a NaN or an infinity, in either part of a complex element, never qualifies,
+ * and w > 2048 answers 0 without looking.
  * The result is passed as mpse_dims.env_unit / mpse_heff.l_unit / r_unit so that the big GEMMs skip that channel.
  * Synchronous (one small read-back). */
 int mpse_env_unit_channel(mpse_ctx* ctx, int dtype, const void* env, int64_t D, int64_t w, double tol,

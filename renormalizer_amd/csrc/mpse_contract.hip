@@ -44,8 +44,12 @@ __global__ __launch_bounds__(256) void k_unit_deviation(const double* env, int D
     for (int c = threadIdx.x; c < D; c += 256) {
       double re = row[c * E] - (c == a ? 1.0 : 0.0);
       double v = fabs(re);
-      if (CPLX) v = fmax(v, fabs(row[c * E + 1]));
-      if (!(v <= 1e300)) v = 1e300;  // NaN / inf never pass for a unit channel
+      if (!(v <= 1e300)) v = 1e300;  // NaN / inf never pass for a unit channel; each part on its own, because
+      if (CPLX) {                    // fmax returns its other argument when one is NaN
+        double vi = fabs(row[c * E + 1]);
+        if (!(vi <= 1e300)) vi = 1e300;
+        v = fmax(v, vi);
+      }
       m = fmax(m, v);
     }
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));

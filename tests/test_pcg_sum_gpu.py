@@ -13,6 +13,7 @@ import pytest
 
 from renormalizer_amd import engine as E
 
+from contract_refs import dense_ft              # (tests/contract_refs.py)
 from kron_problems import _rand, kron_problem   # (tests/kron_problems.py)
 from test_pcg_gpu import Problem, _charges, k_wait   # the exact-solution bookkeeping of the one-operator tests
 
@@ -250,8 +251,9 @@ def test_device_diagonal_of_a_term(eng, legs, trans, cplx):
     d1 = du if legs[0] == UP else dv
     d2 = du if legs[1] == UP else dv
     dev = eng.asdevice
-    w1, w2 = dev(rng.standard_normal((wl1, d1, d1, wr1))), dev(rng.standard_normal((wl2, d2, d2, wr2)))
-    L, R = dev(_rand(rng, (Dl, wl1, wl2, Dl), cplx)), dev(_rand(rng, (Dr, wr1, wr2, Dr), cplx))
+    hw1, hw2 = rng.standard_normal((wl1, d1, d1, wr1)), rng.standard_normal((wl2, d2, d2, wr2))
+    hl, hr = _rand(rng, (Dl, wl1, wl2, Dl), cplx), _rand(rng, (Dr, wr1, wr2, Dr), cplx)
+    w1, w2, L, R = dev(hw1), dev(hw2), dev(hl), dev(hr)
     shape = (Dl, du, dv, Dr)
     term = eng.ft_term(w1, w2, legs[0], legs[1], trans[0], trans[1], shape, L, R)
     n = int(np.prod(shape))
@@ -260,6 +262,10 @@ def test_device_diagonal_of_a_term(eng, legs, trans, cplx):
         e = np.zeros(n, dtype=dense.dtype)
         e[k] = 1.0
         dense[:, k] = eng.heff_apply_ft(term, dev(e.reshape(shape))).to_host().ravel()
+    # the dense operator is built with mpse_heff_apply_ft, itself code under test: anchored to the NumPy statement of
+    # the term (tests/contract_refs.py), so that a convention error shared by the matvec and the diagonal does not pass
+    dense_np = dense_ft(hl, hr, hw1, hw2, legs, trans, shape)
+    assert np.abs(dense - dense_np).max() <= 1e-12 * np.abs(dense_np).max()
     ref = np.real(np.diag(dense))
     fac = eng.site_factor_ft(term)
     d = eng.diag_ft_sum([term], [fac], [1.0], 0.0).to_host().ravel()
