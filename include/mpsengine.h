@@ -630,6 +630,53 @@ int mpse_mps_corr_stats(mpse_ctx* ctx, int64_t* counts, int n);
  * No context, no device work. */
 int mpse_mps_corr_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
 
+/* ------------------------------- one-site reduced density matrices of selected sites */
+
+/* rho_i[p, p'] = sum_{a,a',g,b,b'} conj(A[a,p,g,b]) L_i[a,a'] A[a',p',g,b'] R_i[b,b'] for every selected site i of ONE
+ * chain in one call, L_i and R_i the identity-operator environments of the sites left and right of i (their first index
+ * comes from the conjugated tensor), the ancilla leg g traced; replaces the per-site products and host reads of
+ * mps/mps.py:1547-1598 (calc_1site_rdm) and, traced against a one-site operator O (first index on the bra side), <O> =
+ * sum_{p,p'} O[p,p'] rho_i[p,p'], the per-operator windows of expectations:
+ *   sites[i]    : device site tensors, contiguous (D_l, d, danc, D_r), each MPSE_F64 or MPSE_C128 (dtype[i]; any mixture)
+ *   dims        : nsite rows (D_l, d, danc, D_r), host
+ *   sel         : nsel site indices, strictly ascending, host
+ *   out_host    : the nsel matrices one after the other, each d x d row-major complex pairs: 2 * sum_k d_k^2 doubles
+ * Refusals as mpse_mps_corr: rows with an extent < 1, neighbours whose bonds differ, a first / last bond != 1, or a
+ * selection that is not strictly ascending inside [0, nsite): MPSE_ERR_SHAPE before any device work.  Null pointers, an
+ * empty selection and unknown dtypes: MPSE_ERR_ARG.  A refused call counts nothing, enqueues nothing and leaves out_host
+ * as it was.  Chains that pass mpse_mps_rdm1_plan run as TWO launches with no host read between them: k_rdm1_envs (two
+ * workgroups; one walks from the right with R in LDS, the other from the left with L in LDS, and each leaves its
+ * environment of every selected site in pooled memory) and k_rdm1_sites (one workgroup per selected site closes the two
+ * environments around the site; each p of rho[p, p'] is summed by one wave with lane shuffles); no flag, spin wait or
+ * atomic between workgroups.  Every other chain runs the same contractions as products of the contraction kernel, all
+ * temporaries pooled (MPSE_ERR_OOM when they do not fit; the context stays usable).  The working dtype is complex as
+ * soon as any site is; a real chain returns zero imaginary parts.  A fixed summation order: the same inputs give the same
+ * bits on every call (the two paths sum in different orders and agree to rounding).  MPSE_RDM1_CHAIN=0 in the
+ * environment sends every chain through the enqueued products, =1 every chain whose launches fit through the kernels,
+ * above the bond limit of the rule as well (both for measurements).  Synchronous, one host read at the end; refused
+ * while a deferred list is being recorded. */
+int mpse_mps_rdm1(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype, const int64_t* dims /* nsite x 4 */,
+                  int nsel, const int* sel, double* out_host);
+/* counts[i], i < n, cumulative:  0 calls taken by the chain kernels, 1 calls taken by the enqueued path, 2 sites walked
+ * (nsite per call), 3 matrices produced (nsel per call).  A refused call counts nothing.  Diagnostics for tests; no
+ * device work. */
+int mpse_mps_rdm1_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims table and the number of selected sites alone: returns 1 when the chain kernels take the
+ * call, else 0 (also for a table mpse_mps_rdm1 refuses).  The launches FIT when every bond <= info[10], d, danc and d *
+ * danc <= info[9], nsel >= 1, and the environment plus the largest (sigma, ancilla) slice (rows padded to an odd length
+ * against bank conflicts) lie within info[1] bytes of LDS in the working dtype (complex when any_complex != 0).  The
+ * kernels TAKE a call that fits when every bond is also <= info[0] (profiles/rdm1.md).  info[i], i < n (may be NULL):
+ *    0  the bond limit of the rule
+ *    1  LDS bytes a workgroup may use (the 160 KiB of a gfx950 compute unit)
+ *    2  LDS bytes of either launch (0: not taken)    3  its elements of the environment (0: does not fit)
+ *    4  its elements of a slice    5  threads of a workgroup    6  the largest bond of the table (0: refused)
+ *    7  1 when the table is a chain    8  the cap on nsel (0: none, one workgroup per selected site)
+ *    9  the largest d * danc the kernels take
+ *   10  the bond limit of the LDS: the largest power of two D with a complex D x D environment and slice inside info[1]
+ *   11  LDS bytes of either launch when it fits, whatever info[0] says (0: does not fit)
+ * No context, no device work. */
+int mpse_mps_rdm1_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

@@ -1,5 +1,5 @@
-// What the "whole chain in one engine call" entry points share (mpse_overlap.hip, mpse_sandwich.hip, mpse_corr.hip; no
-// other file includes this).  Each call walks a chain of site tensors either with its own one-workgroup kernel(s), the
+// What the "whole chain in one engine call" entry points share (mpse_overlap.hip, mpse_sandwich.hip, mpse_corr.hip,
+// mpse_rdm1.hip; no other file includes this).  Each call walks a chain of site tensors either with its own one-workgroup kernel(s), the
 // environment in LDS, or as products enqueued back to back; which one, its plan decides from the dims table alone.  A
 // call supplies its descriptor row, its plan (the sizing behind chain_table_ok), its kernel(s) with their loop nests
 // and its enqueued fallback; the element type, the limits of a launch, the publishing tail, the staging, the dispatch

@@ -158,6 +158,9 @@ struct mpse_ctx {
   // mpse_mps_corr (mpse_mps_corr_stats; the order of include/mpsengine.h)
   enum CorrStat { CR_CHAIN, CR_ENQUEUED, CR_SITES, CR_ENTRIES, CR_COUNT };
   long long corr_stats[CR_COUNT] = {0};
+  // mpse_mps_rdm1 (mpse_mps_rdm1_stats; the order of include/mpsengine.h)
+  enum Rdm1Stat { RD_CHAIN, RD_ENQUEUED, RD_SITES, RD_MATRICES, RD_COUNT };
+  long long rdm1_stats[RD_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

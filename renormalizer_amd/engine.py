@@ -187,6 +187,10 @@ _SIGNATURES = {
                       _dblp, _dblp, _dblp, _dblp],
     "mpse_mps_corr_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_mps_corr_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
+    "mpse_mps_rdm1": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p, C.c_int, C.POINTER(C.c_int),
+                      _dblp],
+    "mpse_mps_rdm1_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_rdm1_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -265,6 +269,29 @@ def mps_corr_plan(dims, nsel, any_complex, lib=None):
     rows = [[int(x) for x in r] for r in dims]
     assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
     return _chain_plan(lib.mpse_mps_corr_plan, rows, 4, CORR_PLAN_INFO, int(nsel), int(bool(any_complex)))
+
+
+RDM1_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid",
+                  "nsel_limit", "p_limit", "bond_fit_limit", "lds_fit_bytes")
+
+
+def mps_rdm1_plan(dims, nsel, any_complex, lib=None):
+    """Which path ``Engine.mps_rdm1`` takes for a chain, from its ``dims`` rows (D_l, d, danc, D_r) and the number of
+    selected sites alone (``mpse_mps_rdm1_plan``; needs the built library, no GPU).  Returns (chain kernels?, {info
+    name: value}); ``nsel_limit`` is 0: the kernels take any number of selected sites."""
+    lib = lib or load_library()
+    rows = [[int(x) for x in r] for r in dims]
+    assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
+    return _chain_plan(lib.mpse_mps_rdm1_plan, rows, 4, RDM1_PLAN_INFO, int(nsel), int(bool(any_complex)))
+
+
+def check_selection(call, sel, nsite):
+    """The site selection of a chain call as a list of ints; ValueError unless it is strictly ascending inside
+    [0, nsite) and not empty"""
+    sel = [int(k) for k in sel]
+    if not sel or sel[0] < 0 or sel[-1] >= nsite or any(b <= a for a, b in zip(sel, sel[1:])):
+        raise ValueError(f"{call}: the selection {sel} is not strictly ascending inside [0, {nsite})")
+    return sel
 
 
 def _site_args(sites):
@@ -820,6 +847,33 @@ class Engine:
             self.ctx, n, *_site_args(sites), dims, nsel, (C.c_int * nsel)(*[int(k) for k in sel]),
             *[p.ctypes.data_as(_dblp) for p in packed], out.ctypes.data_as(_dblp)))
         return out
+
+    # -- one-site reduced density matrices
+    RDM1_STATS = ("chain_kernel", "enqueued", "sites", "matrices")
+
+    def mps_rdm1_stats(self):
+        """{name: count} of the ``mps_rdm1`` calls of this context, cumulative (``mpse_mps_rdm1_stats``): calls taken by
+        the chain kernels, calls taken by the enqueued products, sites walked, matrices produced."""
+        return self._stats_dict(self.lib.mpse_mps_rdm1_stats, self.RDM1_STATS)
+
+    def mps_rdm1(self, sites, sel):
+        """rho_i[p, p'] = sum conj(A[a,p,g,b]) L_i[a,a'] A[a',p',g,b'] R_i[b,b'] for the sites ``sel`` (strictly
+        ascending) of a chain of device site tensors (D_l, d[, danc], D_r), in one engine call (``mpse_mps_rdm1``); L_i
+        and R_i are the identity-operator environments of the other sites, the ancilla leg of density-operator sites is
+        traced.  Returns a list of (d, d) complex128 arrays, one per selected site."""
+        rows = self.corr_dims(sites)
+        n = len(rows)
+        if n == 0:
+            raise ValueError("mps_rdm1: no sites")
+        sel = check_selection("mps_rdm1", sel, n)
+        nsel = len(sel)
+        dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
+        sizes = [rows[k][1] ** 2 for k in sel]
+        out = np.zeros(sum(sizes), dtype=np.complex128)
+        self._check(self.lib.mpse_mps_rdm1(
+            self.ctx, n, *_site_args(sites), dims, nsel, (C.c_int * nsel)(*sel), out.ctypes.data_as(_dblp)))
+        ends = np.cumsum(sizes)
+        return [out[e - sz:e].reshape(rows[k][1], rows[k][1]) for k, sz, e in zip(sel, sizes, ends)]
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""

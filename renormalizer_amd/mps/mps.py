@@ -580,6 +580,66 @@ class Mps:
                 lenv = contract_one_site(lenv, ms, ident[i], "L")
         return rdm
 
+    def site_rdms(self, idx=None) -> Dict[int, np.ndarray]:
+        """The value of ``calc_1site_rdm(idx)`` as ONE engine call (``Engine.mps_rdm1`` -> ``mpse_mps_rdm1``): both
+        environment passes and the closing products of every requested site run inside the engine, by two launches
+        where every bond is inside the limit of its path rule, and the host reads once.  Same keys, shapes and dtype
+        (a real array for a real state); ``idx``: a site, a list of sites or None for all.  For the local observables
+        taken after every step; ``calc_1site_rdm`` itself stays as it is (its values are pinned bit for bit).  The two
+        sum in different orders and agree to rounding.  Works for ``Mps`` and ``MpDm`` (the ancilla leg is traced); the
+        ``coeff`` factor is not included."""
+        if idx is None:
+            idx = range(self.site_num)
+        elif isinstance(idx, (int, np.integer)):
+            idx = [int(idx)]
+        sel = sorted(set(int(i) for i in idx))
+        mats = get_engine().mps_rdm1(self._mp, sel)
+        return {i: (m if self.is_complex else np.ascontiguousarray(m.real)) for i, m in zip(sel, mats)}
+
+    def site_expectations(self, symbol, dofs) -> np.ndarray:
+        """<psi| Op(symbol, dof) |psi> of a one-site operator for every dof of ``dofs``, each as sum(O * rho_site) with
+        the site's reduced density matrix from ONE engine call over the sites that carry a requested dof
+        (``site_rdms``); dofs on one site share its matrix.  The values of ``expectations([Mpo(model, Op(symbol, dof))
+        for dof in dofs])`` without an operator window and a host read per dof; ``expectations`` itself stays as it is
+        (its values are pinned bit for bit), the two sum in different orders and agree to rounding.  Real when every
+        imaginary part vanishes to ``np.isclose``, as in ``expectation``.  ValueError for an operator that is not a
+        one-site operator.  The ``coeff`` factor is not included."""
+        return self._site_expectations([(symbol, dof) for dof in dofs])[0]
+
+    def _site_expectations(self, *groups):
+        """one array per group of (symbol, dof) pairs, all from one ``site_rdms`` call"""
+        local = []
+        for group in groups:
+            for symbol, dof in group:
+                if isinstance(dof, list) or dof not in self.model.dof_to_siteidx:
+                    raise ValueError(f"Op({symbol!r}, {dof!r}) is not a one-site operator on a dof of the model")
+                local.append(self._local_matrix(symbol, dof))
+        if not local:
+            return [np.zeros(0) for _ in groups]
+        rdms = self.site_rdms([site for site, _ in local])
+        vals = np.array([np.sum(mat * rdms[site]) for site, mat in local], dtype=np.complex128)
+        out, at = [], 0
+        for group in groups:
+            v = vals[at:at + len(group)]
+            at += len(group)
+            out.append(v.real.copy() if np.isclose(v.imag, 0).all() else v)
+        return out
+
+    def occupations(self):
+        """(``e_occupations``, ``ph_occupations``) from ONE engine call over the union of their sites
+        (``site_rdms``), instead of one operator window and one host read per degree of freedom.  The two properties
+        themselves stay as they are (their values are pinned bit for bit); the two sum in different orders and agree
+        to rounding.  Real when the imaginary parts vanish to ``np.isclose``, as in ``expectation``."""
+        e_occ, ph_occ = self._site_expectations([(r"a^\dagger a", dof) for dof in self.model.e_dofs],
+                                                [("n", dof) for dof in self.model.v_dofs])
+        return e_occ, ph_occ
+
+    def site_entropies(self) -> Dict[int, float]:
+        """The values of ``calc_entropy("1site")``, the von Neumann entropy of every one-site reduced density matrix,
+        from ``site_rdms()``: one engine call for the whole chain.  ``calc_entropy`` itself stays as it is; the two
+        sum in different orders and agree to rounding."""
+        return {k: _vn_entropy(np.linalg.eigvalsh(dm)) for k, dm in self.site_rdms().items()}
+
     def calc_2site_rdm(self) -> Dict:
         """Two-site reduced density matrices of all pairs i < j (mps/mps.py:1600-1655):
         rdm[(i, j)][(p, q), (p', q')] = sum conj(A_i)[.,p,.] conj(A_j)[.,q,.] A_i[.,p',.] A_j[.,q',.] with the identity
