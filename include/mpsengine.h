@@ -178,7 +178,7 @@ int mpse_gemm(mpse_ctx* ctx, const mpse_gemm_desc* desc, const void* A, const vo
 
 /* How the contraction kernel was launched: cumulative counts of this context, counted on the host where the launcher
  * decides (a call that returns early or is refused counts nothing; a deferred call counts when it runs).  counts[i]
- * for i < min(n, 15), in this order:
+ * for i < min(n, 16), in this order:
  *    0  launches of the kernel by mpse_gemm and the contraction plans (grouped launches excepted)
  *    1  of them through the general kernel (a two-level K index, a negative stride or an operand span of 4 GB or more)
  *    2  eight waves per workgroup (one workgroup per compute unit or fewer, at least two K tiles)
@@ -194,6 +194,7 @@ int mpse_gemm(mpse_ctx* ctx, const mpse_gemm_desc* desc, const void* A, const vo
  *   12  of them with every tile halved between two workgroups
  *   13  of them that form their beta term in the epilogue from blocks of the MPO site (epilogue mix)
  *   14  launches of the elementwise MPO pass (k_wmix) by the contraction plans
+ *   15  grouped launches that left the result tiles outside the solve's structural mask unwritten (MPSE_OUT_MASK)
  * Diagnostics for tests (which path ran); no device work. */
 int mpse_gemm_path_stats(mpse_ctx* ctx, int64_t* counts, int n);
 

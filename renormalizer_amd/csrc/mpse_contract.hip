@@ -439,10 +439,11 @@ static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in
         gd.split2 = true;
         gd.c2 = const_cast<void*>(bufs[B_OUT2]);
       }
-      // the last step completes the result: it carries the caller's dot request
+      // the last step completes the result: it carries the caller's dot request and result mask
       const bool completes =
           &s == &p.steps.back() && gd.ngrp == 1 && s.groups[0].cbuf == B_OUT && s.groups[0].c_off == 0;
-      MPSE_TRY(gemm_grouped(ctx, gd, sc, completes ? dot : nullptr));
+      MPSE_TRY(gemm_grouped(ctx, gd, sc, completes ? dot : nullptr,
+                            completes && mv && mv->out_mask.mask ? &mv->out_mask : nullptr));
       continue;
     }
     const char* a = (const char*)bufs[s.a] + size_t(s.a_off) * dtype_size(s.dta);

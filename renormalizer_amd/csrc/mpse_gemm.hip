@@ -97,6 +97,13 @@ struct GemmGroups {
   long long mix_ld;
   const double* mix_w;
   GMix mix[GMAX_MIX];
+  // result mask (MatvecReq::OutMask; one group, the launch carries the dot request): the caller reads the result only
+  // where omask says - rows of om_d * N elements, the product's rows being (a, sigma), sigma < om_d.  k_tile_order marks
+  // the tiles that lie wholly outside (mpse_plans.h out_tile_live) in the launch order as ~tile: their workgroups store
+  // a zero dot partial and nothing else.
+  const unsigned char* omask;
+  int om_pitch, om_d;
+  int dot4;     // eight-wave form: the dot partial in the summation order of the four-wave form (see the epilogue)
 };
 
 struct GemmArgs {
@@ -154,6 +161,28 @@ __device__ __forceinline__ long long idx_off(const IdxMap& m, int i) {
   const int hi = i / m.lo;
   const int l = i - hi * m.lo;
   return (long long)hi * m.s_hi + (long long)l * m.s_lo;
+}
+
+// one record of the debug timeline (MPSE_GEMM_TRACE), written by one thread of a workgroup as it leaves the kernel
+__device__ __forceinline__ void trace_record(const GemmArgs& g, bool ca, bool cb, unsigned long long t0,
+                                             unsigned long long rt0, unsigned long long t1, unsigned long long t2,
+                                             unsigned long long t3, int ktd) {
+  const unsigned long long slot = atomicAdd(g.trace, 1ull);
+  if (slot >= GEMM_TRACE_CAP) return;
+  unsigned long long* r = g.trace + 1 + slot * GEMM_TRACE_WORDS;
+  r[0] = ((unsigned long long)gridDim.x << 32) | (unsigned long long)blockIdx.x;
+  r[1] = ((unsigned long long)(ca ? 1 : 0) << 62) | ((unsigned long long)(cb ? 1 : 0) << 61) |
+         ((unsigned long long)g.ksplit << 40) | ((unsigned long long)(unsigned)g.K << 8);
+  // where the workgroup ran: HW_ID (wave / SIMD / CU / SH / SE fields) and the die (XCC_ID)
+  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
+  r[2] = (unsigned long long)(unsigned)ktd | ((unsigned long long)(((xc & 0xf) << 16) | (hw & 0xffff)) << 32);
+  r[3] = t0;
+  r[4] = t1;
+  r[5] = t2;
+  r[6] = t3;
+  r[7] = __builtin_readcyclecounter();
+  r[8] = rt0;
+  r[9] = __builtin_amdgcn_s_memrealtime();
 }
 
 #ifndef MPSE_GEMM_3M
@@ -229,9 +258,29 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   const int ks_id = bs - b * g.ksplit;
   // heaviest tiles first (k_tile_order); the odd slices of a split product run through the order backwards, so that
   // the compute unit that receives a heavy tile's slice in one round receives a light one in the next
-  if (g.perm) t = g.perm[(ks_id & 1) ? ntile - 1 - t : t];
+  bool dead = false;                     // grouped launch with a result mask: nobody reads this tile
+  if (g.perm) {
+    t = g.perm[(ks_id & 1) ? ntile - 1 - t : t];
+    if constexpr (GRP) {
+      dead = t < 0;
+      t = dead ? ~t : t;
+    }
+  }
   int tm = t / g.tiles_n;
   int tn = t - tm * g.tiles_n;
+  if constexpr (GRP) {
+    // (workgroup-uniform; before anything of the operands, the beta term, the mix or the dot partner is asked for.
+    // The partial's slot is the tile's, as in the epilogue: the sum over the slots keeps its order.)
+    if (dead) {
+      if (g.dot_y && tid == 0) {
+        const long long slot = (long long)bs * ntile + t;
+        g.dot_part[2 * slot] = 0.0;
+        g.dot_part[2 * slot + 1] = 0.0;
+      }
+      if (g.trace && tid == 0) trace_record(g, CA, CB, tr0, rt0, tr0, tr0, tr0, 0);   // (an empty workgroup of the timeline)
+      return;
+    }
+  }
   // unsplit products without a sorted order: all tiles of a tile row (die_group 1) or tile column (2) on one die -
   // position p runs on die p mod 8, so die x takes rows x, x + 8, .. with every column: the larger operand's panels are
   // fetched into one L2 instead of into all eight
@@ -778,26 +827,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     int tid;
     int& ktd;
     __device__ ~TraceEnd() {
-      if (g.trace && tid == 0) {
-        const unsigned long long slot = atomicAdd(g.trace, 1ull);
-        if (slot < GEMM_TRACE_CAP) {
-          unsigned long long* r = g.trace + 1 + slot * GEMM_TRACE_WORDS;
-          unsigned xcc = 0;
-          r[0] = ((unsigned long long)gridDim.x << 32) | (unsigned long long)blockIdx.x;
-          r[1] = ((unsigned long long)(CA ? 1 : 0) << 62) | ((unsigned long long)(CB ? 1 : 0) << 61) |
-                 ((unsigned long long)g.ksplit << 40) | ((unsigned long long)(unsigned)g.K << 8) | xcc;
-          // where the workgroup ran: HW_ID (wave / SIMD / CU / SH / SE fields) and the die (XCC_ID)
-          const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-          r[2] = (unsigned long long)(unsigned)ktd | ((unsigned long long)(((xc & 0xf) << 16) | (hw & 0xffff)) << 32);
-          r[3] = t0;
-          r[4] = t1;
-          r[5] = t2;
-          r[6] = t3;
-          r[7] = __builtin_readcyclecounter();
-          r[8] = rt0;
-          r[9] = __builtin_amdgcn_s_memrealtime();
-        }
-      }
+      if (g.trace && tid == 0) trace_record(g, CA, CB, t0, rt0, t1, t2, t3, ktd);
     }
   } trace_end{g, tr0, rt0, tr1, tr2, tr3, tid, kt_done};
   if (g.kt_counter && tid == 0 && kt_done) atomicAdd(g.kt_counter, (unsigned long long)kt_done);
@@ -928,10 +958,27 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
         }
     }
   }
+  // Eight waves with the dot partial of the four-wave form (GemmGroups::dot4; whole tiles only).  There a lane sums its
+  // 16 products in the order (j, i, r); here the rows i = 0 / 1 of that lane belong to the same lane of the waves
+  // wm = 2 m / 2 m + 1.  The running sum goes from one to the other through LDS - even wave columns j = 0, odd wave
+  // j = 0, even j = 1, odd j = 1 - so the odd waves end with the four-wave lanes' values; the even ones count as zero.
+  constexpr bool HAND = GRP && PRE && WI == 1;
+  bool hand = false;
+  auto hslot = [&]() { return smem + 1024 + (((wm >> 1) * 2 + wn) * 64 + lane) * 2; };   // (behind the weights of the mix)
+  if constexpr (HAND) {
+    hand = g.gg.dot4 != 0 && need_y;   // workgroup-uniform
+    if (hand) __syncthreads();         // every wave has left the K loop and the mix: the panels are free
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int gj = tn * TBN + wn * 32 + j * 16 + (lane & 15);
     if (gj >= g.N) continue;
+    if constexpr (HAND) {
+      if (hand) {
+        if (wm & 1) __syncthreads();                       // the even wave's columns j are in
+        if ((wm & 1) || j > 0) dre = hslot()[0], dim = hslot()[1];
+      }
+    }
     const long long coffn = idx_off(g.nC, gj);
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
@@ -971,6 +1018,20 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
         }
       }
     }
+    if constexpr (HAND) {
+      if (hand) {
+        if (!((wm & 1) && j == 1)) hslot()[0] = dre, hslot()[1] = dim;
+        if (!(wm & 1)) {
+          __syncthreads();
+          if (j == 0) __syncthreads();                     // the odd wave's columns 0 are in
+        } else if (j == 0) {
+          __syncthreads();
+        }
+      }
+    }
+  }
+  if constexpr (HAND) {
+    if (hand && !(wm & 1)) dre = dim = 0.0;
   }
   if constexpr (WS == 2) {
     if (g.dot_y) {   // workgroup-uniform
@@ -1032,25 +1093,30 @@ __global__ __launch_bounds__(1024) void k_tile_order(const unsigned long long* _
                                                        const unsigned long long* __restrict__ bmask, int nkw, int nkt,
                                                        int tiles_m, int tiles_n, int by_die, int* __restrict__ perm,
                                                        const int* __restrict__ skip, const GemmGroups gg,
-                                                       unsigned char* __restrict__ flags_out, int flags_pitch) {
+                                                       unsigned char* __restrict__ flags_out, int flags_pitch,
+                                                       int om_M, int om_N) {
   if (skip && *skip) return;
   __shared__ unsigned key[2048], ckey[2048];
   __shared__ int colw[2048];
-  __shared__ unsigned char die_of[2048];
+  __shared__ unsigned char die_of[2048], dead[2048];
   const int ntile = tiles_m * tiles_n, tid = threadIdx.x;
   const bool part = by_die && tiles_n % 8 == 0 && tiles_n <= 2048;
   for (int c = tid; c < 2048; c += 1024) colw[c] = 0;
   __syncthreads();
   for (int i = tid; i < 2048; i += 1024) {
     unsigned cnt = 0;
+    dead[i] = 0;
     if (i < ntile) {
       const int tm = i / tiles_n, tn = i - tm * tiles_n;
       if (gg.ngrp > 0) {   // grouped launch: the segments of the tile row's group, byte flags per operand
         const int grp = tm / gg.tiles_m_grp, tml = tm - grp * gg.tiles_m_grp;
         const GGrp& G = gg.g[grp];
+        // a tile outside the result mask (one group): no flags - weight 0, last in the order - and marked there
+        const bool off = gg.omask && !mpse_plan::out_tile_live(gg.omask, gg.om_pitch, gg.om_d, om_N, om_M, tm, tn);
+        dead[i] = off ? 1 : 0;
         for (int q = 0; q < G.nseg; ++q)
           for (int l = 0; l < gg.nkt_seg; ++l) {
-            unsigned v = 1;
+            unsigned v = off ? 0 : 1;
             if (G.seg[q].am) v &= G.seg[q].am[(long long)tml * gg.am_pitch + l];
             if (G.seg[q].bm) v &= G.seg[q].bm[(long long)tn * gg.bm_pitch + l];
             cnt += v;
@@ -1096,7 +1162,8 @@ __global__ __launch_bounds__(1024) void k_tile_order(const unsigned long long* _
   const int per_die = ntile / 8;           // part: every die owns tiles_n / 8 columns of tiles_m tiles
   for (int i = tid; i < ntile; i += 1024) {
     const int s = part ? (7 - (i & 7)) * per_die + (i >> 3) : i;
-    perm[i] = 0xFFFF - (int)(key[s] & 0xFFFFu);
+    const int t = 0xFFFF - (int)(key[s] & 0xFFFFu);
+    perm[i] = dead[t] ? ~t : t;
   }
 }
 
@@ -1583,7 +1650,7 @@ static int gemm_impl(mpse_ctx* ctx, const mpse_gemm_desc* d, const void* A, cons
                          size_t(g.tiles_m) * g.tiles_n * sizeof(int), PERM, &pp, &sort));
     if (sort)
       hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, ctx->stream, g.amask, g.bmask, g.nkw, p.nkt, g.tiles_m,
-                         g.tiles_n, 1, pp, g.skip, GemmGroups(), (unsigned char*)nullptr, 0);
+                         g.tiles_n, 1, pp, g.skip, GemmGroups(), (unsigned char*)nullptr, 0, 0, 0);
     g.perm = pp;
   }
 
@@ -1625,20 +1692,42 @@ int occ_mask_get(mpse_ctx* ctx, SolveScope* sc, const void* ptr, int dtype, mpse
   return MPSE_OK;
 }
 
-// compulsory reads of an epilogue mix beyond the one beta term already counted: its distinct sources
-static double mix_sources(const GroupedDesc& d) {
-  int n = 0;
-  for (int t = 0; t < d.nmix; ++t) {
-    bool seen = false;
-    for (int u = 0; u < t; ++u) seen = seen || d.mix[u].src == d.mix[t].src;
-    n += seen ? 0 : 1;
+// Compulsory traffic of a grouped launch (M x K first operands, K x N second, M x N results): every DISTINCT operand
+// read once - the groups of the products with L share the centre tensor, which used to be counted once per group -
+// every result written once, the beta term of a group read once; a group with an epilogue mix reads, in the place of
+// its beta term, the distinct sources of the mix that are not operands of the launch already (the centre tensor is
+// both where a plane is the centre itself).
+static double grouped_bytes(const GroupedDesc& d, double M, double N, double K, bool ca) {
+  const void* seen[3][GMAX_GRP * GMAX_SEG + GMAX_MIX];
+  int n[3] = {0, 0, 0};
+  auto fresh = [&](int w, const void* p) {
+    for (int i = 0; i < n[w]; ++i)
+      if (seen[w][i] == p) return false;
+    seen[w][n[w]++] = p;
+    return true;
+  };
+  double bytes = 0.0, betas = 0.0;
+  for (int i = 0; i < d.ngrp; ++i) {
+    for (int q = 0; q < d.grp[i].nseg; ++q) {
+      if (fresh(0, d.grp[i].seg[q].A)) bytes += M * K * (ca ? 16.0 : 8.0);
+      if (fresh(1, d.grp[i].seg[q].B)) bytes += K * N * 16.0;
+    }
+    bytes += M * N * 16.0;
+    betas += d.grp[i].beta != 0.0 ? 1.0 : 0.0;
   }
-  return n > 1 ? double(n - 1) : 0.0;
+  if (d.nmix > 0) {
+    betas -= 1.0;
+    const int w = (K == N && ca) ? 0 : 2;      // (a source is laid out like the result: the extent of a first operand when K = N)
+    for (int t = 0; t < d.nmix; ++t)
+      if (fresh(w, d.mix[t].src)) bytes += M * N * 16.0;
+  }
+  return bytes + betas * M * N * 16.0;
 }
 
 // Grouped launch of the contraction kernel (mpse_internal.h GroupedDesc; folded one-site matvec of mpse_plans.h).
 // dot: the caller's dot request when this launch completes a matvec result (one group only), else null.
-int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq::Dot* dot) {
+int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq::Dot* dot,
+                 const MatvecReq::OutMask* om) {
   // ---- check
   GemmArgs g = {};
   if (d.ngrp < 1 || d.ngrp > GMAX_GRP) return mpse_fail(ctx, MPSE_ERR_ARG, "grouped product: 1 .. %d groups", GMAX_GRP);
@@ -1701,7 +1790,15 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq:
 
   // ---- plan
   const int nkt_max = max_seg * gg.nkt_seg;
-  const mpse_plan::GroupedPlan p = mpse_plan::grouped_plan(g.M, g.N, d.ngrp, nkt_max, any_mask, d.split2, ca, n_cu_of(ctx));
+  // The result mask is taken by a launch that completes the result of one group WITH the dot request riding - else a
+  // reduction of its own would read the tiles left unwritten - and whose rows are whole (a, sigma) runs of the mask's
+  // layout.  Which tiles are left out is recorded in the launch order.
+  const long long nwg_all = (long long)((g.M + BM - 1) / BM) * g.tiles_n * (d.split2 ? 2 : 1);
+  const int om_d = om && om->mask && om->row > 0 && om->row % g.N == 0 ? om->row / g.N : 0;
+  const bool om_fits = om_d > 0 && d.ngrp == 1 && dot && nwg_all <= dot->cap && g.M % om_d == 0 &&
+                       (g.M / om_d + 15) / 16 <= om->pitch && om->row % 64 == 0;
+  const mpse_plan::GroupedPlan p =
+      mpse_plan::grouped_plan(g.M, g.N, d.ngrp, nkt_max, any_mask, d.split2, ca, n_cu_of(ctx), om_fits);
   const long long ntile = (long long)p.tiles_m * p.tiles_n;
   if (ntile > 0x7fffffffLL) return mpse_fail(ctx, MPSE_ERR_SHAPE, "grouped product: grid too large");
   g.tiles_m = p.tiles_m;
@@ -1712,13 +1809,13 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq:
     g.dot_part = dot->part;
     dot->nb_out = (int)p.nwg;
   }
+  const bool out_mask = om_fits && p.order && g.dot_y;
+  if (out_mask) gg.omask = om->mask, gg.om_pitch = om->pitch, gg.om_d = om_d;
   mpse_ctx::ProfRec rec;
   const int variant = (ca ? 1 : 0) + (cb ? 2 : 0);
   const double mnk = double(g.M) * double(g.N) * double(g.K) * segs;
   const bool prof_this = prof_begin(ctx, variant, mnk * ((ca && cb) ? 8.0 : 4.0),
-                                    segs * (double(g.M) * g.K * (ca ? 16 : 8) + double(g.K) * g.N * 16.0) +
-                                        double(d.ngrp) * double(g.M) * g.N * 16.0 * (any_beta ? 2 : 1) +
-                                        mix_sources(d) * double(g.M) * g.N * 16.0,
+                                    grouped_bytes(d, double(g.M), double(g.N), double(g.K), ca),
                                     &rec);
   g.kt_counter = prof_this && ctx->prof_ktiles ? ctx->prof_ktiles + variant : nullptr;
 
@@ -1731,19 +1828,26 @@ int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq:
     int* pp = nullptr;
     bool sort = false;
     MPSE_TRY(perm_source(ctx, sc && sc->keeps_env_masks && d.masks_stable ? sc : nullptr,
-                         {gg.g[0].seg[0].am, gg.g[0].seg[0].bm, g.tiles_m, g.tiles_n, nkt_max + 1000 * d.ngrp, nullptr},
+                         {gg.g[0].seg[0].am, gg.g[0].seg[0].bm, g.tiles_m, g.tiles_n,
+                          nkt_max + 1000 * d.ngrp + (out_mask ? 1000000 : 0), nullptr},
                          perm_bytes + size_t(ntile) * flag_pitch, PERM, &pp, &sort));
     if (sort)
       hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long*)nullptr,
                          (const unsigned long long*)nullptr, 0, nkt_max, g.tiles_m, g.tiles_n, d.split2 ? 0 : 1, pp,
-                         g.skip, gg, reinterpret_cast<unsigned char*>(pp) + perm_bytes, (int)flag_pitch);
+                         g.skip, gg, reinterpret_cast<unsigned char*>(pp) + perm_bytes, (int)flag_pitch, g.M, g.N);
     g.perm = pp;
     g.gg.flags = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(pp) + perm_bytes);
   }
 
   // ---- launch
   count_paths(ctx->gemm_paths, d);
-  launch_gemm(ctx, g, p.nwg, ca, cb, true, p.wide, true);
+  ctx->gemm_paths[mpse_ctx::GP_GROUPED_OUTMASK] += out_mask;
+  // With the dead tiles gone a compute unit mostly holds ONE working workgroup of a halved launch: eight waves on it,
+  // as for launches of one workgroup per unit - with the dot partial of the four-wave form, so that the switch does not
+  // change a bit of the solve.
+  const bool om_wide = out_mask && d.split2 && ca && !p.wide && g.N % BN == 0;
+  gg.dot4 = om_wide ? 1 : 0;
+  launch_gemm(ctx, g, p.nwg, ca, cb, true, p.wide || om_wide, true);
   if (prof_this) prof_end(ctx, rec);
   MPSE_HIP(ctx, hipGetLastError());
   return MPSE_OK;

@@ -117,7 +117,7 @@ struct mpse_ctx {
   // launch decisions of the contraction kernel (mpse_gemm_path_stats; the order of include/mpsengine.h)
   enum GemmPath {
     GP_LAUNCH, GP_GENERAL, GP_WIDE, GP_SPLIT_B1, GP_SPLIT_BN, GP_DIE1, GP_DIE2, GP_SKEW, GP_ORDER, GP_MASK,
-    GP_MASK_GLOBAL, GP_GROUPED, GP_GROUPED_SPLIT2, GP_GROUPED_MIX, GP_WMIX, GP_COUNT
+    GP_MASK_GLOBAL, GP_GROUPED, GP_GROUPED_SPLIT2, GP_GROUPED_MIX, GP_WMIX, GP_GROUPED_OUTMASK, GP_COUNT
   };
   long long gemm_paths[GP_COUNT] = {0};
   // mpse_block_qr: decompositions that took the Cholesky-QR path / that fell back from it to Householder
@@ -383,9 +383,18 @@ struct MatvecReq {
     const unsigned long long* mask = nullptr;
     int mask_row = 0, mask_tiles = 0;
   } parts;
+  // Only these tiles of the result are needed: the caller reads the result nowhere else (the Lanczos update under the
+  // structural mask of the centre, with the same three quantities: the result as rows of `row` elements, byte
+  // [(column / 64) * pitch + row / 16], zero = never read).  The launch that completes the result may leave the tiles
+  // that lie wholly outside unwritten - only together with the dot request, whose partials of such tiles are (0, 0).
+  struct OutMask {
+    const unsigned char* mask = nullptr;
+    int row = 0, pitch = 0;
+  } out_mask;
 };
 
-// What run_plan asks of one product beyond its descriptor (gemm_call; gemm_grouped takes the dot request alone)
+// What run_plan asks of one product beyond its descriptor (gemm_call; gemm_grouped takes the dot request and the
+// result mask as arguments)
 struct ProductReq {
   MatvecReq::Dot* dot = nullptr;   // the product completes the matvec result: it carries the caller's dot request
   // beta source: C = A.B + beta * Cin(i, j) with Cin's own index maps
@@ -520,7 +529,9 @@ struct GroupedDesc {
   int mix_d = 0, mix_wr = 0;
   long long mix_ld = 0;
 };
-int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq::Dot* dot);
+// om: MatvecReq::out_mask of the caller when this launch completes a matvec result, else null; taken only with `dot`
+int gemm_grouped(mpse_ctx* ctx, const GroupedDesc& d, SolveScope* sc, MatvecReq::Dot* dot,
+                 const MatvecReq::OutMask* om = nullptr);
 int occ_mask_get(mpse_ctx* ctx, SolveScope* sc, const void* ptr, int dtype, mpse_index r, mpse_index k,
                  TmpBuf& tmp, const unsigned char** flags, int* pitch, bool* stable);
 

@@ -851,6 +851,10 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
       vm_kw = (int)(nkw * 8);
     }
   }
+  static const bool omask_on = [] {
+    const char* e = getenv("MPSE_OUT_MASK");   // MPSE_OUT_MASK=0: the matvec writes every tile of its result
+    return !(e && e[0] == '0');
+  }();
   // (the vector launches are bracketed for the profiler: variant 4, algorithmic bytes)
   auto dot_partials = [&](const void* x, const void* y, double* dst) {
     ProfScope ps(ctx, 4, 0.0, 2.0 * vbytes);
@@ -897,6 +901,9 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
     mv.parts.cap_elems = wcap;
     mv.parts.n = n;
     mv.parts.masked_ok = f0_parts > 0 && vec16;
+    // the update below reads the result only inside the structural mask (a matvec that answers with a part mask of its
+    // own is one that does not look at this request)
+    if (vmask && omask_on) mv.out_mask.mask = vmask, mv.out_mask.row = vm_row, mv.out_mask.pitch = vm_kw;
     MPSE_TRY(heff_apply(ctx, dtype, h, vec(j), W.p, &scope, &mv));
     const unsigned long long* pmask = mv.parts.mask;
     const int prow = mv.parts.mask_row, ptiles = mv.parts.mask_tiles;

@@ -1259,14 +1259,34 @@ inline GemmPlan launch_plan(const GemmShape& s) {
   return p;
 }
 
+// Result tiles of the products with R against the structural mask of the centre.  The result is the centre's layout:
+// rows a, columns (sigma, l), row length d * Dr; mask byte [(column / 64) * pitch + a / 16], zero = nothing of that
+// 16 x 64 block is ever read.  The product's own tile (tm, tn) covers rows (a, sigma) in [64 tm, 64 tm + 64) of its M
+// rows and columns l in [64 tn, 64 tn + 64): it is live when any byte it touches is set.  Any d: a tile may hold several
+// a (also across a 16-row boundary of the mask) or a part of one.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool out_tile_live(const unsigned char* mask, int pitch, int d, int Dr, int M, int tm, int tn) {
+  const int r1 = 64 * tm + 64 < M ? 64 * tm + 64 : M, l0 = 64 * tn, l1 = 64 * tn + 63 < Dr - 1 ? 64 * tn + 63 : Dr - 1;
+  for (int r = 64 * tm; r < r1; ++r) {
+    const int a = r / d, sg = r - a * d;
+    for (int ct = (sg * Dr + l0) >> 6; ct <= (sg * Dr + l1) >> 6; ++ct)
+      if (mask[(long long)ct * pitch + (a >> 4)]) return true;
+  }
+  return false;
+}
+
 // Grouped launch: ngrp groups of M rows each, complex second operand, nkt_max = K tiles of the longest group.
 struct GroupedPlan {
   int tiles_m, tiles_n, nkw, die_group;
   bool order, wide;
   long long nwg;
 };
+// out_mask: the launch would leave the result tiles outside the caller's mask unwritten (out_tile_live) - which tiles
+// those are is recorded with the launch order, so such a launch is ordered whatever its size
 inline GroupedPlan grouped_plan(long long M, long long N, int ngrp, int nkt_max, bool any_mask, bool split2, bool ca,
-                                int n_cu) {
+                                int n_cu, bool out_mask = false) {
   GroupedPlan p{};
   p.tiles_m = int((M + 63) / 64) * ngrp, p.tiles_n = int((N + 63) / 64);
   const long long ntile = (long long)p.tiles_m * p.tiles_n;
@@ -1274,7 +1294,7 @@ inline GroupedPlan grouped_plan(long long M, long long N, int ngrp, int nkt_max,
   p.nkw = (any_mask && (nkt_max + 7) / 8 <= 64) ? (nkt_max + 7) / 8 : 0;   // (a tile's flag words must fit its LDS copy)
   // products with more tiles than slots (heaviest first, die aware), and halved products (their position -> (tile,
   // half) map pairs heavy and light halves per compute unit through the order; plain sorted order)
-  p.order = p.nkw > 0 && order_pays(ntile, ntile, n_cu, split2);
+  p.order = p.nkw > 0 && order_pays(ntile, ntile, n_cu, split2 || out_mask);
   if (!p.order) p.die_group = die_group_rule(ntile, p.tiles_m, p.tiles_n, double(M) * ngrp * (ca ? 2 : 1), double(N) * 2);
   p.wide = p.nwg <= n_cu;
   return p;

@@ -897,12 +897,13 @@ class Engine:
 
     def wfold_path_stats(self):
         """{"grouped_mix": grouped launches that formed their beta term in the epilogue from blocks of the MPO site,
-        "wmix": launches of the elementwise MPO pass by the contraction plans}, cumulative (counters 13 and 14 of
+        "wmix": launches of the elementwise MPO pass by the contraction plans, "grouped_outmask": grouped launches that
+        skipped the result tiles outside the solve's structural mask}, cumulative (counters 13 to 15 of
         ``mpse_gemm_path_stats``)."""
         n = len(self.GEMM_PATHS)
-        v = (C.c_int64 * (n + 2))()
-        self._check(self.lib.mpse_gemm_path_stats(self.ctx, v, n + 2))
-        return {"grouped_mix": int(v[n]), "wmix": int(v[n + 1])}
+        v = (C.c_int64 * (n + 3))()
+        self._check(self.lib.mpse_gemm_path_stats(self.ctx, v, n + 3))
+        return {"grouped_mix": int(v[n]), "wmix": int(v[n + 1]), "grouped_outmask": int(v[n + 2])}
 
     def block_qr_optimistic(self, on):
         """Optimistic mode of the Cholesky-QR path (``mpse_block_qr_optimistic``): breakdowns are not read back per
