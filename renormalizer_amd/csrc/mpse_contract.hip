@@ -257,234 +257,223 @@ int copy_call(mpse_ctx* ctx, int dtype, const void* src, void* dst, mpse_index m
   return MPSE_OK;
 }
 
+// One run of a plan: what the executors of its steps share
+struct PlanRun {
+  mpse_ctx* ctx;
+  int dtype;
+  size_t es;                   // element size of the working dtype
+  const void* bufs[B_COUNT];   // operands and temporaries by buffer id
+  SolveScope* sc;              // the solve the plan runs in (may be null) ...
+  MatvecReq* mv;               // ... and the requests of the matvec it computes (may be null)
+  const int* skip;             // sc->skip
+  MatvecReq::Dot* dot;         // mv->dot where the caller gave a partner, else null
+  TmpBuf slices;               // K slices that a product (Step::slices_to) left to the elementwise MPO step ...
+  int slices_used = 0;         // ... and how many (0: none; whether it leaves any is the product's decision when it runs)
+  PlanRun(mpse_ctx* c, int dt, const void* const* b, SolveScope* s, MatvecReq* m)
+      : ctx(c), dtype(dt), es(dtype_size(dt)), sc(s), mv(m), skip(s ? s->skip : nullptr),
+        dot(m && m->dot.y ? &m->dot : nullptr), slices(c) {
+    for (int i = 0; i < B_COUNT; ++i) bufs[i] = b[i];
+  }
+  // *p = element `off` of buffer `buf`, whose elements are of dtype `dt`
+  template <class T>
+  int resolve(int buf, int64_t off, int dt, T** p) const {
+    if (!bufs[buf]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
+    *p = (T*)((char*)const_cast<void*>(bufs[buf]) + size_t(off) * dtype_size(dt));
+    return MPSE_OK;
+  }
+};
+
+// MPO step of a small site (Step::elementwise_w): it adds the K slices that the product of its input channels left it
+int run_wsmall(PlanRun& r, const Step& s) {
+  WsmArgs g;
+  MPSE_TRY(r.resolve(s.a, s.a_off, s.dta, &g.W));
+  MPSE_TRY(r.resolve(s.b, s.b_off, s.dtb, &g.T1));
+  MPSE_TRY(r.resolve(s.c, s.c_off, s.dtb, &g.T2));
+  g.Da = (int)s.w_Da, g.d = (int)s.w_d, g.wl = (int)s.w_wl, g.wr = (int)s.w_wr, g.N = (int)s.w_N;
+  g.skip = r.skip;
+  g.slices = r.slices_used > 0 ? r.slices.as<const double>() : nullptr;
+  g.nslices = r.slices_used, g.slice_stride = s.slice_elems, g.b_lo = (int)s.slice_b_lo, g.b_hi = (int)s.slice_b_hi;
+  r.slices_used = 0;
+  const long long total = s.w_Da * s.w_N;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (s.dtb == MPSE_C128)
+    hipLaunchKernelGGL((k_wsmall<true>), grid, dim3(256), 0, r.ctx->stream, g);
+  else
+    hipLaunchKernelGGL((k_wsmall<false>), grid, dim3(256), 0, r.ctx->stream, g);
+  MPSE_HIP(r.ctx, hipGetLastError());
+  return MPSE_OK;
+}
+
+int run_wmix(PlanRun& r, const Step& s) {
+  WmixArgs g;
+  memset(&g, 0, sizeof(g));
+  MPSE_TRY(r.resolve(s.b, 0, MPSE_F64, &g.W));
+  g.ndst = (int)s.mix.size();
+  g.Da = (int)s.wp_Da, g.d = (int)s.wp_d, g.wr = (int)s.wp_wr, g.Dk = (int)s.wp_Dk;
+  g.nchunk = (g.d + WM_CHUNK - 1) / WM_CHUNK;
+  g.skip = r.skip;
+  int nslot = 0;
+  for (int j = 0; j < g.ndst; ++j) {
+    const WMixDst& q = s.mix[j];
+    MPSE_TRY(r.resolve(q.dst, q.dst_off, r.dtype, &g.dst[j].dst));
+    g.dst[j].s_a = q.s_a, g.dst[j].s_d = q.s_d, g.dst[j].nterm = q.nterm;
+    for (int t = 0; t < q.nterm; ++t) {
+      const WMixTerm& tm = q.term[t];
+      WmixTermDev& o = g.dst[j].term[t];
+      MPSE_TRY(r.resolve(tm.src, tm.src_off, r.dtype, &o.src));
+      o.s_a = tm.s_a, o.s_d = tm.s_d, o.b = tm.b, o.f = tm.f, o.ident = tm.ident ? 1 : 0;
+      o.slot = tm.ident ? 0 : nslot++;
+      memcpy(o.e_lo, tm.e_lo, sizeof(o.e_lo));
+      memcpy(o.e_hi, tm.e_hi, sizeof(o.e_hi));
+    }
+  }
+  g.nslot = nslot;
+  const size_t lds = size_t(nslot > 0 ? nslot : 1) * g.d * g.d * sizeof(double);
+  if (lds > 64 * 1024) return mpse_fail(r.ctx, MPSE_ERR_SHAPE, "plan: MPO blocks of the elementwise step exceed the LDS");
+  const long long total = (long long)s.wp_Da * g.nchunk * s.wp_Dk;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (r.dtype == MPSE_C128)
+    hipLaunchKernelGGL((k_wmix<true>), grid, dim3(256), lds, r.ctx->stream, g);
+  else
+    hipLaunchKernelGGL((k_wmix<false>), grid, dim3(256), lds, r.ctx->stream, g);
+  ++r.ctx->gemm_paths[mpse_ctx::GP_WMIX];
+  MPSE_HIP(r.ctx, hipGetLastError());
+  return MPSE_OK;
+}
+
+// Occupancy of an operand that is scanned once for all segments reading parts of it: the environments, by a scan that
+// the solve keeps (one scan serves every channel).  *flags stays null where the plan asks for none.
+int scan_flags(PlanRun& r, const ScanDesc& sd, TmpBuf& tmp, const unsigned char** flags, int* pitch, bool* stable) {
+  if (!sd.on || !r.bufs[sd.buf]) return MPSE_OK;
+  const char* ptr;
+  MPSE_TRY(r.resolve(sd.buf, sd.off, sd.dt, &ptr));
+  bool st = false;
+  MPSE_TRY(occ_mask_get(r.ctx, r.sc, ptr, sd.dt, sd.r, sd.k, tmp, flags, pitch, &st));
+  *stable = *stable && st;
+  return MPSE_OK;
+}
+
+// Structural mask of the centre (B_C) as operand B of a grouped step: K = its left bond, columns = (e, k); null where
+// the solve has none that fits (prepared operands: pushed through the MPO block)
+const unsigned char* centre_mask(const PlanRun& r, const Step& s, int* pitch) {
+  const int64_t K = s.kb.ext, N = s.nb.ext;
+  const int64_t nkw = ((K + 15) / 16 + 7) / 8, ntn = (N + 63) / 64;
+  if (!r.sc || !r.sc->in_krylov(r.bufs[B_C]) || r.sc->cmask.bytes != ntn * nkw * 8) return nullptr;
+  *pitch = (int)(nkw * 8);
+  return static_cast<const unsigned char*>(r.sc->cmask.ptr);
+}
+
+// the beta term of group `i` formed in the epilogue from the blocks of the MPO site (GGroupPlan::nmix)
+int bind_epilogue_mix(PlanRun& r, const GGroupPlan& g, int i, GroupedDesc& gd) {
+  if (gd.nmix > 0 || !r.bufs[g.wbuf]) return mpse_fail(r.ctx, MPSE_ERR_ARG, "plan: bad epilogue mix");
+  gd.nmix = g.nmix, gd.mix_grp = i;
+  gd.mix_w = r.bufs[g.wbuf];
+  gd.mix_d = (int)g.mix_d, gd.mix_wr = (int)g.mix_wr, gd.mix_ld = g.mix_ld;
+  for (int t = 0; t < g.nmix; ++t) {
+    const EpiTerm& m = g.mix[t];
+    MPSE_TRY(r.resolve(m.src, m.src_off, r.dtype, &gd.mix[t].src));
+    gd.mix[t].b = m.b, gd.mix[t].f = m.f, gd.mix[t].delta = m.delta;
+  }
+  return MPSE_OK;
+}
+
+int run_ggemm(PlanRun& r, const Step& s) {
+  GroupedDesc gd;
+  gd.dta = s.dta, gd.dtb = s.dtb;
+  gd.ma = s.ma, gd.ka = s.ka, gd.kb = s.kb, gd.nb = s.nb, gd.mc = s.mc, gd.nc = s.nc;
+  gd.ngrp = (int)s.groups.size();
+  TmpBuf MA(r.ctx), MB(r.ctx);
+  const unsigned char *fa = nullptr, *fb = nullptr;
+  bool stable = true;
+  MPSE_TRY(scan_flags(r, s.scan_a, MA, &fa, &gd.am_pitch, &stable));
+  MPSE_TRY(scan_flags(r, s.scan_b, MB, &fb, &gd.bm_pitch, &stable));
+  int cm_pitch = 0;
+  const unsigned char* cm = centre_mask(r, s, &cm_pitch);
+  for (int i = 0; i < gd.ngrp; ++i) {
+    const GGroupPlan& g = s.groups[i];
+    GroupedGrp& o = gd.grp[i];
+    MPSE_TRY(r.resolve(g.cbuf, g.c_off, r.dtype, &o.C));
+    o.nseg = g.nseg;
+    o.beta = g.beta;
+    if (g.nmix > 0) MPSE_TRY(bind_epilogue_mix(r, g, i, gd));
+    for (int q = 0; q < g.nseg; ++q) {
+      const GSegPlan& sg = g.seg[q];
+      MPSE_TRY(r.resolve(sg.abuf, sg.a_off, s.dta, &o.seg[q].A));
+      MPSE_TRY(r.resolve(sg.bbuf, sg.b_off, s.dtb, &o.seg[q].B));
+      if (fa && sg.am_row0 >= 0) o.seg[q].am = fa + size_t(sg.am_row0) * gd.am_pitch;
+      if (sg.bm_kind == BM_SCAN && fb) {
+        o.seg[q].bm = fb + sg.bm_kt0;
+      } else if (sg.bm_kind == BM_CENTRE && cm) {
+        o.seg[q].bm = cm;
+        gd.bm_pitch = cm_pitch;
+      }
+    }
+  }
+  gd.masks_stable = stable;
+  if (gd.ngrp == 1 && s.groups[0].split2) {
+    if (!r.bufs[B_OUT2]) return mpse_fail(r.ctx, MPSE_ERR_ARG, "plan: missing second result");
+    gd.split2 = true;
+    gd.c2 = const_cast<void*>(r.bufs[B_OUT2]);
+  }
+  // the step that completes the result carries the caller's dot request and result mask
+  MPSE_TRY(gemm_grouped(r.ctx, gd, r.sc, s.completes ? r.dot : nullptr,
+                        s.completes && r.mv && r.mv->out_mask.mask ? &r.mv->out_mask : nullptr));
+  return MPSE_OK;
+}
+
+// plain product (K_GEMM) or copy (K_COPY)
+int run_product(PlanRun& r, const Step& s) {
+  const int dtc = (s.dta == MPSE_C128 || s.dtb == MPSE_C128) ? MPSE_C128 : MPSE_F64;
+  if (dtc != r.dtype)  // every step of a plan must produce the working dtype
+    return mpse_fail(r.ctx, MPSE_ERR_ARG, "plan step dtype mismatch (got %d want %d)", dtc, r.dtype);
+  const char *a, *b;
+  char* c;
+  MPSE_TRY(r.resolve(s.a, s.a_off, s.dta, &a));
+  MPSE_TRY(r.resolve(s.b, s.b_off, s.dtb, &b));
+  MPSE_TRY(r.resolve(s.c, s.c_off, dtc, &c));
+  if (s.kind == K_COPY) return copy_call(r.ctx, dtc, a, c, s.ma, s.ka, s.mc, s.nc, r.skip);
+  ProductReq rq;
+  if (s.completes) rq.dot = r.dot;   // a plain product into the whole of `out` takes the caller's dot request along
+  if (s.cin >= 0) {
+    if (!r.bufs[s.cin]) return mpse_fail(r.ctx, MPSE_ERR_ARG, "plan: missing beta source");
+    rq.cin = (const char*)r.bufs[s.cin] + size_t(s.cin_off) * dtype_size(dtc);
+    rq.cin_m = s.mcin;
+    rq.cin_n = s.ncin;
+  }
+  if (s.slices_to >= 0) {
+    // room for four slices of this product's result (more: the product reduces them itself, as usual); without the
+    // room the offer is withdrawn
+    const size_t blk = size_t(s.mc.ext) * size_t(s.nc.ext) * dtype_size(dtc);
+    if (r.slices.alloc(4 * blk) == MPSE_OK) {
+      rq.slices = r.slices.p;
+      rq.slices_cap = 4 * blk;
+    }
+  }
+  MPSE_TRY(gemm_call(r.ctx, s.dta, s.dtb, s.conja, s.conjb, s.ma, s.ka, s.kb, s.nb, s.mc, s.nc, s.batch, s.sba, s.sbb,
+                     s.sbc, a, b, c, 1.0, s.beta, s.skip_zero, r.sc, &rq));
+  if (rq.slices_used > 0) r.slices_used = rq.slices_used;
+  return MPSE_OK;
+}
+
 }  // namespace
 
 // sc: the solve the plan runs in, mv: the requests of the matvec it computes (both may be null)
 static int run_plan(mpse_ctx* ctx, int dtype, const Plan& p, const void* bufs_in[B_COUNT],
                     SolveScope* sc = nullptr, MatvecReq* mv = nullptr) {
   if (p.error) return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s", p.error);
-  const int* skip = sc ? sc->skip : nullptr;
-  MatvecReq::Dot* dot = mv && mv->dot.y ? &mv->dot : nullptr;
-  const void* bufs[B_COUNT];
-  for (int i = 0; i < B_COUNT; ++i) bufs[i] = bufs_in[i];
   TmpBuf t1(ctx), t2(ctx), t3(ctx);
-  const size_t es = dtype_size(dtype);
-  if (p.tmp_elems[0]) {
-    MPSE_TRY(t1.alloc(size_t(p.tmp_elems[0]) * es));
-    bufs[B_T1] = t1.p;
-  }
-  if (p.tmp_elems[1]) {
-    MPSE_TRY(t2.alloc(size_t(p.tmp_elems[1]) * es));
-    bufs[B_T2] = t2.p;
-  }
-  if (p.tmp_elems[2]) {
-    MPSE_TRY(t3.alloc(size_t(p.tmp_elems[2]) * es));
-    bufs[B_T3] = t3.p;
-  }
-  // The elementwise MPO step of a small site adds the K slices of the ONE product that forms its input channels itself
-  // (no reduction launch between them): which step that is, and where its slices go
-  auto small_wstep = [](const Step& s) {
-    return s.kind == K_GEMM && s.is_wstep && s.dta == MPSE_F64 && s.a_off == 0 && s.b_off == 0 && s.c_off == 0 &&
-           s.beta == 0.0 && s.w_wl * s.w_d <= 16 && s.w_d * s.w_wr <= 16;
-  };
-  const Step* slice_producer = nullptr;
-  const Step* slice_consumer = nullptr;
-  {
-    int n_t1 = 0;
-    const Step* prod = nullptr;
-    const Step* cons = nullptr;
-    for (const Step& s : p.steps) {
-      if (small_wstep(s) && s.b == B_T1 && !cons) cons = &s;
-      if (!cons && s.kind == K_GEMM && !s.is_wstep && s.c == B_T1) ++n_t1, prod = &s;
+  TmpBuf* tmp[3] = {&t1, &t2, &t3};
+  PlanRun r(ctx, dtype, bufs_in, sc, mv);
+  for (int i = 0; i < 3; ++i)
+    if (p.tmp_elems[i]) {
+      MPSE_TRY(tmp[i]->alloc(size_t(p.tmp_elems[i]) * r.es));
+      r.bufs[B_T1 + i] = tmp[i]->p;
     }
-    // (the product's rows are (channel | bra bond) over whole channels of the consumer's input, compactly stored)
-    if (cons && n_t1 == 1 && prod->batch == 1 && prod->beta == 0.0 && prod->cin < 0 && cons->w_Da > 0 &&
-        prod->nc.ext == cons->w_d * cons->w_N && prod->mc.ext % cons->w_Da == 0 &&
-        prod->c_off % (cons->w_Da * cons->w_d * cons->w_N) == 0)
-      slice_producer = prod, slice_consumer = cons;
-  }
-  TmpBuf SLC(ctx);
-  int slices_used = 0;
-  long long slice_elems = 0, slice_b_lo = 0, slice_b_hi = 0;
-  for (const Step& s : p.steps) {
-    if (small_wstep(s)) {
-      if (!bufs[s.a] || !bufs[s.b] || !bufs[s.c]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-      WsmArgs g;
-      g.T1 = (const double*)bufs[s.b];
-      g.T2 = (double*)const_cast<void*>(bufs[s.c]);
-      g.W = (const double*)bufs[s.a];
-      g.Da = (int)s.w_Da, g.d = (int)s.w_d, g.wl = (int)s.w_wl, g.wr = (int)s.w_wr, g.N = (int)s.w_N;
-      g.skip = skip;
-      g.slices = slices_used > 0 ? SLC.as<const double>() : nullptr;
-      g.nslices = slices_used, g.slice_stride = slice_elems, g.b_lo = (int)slice_b_lo, g.b_hi = (int)slice_b_hi;
-      slices_used = 0;
-      const long long total = s.w_Da * s.w_N;
-      const dim3 grid((unsigned)((total + 255) / 256));
-      if (s.dtb == MPSE_C128)
-        hipLaunchKernelGGL((k_wsmall<true>), grid, dim3(256), 0, ctx->stream, g);
-      else
-        hipLaunchKernelGGL((k_wsmall<false>), grid, dim3(256), 0, ctx->stream, g);
-      MPSE_HIP(ctx, hipGetLastError());
-      continue;
-    }
-    if (s.kind == K_WMIX) {
-      if (!bufs[s.b]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-      WmixArgs g;
-      memset(&g, 0, sizeof(g));
-      g.W = (const double*)bufs[s.b];
-      g.ndst = (int)s.mix.size();
-      g.Da = (int)s.wp_Da, g.d = (int)s.wp_d, g.wr = (int)s.wp_wr, g.Dk = (int)s.wp_Dk;
-      g.nchunk = (g.d + WM_CHUNK - 1) / WM_CHUNK;
-      g.skip = skip;
-      int nslot = 0;
-      for (int j = 0; j < g.ndst; ++j) {
-        const WMixDst& q = s.mix[j];
-        if (!bufs[q.dst]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-        g.dst[j].dst = (double*)((char*)const_cast<void*>(bufs[q.dst]) + size_t(q.dst_off) * es);
-        g.dst[j].s_a = q.s_a, g.dst[j].s_d = q.s_d, g.dst[j].nterm = q.nterm;
-        for (int t = 0; t < q.nterm; ++t) {
-          const WMixTerm& tm = q.term[t];
-          if (!bufs[tm.src]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-          WmixTermDev& o = g.dst[j].term[t];
-          o.src = (const double*)((const char*)bufs[tm.src] + size_t(tm.src_off) * es);
-          o.s_a = tm.s_a, o.s_d = tm.s_d, o.b = tm.b, o.f = tm.f, o.ident = tm.ident ? 1 : 0;
-          o.slot = tm.ident ? 0 : nslot++;
-          memcpy(o.e_lo, tm.e_lo, sizeof(o.e_lo));
-          memcpy(o.e_hi, tm.e_hi, sizeof(o.e_hi));
-        }
-      }
-      g.nslot = nslot;
-      const size_t lds = size_t(nslot > 0 ? nslot : 1) * g.d * g.d * sizeof(double);
-      if (lds > 64 * 1024) return mpse_fail(ctx, MPSE_ERR_SHAPE, "plan: MPO blocks of the elementwise step exceed the LDS");
-      const long long total = (long long)s.wp_Da * g.nchunk * s.wp_Dk;
-      const dim3 grid((unsigned)((total + 255) / 256));
-      if (dtype == MPSE_C128)
-        hipLaunchKernelGGL((k_wmix<true>), grid, dim3(256), lds, ctx->stream, g);
-      else
-        hipLaunchKernelGGL((k_wmix<false>), grid, dim3(256), lds, ctx->stream, g);
-      ++ctx->gemm_paths[mpse_ctx::GP_WMIX];
-      MPSE_HIP(ctx, hipGetLastError());
-      continue;
-    }
-    if (s.kind == K_GGEMM) {
-      GroupedDesc gd;
-      gd.dta = s.dta, gd.dtb = s.dtb;
-      gd.ma = s.ma, gd.ka = s.ka, gd.kb = s.kb, gd.nb = s.nb, gd.mc = s.mc, gd.nc = s.nc;
-      gd.ngrp = (int)s.groups.size();
-      // occupancy of the operands: the environments by a scan that the solve keeps (one scan serves every channel),
-      // the centre tensor by the structural mask of the solve - pushed through the MPO block for prepared operands
-      TmpBuf MA(ctx), MB(ctx);
-      const unsigned char *fa = nullptr, *fb = nullptr;
-      bool stable = true;
-      if (s.scan_a.on && bufs[s.scan_a.buf]) {
-        bool st = false;
-        MPSE_TRY(occ_mask_get(ctx, sc, (const char*)bufs[s.scan_a.buf] + size_t(s.scan_a.off) * dtype_size(s.scan_a.dt),
-                              s.scan_a.dt, s.scan_a.r, s.scan_a.k, MA, &fa, &gd.am_pitch, &st));
-        stable = stable && st;
-      }
-      if (s.scan_b.on && bufs[s.scan_b.buf]) {
-        bool st = false;
-        MPSE_TRY(occ_mask_get(ctx, sc, (const char*)bufs[s.scan_b.buf] + size_t(s.scan_b.off) * dtype_size(s.scan_b.dt),
-                              s.scan_b.dt, s.scan_b.r, s.scan_b.k, MB, &fb, &gd.bm_pitch, &st));
-        stable = stable && st;
-      }
-      // structural mask of the centre (B_C) as operand B: K = its left bond, columns = (e, k)
-      const unsigned char* cm = nullptr;
-      int cm_pitch = 0;
-      {
-        const char* pc = (const char*)bufs[B_C];
-        const int64_t K = s.kb.ext, N = s.nb.ext;
-        const int64_t nkw = ((K + 15) / 16 + 7) / 8, ntn = (N + 63) / 64;
-        if (sc && sc->in_krylov(pc) && sc->cmask.bytes == ntn * nkw * 8) {
-          cm = static_cast<const unsigned char*>(sc->cmask.ptr);
-          cm_pitch = (int)(nkw * 8);
-        }
-      }
-      for (int i = 0; i < gd.ngrp; ++i) {
-        const GGroupPlan& g = s.groups[i];
-        GroupedGrp& o = gd.grp[i];
-        if (!bufs[g.cbuf]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-        o.C = (char*)const_cast<void*>(bufs[g.cbuf]) + size_t(g.c_off) * es;
-        o.nseg = g.nseg;
-        o.beta = g.beta;
-        if (g.nmix > 0) {       // the beta term formed in the epilogue from the blocks of the MPO site
-          if (gd.nmix > 0 || !bufs[g.wbuf]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: bad epilogue mix");
-          gd.nmix = g.nmix, gd.mix_grp = i;
-          gd.mix_w = bufs[g.wbuf];
-          gd.mix_d = (int)g.mix_d, gd.mix_wr = (int)g.mix_wr, gd.mix_ld = g.mix_ld;
-          for (int t = 0; t < g.nmix; ++t) {
-            const EpiTerm& m = g.mix[t];
-            if (!bufs[m.src]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-            gd.mix[t].src = (const char*)bufs[m.src] + size_t(m.src_off) * es;
-            gd.mix[t].b = m.b, gd.mix[t].f = m.f, gd.mix[t].delta = m.delta;
-          }
-        }
-        for (int q = 0; q < g.nseg; ++q) {
-          const GSegPlan& sg = g.seg[q];
-          if (!bufs[sg.abuf] || !bufs[sg.bbuf]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-          o.seg[q].A = (const char*)bufs[sg.abuf] + size_t(sg.a_off) * dtype_size(s.dta);
-          o.seg[q].B = (const char*)bufs[sg.bbuf] + size_t(sg.b_off) * dtype_size(s.dtb);
-          if (fa && sg.am_row0 >= 0) o.seg[q].am = fa + size_t(sg.am_row0) * gd.am_pitch;
-          if (sg.bm_kind == BM_SCAN && fb) {
-            o.seg[q].bm = fb + sg.bm_kt0;
-          } else if (sg.bm_kind == BM_CENTRE && cm) {
-            o.seg[q].bm = cm;
-            gd.bm_pitch = cm_pitch;
-          }
-        }
-      }
-      gd.masks_stable = stable;
-      if (gd.ngrp == 1 && s.groups[0].split2) {
-        if (!bufs[B_OUT2]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing second result");
-        gd.split2 = true;
-        gd.c2 = const_cast<void*>(bufs[B_OUT2]);
-      }
-      // the last step completes the result: it carries the caller's dot request and result mask
-      const bool completes =
-          &s == &p.steps.back() && gd.ngrp == 1 && s.groups[0].cbuf == B_OUT && s.groups[0].c_off == 0;
-      MPSE_TRY(gemm_grouped(ctx, gd, sc, completes ? dot : nullptr,
-                            completes && mv && mv->out_mask.mask ? &mv->out_mask : nullptr));
-      continue;
-    }
-    const char* a = (const char*)bufs[s.a] + size_t(s.a_off) * dtype_size(s.dta);
-    const char* b = (const char*)bufs[s.b] + size_t(s.b_off) * dtype_size(s.dtb);
-    const int dtc = (s.dta == MPSE_C128 || s.dtb == MPSE_C128) ? MPSE_C128 : MPSE_F64;
-    if (dtc != dtype)  // every step of a plan must produce the working dtype
-      return mpse_fail(ctx, MPSE_ERR_ARG, "plan step dtype mismatch (got %d want %d)", dtc, dtype);
-    char* c = (char*)const_cast<void*>(bufs[s.c]) + size_t(s.c_off) * dtype_size(dtc);
-    if (!bufs[s.a] || !bufs[s.b] || !bufs[s.c]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing buffer");
-    if (s.kind == K_COPY) {
-      MPSE_TRY(copy_call(ctx, dtc, a, c, s.ma, s.ka, s.mc, s.nc, skip));
-      continue;
-    }
-    ProductReq rq;
-    // the last step completes the result: it takes the caller's dot request along when it is a plain product into
-    // the whole of `out`
-    if (&s == &p.steps.back() && s.c == B_OUT && s.c_off == 0 && s.batch == 1) rq.dot = dot;
-    if (s.cin >= 0) {
-      if (!bufs[s.cin]) return mpse_fail(ctx, MPSE_ERR_ARG, "plan: missing beta source");
-      rq.cin = (const char*)bufs[s.cin] + size_t(s.cin_off) * dtype_size(dtc);
-      rq.cin_m = s.mcin;
-      rq.cin_n = s.ncin;
-    }
-    if (&s == slice_producer) {
-      // room for four slices of this product's result (more: the product reduces them itself, as usual)
-      const size_t blk = size_t(s.mc.ext) * size_t(s.nc.ext) * dtype_size(dtc);
-      if (SLC.alloc(4 * blk) == MPSE_OK) {
-        rq.slices = SLC.p;
-        rq.slices_cap = 4 * blk;
-      }
-    }
-    MPSE_TRY(gemm_call(ctx, s.dta, s.dtb, s.conja, s.conjb, s.ma, s.ka, s.kb, s.nb, s.mc, s.nc, s.batch, s.sba, s.sbb,
-                       s.sbc, a, b, c, 1.0, s.beta, s.skip_zero, sc, &rq));
-    if (rq.slices_used > 0) {
-      // rows of the product = (channel - b_lo | bra bond): which channels of T1 it forms
-      slices_used = rq.slices_used;
-      slice_elems = (long long)s.mc.ext * s.nc.ext;
-      slice_b_lo = s.c_off / (slice_consumer->w_Da * slice_consumer->w_d * slice_consumer->w_N);
-      slice_b_hi = slice_b_lo + s.mc.ext / slice_consumer->w_Da;
-    }
-  }
+  for (const Step& s : p.steps)
+    MPSE_TRY(s.elementwise_w ? run_wsmall(r, s)
+             : s.kind == K_WMIX ? run_wmix(r, s)
+             : s.kind == K_GGEMM ? run_ggemm(r, s)
+                                 : run_product(r, s));
   return MPSE_OK;
 }
 
@@ -516,12 +505,7 @@ int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void
   Plan p = plan_heff(dtype, *h, static_cast<const WSiteInfo*>(wi_keep.get()), two_ok, fold_epi());
   if (pr) pr->used = 0;
   const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = h->L;
-  bufs[B_R] = h->R;
-  bufs[B_W0] = h->W0;
-  bufs[B_W1] = h->W1;
-  bufs[B_C] = C;
-  bufs[B_OUT] = out;
+  bind_heff(bufs, *h, C, out);
   // halved tiles: part 0 is `out` itself (it holds the beta term), part 1 the second slot of the caller's buffer;
   // split products: all parts in the caller's buffer (mpse_gemm.hip sets `used`)
   if (p.two_results) bufs[B_OUT2] = static_cast<char*>(pr->ptr) + size_t(pr->n) * dtype_size(dtype);
@@ -580,11 +564,7 @@ extern "C" int mpse_env_update(mpse_ctx* ctx, int dtype, int domain, const mpse_
   }
   Plan p = plan_env(dtype, domain, *dims, env_dtype, w_dtype, bra_conj, static_cast<const WSiteInfo*>(wi_keep.get()));
   const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = env;
-  bufs[B_W0] = W;
-  bufs[B_C] = ket;
-  bufs[B_BRA] = bra;
-  bufs[B_OUT] = out;
+  bind_env(bufs, env, ket, bra, out, 1, &W);
   return run_plan(ctx, dtype, p, bufs);
 }
 
@@ -603,15 +583,10 @@ extern "C" int mpse_env_update_multi(mpse_ctx* ctx, int dtype, int domain, const
       return mpse_fail(ctx, MPSE_ERR_SHAPE, "env_update_multi: bra==NULL needs equal bonds");
   }
   Plan p = plan_env_multi(dtype, domain, *dims, n_mpo, wl, wr, env_dtype, w_dtype, bra_conj);
-  const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = env;
-  for (int i = 0; i < n_mpo; ++i) {
+  for (int i = 0; i < n_mpo; ++i)
     if (!W[i]) return MPSE_ERR_ARG;
-    bufs[w_buf(i)] = W[i];
-  }
-  bufs[B_C] = ket;
-  bufs[B_BRA] = bra;
-  bufs[B_OUT] = out;
+  const void* bufs[B_COUNT] = {nullptr};
+  bind_env(bufs, env, ket, bra, out, n_mpo, W);
   return run_plan(ctx, dtype, p, bufs);
 }
 
@@ -622,12 +597,7 @@ int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, voi
     return mpse_fail(ctx, MPSE_ERR_ARG, "heff_apply2: real centre with complex operator parts");
   Plan p = plan_heff2(dtype, *h);
   const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = h->L;
-  bufs[B_R] = h->R;
-  bufs[B_W0] = h->W0;
-  bufs[B_W1] = h->W1;
-  bufs[B_C] = C;
-  bufs[B_OUT] = out;
+  bind_heff(bufs, *h, C, out);
   return run_plan(ctx, dtype, p, bufs, sc);
 }
 
@@ -643,12 +613,7 @@ int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C
     return mpse_fail(ctx, MPSE_ERR_ARG, "heff_apply_ft: real centre with complex operator parts");
   Plan p = plan_heff_ft(dtype, *h);
   const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = h->L;
-  bufs[B_R] = h->R;
-  bufs[B_W0] = h->W1;
-  bufs[B_W1] = h->W2;
-  bufs[B_C] = C;
-  bufs[B_OUT] = out;
+  bind_heff_ft(bufs, *h, C, out);
   return run_plan(ctx, dtype, p, bufs, sc);
 }
 
@@ -663,13 +628,9 @@ extern "C" int mpse_env_update_ft(mpse_ctx* ctx, int dtype, int domain, const mp
   if (dtype != MPSE_C128 && (env_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
     return mpse_fail(ctx, MPSE_ERR_ARG, "env_update_ft: real site with complex env/mpo");
   Plan p = plan_env_ft(dtype, domain, *h, env_dtype);
+  const void* const W[2] = {h->W1, h->W2};
   const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = env;
-  bufs[B_W0] = h->W1;
-  bufs[B_W1] = h->W2;
-  bufs[B_C] = X;
-  bufs[B_BRA] = X;
-  bufs[B_OUT] = out;
+  bind_env(bufs, env, X, X, out, 2, W);
   return run_plan(ctx, dtype, p, bufs);
 }
 

@@ -154,6 +154,13 @@ struct Step {
   int cin = -1;                // K_GEMM with beta != 0: buffer the beta term is read from (-1: C itself) ...
   int64_t cin_off = 0;         // ... at this element offset, through these index maps
   mpse_index mcin{}, ncin{};
+  // Marks (set by `marked`, below, for every plan a planner returns): what the step is within its plan, so that the
+  // executors read it instead of inferring it from the step list
+  bool elementwise_w = false;  // a small-site MPO step: runs as the elementwise kernel (k_wsmall), not as MFMA tiles
+  int slices_to = -1;          // a product that may leave its K slices to that elementwise step (index; -1: none) ...
+  int64_t slice_b_lo = 0, slice_b_hi = 0;   // ... on that step: the channels of its input the slices form, [b_lo, b_hi),
+  int64_t slice_elems = 0;                  // and the elements of one slice (mc.ext * nc.ext of the product)
+  bool completes = false;      // the step finishes the caller's result: it may carry MatvecReq::dot / out_mask
 };
 
 struct Plan {
@@ -280,6 +287,52 @@ inline void push_w(Plan& p, int wbuf, int w_dtype, int tin, int tout, int t_dtyp
   s.w_Da = na, s.w_wl = wl, s.w_d = d, s.w_wr = wr, s.w_N = N;
 }
 
+// The marks of a plan (Step::elementwise_w .. completes); every planner returns its plan through this.
+//   * elementwise: the MPO step of a small real site (wl d <= 16 inputs, d wr <= 16 outputs) over whole tensors;
+//   * hand-off: the first elementwise step that reads T1 adds the K slices of the ONE product that forms its input
+//     channels itself (no reduction launch between them), when that product's rows are (channel | bra bond) over whole
+//     channels of T1, compactly stored.  Whether the product really leaves slices is decided when it runs;
+//   * completes: the last step, when it is a plain product, or a grouped one of a single group, into the whole of `out`.
+inline Plan marked(Plan p) {
+  Step *prod = nullptr, *cons = nullptr;
+  int n_t1 = 0;
+  for (Step& s : p.steps) {
+    s.elementwise_w = s.kind == K_GEMM && s.is_wstep && s.dta == MPSE_F64 && s.a_off == 0 && s.b_off == 0 &&
+                      s.c_off == 0 && s.beta == 0.0 && s.w_wl * s.w_d <= 16 && s.w_d * s.w_wr <= 16;
+    s.slices_to = -1, s.slice_b_lo = s.slice_b_hi = s.slice_elems = 0, s.completes = false;
+    if (s.elementwise_w && s.b == B_T1 && !cons) cons = &s;
+    if (!cons && s.kind == K_GEMM && !s.is_wstep && s.c == B_T1) ++n_t1, prod = &s;
+  }
+  if (cons && n_t1 == 1 && prod->batch == 1 && prod->beta == 0.0 && prod->cin < 0 && cons->w_Da > 0 &&
+      prod->nc.ext == cons->w_d * cons->w_N && prod->mc.ext % cons->w_Da == 0 &&
+      prod->c_off % (cons->w_Da * cons->w_d * cons->w_N) == 0) {
+    prod->slices_to = int(cons - p.steps.data());
+    cons->slice_b_lo = prod->c_off / (cons->w_Da * cons->w_d * cons->w_N);
+    cons->slice_b_hi = cons->slice_b_lo + prod->mc.ext / cons->w_Da;
+    cons->slice_elems = prod->mc.ext * prod->nc.ext;
+  }
+  if (!p.steps.empty()) {
+    Step& s = p.steps.back();
+    s.completes = s.kind == K_GEMM ? s.c == B_OUT && s.c_off == 0 && s.batch == 1
+                                   : s.kind == K_GGEMM && s.groups.size() == 1 && s.groups[0].cbuf == B_OUT &&
+                                         s.groups[0].c_off == 0;
+  }
+  return p;
+}
+
+// The operands of a plan by buffer id, one helper per operator family (bufs: B_COUNT entries, zeroed by the caller)
+inline void bind_heff(const void** bufs, const mpse_heff& h, const void* C, void* out) {
+  bufs[B_L] = h.L, bufs[B_R] = h.R, bufs[B_W0] = h.W0, bufs[B_W1] = h.W1, bufs[B_C] = C, bufs[B_OUT] = out;
+}
+inline void bind_heff_ft(const void** bufs, const mpse_heff_ft& h, const void* C, void* out) {
+  bufs[B_L] = h.L, bufs[B_R] = h.R, bufs[B_W0] = h.W1, bufs[B_W1] = h.W2, bufs[B_C] = C, bufs[B_OUT] = out;
+}
+inline void bind_env(const void** bufs, const void* env, const void* ket, const void* bra, void* out, int n_mpo,
+                     const void* const* W) {
+  bufs[B_L] = env, bufs[B_C] = ket, bufs[B_BRA] = bra, bufs[B_OUT] = out;
+  for (int i = 0; i < n_mpo; ++i) bufs[w_buf(i)] = W[i];
+}
+
 // Effective Hamiltonian matvec, mps/hop_expr.py:57-115.  The bra-side bonds (rows of L / R, bonds of `out`) may
 // differ from the ket-side bonds (columns of L / R, bonds of C): that is the projection of H C onto another
 // state's bond spaces used by the variational compression (mps/mp.py:513-650); the Krylov / Davidson drivers
@@ -306,7 +359,7 @@ inline Plan plan_heff(int dtype, const mpse_heff& h, const WSiteInfo* wi = nullp
     p.tmp_elems[0] = Dlb * wl * Dr;
     push_env_times(p, B_L, h.l_dtype, B_C, dtype, B_T1, Dlb, wl, Dl, Dr, h.l_unit, false);
     push_times_env(p, B_T1, dtype, B_R, h.r_dtype, B_OUT, Dlb, 1, wr, Dr, Drb, h.r_unit);
-    return p;
+    return marked(std::move(p));
   }
   if (h.nsite == 1) {
     if (wi) {
@@ -323,7 +376,7 @@ inline Plan plan_heff(int dtype, const mpse_heff& h, const WSiteInfo* wi = nullp
     push_w(p, B_W0, h.w_dtype, B_T1, B_T2, dtype, Dlb, wl, d, wr, Nb);
     // out[(a,d,g),l] = sum_{f,k} T2[a,d,f,g,k] R[l,f,k]
     push_times_env(p, B_T2, dtype, B_R, h.r_dtype, B_OUT, Dlb * d, anc, wr, Dr, Drb, h.r_unit);
-    return p;
+    return marked(std::move(p));
   }
   if (h.nsite == 2) {
     // abc,bdef,fghj,ljk,cehk->adgl (hop_expr.py:99-103); ancilla cemhnk->admgnl (111-115): the two ancilla legs m, n
@@ -348,7 +401,7 @@ inline Plan plan_heff(int dtype, const mpse_heff& h, const WSiteInfo* wi = nullp
            /*C: (g,j),(n,k)*/ i1(d1 * wr, n2), i1(n2, 1), Dlb * d0, 0, wm * a0 * d1 * n2, a0 * d1 * wr * n2);
     // out[(a,d,m,g,n),l] = sum_{j,k} T3[a,d,m,g,j,n,k] R[l,j,k]
     push_times_env(p, B_T3, dtype, B_R, h.r_dtype, B_OUT, Dlb * d0 * a0 * d1, a1, wr, Dr, Drb, h.r_unit);
-    return p;
+    return marked(std::move(p));
   }
   p.error = "heff: nsite must be 0, 1 or 2";
   return p;
@@ -619,7 +672,7 @@ inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, 
     p.steps.push_back(st);
     out_init = true;
   }
-  return p;
+  return marked(std::move(p));
 }
 
 // Environment update, mps/lib.py:169-250.  Buffers: B_L = incoming environment (either
@@ -707,7 +760,7 @@ inline Plan plan_env(int dtype, int domain, const mpse_dims& s, int env_dtype, i
     push(p, B_BRA, 0, dtype, bra_conj, B_T2, 0, dtype, 0, B_OUT, 0, i1(Drb, 1), i1(Dlb * d * anc, Drb),
          i2(Dlb * d, anc, wr * anc * Drk, Drk), i2(wr, Drk, anc * Drk, 1), i1(Drb, wr * Drk), i1(wr * Drk, 1));
     p.steps.back().skip_zero = skip_pays(Drb, Dlb * d * anc, wr * Drk, 1);   // B = the big intermediate: bra side only
-    return p;
+    return marked(std::move(p));
   }
   if (domain == MPSE_DOMAIN_R) {
     // env R[a,b,c] ; ket A[h,e,g,c] ; W[q,d,e,b] ; bra Ab[p,d,g,a] -> out[p,q,h]
@@ -741,7 +794,7 @@ inline Plan plan_env(int dtype, int domain, const mpse_dims& s, int env_dtype, i
     push(p, B_BRA, 0, dtype, bra_conj, B_T2, 0, dtype, 0, B_OUT, 0, i1(Dlb, d * anc * Drb), i1(d * anc * Drb, 1),
          i1(d * anc * Drb, 1), i2(wl, Dlk, d * anc * Drb, wl * d * anc * Drb), i1(Dlb, wl * Dlk), i1(wl * Dlk, 1));
     p.steps.back().skip_zero = skip_pays(Dlb, d * anc * Drb, wl * Dlk, 1);
-    return p;
+    return marked(std::move(p));
   }
   p.error = "env: bad domain";
   return p;
@@ -920,7 +973,7 @@ inline Plan plan_env_multi(int dtype, int domain, const mpse_dims& s, int n, con
     // out[p, (F, h)] = sum_{a, y, g} bra*[(a, y, g), p] T_0[(a, y), F, g, h]
     push(p, B_BRA, 0, dtype, bra_conj, tb, 0, dtype, 0, B_OUT, 0, i1(Drb, 1), i1(Dlb * d * anc, Drb),
          i2(Dlb * d, anc, WR * anc * Drk, Drk), i2(WR, Drk, anc * Drk, 1), i1(Drb, WR * Drk), i1(WR * Drk, 1));
-    return p;
+    return marked(std::move(p));
   }
   // R: T_n[h, x, g, (b_1..b_n), a] = sum_c ket[(h, x, g), c] E[a, (b), c]
   push(p, B_C, 0, dtype, 0, B_L, 0, env_dtype, 0, tb, 0, i1(Dlk * d * anc, Drk), i1(Drk, 1), i1(Drk, 1),
@@ -940,7 +993,7 @@ inline Plan plan_env_multi(int dtype, int domain, const mpse_dims& s, int n, con
   // out[p, (Q, h)] = sum_{y, g, a} bra*[p, (y, g, a)] T_0[h, Q, (y, g, a)]
   push(p, B_BRA, 0, dtype, bra_conj, tb, 0, dtype, 0, B_OUT, 0, i1(Dlb, d * anc * Drb), i1(d * anc * Drb, 1),
        i1(d * anc * Drb, 1), i2(WL, Dlk, d * anc * Drb, WL * d * anc * Drb), i1(Dlb, WL * Dlk), i1(WL * Dlk, 1));
-  return p;
+  return marked(std::move(p));
 }
 
 // Two-layer effective Hamiltonian of the (H - omega)^2 functional, mps/hop_expr.py:24-52 (same MPO sites in both
@@ -981,7 +1034,7 @@ inline Plan plan_heff2(int dtype, const mpse_heff& h) {
     contract(p, W2, T2, T3, "hi", "cf", "zjg", "d");
     View O(B_OUT, dtype, {{'d', Dl}, {'h', d0}, {'z', nz}, {'k', Dr}});
     contract(p, T3, R, O, "dhz", "jgi", "k");
-    return p;
+    return marked(std::move(p));
   }
   if (s.danc > 1) {
     p.error = "heff (two layers, 2-site): the batch index is danc1, danc must be 1";
@@ -1013,7 +1066,7 @@ inline Plan plan_heff2(int dtype, const mpse_heff& h) {
   contract(p, Wd, T4, T5, "mn", "ik", "zol", "dh");
   View O(B_OUT, dtype, {{'d', Dl}, {'h', d0}, {'m', d1}, {'z', nz}, {'p', Dr}});
   contract(p, T5, R, O, "dhmz", "oln", "p");
-  return p;
+  return marked(std::move(p));
 }
 
 // Two MPO layers on a centre with two physical legs (a site of an operator in MPS form: C (Dl, d_up, d_down, Dr)),
@@ -1098,7 +1151,7 @@ inline Plan plan_heff_ft(int dtype, const mpse_heff_ft& h) {
   View R(B_R, h.r_dtype, {{'j', h.Dr}, {'g', h.wr1}, {'i', h.wr2}, {'k', h.Dr}});
   View O(B_OUT, dtype, {{'d', h.Dl}, {up, h.d_up}, {down, h.d_down}, {'k', h.Dr}});
   contract(p, T3, R, O, std::string("d") + up + down, kr, "k");
-  return p;
+  return marked(std::move(p));
 }
 
 // Environment of a term moved over one site X (Dl, d_up, d_down, Dr): bra = conj(X), ket = X, every layer contracts its
@@ -1120,7 +1173,7 @@ inline Plan plan_env_ft(int dtype, int domain, const mpse_heff_ft& h, int env_dt
     View BRA(B_BRA, dtype, {{'d', Dl}, {up, du}, {down, dv}, {'k', Dr}});
     View O(B_OUT, dtype, {{'j', Dr}, {'g', h.wr1}, {'i', h.wr2}, {'k', Dr}});
     contract(p, BRA, T3, O, "k", std::string("d") + up + down, kr, "", "", conj);
-    return p;
+    return marked(std::move(p));
   }
   if (domain != MPSE_DOMAIN_R) {
     p.error = "env: bad domain";
@@ -1141,7 +1194,7 @@ inline Plan plan_env_ft(int dtype, int domain, const mpse_heff_ft& h, int env_dt
     contract(p, W2, T2, T3, "cy", "xi", "vk", "ab");
     View BRA(B_BRA, dtype, {{'d', Dl}, {'y', du}, {'v', dv}, {'k', Dr}});
     contract(p, BRA, T3, O, "d", "yvk", "abc", "", "", conj);
-    return p;
+    return marked(std::move(p));
   }
   if (h.leg1 == MPSE_LEG_DOWN && h.leg2 == MPSE_LEG_DOWN) {
     View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'v', 's', dv, 'g', h.wr1);
@@ -1152,7 +1205,7 @@ inline Plan plan_env_ft(int dtype, int domain, const mpse_heff_ft& h, int env_dt
     contract(p, W2, T2, T3, "ct", "si", "k", "aub");
     View BRA(B_BRA, dtype, {{'d', Dl}, {'u', du}, {'t', dv}, {'k', Dr}});
     contract(p, BRA, T3, O, "d", "utk", "abc", "", "", conj);
-    return p;
+    return marked(std::move(p));
   }
   View W1 = ft_w_view(B_W0, h.w_dtype, t1, 'b', h.wl1, 'u', 'x', du, 'g', h.wr1);
   View W2 = ft_w_view(B_W1, h.w_dtype, t2, 'c', h.wl2, 'v', 's', dv, 'i', h.wr2);
@@ -1162,7 +1215,7 @@ inline Plan plan_env_ft(int dtype, int domain, const mpse_heff_ft& h, int env_dt
   contract(p, W2, T2, T3, "cs", "vi", "k", "abx");
   View BRA(B_BRA, dtype, {{'d', Dl}, {'x', du}, {'s', dv}, {'k', Dr}});
   contract(p, BRA, T3, O, "d", "xsk", "abc", "", "", conj);
-  return p;
+  return marked(std::move(p));
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -26,12 +26,7 @@ extern "C" int emu_heff_apply_ft(int dtype, const mpse_heff_ft* h, const void* C
   Plan p = plan_heff_ft(dtype, *h);
   if (!p.error && !temporaries_fit(p)) return -1;
   const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = h->L;
-  bufs[B_R] = h->R;
-  bufs[B_W0] = h->W1;
-  bufs[B_W1] = h->W2;
-  bufs[B_C] = C;
-  bufs[B_OUT] = out;
+  bind_heff_ft(bufs, *h, C, out);
   return run(dtype, p, bufs);
 }
 
@@ -39,13 +34,9 @@ extern "C" int emu_env_update_ft(int dtype, int domain, const mpse_heff_ft* h, c
                                  const void* X, void* out) {
   Plan p = plan_env_ft(dtype, domain, *h, env_dtype);
   if (!p.error && !temporaries_fit(p)) return -1;
+  const void* const W[2] = {h->W1, h->W2};
   const void* bufs[B_COUNT] = {nullptr};
-  bufs[B_L] = env;
-  bufs[B_W0] = h->W1;
-  bufs[B_W1] = h->W2;
-  bufs[B_C] = X;
-  bufs[B_BRA] = X;
-  bufs[B_OUT] = out;
+  bind_env(bufs, env, X, X, out, 2, W);
   return run(dtype, p, bufs);
 }
 

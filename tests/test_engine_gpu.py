@@ -9,6 +9,8 @@ import pytest
 from oracle import mps_oracle as orc
 from renormalizer_amd import engine as E
 from renormalizer_amd.mps.hop_expr import hop_expr
+from contract_refs import ref_env, ref_heff        # (tests/contract_refs.py)
+from gemm_policy import plain_plan                 # (tests/gemm_policy.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -344,6 +346,32 @@ def test_contractions_midsize_vs_oracle(eng, cplx):
     x, y = _rand(rng, (Dl, d, Dr), cplx), _rand(rng, (Dl, d, Dr), cplx)
     hx, hy = dev_heff_apply(eng, lh, rh, [wh], x), dev_heff_apply(eng, lh, rh, [wh], y)
     assert abs(np.vdot(x, hy) - np.vdot(hx, y)) < 1e-9 * abs(np.vdot(x, hy))
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+@pytest.mark.parametrize("case", ["one_site", "two_site", "env_L"])
+def test_small_site_mpo_step_adds_k_slices(eng, case, cplx):
+    """The hand-off the plans mark (mpse_plans.h Step::slices_to): the product L . C has too few tiles for the device,
+    splits along K and leaves its four slices to the elementwise MPO step of the d = 2 site, which adds them while it
+    reads.  The launch policy is asked first that the shape takes that path on this device; then the result against
+    the tensordot references."""
+    Dl, d, wl, wr = 128, 2, 4, 4
+    Dr, d1, wm = (128, 2, 4) if case == "two_site" else (256, 1, 1)
+    M, N, K = wl * Dl, d * d1 * Dr, Dl                         # T1[(b, a), (e, .., k)] = sum_c L[a, b, c] C[c, (e, .., k)]
+    assert N == 512 and M * K * N < 1 << 27                    # (no unit-channel shortcut, no scan for empty tiles)
+    plan = plain_plan(eng.n_cu, M, N, K, 1, ca=cplx, cb=cplx, slices_cap=4 * M * N * (16 if cplx else 8))
+    assert plan["leave_slices"] == 1 and 2 <= plan["ksplit"] <= 4, plan
+    rng = np.random.default_rng(29)
+    l = _rand(rng, (Dl, wl, Dl), cplx)
+    if case == "env_L":
+        ket, w = _rand(rng, (Dl, d, Dr), cplx), _rand(rng, (wl, d, d, wr), False)
+        assert _relerr(dev_env_update(eng, l, ket, w, "L"), ref_env("L", l, ket, w)) < 1e-12
+        return
+    r = _rand(rng, (Dr, wr, Dr), cplx)
+    ws = [_rand(rng, (wl, d, d, wr), False)] if case == "one_site" else [_rand(rng, (wl, d, d, wm), False),
+                                                                         _rand(rng, (wm, d1, d1, wr), False)]
+    c = _rand(rng, (Dl, d, Dr) if case == "one_site" else (Dl, d, d1, Dr), cplx)
+    assert _relerr(dev_heff_apply(eng, l, r, ws, c), ref_heff(l, r, ws, c)) < 1e-12
 
 
 # ---------------------------------------------------------------- Lanczos

@@ -1,6 +1,6 @@
 """CPU check of the folded one-site matvec plan with the epilogue mix (mpse_plans.h: plan_heff1_fold(...,
 mix_epilogue)): the plane of R's unit channel formed in the epilogue of the first product with R.  The plans run on host
-memory through a small runner of their own (tests/host_emu/plan_emu_epi.cpp) against the dense contraction."""
+memory through the naive executor of tests/host_emu (plan_emu_epi.cpp: its exports) against the dense contraction."""
 import ctypes as C
 import os
 import subprocess
