@@ -678,6 +678,55 @@ int mpse_mps_rdm1_stats(mpse_ctx* ctx, int64_t* counts, int n);
  * No context, no device work. */
 int mpse_mps_rdm1_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
 
+/* ------------------------------- two-site reduced density matrices of all pairs of selected sites */
+
+/* rho_kl[(p,q),(p',q')] = sum conj(A_k)[.,p,g,.] conj(A_l)[.,q,g',.] A_k[.,p',g,.] A_l[.,q',g',.] for every pair k < l of
+ * the selected sites of ONE chain in one call: identity environments outside the pair, identity transfer matrices in
+ * between, the ancilla legs g, g' traced wherever a site meets its conjugate; replaces the per-pair products and host
+ * reads of mps/mps.py:1600-1655 (calc_2site_rdm).  It is the walk of mpse_mps_corr with every elementary matrix |p><p'|
+ * opened at k and every |q><q'| closed at l, sharing the walk:
+ *   sites[i]    : device site tensors, contiguous (D_l, d, danc, D_r), each MPSE_F64 or MPSE_C128 (dtype[i]; any mixture)
+ *   dims        : nsite rows (D_l, d, danc, D_r), host
+ *   sel         : nsel >= 2 site indices, strictly ascending, host
+ *   out_host    : the pairs of the selection in the order (0,1), (0,2), .., (0,nsel-1), (1,2), .., each one block
+ *                 [p][p'][q][q'] of row-major complex pairs: 2 * sum_{k<l} d_k^2 d_l^2 doubles
+ * Refusals as mpse_mps_corr / mpse_mps_rdm1, with the same codes: rows with an extent < 1, neighbours whose bonds differ,
+ * a first / last bond != 1, or a selection that is not strictly ascending inside [0, nsite): MPSE_ERR_SHAPE before any
+ * device work.  Null pointers, nsel < 2 and unknown dtypes: MPSE_ERR_ARG.  A refused call counts nothing, enqueues
+ * nothing and leaves out_host as it was.  Chains that pass mpse_mps_rdm2_plan run as TWO launches with no host read
+ * between them: k_rdm2_envs (two workgroups; one walks from the right with R in LDS and leaves the d_l^2 closed
+ * environments G_l^{qq'} of every selected site but the first in pooled memory, the other walks from the left and leaves
+ * L_k of every selected site but the last) and k_rdm2_rows (one workgroup per (k, p, p') starts from L_k at sel[k],
+ * carries the opened state to the right and closes against all G_l^{qq'} at every later selected site, one wave per
+ * entry (q, q'), summed with lane shuffles); no flag, spin wait or atomic between workgroups.  Every other chain runs
+ * the same passes as products of the contraction kernel, the open rows as one stack that grows by d_k^2 rows per opening
+ * site and is walked in chunks of whole opening sites (one that alone exceeds the bound: split by rows) whose two stacks
+ * plus X1 stay under 256 MiB (info[14] of the plan; MPSE_RDM2_STACK_BYTES in the environment overrides it, read per
+ * call); all temporaries pooled (MPSE_ERR_OOM when they do not fit; the context stays usable).  The working dtype is
+ * complex as soon as any site is; a real chain returns zero imaginary parts.  A fixed summation order: the same inputs
+ * give the same bits on every call (the two paths sum in different orders and agree to rounding).  MPSE_RDM2_CHAIN=0 in
+ * the environment sends every chain through the enqueued products, =1 every chain whose launches fit through the
+ * kernels, above the bond limit of the rule as well (both for measurements).  Synchronous, one host read at the end;
+ * refused while a deferred list is being recorded. */
+int mpse_mps_rdm2(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype, const int64_t* dims /* nsite x 4 */,
+                  int nsel, const int* sel, double* out_host);
+/* counts[i], i < n, cumulative:  0 calls taken by the chain kernels, 1 calls taken by the enqueued path, 2 sites walked
+ * (nsite per call), 3 pairs produced (nsel (nsel - 1) / 2 per call).  A refused call counts nothing.  Diagnostics for
+ * tests; no device work. */
+int mpse_mps_rdm2_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims table and the selection alone (the grid and the size of the result depend on the
+ * selection): returns 1 when the chain kernels take the call, else 0 (also for a table or a selection mpse_mps_rdm2
+ * refuses).  The launches FIT under the bond, extent and LDS conditions of mpse_mps_rdm1_plan when nsel >= 2 and the
+ * pooled environments and the result each stay below 2^31 elements (device offsets are 32-bit).  The kernels TAKE a
+ * call that fits when every bond is also <= info[0], a measured limit (profiles/rdm2.md: ahead of the enqueued products
+ * up to bond 32 on a chain with d = 2 / 4, behind on a chain with d = 16 at every bond).  info[i], i < n (may be NULL): 0
+ * to 11 as for mpse_mps_rdm1_plan, then
+ *   12  workgroups of the second launch: sum of d_k^2 over the selected sites but the last
+ *   13  complex elements of the result: sum over k < l of d_k^2 d_l^2
+ *   14  the byte bound of a chunk of the enqueued path
+ * 12 and 13 are 0 for a table or a selection that is refused.  No context, no device work. */
+int mpse_mps_rdm2_plan(int nsite, const int64_t* dims, int nsel, const int* sel, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

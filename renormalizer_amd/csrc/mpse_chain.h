@@ -1,5 +1,5 @@
 // What the "whole chain in one engine call" entry points share (mpse_overlap.hip, mpse_sandwich.hip, mpse_corr.hip,
-// mpse_rdm1.hip; no other file includes this).  Each call walks a chain of site tensors either with its own one-workgroup kernel(s), the
+// mpse_rdm1.hip, mpse_rdm2.hip; no other file includes this).  Each call walks a chain of site tensors either with its own one-workgroup kernel(s), the
 // environment in LDS, or as products enqueued back to back; which one, its plan decides from the dims table alone.  A
 // call supplies its descriptor row, its plan (the sizing behind chain_table_ok), its kernel(s) with their loop nests
 // and its enqueued fallback; the element type, the limits of a launch, the publishing tail, the staging, the dispatch
@@ -85,6 +85,75 @@ __device__ __forceinline__ void chain_publish2(double* out, double* pub, volatil
     __threadfence_system();
     *seq_slot = seq;
     __threadfence_system();
+  }
+}
+
+// The walk from the left that leaves the identity environment L of selected sites in pooled memory: workgroup 1 of
+// k_rdm1_envs and of k_rdm2_envs.  `Row`: a descriptor row with a, Dl, d, danc, Dr, cplx, sel (>= 0: selected) and eoff
+// (working elements before L of the site in `pool`).  L_0 = 1.  At a selected site L goes to the pooled buffer; the
+// walk ends at site `last`.  Else per site from the left, per (sigma, a) in ascending order:
+//   T[b, c'] = sum_c L[b, c] A[c, sigma, a, c']                                             (into LDS)
+//   L'[b', c'] += sum_b conj(A[b, sigma, a, b']) T[b, c']                                   (registers of the owner)
+// Threads take (b', c') with c' fastest; OUT_PER_THREAD entries of L' each.
+template <bool CPLX, int OUT_PER_THREAD, class Row>
+__device__ void chain_walk_left(const Row* __restrict__ sites, int last, typename ChainEl<CPLX>::T* E,
+                                typename ChainEl<CPLX>::T* Ts, typename ChainEl<CPLX>::T* pool) {
+  using El = ChainEl<CPLX>;
+  using T = typename El::T;
+  const int tid = threadIdx.x;
+  if (tid == 0) E[0] = El::one();
+  __syncthreads();
+  for (int i = 0; i <= last; ++i) {
+    const Row s = sites[i];
+    const int Dl = s.Dl, Dr = s.Dr;
+    const int p = s.d * s.danc, row = p * Dr;
+    const int pe = Dl | 1, pe_new = Dr | 1;
+    const int nT = Dl * Dr, nE = Dr * Dr;
+    if (s.sel >= 0) {
+      T* L = pool + s.eoff;
+      for (int o = tid; o < Dl * Dl; o += CHAIN_THREADS) {
+        const int b = o / Dl, c = o - b * Dl;
+        L[o] = E[b * pe + c];
+      }
+    }
+    if (i == last) break;
+    T acc[OUT_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < OUT_PER_THREAD; ++j) acc[j] = El::zero();
+    for (int sa = 0; sa < p; ++sa) {
+      for (int o = tid; o < nT; o += CHAIN_THREADS) {
+        const int b = o / Dr, cc = o - b * Dr;
+        const T* e_row = E + b * pe;
+        const int a0 = sa * Dr + cc;
+        T sum = El::zero();
+#pragma unroll 4
+        for (int c = 0; c < Dl; ++c) El::fma(sum, e_row[c], El::ld(s.a, s.cplx, c * row + a0));
+        Ts[o] = sum;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < OUT_PER_THREAD; ++j) {
+        const int o = tid + j * CHAIN_THREADS;
+        if (o < nE) {
+          const int bb = o / Dr, cc = o - bb * Dr;
+          const int b0 = sa * Dr + bb;
+          T S = El::zero();
+#pragma unroll 4
+          for (int b = 0; b < Dl; ++b) El::fma(S, El::cj(El::ld(s.a, s.cplx, b * row + b0)), Ts[b * Dr + cc]);
+          El::add(acc[j], S);
+        }
+      }
+      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of L is done as well
+    }
+#pragma unroll
+    for (int j = 0; j < OUT_PER_THREAD; ++j) {
+      const int o = tid + j * CHAIN_THREADS;
+      if (o < nE) {
+        const int bb = o / Dr, cc = o - bb * Dr;
+        E[bb * pe_new + cc] = acc[j];
+      }
+    }
+    __syncthreads();
   }
 }
 
@@ -197,5 +266,21 @@ static inline int widen_site(mpse_ctx* ctx, TmpBuf& buf, const void** site, int6
   if (!buf.p) MPSE_TRY(buf.alloc((size_t)cap * 16));
   MPSE_TRY(mpse_cast_f64_to_c128(ctx, buf.p, *site, n));
   *site = buf.p;
+  return MPSE_OK;
+}
+
+// The sites of a chain call with dims rows (D_l, d, danc, D_r) in ONE working dtype: (*site)[i] is sites[i], or, for a
+// real site of a complex call, its widened copy in a pooled buffer of `wide`, which lives as long as its owner
+static inline int chain_widen_sites(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype,
+                                    const int64_t* dims, bool cplx, std::vector<std::unique_ptr<TmpBuf>>* wide,
+                                    std::vector<const void*>* site) {
+  site->assign(sites, sites + nsite);
+  for (int i = 0; i < nsite; ++i) {
+    if (!cplx || dtype[i] == MPSE_C128) continue;
+    const int64_t* d = dims + 4 * i;
+    const int64_t n = d[0] * d[1] * d[2] * d[3];
+    wide->emplace_back(new TmpBuf(ctx));
+    MPSE_TRY(widen_site(ctx, *wide->back(), &(*site)[i], n, n));
+  }
   return MPSE_OK;
 }

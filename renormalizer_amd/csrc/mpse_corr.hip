@@ -386,15 +386,8 @@ int corr_enqueued(mpse_ctx* ctx, const CrArgs& a, bool cplx, double* out_host) {
   }
   // widened copies of the real sites of a complex call live to the end of the call
   std::vector<std::unique_ptr<TmpBuf>> wide;
-  std::vector<const void*> site((size_t)a.nsite);
-  for (int i = 0; i < a.nsite; ++i) {
-    site[i] = a.sites[i];
-    if (!cplx || a.dtype[i] == MPSE_C128) continue;
-    const int64_t* d = a.dims + 4 * i;
-    const int64_t n = d[0] * d[1] * d[2] * d[3];
-    wide.emplace_back(new TmpBuf(ctx));
-    MPSE_TRY(widen_site(ctx, *wide.back(), &site[i], n, n));
-  }
+  std::vector<const void*> site;
+  MPSE_TRY(chain_widen_sites(ctx, a.nsite, a.sites, a.dtype, a.dims, cplx, &wide, &site));
   TmpBuf mbuf(ctx), gbuf(ctx), res(ctx), r0(ctx), r1(ctx), y1(ctx), y2(ctx);
   MPSE_TRY(mbuf.alloc(mats.size() * sizeof(double)));
   MPSE_TRY(gbuf.alloc((size_t)g_elems * es));

@@ -161,6 +161,9 @@ struct mpse_ctx {
   // mpse_mps_rdm1 (mpse_mps_rdm1_stats; the order of include/mpsengine.h)
   enum Rdm1Stat { RD_CHAIN, RD_ENQUEUED, RD_SITES, RD_MATRICES, RD_COUNT };
   long long rdm1_stats[RD_COUNT] = {0};
+  // mpse_mps_rdm2 (mpse_mps_rdm2_stats; the order of include/mpsengine.h)
+  enum Rdm2Stat { RD2_CHAIN, RD2_ENQUEUED, RD2_SITES, RD2_PAIRS, RD2_COUNT };
+  long long rdm2_stats[RD2_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

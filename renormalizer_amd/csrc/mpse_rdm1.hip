@@ -5,7 +5,7 @@
 // operator window and one host read each).  L_i / R_i: the identity-operator environments left / right of site i, first
 // index from the conjugated tensor.  Two paths, chosen from the dims table alone (rdm1_plan):
 //   chain      two launches, for chains whose bonds are at most RD_BOND_MAX.  k_rdm1_envs: workgroup 0 walks right to
-//              left with R in LDS, workgroup 1 left to right with L in LDS; each leaves its environment of every
+//              left with R in LDS, workgroup 1 left to right with L in LDS (chain_walk_left); each leaves its environment of every
 //              selected site in pooled memory (R transposed, so that k_rdm1_sites reads it along the lanes).
 //              k_rdm1_sites: one workgroup per selected site closes L_i and R_i around the site.  A workgroup reads
 //              only what the launch before it wrote: no flag, no spin wait, no atomic.
@@ -158,73 +158,6 @@ __device__ void rd_walk_right(const RdSite* __restrict__ sites, int nsite, int f
   }
 }
 
-// Workgroup 1 of k_rdm1_envs.  L_0 = 1.  At a selected site L goes to the pooled buffer; the walk ends at the last
-// selected site.  Else per site from the left, per (sigma, a) in ascending order:
-//   T[b, c'] = sum_c L[b, c] A[c, sigma, a, c']                                             (into LDS)
-//   L'[b', c'] += sum_b conj(A[b, sigma, a, b']) T[b, c']                                   (registers of the owner)
-// Threads take (b', c') with c' fastest.
-template <bool CPLX>
-__device__ void rd_walk_left(const RdSite* __restrict__ sites, int last, typename ChainEl<CPLX>::T* E,
-                             typename ChainEl<CPLX>::T* Ts, typename ChainEl<CPLX>::T* pool) {
-  using El = ChainEl<CPLX>;
-  using T = typename El::T;
-  const int tid = threadIdx.x;
-  if (tid == 0) E[0] = El::one();
-  __syncthreads();
-  for (int i = 0; i <= last; ++i) {
-    const RdSite s = sites[i];
-    const int Dl = s.Dl, Dr = s.Dr;
-    const int p = s.d * s.danc, row = p * Dr;
-    const int pe = Dl | 1, pe_new = Dr | 1;
-    const int nT = Dl * Dr, nE = Dr * Dr;
-    if (s.sel >= 0) {
-      T* L = pool + s.eoff;
-      for (int o = tid; o < Dl * Dl; o += CHAIN_THREADS) {
-        const int b = o / Dl, c = o - b * Dl;
-        L[o] = E[b * pe + c];
-      }
-    }
-    if (i == last) break;
-    T acc[RD_OUT_PER_THREAD];
-#pragma unroll
-    for (int j = 0; j < RD_OUT_PER_THREAD; ++j) acc[j] = El::zero();
-    for (int sa = 0; sa < p; ++sa) {
-      for (int o = tid; o < nT; o += CHAIN_THREADS) {
-        const int b = o / Dr, cc = o - b * Dr;
-        const T* e_row = E + b * pe;
-        const int a0 = sa * Dr + cc;
-        T sum = El::zero();
-#pragma unroll 4
-        for (int c = 0; c < Dl; ++c) El::fma(sum, e_row[c], El::ld(s.a, s.cplx, c * row + a0));
-        Ts[o] = sum;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < RD_OUT_PER_THREAD; ++j) {
-        const int o = tid + j * CHAIN_THREADS;
-        if (o < nE) {
-          const int bb = o / Dr, cc = o - bb * Dr;
-          const int b0 = sa * Dr + bb;
-          T S = El::zero();
-#pragma unroll 4
-          for (int b = 0; b < Dl; ++b) El::fma(S, El::cj(El::ld(s.a, s.cplx, b * row + b0)), Ts[b * Dr + cc]);
-          El::add(acc[j], S);
-        }
-      }
-      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of L is done as well
-    }
-#pragma unroll
-    for (int j = 0; j < RD_OUT_PER_THREAD; ++j) {
-      const int o = tid + j * CHAIN_THREADS;
-      if (o < nE) {
-        const int bb = o / Dr, cc = o - bb * Dr;
-        E[bb * pe_new + cc] = acc[j];
-      }
-    }
-    __syncthreads();
-  }
-}
-
 template <bool CPLX>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_rdm1_envs(const RdSite* __restrict__ sites, int nsite, int first,
                                                              int last, int e_elems, void* pool) {
@@ -235,7 +168,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_rdm1_envs(const RdSite* __res
   if (blockIdx.x == 0)
     rd_walk_right<CPLX>(sites, nsite, first, E, Ts, static_cast<T*>(pool));
   else
-    rd_walk_left<CPLX>(sites, last, E, Ts, static_cast<T*>(pool));
+    chain_walk_left<CPLX, RD_OUT_PER_THREAD>(sites, last, E, Ts, static_cast<T*>(pool));   // workgroup 1: mpse_chain.h
 }
 
 // Workgroup k closes the environments of site sel[k] (row nsite + k of the table).  Per (sigma', a) in ascending order:
@@ -379,15 +312,8 @@ int rdm1_enqueued(mpse_ctx* ctx, const RdArgs& a, bool cplx, double* out_host) {
   }
   // widened copies of the real sites of a complex call live to the end of the call
   std::vector<std::unique_ptr<TmpBuf>> wide;
-  std::vector<const void*> site((size_t)a.nsite);
-  for (int i = 0; i < a.nsite; ++i) {
-    site[i] = a.sites[i];
-    if (!cplx || a.dtype[i] == MPSE_C128) continue;
-    const int64_t* d = a.dims + 4 * i;
-    const int64_t n = d[0] * d[1] * d[2] * d[3];
-    wide.emplace_back(new TmpBuf(ctx));
-    MPSE_TRY(widen_site(ctx, *wide.back(), &site[i], n, n));
-  }
+  std::vector<const void*> site;
+  MPSE_TRY(chain_widen_sites(ctx, a.nsite, a.sites, a.dtype, a.dims, cplx, &wide, &site));
   TmpBuf rbuf(ctx), res(ctx), e0(ctx), e1(ctx), x1(ctx), y(ctx);
   MPSE_TRY(rbuf.alloc((size_t)r_elems * es));
   MPSE_TRY(res.alloc((size_t)o_elems * es));

@@ -191,6 +191,10 @@ _SIGNATURES = {
                       _dblp],
     "mpse_mps_rdm1_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_mps_rdm1_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
+    "mpse_mps_rdm2": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p, C.c_int, C.POINTER(C.c_int),
+                      _dblp],
+    "mpse_mps_rdm2_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_rdm2_plan": [C.c_int, _i64p, C.c_int, C.POINTER(C.c_int), C.c_int, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -283,6 +287,22 @@ def mps_rdm1_plan(dims, nsel, any_complex, lib=None):
     rows = [[int(x) for x in r] for r in dims]
     assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
     return _chain_plan(lib.mpse_mps_rdm1_plan, rows, 4, RDM1_PLAN_INFO, int(nsel), int(bool(any_complex)))
+
+
+RDM2_PLAN_INFO = RDM1_PLAN_INFO + ("units", "out_elems", "stack_bytes")
+
+
+def mps_rdm2_plan(dims, sel, any_complex, lib=None):
+    """Which path ``Engine.mps_rdm2`` takes for a chain, from its ``dims`` rows (D_l, d, danc, D_r) and the selected
+    sites alone (``mpse_mps_rdm2_plan``; needs the built library, no GPU).  Returns (chain kernels?, {info name:
+    value}); ``units``: the workgroups of the second launch, ``out_elems``: the complex elements of the result (both 0
+    for a table or a selection the call refuses), ``stack_bytes``: the byte bound of a chunk of the enqueued path."""
+    lib = lib or load_library()
+    rows = [[int(x) for x in r] for r in dims]
+    assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
+    sel = [int(k) for k in sel]
+    return _chain_plan(lib.mpse_mps_rdm2_plan, rows, 4, RDM2_PLAN_INFO, len(sel), (C.c_int * max(len(sel), 1))(*sel),
+                       int(bool(any_complex)))
 
 
 def check_selection(call, sel, nsite):
@@ -874,6 +894,38 @@ class Engine:
             self.ctx, n, *_site_args(sites), dims, nsel, (C.c_int * nsel)(*sel), out.ctypes.data_as(_dblp)))
         ends = np.cumsum(sizes)
         return [out[e - sz:e].reshape(rows[k][1], rows[k][1]) for k, sz, e in zip(sel, sizes, ends)]
+
+    # -- two-site reduced density matrices
+    RDM2_STATS = ("chain_kernel", "enqueued", "sites", "pairs")
+
+    def mps_rdm2_stats(self):
+        """{name: count} of the ``mps_rdm2`` calls of this context, cumulative (``mpse_mps_rdm2_stats``): calls taken by
+        the chain kernels, calls taken by the enqueued products, sites walked, pairs produced."""
+        return self._stats_dict(self.lib.mpse_mps_rdm2_stats, self.RDM2_STATS)
+
+    def mps_rdm2(self, sites, sel):
+        """rho_kl[p, p', q, q'] = sum conj(A_k)[.,p,g,.] conj(A_l)[.,q,g',.] A_k[.,p',g,.] A_l[.,q',g',.] for every pair
+        k < l of the sites ``sel`` (strictly ascending, at least two) of a chain of device site tensors (D_l, d[, danc],
+        D_r), in one engine call (``mpse_mps_rdm2``): identity environments outside the pair, identity transfer matrices
+        in between, the ancilla leg of density-operator sites traced.  Returns {(k, l): (d_k, d_k, d_l, d_l) complex128
+        array} with site indices as keys."""
+        rows = self.corr_dims(sites)
+        n = len(rows)
+        if n == 0:
+            raise ValueError("mps_rdm2: no sites")
+        sel = check_selection("mps_rdm2", sel, n)
+        nsel = len(sel)
+        if nsel < 2:
+            raise ValueError(f"mps_rdm2: a pair needs two selected sites, the selection is {sel}")
+        dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
+        pairs = [(k, l) for i, k in enumerate(sel) for l in sel[i + 1:]]
+        sizes = [rows[k][1] ** 2 * rows[l][1] ** 2 for k, l in pairs]
+        out = np.zeros(sum(sizes), dtype=np.complex128)
+        self._check(self.lib.mpse_mps_rdm2(
+            self.ctx, n, *_site_args(sites), dims, nsel, (C.c_int * nsel)(*sel), out.ctypes.data_as(_dblp)))
+        ends = np.cumsum(sizes)
+        return {(k, l): out[e - sz:e].reshape(rows[k][1], rows[k][1], rows[l][1], rows[l][1])
+                for (k, l), sz, e in zip(pairs, sizes, ends)}
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""
