@@ -1,9 +1,10 @@
-// What the "whole chain in one engine call" entry points share (mpse_overlap.hip, mpse_sandwich.hip, mpse_corr.hip,
-// mpse_rdm1.hip, mpse_rdm2.hip; no other file includes this).  Each call walks a chain of site tensors either with its own one-workgroup kernel(s), the
-// environment in LDS, or as products enqueued back to back; which one, its plan decides from the dims table alone.  A
-// call supplies its descriptor row, its plan (the sizing behind chain_table_ok), its kernel(s) with their loop nests
-// and its enqueued fallback; the element type, the limits of a launch, the publishing tail, the staging, the dispatch
-// and the bookkeeping of the exports are here.
+// What the "whole chain in one engine call" entry points share (mpse_overlap.hip and mpse_sandwich.hip include this; the
+// calls with a site selection, mpse_corr.hip, mpse_rdm1.hip and mpse_rdm2.hip, include it through mpse_chain_walk.h,
+// which adds the walk that those three share; no other file includes either).  Each call walks a chain of site tensors
+// either with its own one-workgroup kernel(s), the environment in LDS, or as products enqueued back to back; which one,
+// its plan decides from the dims table alone.  A call supplies its descriptor row, its plan (the sizing behind
+// chain_table_ok), its kernel(s) with their loop nests and its enqueued fallback; the element type, the limits of a
+// launch, the publishing tail, the staging, the dispatch and the bookkeeping of the exports are here.
 #pragma once
 #include <algorithm>
 #include <initializer_list>
@@ -73,6 +74,9 @@ struct ChainEl<true> {
   __device__ static double im(T a) { return a.y; }
 };
 
+template <bool CPLX>
+using ChainT = typename ChainEl<CPLX>::T;
+
 // Tail of a kernel whose result is one complex scalar, for its one deciding thread: the value goes to out[0..1] and,
 // when pub is set, to the mapped host buffer followed by the sequence number (publish_collect)
 __device__ __forceinline__ void chain_publish2(double* out, double* pub, volatile double* seq_slot, double seq,
@@ -85,75 +89,6 @@ __device__ __forceinline__ void chain_publish2(double* out, double* pub, volatil
     __threadfence_system();
     *seq_slot = seq;
     __threadfence_system();
-  }
-}
-
-// The walk from the left that leaves the identity environment L of selected sites in pooled memory: workgroup 1 of
-// k_rdm1_envs and of k_rdm2_envs.  `Row`: a descriptor row with a, Dl, d, danc, Dr, cplx, sel (>= 0: selected) and eoff
-// (working elements before L of the site in `pool`).  L_0 = 1.  At a selected site L goes to the pooled buffer; the
-// walk ends at site `last`.  Else per site from the left, per (sigma, a) in ascending order:
-//   T[b, c'] = sum_c L[b, c] A[c, sigma, a, c']                                             (into LDS)
-//   L'[b', c'] += sum_b conj(A[b, sigma, a, b']) T[b, c']                                   (registers of the owner)
-// Threads take (b', c') with c' fastest; OUT_PER_THREAD entries of L' each.
-template <bool CPLX, int OUT_PER_THREAD, class Row>
-__device__ void chain_walk_left(const Row* __restrict__ sites, int last, typename ChainEl<CPLX>::T* E,
-                                typename ChainEl<CPLX>::T* Ts, typename ChainEl<CPLX>::T* pool) {
-  using El = ChainEl<CPLX>;
-  using T = typename El::T;
-  const int tid = threadIdx.x;
-  if (tid == 0) E[0] = El::one();
-  __syncthreads();
-  for (int i = 0; i <= last; ++i) {
-    const Row s = sites[i];
-    const int Dl = s.Dl, Dr = s.Dr;
-    const int p = s.d * s.danc, row = p * Dr;
-    const int pe = Dl | 1, pe_new = Dr | 1;
-    const int nT = Dl * Dr, nE = Dr * Dr;
-    if (s.sel >= 0) {
-      T* L = pool + s.eoff;
-      for (int o = tid; o < Dl * Dl; o += CHAIN_THREADS) {
-        const int b = o / Dl, c = o - b * Dl;
-        L[o] = E[b * pe + c];
-      }
-    }
-    if (i == last) break;
-    T acc[OUT_PER_THREAD];
-#pragma unroll
-    for (int j = 0; j < OUT_PER_THREAD; ++j) acc[j] = El::zero();
-    for (int sa = 0; sa < p; ++sa) {
-      for (int o = tid; o < nT; o += CHAIN_THREADS) {
-        const int b = o / Dr, cc = o - b * Dr;
-        const T* e_row = E + b * pe;
-        const int a0 = sa * Dr + cc;
-        T sum = El::zero();
-#pragma unroll 4
-        for (int c = 0; c < Dl; ++c) El::fma(sum, e_row[c], El::ld(s.a, s.cplx, c * row + a0));
-        Ts[o] = sum;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < OUT_PER_THREAD; ++j) {
-        const int o = tid + j * CHAIN_THREADS;
-        if (o < nE) {
-          const int bb = o / Dr, cc = o - bb * Dr;
-          const int b0 = sa * Dr + bb;
-          T S = El::zero();
-#pragma unroll 4
-          for (int b = 0; b < Dl; ++b) El::fma(S, El::cj(El::ld(s.a, s.cplx, b * row + b0)), Ts[b * Dr + cc]);
-          El::add(acc[j], S);
-        }
-      }
-      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of L is done as well
-    }
-#pragma unroll
-    for (int j = 0; j < OUT_PER_THREAD; ++j) {
-      const int o = tid + j * CHAIN_THREADS;
-      if (o < nE) {
-        const int bb = o / Dr, cc = o - bb * Dr;
-        E[bb * pe_new + cc] = acc[j];
-      }
-    }
-    __syncthreads();
   }
 }
 

@@ -226,9 +226,11 @@ def load_library(path=LIB_PATH):
     return lib
 
 
-def _chain_plan(lib_fn, rows, row_len, info_names, *extra):
-    """(chain kernel?, {info name: value}) of one of the ``mpse_mps_*_plan`` exports for ``rows`` of ``row_len`` extents;
-    ``extra``: the integer arguments between the table and the info array"""
+def _chain_plan(lib_fn, dims, row_len, row, info_names, *extra):
+    """(chain kernel?, {info name: value}) of one of the ``mpse_mps_*_plan`` exports for the ``dims`` rows of ``row_len``
+    extents, which ``row`` names; ``extra``: the arguments between the table and the info array"""
+    rows = [[int(x) for x in r] for r in dims]
+    assert all(len(r) == row_len for r in rows), f"dims rows are ({row})"
     flat = (C.c_int64 * max(row_len * len(rows), 1))(*[x for r in rows for x in r])
     info = (C.c_int64 * len(info_names))()
     ok = lib_fn(len(rows), flat, *extra, info, len(info))
@@ -241,10 +243,8 @@ OVERLAP_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elem
 def mps_overlap_plan(dims, any_complex, lib=None):
     """Which path ``Engine.mps_overlap`` takes for a chain, from its ``dims`` rows (Db_l, Dk_l, p, Db_r, Dk_r) alone
     (``mpse_mps_overlap_plan``; needs the built library, no GPU).  Returns (chain kernel?, {info name: value})."""
-    lib = lib or load_library()
-    rows = [[int(x) for x in r] for r in dims]
-    assert all(len(r) == 5 for r in rows), "dims rows are (Db_l, Dk_l, p, Db_r, Dk_r)"
-    return _chain_plan(lib.mpse_mps_overlap_plan, rows, 5, OVERLAP_PLAN_INFO, int(bool(any_complex)))
+    return _chain_plan((lib or load_library()).mpse_mps_overlap_plan, dims, 5, "Db_l, Dk_l, p, Db_r, Dk_r",
+                       OVERLAP_PLAN_INFO, int(bool(any_complex)))
 
 
 SANDWICH_PLAN_INFO = ("lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "acc_per_thread", "acc_needed",
@@ -255,10 +255,8 @@ def mps_sandwich_plan(dims, any_complex, lib=None):
     """Which path ``Engine.mps_sandwich`` takes for a chain, from its ``dims`` rows (Db_l, Dk_l, wl, d, danc, Db_r,
     Dk_r, wr) alone (``mpse_mps_sandwich_plan``; needs the built library, no GPU).  Returns (chain kernel?, {info name:
     value})."""
-    lib = lib or load_library()
-    rows = [[int(x) for x in r] for r in dims]
-    assert all(len(r) == 8 for r in rows), "dims rows are (Db_l, Dk_l, wl, d, danc, Db_r, Dk_r, wr)"
-    return _chain_plan(lib.mpse_mps_sandwich_plan, rows, 8, SANDWICH_PLAN_INFO, int(bool(any_complex)))
+    return _chain_plan((lib or load_library()).mpse_mps_sandwich_plan, dims, 8,
+                       "Db_l, Dk_l, wl, d, danc, Db_r, Dk_r, wr", SANDWICH_PLAN_INFO, int(bool(any_complex)))
 
 
 CORR_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid",
@@ -269,10 +267,8 @@ def mps_corr_plan(dims, nsel, any_complex, lib=None):
     """Which path ``Engine.mps_corr`` takes for a chain, from its ``dims`` rows (D_l, d, danc, D_r) and the number of
     selected sites alone (``mpse_mps_corr_plan``; needs the built library, no GPU).  Returns (chain kernels?, {info
     name: value})."""
-    lib = lib or load_library()
-    rows = [[int(x) for x in r] for r in dims]
-    assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
-    return _chain_plan(lib.mpse_mps_corr_plan, rows, 4, CORR_PLAN_INFO, int(nsel), int(bool(any_complex)))
+    return _chain_plan((lib or load_library()).mpse_mps_corr_plan, dims, 4, "D_l, d, danc, D_r", CORR_PLAN_INFO,
+                       int(nsel), int(bool(any_complex)))
 
 
 RDM1_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid",
@@ -283,10 +279,8 @@ def mps_rdm1_plan(dims, nsel, any_complex, lib=None):
     """Which path ``Engine.mps_rdm1`` takes for a chain, from its ``dims`` rows (D_l, d, danc, D_r) and the number of
     selected sites alone (``mpse_mps_rdm1_plan``; needs the built library, no GPU).  Returns (chain kernels?, {info
     name: value}); ``nsel_limit`` is 0: the kernels take any number of selected sites."""
-    lib = lib or load_library()
-    rows = [[int(x) for x in r] for r in dims]
-    assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
-    return _chain_plan(lib.mpse_mps_rdm1_plan, rows, 4, RDM1_PLAN_INFO, int(nsel), int(bool(any_complex)))
+    return _chain_plan((lib or load_library()).mpse_mps_rdm1_plan, dims, 4, "D_l, d, danc, D_r", RDM1_PLAN_INFO,
+                       int(nsel), int(bool(any_complex)))
 
 
 RDM2_PLAN_INFO = RDM1_PLAN_INFO + ("units", "out_elems", "stack_bytes")
@@ -297,12 +291,9 @@ def mps_rdm2_plan(dims, sel, any_complex, lib=None):
     sites alone (``mpse_mps_rdm2_plan``; needs the built library, no GPU).  Returns (chain kernels?, {info name:
     value}); ``units``: the workgroups of the second launch, ``out_elems``: the complex elements of the result (both 0
     for a table or a selection the call refuses), ``stack_bytes``: the byte bound of a chunk of the enqueued path."""
-    lib = lib or load_library()
-    rows = [[int(x) for x in r] for r in dims]
-    assert all(len(r) == 4 for r in rows), "dims rows are (D_l, d, danc, D_r)"
     sel = [int(k) for k in sel]
-    return _chain_plan(lib.mpse_mps_rdm2_plan, rows, 4, RDM2_PLAN_INFO, len(sel), (C.c_int * max(len(sel), 1))(*sel),
-                       int(bool(any_complex)))
+    return _chain_plan((lib or load_library()).mpse_mps_rdm2_plan, dims, 4, "D_l, d, danc, D_r", RDM2_PLAN_INFO,
+                       len(sel), (C.c_int * max(len(sel), 1))(*sel), int(bool(any_complex)))
 
 
 def check_selection(call, sel, nsite):
@@ -841,6 +832,17 @@ class Engine:
             rows.append([t.shape[0], t.shape[1], t.shape[2] if t.ndim == 4 else 1, t.shape[-1]])
         return rows
 
+    @classmethod
+    def _sel_dims(cls, call, sites, sel):
+        """(rows, number of sites, selection as ints, dims array) of a chain call with a site selection; ValueError for
+        an empty chain or a selection that is not one.  Needs no context."""
+        rows = cls.corr_dims(sites)
+        n = len(rows)
+        if n == 0:
+            raise ValueError(f"{call}: no sites")
+        sel = check_selection(call, sel, n)
+        return rows, n, sel, (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
+
     def mps_corr(self, sites, sel, x_mats, y_mats, z_mats):
         """C[k, l] = <psi| X_k Y_l |psi> (k < l), C[k, k] = <psi| Z_k |psi> for one-site operators on the sites ``sel``
         (strictly ascending) of a chain of device site tensors (D_l, d[, danc], D_r), in one engine call
@@ -881,17 +883,11 @@ class Engine:
         ascending) of a chain of device site tensors (D_l, d[, danc], D_r), in one engine call (``mpse_mps_rdm1``); L_i
         and R_i are the identity-operator environments of the other sites, the ancilla leg of density-operator sites is
         traced.  Returns a list of (d, d) complex128 arrays, one per selected site."""
-        rows = self.corr_dims(sites)
-        n = len(rows)
-        if n == 0:
-            raise ValueError("mps_rdm1: no sites")
-        sel = check_selection("mps_rdm1", sel, n)
-        nsel = len(sel)
-        dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
+        rows, n, sel, dims = self._sel_dims("mps_rdm1", sites, sel)
         sizes = [rows[k][1] ** 2 for k in sel]
         out = np.zeros(sum(sizes), dtype=np.complex128)
         self._check(self.lib.mpse_mps_rdm1(
-            self.ctx, n, *_site_args(sites), dims, nsel, (C.c_int * nsel)(*sel), out.ctypes.data_as(_dblp)))
+            self.ctx, n, *_site_args(sites), dims, len(sel), (C.c_int * len(sel))(*sel), out.ctypes.data_as(_dblp)))
         ends = np.cumsum(sizes)
         return [out[e - sz:e].reshape(rows[k][1], rows[k][1]) for k, sz, e in zip(sel, sizes, ends)]
 
@@ -909,20 +905,14 @@ class Engine:
         D_r), in one engine call (``mpse_mps_rdm2``): identity environments outside the pair, identity transfer matrices
         in between, the ancilla leg of density-operator sites traced.  Returns {(k, l): (d_k, d_k, d_l, d_l) complex128
         array} with site indices as keys."""
-        rows = self.corr_dims(sites)
-        n = len(rows)
-        if n == 0:
-            raise ValueError("mps_rdm2: no sites")
-        sel = check_selection("mps_rdm2", sel, n)
-        nsel = len(sel)
-        if nsel < 2:
+        rows, n, sel, dims = self._sel_dims("mps_rdm2", sites, sel)
+        if len(sel) < 2:
             raise ValueError(f"mps_rdm2: a pair needs two selected sites, the selection is {sel}")
-        dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
         pairs = [(k, l) for i, k in enumerate(sel) for l in sel[i + 1:]]
         sizes = [rows[k][1] ** 2 * rows[l][1] ** 2 for k, l in pairs]
         out = np.zeros(sum(sizes), dtype=np.complex128)
         self._check(self.lib.mpse_mps_rdm2(
-            self.ctx, n, *_site_args(sites), dims, nsel, (C.c_int * nsel)(*sel), out.ctypes.data_as(_dblp)))
+            self.ctx, n, *_site_args(sites), dims, len(sel), (C.c_int * len(sel))(*sel), out.ctypes.data_as(_dblp)))
         ends = np.cumsum(sizes)
         return {(k, l): out[e - sz:e].reshape(rows[k][1], rows[k][1], rows[l][1], rows[l][1])
                 for (k, l), sz, e in zip(pairs, sizes, ends)}
