@@ -1903,6 +1903,7 @@ extern "C" int mpse_transpose_inner(mpse_ctx* ctx, int dtype, void* out, const v
   if (!out || !in) return MPSE_ERR_ARG;
   long long nblk = d0 * ((d1 + 31) / 32) * ((d2 + 31) / 32);
   if (nblk > 0x7fffffffLL) return mpse_fail(ctx, MPSE_ERR_SHAPE, "transpose grid too large");
+  wsite_written(ctx, out, size_t(d0) * size_t(d1) * size_t(d2) * dtype_size(dtype));
   if (dtype == MPSE_C128)
     hipLaunchKernelGGL((k_transpose_inner<true>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (double*)out,
                        (const double*)in, (long long)d0, (int)d1, (int)d2, conj);

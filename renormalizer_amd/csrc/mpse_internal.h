@@ -86,7 +86,12 @@ struct mpse_ctx {
   std::unordered_map<unsigned long long, int> lz_hint;
   // Block structure of MPO sites the caller has described (mpse_mpo_site_hint), by device pointer: large one-site
   // matvecs on such a site take the folded plan (mpse_plans.h).  Dropped when the buffer is freed, and when one of
-  // the element-level entry points writes into it (wsite_written: copies, memset, scal, conj, axpy).
+  // these entry points write into it (wsite_written): mpse_memcpy_h2d, mpse_memcpy_d2d, mpse_memcpy_2d,
+  // mpse_memset_zero, mpse_scal, mpse_conj_inplace, mpse_axpy, mpse_mul_real, mpse_real_part, mpse_cast_f64_to_c128,
+  // mpse_davidson_precond, mpse_gather_cols, mpse_gather_rows, mpse_transpose_inner, and the solution vectors of
+  // mpse_pcg, mpse_pcg_sum and mpse_pcg_batch.  No other writer looks at the map: results of mpse_gemm and the
+  // contractions, the factors of the decompositions and the outputs of the other solvers must not target a described
+  // buffer.
   struct WSiteEntry {
     std::shared_ptr<void> info;      // -> mpse_plan::WSiteInfo
     size_t bytes = 0;                // extent of the described site on the device

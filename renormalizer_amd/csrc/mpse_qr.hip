@@ -304,6 +304,7 @@ int mpse_gather_cols(mpse_ctx* ctx, int dtype, void* out, const void* in, int64_
   if (!ctx || !cols_host || (nrow * ncol_out && (!out || !in))) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (nrow * ncol_out <= 0) return MPSE_OK;
+  wsite_written(ctx, out, size_t(nrow) * size_t(ncol_out) * dtype_size(dtype));
   TmpBuf IDX(ctx);
   MPSE_TRY(IDX.alloc(size_t(ncol_out) * 16));
   MPSE_TRY(stage_h2d(ctx, IDX.p, cols_host, size_t(ncol_out) * 8));
@@ -330,6 +331,7 @@ int mpse_gather_rows(mpse_ctx* ctx, int dtype, void* out, const void* in, int64_
   if (!ctx || !rows_host || (nrow_out * ncol && (!out || !in))) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (nrow_out * ncol <= 0) return MPSE_OK;
+  wsite_written(ctx, out, size_t(nrow_out) * size_t(ncol) * dtype_size(dtype));
   TmpBuf IDX(ctx);
   MPSE_TRY(IDX.alloc(size_t(nrow_out) * 16));
   MPSE_TRY(stage_h2d(ctx, IDX.p, rows_host, size_t(nrow_out) * 8));

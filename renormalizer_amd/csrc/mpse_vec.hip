@@ -135,6 +135,7 @@ int mpse_cast_f64_to_c128(mpse_ctx* ctx, void* dst, const void* src, int64_t n) 
   if (!ctx || (n && (!dst || !src))) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (n <= 0) return MPSE_OK;
+  wsite_written(ctx, dst, size_t(n) * 16);
   hipLaunchKernelGGL(k_cast, dim3(ew_blocks(n)), dim3(256), 0, ctx->stream, (double*)dst, (const double*)src,
                      (long long)n);
   MPSE_HIP(ctx, hipGetLastError());
@@ -175,6 +176,7 @@ int mpse_mul_real(mpse_ctx* ctx, int dtype, void* x, const void* m_f64, int64_t 
   if (!ctx || (n && (!x || !m_f64))) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (n <= 0) return MPSE_OK;
+  wsite_written(ctx, x, size_t(n) * dtype_size(dtype));
   MPSE_LAUNCH_TF_CHK(ctx, dtype == MPSE_C128, k_mul_real, dim3(ew_blocks(n)), dim3(256), (double*)x, (const double*)m_f64,
                      (long long)n);
   return MPSE_OK;
@@ -185,6 +187,7 @@ int mpse_davidson_precond(mpse_ctx* ctx, int dtype, void* out, const void* r, co
   if (!ctx || (n && (!out || !r || !hdiag_f64))) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (n <= 0) return MPSE_OK;
+  wsite_written(ctx, out, size_t(n) * dtype_size(dtype));
   MPSE_LAUNCH_TF_CHK(ctx, dtype == MPSE_C128, k_precond, dim3(ew_blocks(n)), dim3(256), (double*)out, (const double*)r,
                      (const double*)hdiag_f64, (const double*)mask_f64, (long long)n, e, shift);
   return MPSE_OK;
@@ -194,6 +197,7 @@ int mpse_real_part(mpse_ctx* ctx, void* out_f64, const void* z_c128, int64_t n) 
   if (!ctx || (n && (!out_f64 || !z_c128))) return MPSE_ERR_ARG;
   MPSE_BIND(ctx);
   if (n <= 0) return MPSE_OK;
+  wsite_written(ctx, out_f64, size_t(n) * 8);
   hipLaunchKernelGGL(k_real_part, dim3(ew_blocks(n)), dim3(256), 0, ctx->stream, (double*)out_f64,
                      (const double*)z_c128, (long long)n);
   MPSE_HIP(ctx, hipGetLastError());

@@ -571,7 +571,12 @@ class Engine:
     def mpo_site_hint(self, dev, host):
         """Describe a real MPO site to the engine (``mpse_mpo_site_hint``): ``dev`` is the device copy of ``host``
         (wl, d, d, wr).  Large one-site matvecs on that site then take the folded plan.  The hint goes with the
-        buffer; the device copy must not be written to afterwards."""
+        buffer, and these entry points drop it when they write into the described range: ``mpse_memcpy_h2d``,
+        ``mpse_memcpy_d2d``, ``mpse_memcpy_2d``, ``mpse_memset_zero``, ``mpse_scal``, ``mpse_conj_inplace``,
+        ``mpse_axpy``, ``mpse_mul_real``, ``mpse_real_part``, ``mpse_cast_f64_to_c128``, ``mpse_davidson_precond``,
+        ``mpse_gather_cols``, ``mpse_gather_rows``, ``mpse_transpose_inner`` and the solution vectors of ``mpse_pcg``,
+        ``mpse_pcg_sum`` and ``mpse_pcg_batch``.  Any other writer (GEMM and contraction results, the factors of a
+        decomposition, the outputs of the other solvers) must not target a described buffer."""
         host = np.asarray(host)
         if host.ndim != 4 or np.iscomplexobj(host) or dev.is_complex or dev.offset != 0:
             return

@@ -1070,6 +1070,66 @@ def test_described_mpo_site_follows_in_place_writes(eng):
     assert _relerr(hop(cd).to_host().ravel(), orc.hop_apply(l, r, [w3], c).ravel()) < 1e-12
 
 
+def test_described_mpo_site_follows_every_element_writer(eng):
+    """Every element-level entry point that can write a real buffer drops the description of a site it writes into
+    (mpse_internal.h: wsite_written): for each writer the site is described, written through that entry point, and the
+    folded one-site product has to follow the written values, not the analysis of the described ones."""
+    rng = np.random.default_rng(34)
+    D, d = 256, 16
+    w = _holstein_like_site(rng, d)
+    l, r = _rand(rng, (D, w.shape[0], D), True), _rand(rng, (D, w.shape[3], D), True)
+    c = _rand(rng, (D, d, D), True)
+    hop = hop_expr(eng.asdevice(l), eng.asdevice(r), [w], c.shape)
+    cd = eng.asdevice(c)
+    site, n = hop.cmo[0], w.size
+    lib, ctx = eng.lib, eng.ctx
+    assert _relerr(hop(cd).to_host().ravel(), orc.hop_apply(l, r, [w], c).ravel()) < 1e-12
+
+    def mul_real():
+        m = np.ones(w.shape)
+        m[1, :, :, 1] = 0.0                              # one identity channel goes, another is halved
+        m[2, :, :, 2] = 0.5
+        M = eng.asdevice(m)
+        eng._check(lib.mpse_mul_real(ctx, site.code, site.ptr, M.ptr, n))
+        return w * m
+
+    def gather_rows():
+        src = eng.asdevice(w.reshape(w.shape[0], -1))
+        perm = np.array([2, 0, 4, 1, 3], dtype=np.int64)
+        eng._check(lib.mpse_gather_rows(ctx, site.code, site.ptr, src.ptr, src.shape[1],
+                                        perm.ctypes.data_as(C.POINTER(C.c_int64)), None, len(perm)))
+        return w[perm]
+
+    def transpose_inner():
+        a = rng.standard_normal((w.shape[0], d * w.shape[3], d))
+        A = eng.asdevice(a)
+        eng._check(lib.mpse_transpose_inner(ctx, site.code, site.ptr, A.ptr, *a.shape, 0))
+        return a.transpose(0, 2, 1).reshape(w.shape)
+
+    def real_part():
+        z = rng.standard_normal(w.shape) + 1j * rng.standard_normal(w.shape)
+        Z = eng.asdevice(z)
+        eng._check(lib.mpse_real_part(ctx, site.ptr, Z.ptr, n))
+        return z.real.copy()
+
+    def davidson_precond():
+        res, hd = rng.standard_normal(n), rng.uniform(1.0, 3.0, n)
+        R, H = eng.asdevice(res), eng.asdevice(hd)
+        eng._check(lib.mpse_davidson_precond(ctx, site.code, site.ptr, R.ptr, H.ptr, None, n, 0.37, 1e-4))
+        return (res / (hd - 0.37 + 1e-4)).reshape(w.shape)
+
+    errs = {}
+    for writer in (mul_real, gather_rows, transpose_inner, real_part, davidson_precond):
+        eng._check(lib.mpse_memcpy_h2d(ctx, site.ptr, w.ctypes.data, w.nbytes))
+        eng.mpo_site_hint(site, w)
+        expect = writer()
+        written = site.to_host()
+        assert np.allclose(written, expect, rtol=4e-16, atol=0.0), writer.__name__     # the writer itself did its work
+        errs[writer.__name__] = _relerr(hop(cd).to_host().ravel(), orc.hop_apply(l, r, [written], c).ravel())
+    print("hop(c) after a write into the described site, relative error:", {k: f"{v:.2e}" for k, v in errs.items()})
+    assert all(v < 1e-12 for v in errs.values()), errs
+
+
 @pytest.mark.parametrize("cplx", [False, True])
 def test_matrix_module_tensordot_and_paths(eng, cplx):
     """renormalizer_amd.mps.matrix (the module-level names of SURVEY 8(b)): tensordot over device tensors against numpy
