@@ -8,12 +8,16 @@
 // optimal path picks for D >> w, d (mps/hop_expr.py via mps/oe_contract_wrap.py:24-35) -
 // i.e. two large GEMMs around a small batched contraction with the MPO site tensor.
 // All index permutations are absorbed in operand strides; nothing is transposed in memory.
+//
+// One idiom: every planner declares its tensors as labelled views and states each product as one `contract` call
+// (see "Labelled views" below, which also says how to add a product); the strides of every index map are derived from
+// the declared layouts, never multiplied out by hand.  tests/test_plans_pin_host.py pins every plan.
 #pragma once
+#include <cassert>
 #include <cstdint>
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
-#include <string>
 #include <utility>
 #include <vector>
 
@@ -175,10 +179,151 @@ inline mpse_index i2(int64_t hi, int64_t lo, int64_t s_hi, int64_t s_lo) {
   return mpse_index{hi * lo, lo > 0 ? lo : 1, s_hi, s_lo};
 }
 
-inline void push(Plan& p, int a, int64_t ao, int dta, int conja, int b, int64_t bo, int dtb, int conjb, int c,
-                 int64_t co, mpse_index ma, mpse_index ka, mpse_index kb, mpse_index nb, mpse_index mc,
-                 mpse_index nc, int64_t batch = 1, int64_t sba = 0, int64_t sbb = 0, int64_t sbc = 0) {
-  p.steps.push_back(Step{a, b, c, ao, bo, co, dta, dtb, conja, conjb, ma, ka, kb, nb, mc, nc, batch, sba, sbb, sbc});
+// ---------------------------------------------------------------------------------------------------------------
+// Labelled views: the one idiom every planner below is written in.  A tensor is a View - buffer, dtype, element offset
+// and per dimension a one-letter label, an extent and a stride; a product is ONE `contract` call that names the labels
+// of its row, contracted and column index (outer -> inner) and derives every index map from the views.  No planner
+// multiplies out a stride: i1 / i2 are called by labels_index alone.  Nothing here allocates (heff_apply plans at every
+// Krylov iteration); the only heap traffic of a plan is p.steps.push_back.
+//   * a view is built from its row-major extents; `sub` narrows a dimension (a channel range around a unit channel, one
+//     plane of a stack of planes), `as` renames the dimensions by position (K[c, n] read as rows a of X[a, b, n]);
+//   * an index is the listed labels with extent-1 labels dropped and contiguous neighbours merged; at most two levels
+//     per operand - what is left over goes to `batch` (one level) or `loops` (one step per value);
+//   * `copy` is the strided copy (K_COPY) in the same terms.
+// To add a product: declare the views of its operands with the layouts they have in memory, give them shared labels,
+// call contract(p, A, B, C, m, k, n); set what is policy (skip_zero, beta, cin, is_wstep) on the step it returns; add
+// the planner's cases to tests/host_emu/plan_dump.cpp and its numbers to a host emulator test.
+constexpr int VIEW_MAXDIM = 8;
+struct View {
+  int buf = 0, dt = MPSE_F64;
+  int64_t off = 0;
+  int n = 0;
+  char lab[VIEW_MAXDIM] = {0};
+  int64_t ex[VIEW_MAXDIM] = {0}, st[VIEW_MAXDIM] = {0};
+  View() {}
+  View(int b, int d, std::initializer_list<std::pair<char, int64_t>> l) : buf(b), dt(d) {   // memory order, row major
+    assert(l.size() <= size_t(VIEW_MAXDIM));
+    for (auto& q : l) lab[n] = q.first, ex[n] = q.second, ++n;
+    int64_t s = 1;
+    for (int i = n; i-- > 0;) st[i] = s, s *= ex[i];
+  }
+  int find(char c) const {
+    for (int i = 0; i < n; ++i)
+      if (lab[i] == c) return i;
+    return -1;
+  }
+  int64_t ext(char c) const {      // -1 if the label is absent
+    const int i = find(c);
+    return i < 0 ? -1 : ex[i];
+  }
+  int64_t stride(char c) const {   // 0 if the label is absent
+    const int i = find(c);
+    return i < 0 ? 0 : st[i];
+  }
+  View sub(char c, int64_t first, int64_t count) const {   // values [first, first + count) of one dimension
+    View v = *this;
+    const int i = find(c);
+    assert(i >= 0);
+    v.off += first * st[i], v.ex[i] = count;
+    return v;
+  }
+  View as(const char* labels) const {   // the same memory, dimensions renamed by position
+    View v = *this;
+    for (int i = 0; i < n && labels[i]; ++i) v.lab[i] = labels[i];
+    return v;
+  }
+};
+
+inline bool labels_index(const View& v, const char* labels, mpse_index* out) {
+  int64_t le[2], ls[2], total = 1;   // (ext, stride), outer -> inner, merged
+  int nl = 0;
+  for (const char* c = labels; *c; ++c) {
+    const int i = v.find(*c);
+    if (i < 0) return false;
+    const int64_t e = v.ex[i], st = v.st[i];
+    total *= e;
+    if (e == 1) continue;
+    if (nl > 0 && ls[nl - 1] == e * st) {
+      le[nl - 1] *= e, ls[nl - 1] = st;
+    } else {
+      if (nl == 2) return false;
+      le[nl] = e, ls[nl] = st, ++nl;
+    }
+  }
+  *out = nl == 0 ? i1(total, 1) : nl == 1 ? i1(le[0], ls[0]) : i2(le[0], le[1], ls[0], ls[1]);
+  return true;
+}
+
+// the six index maps of C[m, n] = sum_k A[m, k] B[k, n]
+inline bool product_maps(Step& s, const View& A, const View& B, const View& C, const char* m, const char* k, const char* n) {
+  return labels_index(A, m, &s.ma) && labels_index(A, k, &s.ka) && labels_index(B, k, &s.kb) && labels_index(B, n, &s.nb) &&
+         labels_index(C, m, &s.mc) && labels_index(C, n, &s.nc);
+}
+
+// C[batch][m, n] = sum_k A[batch][m, k] B[batch][k, n] for every value of the `loops` labels.  Returns the last step it
+// pushed (valid until the next push), nullptr when it pushed none.
+inline Step* contract(Plan& p, const View& A, const View& B, const View& C, const char* m, const char* k, const char* n,
+                      const char* batch = "", const char* loops = "", int conja = 0) {
+  if (p.error) return nullptr;
+  Step s{};
+  if (!product_maps(s, A, B, C, m, k, n)) {
+    p.error = "plan: an index of a stacked-MPO contraction needs more than two stride levels";
+    return nullptr;
+  }
+  s.a = A.buf, s.b = B.buf, s.c = C.buf, s.dta = A.dt, s.dtb = B.dt, s.conja = conja, s.batch = 1;
+  if (batch[0]) {
+    // a batch label may be absent from A or B (stride 0) but must be a single level where present
+    auto one = [&](const View& v, int64_t* st) {
+      int present = 0, all = 0;
+      for (const char* c = batch; *c; ++c) ++all, present += v.find(*c) >= 0 ? 1 : 0;
+      if (present == 0) {
+        *st = 0;
+        return true;
+      }
+      mpse_index ix;
+      if (present != all || !labels_index(v, batch, &ix) || (ix.lo_ext < ix.ext && ix.ext > 1)) return false;
+      *st = ix.s_lo;
+      return true;
+    };
+    if (!one(A, &s.sba) || !one(B, &s.sbb) || !one(C, &s.sbc)) {
+      p.error = "plan: batch labels of a stacked-MPO contraction do not form one level";
+      return nullptr;
+    }
+    for (const char* c = batch; *c; ++c) s.batch *= C.ext(*c);
+  }
+  int64_t ext[VIEW_MAXDIM], cnt[VIEW_MAXDIM] = {0}, nloop = 1;
+  int nl = 0;
+  for (const char* c = loops; *c && nl < VIEW_MAXDIM; ++c, ++nl) {
+    ext[nl] = C.ext(*c) >= 0 ? C.ext(*c) : (A.ext(*c) >= 0 ? A.ext(*c) : B.ext(*c));
+    nloop *= ext[nl];
+  }
+  for (int64_t it = 0; it < nloop; ++it) {
+    s.a_off = A.off, s.b_off = B.off, s.c_off = C.off;
+    for (int l = 0; l < nl; ++l) {
+      s.a_off += cnt[l] * A.stride(loops[l]);
+      s.b_off += cnt[l] * B.stride(loops[l]);
+      s.c_off += cnt[l] * C.stride(loops[l]);
+    }
+    p.steps.push_back(s);
+    for (int l = nl; l-- > 0;) {
+      if (++cnt[l] < ext[l]) break;
+      cnt[l] = 0;
+    }
+  }
+  return nloop > 0 ? &p.steps.back() : nullptr;
+}
+
+// dst[rows, cols] = src[rows, cols] (K_COPY), both sides through the same labels
+inline void copy(Plan& p, const View& src, const View& dst, const char* rows, const char* cols) {
+  mpse_index mi, ni, mo, no;
+  if (!labels_index(src, rows, &mi) || !labels_index(src, cols, &ni) || !labels_index(dst, rows, &mo) ||
+      !labels_index(dst, cols, &no)) {
+    p.error = "plan: an index of a copy needs more than two stride levels";
+    return;
+  }
+  Step s{src.buf, src.buf, dst.buf, src.off, 0, dst.off, src.dt, src.dt, 0, 0, mi, ni, ni, no, mo, no, 1, 0, 0, 0};
+  s.kind = K_COPY;
+  p.steps.push_back(s);
 }
 
 // Skipping a unit channel trades a (m x k x n) slice of a GEMM for a strided copy kernel: below ~1e8 multiply-adds
@@ -200,12 +345,11 @@ inline int skip_pays(int64_t m, int64_t k, int64_t n, int which = 3) {
   return m * k * n >= (int64_t(1) << 28) ? which : 0;
 }
 
-inline void push_copy(Plan& p, int src, int64_t so, int dst, int64_t dof, int dtype, mpse_index mi, mpse_index ni,
-                      mpse_index mo, mpse_index no) {
-  Step s{src, src, dst, so, 0, dof, dtype, dtype, 0, 0, mi, ni, ni, no, mo, no, 1, 0, 0, 0};
-  s.kind = K_COPY;
-  p.steps.push_back(s);
-}
+// The channels of an environment around its unit channel u (-1: none): at most two ranges [lo, hi)
+struct ChannelRanges {
+  int64_t lo[2], hi[2];
+  ChannelRanges(int64_t u, int64_t w) : lo{0, u + 1}, hi{u >= 0 ? u : w, u >= 0 ? w : 0} {}
+};
 
 // X[a,b,n] = sum_c E[a,b,c] K[c,n] for an environment E (rows, w, cols) and a matrix K (cols, N).
 // `unit` (1-based, 0 = none) names an MPO-bond channel b along which E[:, b, :] is the identity matrix (what a
@@ -217,23 +361,16 @@ inline void push_copy(Plan& p, int src, int64_t so, int dst, int64_t dof, int dt
 inline void push_env_times(Plan& p, int ebuf, int e_dtype, int kbuf, int k_dtype, int xbuf, int64_t rows, int64_t w,
                            int64_t cols, int64_t N, int64_t unit, bool b_outer) {
   const int64_t u = (unit >= 1 && unit <= w && rows == cols && unit_pays(rows, cols, N)) ? unit - 1 : -1;
-  if (u >= 0) {
-    if (b_outer)
-      push_copy(p, kbuf, 0, xbuf, u * rows * N, k_dtype, i1(rows, N), i1(N, 1), i1(rows, N), i1(N, 1));
-    else
-      push_copy(p, kbuf, 0, xbuf, u * N, k_dtype, i1(rows, N), i1(N, 1), i1(rows, w * N), i1(N, 1));
-  }
-  const int64_t lo[2] = {0, u + 1}, hi[2] = {u >= 0 ? u : w, u >= 0 ? w : 0};
+  const View E(ebuf, e_dtype, {{'a', rows}, {'b', w}, {'c', cols}}), K(kbuf, k_dtype, {{'c', cols}, {'n', N}});
+  const View X = b_outer ? View(xbuf, k_dtype, {{'b', w}, {'a', rows}, {'n', N}})
+                         : View(xbuf, k_dtype, {{'a', rows}, {'b', w}, {'n', N}});
+  if (u >= 0) copy(p, K.as("an"), X.sub('b', u, 1), "a", "n");
+  const ChannelRanges cr(u, w);
   for (int r = 0; r < 2; ++r) {
-    const int64_t b0 = lo[r], nb = hi[r] - lo[r];
+    const int64_t b0 = cr.lo[r], nb = cr.hi[r] - cr.lo[r];
     if (nb <= 0) continue;
-    if (b_outer)   // GEMM row i = (b - b0) * rows + a
-      push(p, ebuf, b0 * cols, e_dtype, 0, kbuf, 0, k_dtype, 0, xbuf, b0 * rows * N, i2(nb, rows, cols, w * cols),
-           i1(cols, 1), i1(cols, N), i1(N, 1), i1(nb * rows, N), i1(N, 1));
-    else           // GEMM row i = a * nb + (b - b0)
-      push(p, ebuf, b0 * cols, e_dtype, 0, kbuf, 0, k_dtype, 0, xbuf, b0 * N, i2(rows, nb, w * cols, cols),
-           i1(cols, 1), i1(cols, N), i1(N, 1), i2(rows, nb, w * N, N), i1(N, 1));
-    p.steps.back().skip_zero = skip_pays(rows * nb, cols, N);
+    if (Step* s = contract(p, E.sub('b', b0, nb), K, X.sub('b', b0, nb), b_outer ? "ba" : "ab", "c", "n"))
+      s->skip_zero = skip_pays(rows * nb, cols, N);
   }
 }
 
@@ -242,34 +379,32 @@ inline void push_env_times(Plan& p, int ebuf, int e_dtype, int kbuf, int k_dtype
 inline void push_times_env(Plan& p, int tbuf, int t_dtype, int ebuf, int e_dtype, int obuf, int64_t M1, int64_t anc,
                            int64_t w, int64_t Dk, int64_t Dout, int64_t unit) {
   const int64_t u = (unit >= 1 && unit <= w && Dout == Dk && unit_pays(M1 * anc, Dk, Dout)) ? unit - 1 : -1;
+  const View T(tbuf, t_dtype, {{'m', M1}, {'f', w}, {'g', anc}, {'k', Dk}}), E(ebuf, e_dtype, {{'l', Dout}, {'f', w}, {'k', Dk}});
+  const View O(obuf, t_dtype, {{'m', M1}, {'g', anc}, {'l', Dout}});
   double beta = 0.0;
   // The unit channel contributes T[m, u, g, l] itself: the first product reads it as its beta term straight from T
   // (no copy into `out` first), unless there is no product at all (w == 1) or MPSE_BETA_SOURCE=0.
   const bool direct = u >= 0 && w > 1 && beta_source_on();
+  const View Tu = u >= 0 ? T.sub('f', u, 1).as("mfgl") : T;
   if (u >= 0 && !direct) {
-    push_copy(p, tbuf, u * anc * Dk, obuf, 0, t_dtype, i2(M1, anc, w * anc * Dk, Dk), i1(Dk, 1), i1(M1 * anc, Dout),
-              i1(Dout, 1));
+    copy(p, Tu, O, "mg", "l");
     beta = 1.0;
   }
   bool first = true;
-  const int64_t lo[2] = {0, u + 1}, hi[2] = {u >= 0 ? u : w, u >= 0 ? w : 0};
+  const ChannelRanges cr(u, w);
   for (int r = 0; r < 2; ++r) {
-    const int64_t f0 = lo[r], nf = hi[r] - lo[r];
+    const int64_t f0 = cr.lo[r], nf = cr.hi[r] - cr.lo[r];
     if (nf <= 0) continue;
-    push(p, tbuf, f0 * anc * Dk, t_dtype, 0, ebuf, f0 * Dk, e_dtype, 0, obuf, 0,
-         /*A: m=(m1 | g)*/ i2(M1, anc, w * anc * Dk, Dk), /*k=(f | k)*/ i2(nf, Dk, anc * Dk, 1),
-         /*B=E: k=(f,k), n=l*/ i1(nf * Dk, 1), i1(Dout, w * Dk), i1(M1 * anc, Dout), i1(Dout, 1));
+    Step* s = contract(p, T.sub('f', f0, nf), E.sub('f', f0, nf), O, "mg", "fk", "l");
+    if (!s) return;
     if (direct && first) {
-      Step& s = p.steps.back();
-      s.cin = tbuf;
-      s.cin_off = u * anc * Dk;
-      s.mcin = i2(M1, anc, w * anc * Dk, Dk);
-      s.ncin = i1(Dk, 1);
+      s->cin = Tu.buf, s->cin_off = Tu.off;
+      labels_index(Tu, "mg", &s->mcin), labels_index(Tu, "l", &s->ncin);
       beta = 1.0;
     }
     first = false;
-    p.steps.back().beta = beta;
-    p.steps.back().skip_zero = skip_pays(M1 * anc, nf * Dk, Dout, 2);   // A = the big intermediate: environment side only
+    s->beta = beta;
+    s->skip_zero = skip_pays(M1 * anc, nf * Dk, Dout, 2);   // A = the big intermediate: environment side only
     beta = 1.0;
   }
 }
@@ -278,14 +413,14 @@ inline void push_times_env(Plan& p, int tbuf, int t_dtype, int ebuf, int e_dtype
 // T_in in the channel-outer layout written by push_env_times(b_outer = true))
 inline void push_w(Plan& p, int wbuf, int w_dtype, int tin, int tout, int t_dtype, int64_t na, int64_t wl, int64_t d,
                    int64_t wr, int64_t N) {
-  push(p, wbuf, 0, w_dtype, 0, tin, 0, t_dtype, 0, tout, 0,
-       /*A=W: i=(d | f), k=(b | e)*/ i2(d, wr, d * wr, 1), i2(wl, d, d * d * wr, wr),
-       /*B=T_in[:, a]: k=(b | e), n*/ i2(wl, d, na * d * N, N), i1(N, 1),
-       /*C=T_out[a]: (d,f), n*/ i1(d * wr, N), i1(N, 1), na, 0, d * N, d * wr * N);
-  Step& s = p.steps.back();
-  s.is_wstep = true;
-  s.w_Da = na, s.w_wl = wl, s.w_d = d, s.w_wr = wr, s.w_N = N;
+  const View W(wbuf, w_dtype, {{'b', wl}, {'y', d}, {'e', d}, {'f', wr}});
+  const View Tin(tin, t_dtype, {{'b', wl}, {'a', na}, {'e', d}, {'n', N}}), Tout(tout, t_dtype, {{'a', na}, {'y', d}, {'f', wr}, {'n', N}});
+  if (Step* s = contract(p, W, Tin, Tout, "yf", "be", "n", "a")) {
+    s->is_wstep = true;
+    s->w_Da = na, s->w_wl = wl, s->w_d = d, s->w_wr = wr, s->w_N = N;
+  }
 }
+
 
 // The marks of a plan (Step::elementwise_w .. completes); every planner returns its plan through this.
 //   * elementwise: the MPO step of a small real site (wl d <= 16 inputs, d wr <= 16 outputs) over whole tensors;
@@ -393,12 +528,11 @@ inline Plan plan_heff(int dtype, const mpse_heff& h, const WSiteInfo* wi = nullp
     push_env_times(p, B_L, h.l_dtype, B_C, dtype, B_T1, Dlb, wl, Dl, N, h.l_unit, true);
     // T2[a,d,f,(m,h,n,k)]
     push_w(p, B_W0, h.w_dtype, B_T1, B_T2, dtype, Dlb, wl, d0, wm, n1);
-    // T3[(a,d),m,g,j,(n,k)] = sum_{f,h} W1[f,g,h,j] T2[(a,d),f,m,h,(n,k)]   batch (a,d); one step per m
-    for (int64_t m = 0; m < a0; ++m)
-      push(p, B_W1, 0, h.w_dtype, 0, B_T2, m * d1 * n2, dtype, 0, B_T3, m * d1 * wr * n2,
-           i2(d1, wr, d1 * wr, 1), i2(wm, d1, d1 * d1 * wr, wr),
-           /*B: k=(f | h)*/ i2(wm, d1, a0 * d1 * n2, n2), i1(n2, 1),
-           /*C: (g,j),(n,k)*/ i1(d1 * wr, n2), i1(n2, 1), Dlb * d0, 0, wm * a0 * d1 * n2, a0 * d1 * wr * n2);
+    // T3[A,m,g,j,N] = sum_{f,h} W1[f,g,h,j] T2[A,f,m,h,N]   batch A = (a,d), N = (n,k); one step per m
+    const View W1(B_W1, h.w_dtype, {{'f', wm}, {'g', d1}, {'h', d1}, {'j', wr}});
+    const View T2(B_T2, dtype, {{'A', Dlb * d0}, {'f', wm}, {'m', a0}, {'h', d1}, {'N', n2}});
+    const View T3(B_T3, dtype, {{'A', Dlb * d0}, {'m', a0}, {'g', d1}, {'j', wr}, {'N', n2}});
+    contract(p, W1, T2, T3, "gj", "fh", "N", "A", "m");
     // out[(a,d,m,g,n),l] = sum_{j,k} T3[a,d,m,g,j,n,k] R[l,j,k]
     push_times_env(p, B_T3, dtype, B_R, h.r_dtype, B_OUT, Dlb * d0 * a0 * d1, a1, wr, Dr, Drb, h.r_unit);
     return marked(std::move(p));
@@ -444,35 +578,73 @@ inline int64_t& fold_align() {   // bra-bond multiple the device needs (a 64-row
   return v;
 }
 
-// Folded one-site matvec (see above); p.error is set when the site does not qualify and the caller takes plan_heff.
-inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, bool two_results = false,
-                            bool mix_epilogue = false) {
-  Plan p;
+// One term of the elementwise pass: block `k` of the site applied to src[a, x, k], with the columns e that the rows of
+// each chunk of WM_CHUNK rows need
+inline WMixTerm wmix_term(const WSiteInfo& wi, const WBlock& k, const View& src) {
+  WMixTerm t;
+  t.b = k.b, t.f = k.f, t.ident = k.ident;
+  t.src = src.buf, t.src_off = src.off, t.s_a = src.stride('a'), t.s_d = src.stride('x');
+  const int64_t d = wi.d, nchunk = (d + WM_CHUNK - 1) / WM_CHUNK;
+  for (int64_t c = 0; c < nchunk; ++c) {
+    int64_t lo = d, hi = 0;
+    for (int64_t x = c * WM_CHUNK; x < std::min<int64_t>(d, (c + 1) * WM_CHUNK); ++x)
+      for (int64_t e = 0; e < d; ++e)
+        if (wi.w[((k.b * d + x) * d + e) * wi.wr + k.f] != 0.0) lo = std::min(lo, e), hi = std::max(hi, e + 1);
+    t.e_lo[c] = (unsigned char)(hi > lo ? lo : 0), t.e_hi[c] = (unsigned char)(hi > lo ? hi : 0);
+  }
+  return t;
+}
+inline bool wmix_fits_lds(int64_t nslot, int64_t d) { return nslot * d * d <= 8192; }   // 64 KB of LDS for the dense blocks
+
+// Folded one-site matvec (see above), analysis: what becomes of every channel of the site - no step yet.  `error` is
+// set when the site does not qualify (the caller then takes the three-step chain of plan_heff).
+struct FoldAnalysis {
+  const char* error = nullptr;
+  const WSiteInfo* wi = nullptr;
+  int64_t lu = -1, ru = -1;                                   // unit channels of L / R (0-based, -1: none)
+  std::vector<std::vector<const WBlock*>> by_f, by_b;        // the blocks per channel of R / of L
+  // where the product of channel b goes: straight into the plane of its channel f (direct_f), or into a temporary
+  // (tmp_of, ntmp of them); planes: storage for every channel f != ru that is not the centre tensor itself (plane_of,
+  // nplanes of them; alias: it is); mixed: the planes the elementwise pass forms, in its order
+  std::vector<int64_t> direct_f, tmp_of, plane_of, mixed;
+  std::vector<char> alias, present;
+  int64_t ntmp = 0, nplanes = 0;
+  // epilogue mix: the plane f = ru as diagonals (block, delta) applied by the first product with R; epi_direct_b: the
+  // channel whose product is written straight into `out` and read back as a term
+  bool epi = false, split2 = false, out_init = false;         // out_init: `out` holds a plane before the products with R
+  int64_t epi_direct_b = -1;
+  std::vector<std::pair<const WBlock*, int>> epi_diag;
+  // the operands; T1 / T2 are stacks of planes [a, x, k] like the centre, and so is `out` where it serves as one
+  View L, C, R, T1, T2, OUT;
+  View dest(int64_t f) const { return f == ru ? OUT.as("axk") : T2.sub('p', plane_of[f], 1); }
+  View src(int64_t b) const { return b == lu ? C.as("axk") : b == epi_direct_b ? OUT.as("axk") : T1.sub('t', tmp_of[b], 1); }
+};
+
+inline FoldAnalysis fold_analyse(int dtype, const mpse_heff& h, const WSiteInfo& wi, bool two_results, bool mix_epilogue) {
+  FoldAnalysis a;
+  a.wi = &wi;
   const mpse_dims& s = h.dims;
   const int64_t Dl = s.Dl_ket, Dr = s.Dr_ket, wl = s.wl, wr = s.wr, d = s.d0;
   const int64_t Dlb = s.Dl_bra > 0 ? s.Dl_bra : Dl, Drb = s.Dr_bra > 0 ? s.Dr_bra : Dr;
   if (h.nsite != 1 || s.danc > 1 || h.w_dtype != MPSE_F64 || wi.wl != wl || wi.d != d || wi.wr != wr ||
       ((dtype != MPSE_C128 || h.r_dtype != MPSE_C128) && fold_align() == 64)) {   // (the grouped kernel is built for a
                                                     // complex second operand: centre and R; host emulation: any)
-    p.error = "fold: not a plain complex one-site centre with a real MPO site";
-    return p;
+    a.error = "fold: not a plain complex one-site centre with a real MPO site";
+    return a;
   }
   if (Dlb % fold_align() != 0 || Dl % std::min<int64_t>(16, fold_align()) != 0 ||
       Dr % std::min<int64_t>(16, fold_align()) != 0 || d > WM_CHUNK * WM_MAXCHUNKS || Dl * d * Dr * Dlb < fold_min()) {
-    p.error = "fold: centre too small or not tile aligned";
-    return p;
+    a.error = "fold: centre too small or not tile aligned";
+    return a;
   }
-  const int64_t lu = (h.l_unit >= 1 && h.l_unit <= wl && Dlb == Dl) ? h.l_unit - 1 : -1;
-  const int64_t ru = (h.r_unit >= 1 && h.r_unit <= wr && Drb == Dr) ? h.r_unit - 1 : -1;
-  const int64_t N = d * Dr, plane = Dlb * N;
-  std::vector<std::vector<const WBlock*>> by_f(wr), by_b(wl);
+  const int64_t lu = a.lu = (h.l_unit >= 1 && h.l_unit <= wl && Dlb == Dl) ? h.l_unit - 1 : -1;
+  const int64_t ru = a.ru = (h.r_unit >= 1 && h.r_unit <= wr && Drb == Dr) ? h.r_unit - 1 : -1;
+  auto &by_f = a.by_f, &by_b = a.by_b;
+  by_f.resize(wr), by_b.resize(wl);
   for (const WBlock& k : wi.blocks) by_f[k.f].push_back(&k), by_b[k.b].push_back(&k);
   // Epilogue mix: the plane f = ru, where it is a sum of narrow bands and a product with R follows to carry it.  One
   // identity block whose channel b feeds nothing else is written straight into `out` by the product with L (nothing
   // else writes `out` before the products with R) and read back as a term of its own.
-  bool epi = false;
-  int64_t epi_direct_b = -1;
-  std::vector<std::pair<const WBlock*, int>> epi_diag;    // (block, delta)
   if (mix_epilogue && ru >= 0 && !by_f[ru].empty() && d > 0 && 64 % d == 0) {
     bool sum = true, follows = false;
     {
@@ -484,7 +656,7 @@ inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, 
     bool narrow = true;
     for (const WBlock* k : by_f[ru]) {
       if (k->ident) {
-        epi_diag.push_back({k, 0});
+        a.epi_diag.push_back({k, 0});
         continue;
       }
       bool diag[2 * EPI_MAXBAND + 1] = {false};
@@ -497,197 +669,188 @@ inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, 
               diag[e - x + EPI_MAXBAND] = true;
           }
       for (int q = 0; q <= 2 * EPI_MAXBAND; ++q)
-        if (diag[q]) epi_diag.push_back({k, q - EPI_MAXBAND});
+        if (diag[q]) a.epi_diag.push_back({k, q - EPI_MAXBAND});
     }
-    epi = sum && follows && narrow && (int)epi_diag.size() <= EPI_MAXTERM;
-    if (epi)
+    a.epi = sum && follows && narrow && (int)a.epi_diag.size() <= EPI_MAXTERM;
+    if (a.epi)
       for (const WBlock* k : by_f[ru])
         if (k->ident && k->b != lu && by_b[k->b].size() == 1) {
-          epi_direct_b = k->b;
+          a.epi_direct_b = k->b;
           break;
         }
   }
-  // where the product of channel b goes: straight into the plane of its channel f, or into a temporary
-  std::vector<int64_t> direct_f(wl, -1), tmp_of(wl, -1);
-  int64_t ntmp = 0, ngemm = 0;
+  a.direct_f.assign(wl, -1), a.tmp_of.assign(wl, -1);
+  int64_t ngemm = 0;
   for (int64_t b = 0; b < wl; ++b) {
     if (b == lu || by_b[b].empty()) continue;
     ++ngemm;
-    if (b == epi_direct_b)
-      direct_f[b] = ru;
+    if (b == a.epi_direct_b)
+      a.direct_f[b] = ru;
     else if (by_b[b].size() == 1 && by_b[b][0]->ident && by_f[by_b[b][0]->f].size() == 1)
-      direct_f[b] = by_b[b][0]->f;
+      a.direct_f[b] = by_b[b][0]->f;
     else
-      tmp_of[b] = ntmp++;
+      a.tmp_of[b] = a.ntmp++;
   }
   if (ngemm > G_MAXGRP) {
-    p.error = "fold: too many channels";
-    return p;
+    a.error = "fold: too many channels";
+    return a;
   }
-  // planes: storage for every channel f != ru that is not the centre tensor itself
-  std::vector<int64_t> plane_of(wr, -1);
-  std::vector<char> alias(wr, 0), present(wr, 0);
-  int64_t nplanes = 0;
+  a.plane_of.assign(wr, -1), a.alias.assign(wr, 0), a.present.assign(wr, 0);
+  int64_t ncseg = 0;      // channels the products with R run over
   for (int64_t f = 0; f < wr; ++f) {
     if (by_f[f].empty()) continue;
-    present[f] = 1;
+    a.present[f] = 1;
     if (f == ru) continue;
+    ++ncseg;
     if (by_f[f].size() == 1 && by_f[f][0]->b == lu && by_f[f][0]->ident)
-      alias[f] = 1;
+      a.alias[f] = 1;
     else
-      plane_of[f] = nplanes++;
+      a.plane_of[f] = a.nplanes++;
   }
   // The products with R as halved tiles (split2) when the caller takes the result in two parts, they have at most one
   // tile per compute unit and fit one launch.
-  int64_t ncseg = 0;
-  for (int64_t f = 0; f < wr; ++f)
-    if (present[f] && f != ru) ++ncseg;
   const int64_t ctiles = ((Dlb * d + 63) / 64) * ((Drb + 63) / 64);
-  const bool split2 = two_results && fold_split2() && ncseg >= 1 && ncseg <= G_MAXSEG && ctiles <= fold_cus() && ncseg * ((Dr + 15) / 16) >= fold_split2_min_kt() &&
-                      (Dlb * d) % 64 == 0 && Drb == Dr && dtype == MPSE_C128;
-  auto dest = [&](int64_t f, int* buf, int64_t* off) {
-    if (f == ru)
-      *buf = B_OUT, *off = 0;
-    else
-      *buf = B_T2, *off = plane_of[f] * plane;
-  };
-  // A: all products L[:, b, :] . C in one grouped launch
+  a.split2 = two_results && fold_split2() && ncseg >= 1 && ncseg <= G_MAXSEG && ctiles <= fold_cus() &&
+             ncseg * ((Dr + 15) / 16) >= fold_split2_min_kt() && (Dlb * d) % 64 == 0 && Drb == Dr && dtype == MPSE_C128;
+  // the planes that are sums of blocks: the elementwise pass
+  int64_t nslot = 0;
+  for (int64_t f = 0; f < wr; ++f) {
+    if (!a.present[f] || a.alias[f]) continue;
+    if (a.epi && f == ru) continue;        // formed by the first product with R
+    bool is_direct = false;
+    for (const WBlock* k : by_f[f])
+      if (k->b != lu && a.direct_f[k->b] == f) is_direct = true;
+    if (is_direct) continue;
+    if ((int)a.mixed.size() >= WM_MAXDST || (int)by_f[f].size() > WM_MAXTERM) {
+      a.error = "fold: too many blocks per channel";
+      return a;
+    }
+    a.mixed.push_back(f);
+    for (const WBlock* k : by_f[f]) nslot += k->ident ? 0 : 1;
+  }
+  if (!wmix_fits_lds(nslot, d)) {
+    a.error = "fold: blocks too large for the elementwise pass";
+    return a;
+  }
+  a.out_init = ru >= 0 && a.present[ru];
+  if (ncseg == 0 && !a.out_init) {
+    a.error = "fold: the MPO site is zero";
+    return a;
+  }
+  a.L = View(B_L, h.l_dtype, {{'a', Dlb}, {'b', wl}, {'c', Dl}}), a.R = View(B_R, h.r_dtype, {{'l', Drb}, {'f', wr}, {'k', Dr}});
+  a.C = View(B_C, dtype, {{'c', Dl}, {'x', d}, {'k', Dr}}), a.OUT = View(B_OUT, dtype, {{'a', Dlb}, {'x', d}, {'l', Drb}});
+  a.T1 = View(B_T1, dtype, {{'t', a.ntmp}, {'a', Dlb}, {'x', d}, {'k', Dr}});
+  a.T2 = View(B_T2, dtype, {{'p', a.nplanes}, {'a', Dlb}, {'x', d}, {'k', Dr}});
+  return a;
+}
+
+// L products: all L[:, b, :] . C in one grouped launch, each into its plane or its temporary
+inline void fold_emit_l(Plan& p, const FoldAnalysis& a) {
   Step ga{};
   ga.kind = K_GGEMM;
-  ga.dta = h.l_dtype, ga.dtb = dtype;
-  ga.ma = i1(Dlb, wl * Dl), ga.ka = i1(Dl, 1), ga.kb = i1(Dl, N), ga.nb = i1(N, 1), ga.mc = i1(Dlb, N), ga.nc = i1(N, 1);
+  ga.dta = a.L.dt, ga.dtb = a.C.dt;
+  product_maps(ga, a.L, a.C, a.T1, "a", "c", "xk");
   ga.batch = 1;
   ga.scan_a.on = true;        // L as (channel | bra bond) rows: every 64-row tile belongs to one channel
-  ga.scan_a.buf = B_L, ga.scan_a.dt = h.l_dtype, ga.scan_a.off = 0;
-  ga.scan_a.r = i2(wl, Dlb, Dl, wl * Dl), ga.scan_a.k = i1(Dl, 1);
-  for (int64_t b = 0; b < wl; ++b) {
-    if (direct_f[b] < 0 && tmp_of[b] < 0) continue;
+  ga.scan_a.buf = a.L.buf, ga.scan_a.dt = a.L.dt, ga.scan_a.off = a.L.off;
+  labels_index(a.L, "ba", &ga.scan_a.r), labels_index(a.L, "c", &ga.scan_a.k);
+  for (int64_t b = 0; b < (int64_t)a.tmp_of.size(); ++b) {
+    if (a.direct_f[b] < 0 && a.tmp_of[b] < 0) continue;
+    const View Lb = a.L.sub('b', b, 1), dst = a.direct_f[b] >= 0 ? a.dest(a.direct_f[b]) : a.T1.sub('t', a.tmp_of[b], 1);
     GGroupPlan g;
     g.nseg = 1;
-    g.seg[0].abuf = B_L, g.seg[0].a_off = b * Dl, g.seg[0].am_row0 = b * (Dlb / 64);
-    g.seg[0].bbuf = B_C, g.seg[0].b_off = 0, g.seg[0].bm_kind = BM_CENTRE;
-    if (direct_f[b] >= 0)
-      dest(direct_f[b], &g.cbuf, &g.c_off);
-    else
-      g.cbuf = B_T1, g.c_off = tmp_of[b] * plane;
+    g.seg[0].abuf = Lb.buf, g.seg[0].a_off = Lb.off, g.seg[0].am_row0 = b * (a.L.ext('a') / 64);
+    g.seg[0].bbuf = a.C.buf, g.seg[0].b_off = a.C.off, g.seg[0].bm_kind = BM_CENTRE;
+    g.cbuf = dst.buf, g.c_off = dst.off;
     ga.groups.push_back(g);
   }
-  // W: the planes that are sums of blocks
+  if (!ga.groups.empty()) p.steps.push_back(ga);
+}
+
+// elementwise mix: the planes that are sums of blocks
+inline void fold_emit_mix(Plan& p, const FoldAnalysis& a) {
   Step mix{};
   mix.kind = K_WMIX;
   mix.b = B_W0;
-  mix.dta = dtype, mix.dtb = h.w_dtype;
-  mix.wp_Da = Dlb, mix.wp_d = d, mix.wp_Dk = Dr, mix.wp_wr = wr;
-  const int64_t nchunk = (d + WM_CHUNK - 1) / WM_CHUNK;
-  for (int64_t f = 0; f < wr; ++f) {
-    if (!present[f] || alias[f]) continue;
-    if (epi && f == ru) continue;        // formed by the first product with R
-    bool is_direct = false;
-    for (const WBlock* k : by_f[f])
-      if (k->b != lu && direct_f[k->b] == f) is_direct = true;
-    if (is_direct) continue;
-    if ((int)mix.mix.size() >= WM_MAXDST || (int)by_f[f].size() > WM_MAXTERM) {
-      p.error = "fold: too many blocks per channel";
-      return p;
-    }
+  mix.dta = a.C.dt, mix.dtb = MPSE_F64;   // (a real MPO site: fold_analyse refuses any other)
+  mix.wp_Da = a.L.ext('a'), mix.wp_d = a.C.ext('x'), mix.wp_Dk = a.C.ext('k'), mix.wp_wr = a.R.ext('f');
+  for (int64_t f : a.mixed) {
+    const View dst = a.dest(f);
     WMixDst q;
-    dest(f, &q.dst, &q.dst_off);
-    q.s_a = N, q.s_d = Dr;
-    for (const WBlock* k : by_f[f]) {
-      WMixTerm& t = q.term[q.nterm++];
-      t.b = k->b, t.f = k->f, t.ident = k->ident;
-      if (k->b == lu)
-        t.src = B_C, t.src_off = 0;
-      else
-        t.src = B_T1, t.src_off = tmp_of[k->b] * plane;
-      t.s_a = N, t.s_d = Dr;
-      for (int64_t c = 0; c < nchunk; ++c) {
-        int64_t lo = d, hi = 0;
-        for (int64_t x = c * WM_CHUNK; x < std::min<int64_t>(d, (c + 1) * WM_CHUNK); ++x)
-          for (int64_t e = 0; e < d; ++e)
-            if (wi.w[((k->b * d + x) * d + e) * wr + k->f] != 0.0) lo = std::min(lo, e), hi = std::max(hi, e + 1);
-        t.e_lo[c] = (unsigned char)(hi > lo ? lo : 0), t.e_hi[c] = (unsigned char)(hi > lo ? hi : 0);
-      }
-    }
+    q.dst = dst.buf, q.dst_off = dst.off, q.s_a = dst.stride('a'), q.s_d = dst.stride('x');
+    for (const WBlock* k : a.by_f[f]) q.term[q.nterm++] = wmix_term(*a.wi, *k, a.src(k->b));
     mix.mix.push_back(q);
   }
-  {
-    int64_t nslot = 0;
-    for (const WMixDst& q : mix.mix)
-      for (int t = 0; t < q.nterm; ++t) nslot += q.term[t].ident ? 0 : 1;
-    if (nslot * d * d > 8192) {          // 64 KB of LDS for the dense blocks
-      p.error = "fold: blocks too large for the elementwise pass";
-      return p;
-    }
-  }
-  // C: out (+)= sum_{f != ru} P_f . R[:, f, :]^T, one group, at most G_MAXSEG channels per launch
+  if (!mix.mix.empty()) p.steps.push_back(mix);
+}
+
+// R products: out (+)= sum_{f != ru} P_f . R[:, f, :]^T, one group, at most G_MAXSEG channels per launch
+inline void fold_emit_r(Plan& p, const FoldAnalysis& a) {
   Step gc{};
   gc.kind = K_GGEMM;
-  gc.dta = dtype, gc.dtb = h.r_dtype;
-  gc.ma = i1(Dlb * d, Dr), gc.ka = i1(Dr, 1), gc.kb = i1(Dr, 1), gc.nb = i1(Drb, wr * Dr), gc.mc = i1(Dlb * d, Drb),
-  gc.nc = i1(Drb, 1);
+  gc.dta = a.C.dt, gc.dtb = a.R.dt;
+  product_maps(gc, a.T2, a.R, a.OUT, "ax", "k", "l");
   gc.batch = 1;
   gc.scan_b.on = true;        // R as (bra bond) x (channel | ket bond)
-  gc.scan_b.buf = B_R, gc.scan_b.dt = h.r_dtype, gc.scan_b.off = 0;
-  gc.scan_b.r = i1(Drb, wr * Dr), gc.scan_b.k = i1(wr * Dr, 1);
-  std::vector<GSegPlan> csegs;
-  for (int64_t f = 0; f < wr; ++f) {
-    if (!present[f] || f == ru) continue;
+  gc.scan_b.buf = a.R.buf, gc.scan_b.dt = a.R.dt, gc.scan_b.off = a.R.off;
+  labels_index(a.R, "l", &gc.scan_b.r), labels_index(a.R, "fk", &gc.scan_b.k);
+  std::vector<GSegPlan> segs;
+  for (int64_t f = 0; f < (int64_t)a.present.size(); ++f) {
+    if (!a.present[f] || f == a.ru) continue;
+    const View P = a.alias[f] ? a.C : a.T2.sub('p', a.plane_of[f], 1), Rf = a.R.sub('f', f, 1);
     GSegPlan sg;
-    sg.abuf = alias[f] ? B_C : B_T2, sg.a_off = alias[f] ? 0 : plane_of[f] * plane;
-    sg.bbuf = B_R, sg.b_off = f * Dr;
-    sg.bm_kind = BM_SCAN, sg.bm_kt0 = f * (Dr / 16);
-    csegs.push_back(sg);
+    sg.abuf = P.buf, sg.a_off = P.off;
+    sg.bbuf = Rf.buf, sg.b_off = Rf.off;
+    sg.bm_kind = BM_SCAN, sg.bm_kt0 = f * (a.R.ext('k') / 16);
+    segs.push_back(sg);
   }
-  bool out_init = ru >= 0 && present[ru];
-  if (csegs.empty() && !out_init) {
-    p.error = "fold: the MPO site is zero";
-    return p;
-  }
-  p.tmp_elems[0] = ntmp * plane;
-  p.tmp_elems[1] = nplanes * plane;
-  if (!ga.groups.empty()) p.steps.push_back(ga);
-  if (!mix.mix.empty()) p.steps.push_back(mix);
-  for (size_t i = 0; i < csegs.size(); i += G_MAXSEG) {
+  for (size_t i = 0; i < segs.size(); i += G_MAXSEG) {
     Step st = gc;
     GGroupPlan g;
-    g.cbuf = B_OUT, g.c_off = 0;
-    g.beta = out_init ? 1.0 : 0.0;
-    if (split2) g.split2 = true, p.two_results = true;
-    for (size_t j = i; j < csegs.size() && j < i + G_MAXSEG; ++j) g.seg[g.nseg++] = csegs[j];
-    if (epi && i == 0) {
-      g.wbuf = B_W0, g.mix_d = d, g.mix_wr = wr, g.mix_ld = Dr;
-      for (const auto& kd : epi_diag) {
+    g.cbuf = a.OUT.buf, g.c_off = a.OUT.off;
+    g.beta = (a.out_init || i > 0) ? 1.0 : 0.0;     // the first launch starts `out` unless a plane is there already
+    if (a.split2) g.split2 = true, p.two_results = true;
+    for (size_t j = i; j < segs.size() && j < i + G_MAXSEG; ++j) g.seg[g.nseg++] = segs[j];
+    if (a.epi && i == 0) {
+      g.wbuf = B_W0, g.mix_d = a.C.ext('x'), g.mix_wr = a.R.ext('f'), g.mix_ld = a.T2.stride('x');
+      for (const auto& kd : a.epi_diag) {
+        const View src = a.src(kd.first->b);
         EpiTerm& t = g.mix[g.nmix++];
         t.b = kd.first->b, t.f = kd.first->f, t.delta = kd.second;
-        if (kd.first->b == lu)
-          t.src = B_C, t.src_off = 0;
-        else if (kd.first->b == epi_direct_b)
-          t.src = B_OUT, t.src_off = 0;
-        else
-          t.src = B_T1, t.src_off = tmp_of[kd.first->b] * plane;
+        t.src = src.buf, t.src_off = src.off;
       }
     }
     st.groups.push_back(g);
     p.steps.push_back(st);
-    out_init = true;
   }
+}
+
+// Folded one-site matvec; p.error is set when the site does not qualify and the caller takes plan_heff.
+inline Plan plan_heff1_fold(int dtype, const mpse_heff& h, const WSiteInfo& wi, bool two_results = false,
+                            bool mix_epilogue = false) {
+  Plan p;
+  const FoldAnalysis a = fold_analyse(dtype, h, wi, two_results, mix_epilogue);
+  if ((p.error = a.error)) return p;
+  p.tmp_elems[0] = a.ntmp * a.T1.stride('t');
+  p.tmp_elems[1] = a.nplanes * a.T2.stride('p');
+  fold_emit_l(p, a);
+  fold_emit_mix(p, a);
+  fold_emit_r(p, a);
   return marked(std::move(p));
 }
+
 
 // Environment update, mps/lib.py:169-250.  Buffers: B_L = incoming environment (either
 // domain), B_C = ket site, B_BRA = bra site, B_W0 = mpo site, B_OUT = new environment.
 // MPO step of an environment update as the elementwise pass of the folded matvec (K_WMIX) instead of a batched
 // real x complex product: for a large physical index and a site the caller has described (mpse_mpo_site_hint) the
 // product moves ~130 MB to apply a handful of identity / diagonal / tridiagonal blocks.  in_left: the incoming channel is
-// the LEFT index of W (domain L); otherwise the right one (domain R).  Tensors: src[a, (channel), e, k] / dst[a, (channel),
-// dd, k] through the offsets and strides given per channel.  Returns false (nothing pushed) when the site does not fit the pass.
-inline bool push_env_wmix(Plan& p, const WSiteInfo& wi, bool in_left, int dtype, int w_dtype, int tin, int tout, int64_t Da,
-                          int64_t Dk, int64_t src_ch_stride, int64_t src_sa, int64_t src_sd, int64_t dst_ch_stride,
-                          int64_t dst_sa, int64_t dst_sd) {
-  const int64_t d = wi.d, wl = wi.wl, wr = wi.wr, nout = in_left ? wr : wl;
-  const int64_t nchunk = (d + WM_CHUNK - 1) / WM_CHUNK;
-  if (d > 32 || nchunk > WM_MAXCHUNKS) return false;
+// the LEFT index of W (domain L); otherwise the right one (domain R).  Tensors: src[a, c, x, k] / dst[a, c, x, k] with c
+// the channel and x the physical index, in whatever order the views hold them.  Returns false (nothing pushed) when the
+// site does not fit the pass.
+inline bool push_env_wmix(Plan& p, const WSiteInfo& wi, bool in_left, int w_dtype, const View& src, const View& dst) {
+  const int64_t d = wi.d, nout = in_left ? wi.wr : wi.wl;
+  if (d > 32 || (d + WM_CHUNK - 1) / WM_CHUNK > WM_MAXCHUNKS) return false;
   std::vector<std::vector<const WBlock*>> by_out(nout);
   int64_t nslot = 0;
   for (const WBlock& k : wi.blocks) {
@@ -696,42 +859,38 @@ inline bool push_env_wmix(Plan& p, const WSiteInfo& wi, bool in_left, int dtype,
   }
   for (auto& v : by_out)
     if ((int)v.size() > WM_MAXTERM) return false;
-  if (nslot * d * d > 8192) return false;          // 64 KB of LDS for the dense blocks
-  std::vector<Step> steps;
+  if (!wmix_fits_lds(nslot, d)) return false;
   Step mix{};
-  auto fresh = [&] {
-    mix = Step{};
-    mix.kind = K_WMIX;
-    mix.b = B_W0;
-    mix.dta = dtype, mix.dtb = w_dtype;
-    mix.wp_Da = Da, mix.wp_d = d, mix.wp_Dk = Dk, mix.wp_wr = wr;
-  };
-  fresh();
+  mix.kind = K_WMIX;
+  mix.b = B_W0;
+  mix.dta = src.dt, mix.dtb = w_dtype;
+  mix.wp_Da = src.ext('a'), mix.wp_d = d, mix.wp_Dk = src.ext('k'), mix.wp_wr = wi.wr;
+  Step part = mix;
   for (int64_t o = 0; o < nout; ++o) {
+    const View dv = dst.sub('c', o, 1);
     WMixDst q;
-    q.dst = tout, q.dst_off = o * dst_ch_stride, q.s_a = dst_sa, q.s_d = dst_sd;
-    for (const WBlock* k : by_out[o]) {
-      WMixTerm& t = q.term[q.nterm++];
-      t.b = k->b, t.f = k->f, t.ident = k->ident;
-      t.src = tin, t.src_off = (in_left ? k->b : k->f) * src_ch_stride;
-      t.s_a = src_sa, t.s_d = src_sd;
-      for (int64_t c = 0; c < nchunk; ++c) {
-        int64_t lo = d, hi = 0;
-        for (int64_t x = c * WM_CHUNK; x < std::min<int64_t>(d, (c + 1) * WM_CHUNK); ++x)
-          for (int64_t e = 0; e < d; ++e)
-            if (wi.w[((k->b * d + x) * d + e) * wr + k->f] != 0.0) lo = std::min(lo, e), hi = std::max(hi, e + 1);
-        t.e_lo[c] = (unsigned char)(hi > lo ? lo : 0), t.e_hi[c] = (unsigned char)(hi > lo ? hi : 0);
-      }
-    }
-    mix.mix.push_back(q);          // (a channel without blocks: nterm = 0, the pass writes zeros)
-    if ((int)mix.mix.size() == WM_MAXDST) {
-      steps.push_back(mix);
-      fresh();
+    q.dst = dv.buf, q.dst_off = dv.off, q.s_a = dv.stride('a'), q.s_d = dv.stride('x');
+    for (const WBlock* k : by_out[o]) q.term[q.nterm++] = wmix_term(wi, *k, src.sub('c', in_left ? k->b : k->f, 1));
+    part.mix.push_back(q);         // (a channel without blocks: nterm = 0, the pass writes zeros)
+    if ((int)part.mix.size() == WM_MAXDST) {
+      p.steps.push_back(part);
+      part = mix;
     }
   }
-  if (!mix.mix.empty()) steps.push_back(mix);
-  for (Step& st : steps) p.steps.push_back(st);
+  if (!part.mix.empty()) p.steps.push_back(part);
   return true;
+}
+
+// The products with the bra that close an environment update (Y = the last intermediate, K = everything contracted):
+//   L: out[p,(f,h)] = sum_{A,g} bra*[(A,g),p] Y[A,f,g,h]      A = (bra bond, physical), g = traced ancilla
+//   R: out[p,(q,h)] = sum_K bra*[p,K] Y[h,q,K]                K = (physical, ancilla, bra bond)
+inline Step* push_bra_l(Plan& p, int ybuf, int dtype, int bra_conj, int64_t A, int64_t anc, int64_t wr, int64_t Drk, int64_t Drb) {
+  const View BRA(B_BRA, dtype, {{'A', A}, {'g', anc}, {'p', Drb}}), Y(ybuf, dtype, {{'A', A}, {'f', wr}, {'g', anc}, {'h', Drk}});
+  return contract(p, BRA, Y, View(B_OUT, dtype, {{'p', Drb}, {'f', wr}, {'h', Drk}}), "p", "Ag", "fh", "", "", bra_conj);
+}
+inline Step* push_bra_r(Plan& p, int ybuf, int dtype, int bra_conj, int64_t K, int64_t wl, int64_t Dlk, int64_t Dlb) {
+  const View BRA(B_BRA, dtype, {{'p', Dlb}, {'K', K}}), Y(ybuf, dtype, {{'h', Dlk}, {'q', wl}, {'K', K}});
+  return contract(p, BRA, Y, View(B_OUT, dtype, {{'p', Dlb}, {'q', wl}, {'h', Dlk}}), "p", "K", "qh", "", "", bra_conj);
 }
 
 inline Plan plan_env(int dtype, int domain, const mpse_dims& s, int env_dtype, int w_dtype, int bra_conj,
@@ -748,172 +907,50 @@ inline Plan plan_env(int dtype, int domain, const mpse_dims& s, int env_dtype, i
     const int64_t N = d * anc * Drk;
     p.tmp_elems[0] = Dlb * wl * N;
     p.tmp_elems[1] = Dlb * d * wr * anc * Drk;
-    // X[a,b,(e,g,h)] = sum_c L[(a,b),c] A[c,(e,g,h)]
+    // X[b,a,(e,g,h)] = sum_c L[(a,b),c] A[c,(e,g,h)]
     push_env_times(p, B_L, env_dtype, B_C, dtype, B_T1, Dlb, wl, Dlk, N, s.env_unit, true);
-    // Y[a,d,f,(g,h)] = sum_{b,e} W[b,d,e,f] X[a,b,e,(g,h)]
-    if (!(wfold && push_env_wmix(p, *wi, true, dtype, w_dtype, B_T1, B_T2, Dlb, Drk, /*src X[b, a, e, h]: channel b*/ Dlb * d * Drk, d * Drk, Drk,
-                                 /*dst: channel f*/ Drk, d * wr * Drk, wr * Drk)))
+    // Y[a,d,f,(g,h)] = sum_{b,e} W[b,d,e,f] X[b,a,e,(g,h)]
+    if (!(wfold && push_env_wmix(p, *wi, true, w_dtype, View(B_T1, dtype, {{'c', wl}, {'a', Dlb}, {'x', d}, {'k', Drk}}),
+                                 View(B_T2, dtype, {{'a', Dlb}, {'x', d}, {'c', wr}, {'k', Drk}}))))
       push_w(p, B_W0, w_dtype, B_T1, B_T2, dtype, Dlb, wl, d, wr, anc * Drk);
     // out[p,(f,h)] = sum_{a,d,g} bra*[(a,d,g),p] Y[a,d,f,g,h]
-    //   A = bra^T: m = p (stride 1), k = (a,d,g) (stride Drb)
-    //   B = Y: k = ((a,d) | g): s_hi = wr*anc*Drk, s_lo = Drk ; n = (f | h): s_hi = anc*Drk, s_lo = 1
-    push(p, B_BRA, 0, dtype, bra_conj, B_T2, 0, dtype, 0, B_OUT, 0, i1(Drb, 1), i1(Dlb * d * anc, Drb),
-         i2(Dlb * d, anc, wr * anc * Drk, Drk), i2(wr, Drk, anc * Drk, 1), i1(Drb, wr * Drk), i1(wr * Drk, 1));
-    p.steps.back().skip_zero = skip_pays(Drb, Dlb * d * anc, wr * Drk, 1);   // B = the big intermediate: bra side only
+    if (Step* st = push_bra_l(p, B_T2, dtype, bra_conj, Dlb * d, anc, wr, Drk, Drb))
+      st->skip_zero = skip_pays(Drb, Dlb * d * anc, wr * Drk, 1);   // B = the big intermediate: bra side only
     return marked(std::move(p));
   }
   if (domain == MPSE_DOMAIN_R) {
     // env R[a,b,c] ; ket A[h,e,g,c] ; W[q,d,e,b] ; bra Ab[p,d,g,a] -> out[p,q,h]
     p.tmp_elems[0] = Dlk * d * anc * wr * Drb;
     p.tmp_elems[1] = Dlk * wl * d * anc * Drb;
-    // X[(h,e,g),(b,a)] = sum_c A[(h,e,g),c] R[a,b,c]   (n ordered (b | a) through the strides of R)
-    {
-      const int64_t M = Dlk * d * anc;
-      const int64_t u = (s.env_unit >= 1 && s.env_unit <= wr && Drb == Drk && unit_pays(M, Drk, Drb)) ? s.env_unit - 1 : -1;
-      // unit channel: R[a,u,c] = delta(a,c)  =>  X[m,u,a] = A[m,a]
-      if (u >= 0) push_copy(p, B_C, 0, B_T1, u * Drb, dtype, i1(M, Drk), i1(Drk, 1), i1(M, wr * Drb), i1(Drb, 1));
-      const int64_t lo[2] = {0, u + 1}, hi[2] = {u >= 0 ? u : wr, u >= 0 ? wr : 0};
-      for (int r = 0; r < 2; ++r) {
-        const int64_t b0 = lo[r], nb = hi[r] - lo[r];
-        if (nb <= 0) continue;
-        push(p, B_C, 0, dtype, 0, B_L, b0 * Drk, env_dtype, 0, B_T1, b0 * Drb, i1(M, Drk), i1(Drk, 1), i1(Drk, 1),
-             i2(nb, Drb, Drk, wr * Drk), i1(M, wr * Drb), i1(nb * Drb, 1));
-        p.steps.back().skip_zero = skip_pays(M, Drk, nb * Drb);
-      }
+    // X[m,b,a] = sum_c A[m,c] R[a,b,c]   m = (h,e,g); columns ordered (b | a) through the strides of R
+    const int64_t M = Dlk * d * anc;
+    const int64_t u = (s.env_unit >= 1 && s.env_unit <= wr && Drb == Drk && unit_pays(M, Drk, Drb)) ? s.env_unit - 1 : -1;
+    const View A(B_C, dtype, {{'m', M}, {'c', Drk}}), R(B_L, env_dtype, {{'a', Drb}, {'b', wr}, {'c', Drk}});
+    const View X(B_T1, dtype, {{'m', M}, {'b', wr}, {'a', Drb}});
+    // unit channel: R[a,u,c] = delta(a,c)  =>  X[m,u,a] = A[m,a]
+    if (u >= 0) copy(p, A.as("ma"), X.sub('b', u, 1), "m", "a");
+    const ChannelRanges cr(u, wr);
+    for (int r = 0; r < 2; ++r) {
+      const int64_t b0 = cr.lo[r], nb = cr.hi[r] - cr.lo[r];
+      if (nb <= 0) continue;
+      if (Step* st = contract(p, A, R.sub('b', b0, nb), X.sub('b', b0, nb), "m", "c", "ba"))
+        st->skip_zero = skip_pays(M, Drk, nb * Drb);
     }
-    // Y[h,q,d,g,a] = sum_{e,b} W[q,d,e,b] X[h,e,g,b,a] ; batch h ; one step per ancilla value g
-    if (wfold && push_env_wmix(p, *wi, false, dtype, w_dtype, B_T1, B_T2, Dlk, Drb, /*src: channel b*/ Drb, d * wr * Drb, wr * Drb,
-                               /*dst: channel q*/ d * Drb, wl * d * Drb, Drb)) {
-    } else
-    for (int64_t g = 0; g < anc; ++g)
-      push(p, B_W0, 0, w_dtype, 0, B_T1, g * wr * Drb, dtype, 0, B_T2, g * Drb,
-           /*A=W: m=(q,d), k=(e,b)*/ i1(wl * d, d * wr), i1(d * wr, 1),
-           /*B: k=(e | b), n=a*/ i2(d, wr, anc * wr * Drb, Drb), i1(Drb, 1),
-           /*C: m=(q,d), n=a*/ i1(wl * d, anc * Drb), i1(Drb, 1), Dlk, 0, d * anc * wr * Drb, wl * d * anc * Drb);
+    // Y[h,q,y,g,a] = sum_{e,b} W[q,y,e,b] X[h,e,g,b,a] ; batch h ; one step per ancilla value g
+    if (!(wfold && push_env_wmix(p, *wi, false, w_dtype, View(B_T1, dtype, {{'a', Dlk}, {'x', d}, {'c', wr}, {'k', Drb}}),
+                                 View(B_T2, dtype, {{'a', Dlk}, {'c', wl}, {'x', d}, {'k', Drb}}))))
+      contract(p, View(B_W0, w_dtype, {{'q', wl}, {'y', d}, {'e', d}, {'b', wr}}),
+               View(B_T1, dtype, {{'h', Dlk}, {'e', d}, {'g', anc}, {'b', wr}, {'a', Drb}}),
+               View(B_T2, dtype, {{'h', Dlk}, {'q', wl}, {'y', d}, {'g', anc}, {'a', Drb}}), "qy", "eb", "a", "h", "g");
     // out[p,(q,h)] = sum_{d,g,a} bra*[p,(d,g,a)] Y[h,q,(d,g,a)]
-    push(p, B_BRA, 0, dtype, bra_conj, B_T2, 0, dtype, 0, B_OUT, 0, i1(Dlb, d * anc * Drb), i1(d * anc * Drb, 1),
-         i1(d * anc * Drb, 1), i2(wl, Dlk, d * anc * Drb, wl * d * anc * Drb), i1(Dlb, wl * Dlk), i1(wl * Dlk, 1));
-    p.steps.back().skip_zero = skip_pays(Dlb, d * anc * Drb, wl * Dlk, 1);
+    if (Step* st = push_bra_r(p, B_T2, dtype, bra_conj, d * anc * Drb, wl, Dlk, Dlb))
+      st->skip_zero = skip_pays(Dlb, d * anc * Drb, wl * Dlk, 1);
     return marked(std::move(p));
   }
   p.error = "env: bad domain";
   return p;
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Labelled views: the plans for stacked MPO layers (mps/lib.py:121-166, mps/hop_expr.py:24-52) are written as
-// pairwise contractions of tensors whose dimensions carry one-letter labels; `contract` turns one contraction into
-// strided-GEMM steps (labels listed outer -> inner; adjacent labels are merged when their strides are contiguous;
-// an index may have at most two levels per operand, everything else goes to `loops`, one step per value).
-struct View {
-  int buf = 0, dt = MPSE_F64;
-  int64_t off = 0;
-  std::vector<std::pair<char, int64_t>> dims;   // memory order, row major
-  View() {}
-  View(int b, int d, std::initializer_list<std::pair<char, int64_t>> l) : buf(b), dt(d), dims(l) {}
-  int64_t ext(char c) const {
-    for (auto& p : dims)
-      if (p.first == c) return p.second;
-    return -1;
-  }
-  int64_t stride(char c) const {   // 0 if the label is absent
-    int64_t s = 1;
-    for (size_t i = dims.size(); i-- > 0;) {
-      if (dims[i].first == c) return s;
-      s *= dims[i].second;
-    }
-    return 0;
-  }
-  int64_t size() const {
-    int64_t s = 1;
-    for (auto& p : dims) s *= p.second;
-    return s;
-  }
-};
-
-inline bool labels_index(const View& v, const std::string& labels, mpse_index* out) {
-  std::vector<std::pair<int64_t, int64_t>> lv;  // (ext, stride), outer -> inner, merged
-  int64_t total = 1;
-  for (char c : labels) {
-    const int64_t e = v.ext(c), st = v.stride(c);
-    if (e < 0) return false;
-    total *= e;
-    if (e == 1) continue;
-    if (!lv.empty() && lv.back().second == e * st)
-      lv.back().first *= e, lv.back().second = st;
-    else
-      lv.push_back({e, st});
-  }
-  if (lv.empty()) {
-    *out = i1(total, 1);
-    return true;
-  }
-  if (lv.size() == 1) {
-    *out = i1(lv[0].first, lv[0].second);
-    return true;
-  }
-  if (lv.size() == 2) {
-    *out = i2(lv[0].first, lv[1].first, lv[0].second, lv[1].second);
-    return true;
-  }
-  return false;
-}
-
-// C[batch][m, n] = sum_k A[batch][m, k] B[batch][k, n] for every value of the `loops` labels
-inline void contract(Plan& p, const View& A, const View& B, const View& C, const std::string& m, const std::string& k,
-                     const std::string& n, const std::string& batch = "", const std::string& loops = "",
-                     int conja = 0) {
-  if (p.error) return;
-  mpse_index ma, ka, kb, nb, mc, nc, ba, bb, bc;
-  if (!labels_index(A, m, &ma) || !labels_index(A, k, &ka) || !labels_index(B, k, &kb) || !labels_index(B, n, &nb) ||
-      !labels_index(C, m, &mc) || !labels_index(C, n, &nc)) {
-    p.error = "plan: an index of a stacked-MPO contraction needs more than two stride levels";
-    return;
-  }
-  int64_t nbatch = 1, sba = 0, sbb = 0, sbc = 0;
-  if (!batch.empty()) {
-    // a batch label may be absent from A or B (stride 0) but must be a single level where present
-    auto one = [&](const View& v, int64_t* st) {
-      std::string present;
-      for (char c : batch)
-        if (v.ext(c) >= 0) present.push_back(c);
-      if (present.empty()) {
-        *st = 0;
-        return true;
-      }
-      if (present.size() != batch.size()) return false;
-      mpse_index ix;
-      if (!labels_index(v, batch, &ix) || (ix.lo_ext < ix.ext && ix.ext > 1)) return false;
-      *st = ix.s_lo;
-      return true;
-    };
-    if (!one(A, &sba) || !one(B, &sbb) || !one(C, &sbc)) {
-      p.error = "plan: batch labels of a stacked-MPO contraction do not form one level";
-      return;
-    }
-    for (char c : batch) nbatch *= C.ext(c);
-  }
-  std::vector<int64_t> ext, cnt(loops.size(), 0);
-  int64_t nloop = 1;
-  for (char c : loops) {
-    const int64_t e = C.ext(c) >= 0 ? C.ext(c) : (A.ext(c) >= 0 ? A.ext(c) : B.ext(c));
-    ext.push_back(e);
-    nloop *= e;
-  }
-  for (int64_t it = 0; it < nloop; ++it) {
-    int64_t oa = A.off, ob = B.off, oc = C.off;
-    for (size_t l = 0; l < loops.size(); ++l) {
-      oa += cnt[l] * A.stride(loops[l]);
-      ob += cnt[l] * B.stride(loops[l]);
-      oc += cnt[l] * C.stride(loops[l]);
-    }
-    push(p, A.buf, oa, A.dt, conja, B.buf, ob, B.dt, 0, C.buf, oc, ma, ka, kb, nb, mc, nc, nbatch, sba, sbb, sbc);
-    for (size_t l = loops.size(); l-- > 0;) {
-      if (++cnt[l] < ext[l]) break;
-      cnt[l] = 0;
-    }
-  }
-}
 
 // Environment update with a stack of n MPO sites (mps/lib.py:121-166 contract_one_site_multi_mpo), n >= 1:
 //   L: env E[a, b_1..b_n, c], bra[a, x_0, g, p], W_i[b_i, x_{i-1}, x_i, f_i], ket[c, x_n, g, h] -> out[p, f_1..f_n, h]
@@ -942,7 +979,6 @@ inline Plan plan_env_multi(int dtype, int domain, const mpse_dims& s, int n, con
   for (int i = 0; i < n; ++i) win[i] = left ? wl[i] : wr[i], wout[i] = left ? wr[i] : wl[i];
   const int64_t Da = left ? Dlb : Drb;      // bond of the environment row that stays open until the last step
   const int64_t Dh = left ? Drk : Dlk;      // open ket bond
-  const int64_t Din = left ? Dlk : Drk;     // contracted ket bond
   int64_t cur = Da * d * anc * Dh;
   for (int i = 0; i < n; ++i) cur *= win[i];
   int64_t maxsz = cur;
@@ -971,13 +1007,12 @@ inline Plan plan_env_multi(int dtype, int domain, const mpse_dims& s, int n, con
       F *= wr[i];
     }
     // out[p, (F, h)] = sum_{a, y, g} bra*[(a, y, g), p] T_0[(a, y), F, g, h]
-    push(p, B_BRA, 0, dtype, bra_conj, tb, 0, dtype, 0, B_OUT, 0, i1(Drb, 1), i1(Dlb * d * anc, Drb),
-         i2(Dlb * d, anc, WR * anc * Drk, Drk), i2(WR, Drk, anc * Drk, 1), i1(Drb, WR * Drk), i1(WR * Drk, 1));
+    push_bra_l(p, tb, dtype, bra_conj, Dlb * d, anc, WR, Drk, Drb);
     return marked(std::move(p));
   }
   // R: T_n[h, x, g, (b_1..b_n), a] = sum_c ket[(h, x, g), c] E[a, (b), c]
-  push(p, B_C, 0, dtype, 0, B_L, 0, env_dtype, 0, tb, 0, i1(Dlk * d * anc, Drk), i1(Drk, 1), i1(Drk, 1),
-       i2(WR, Drb, Drk, WR * Drk), i1(Dlk * d * anc, WR * Drb), i1(WR * Drb, 1));
+  contract(p, View(B_C, dtype, {{'m', Dlk * d * anc}, {'c', Drk}}), View(B_L, env_dtype, {{'a', Drb}, {'b', WR}, {'c', Drk}}),
+           View(tb, dtype, {{'m', Dlk * d * anc}, {'b', WR}, {'a', Drb}}), "m", "c", "ba");
   // layer i = n..1: T_{i-1}[h, q_i, Q, y, g, P, a] = sum_{x, b_i} W_i[q_i, y, x, b_i] T_i[h, Q, x, g, P, b_i, a]
   int64_t P = WR, Q = 1;
   for (int i = n - 1; i >= 0; --i) {
@@ -991,8 +1026,7 @@ inline Plan plan_env_multi(int dtype, int domain, const mpse_dims& s, int n, con
     Q *= wl[i];
   }
   // out[p, (Q, h)] = sum_{y, g, a} bra*[p, (y, g, a)] T_0[h, Q, (y, g, a)]
-  push(p, B_BRA, 0, dtype, bra_conj, tb, 0, dtype, 0, B_OUT, 0, i1(Dlb, d * anc * Drb), i1(d * anc * Drb, 1),
-       i1(d * anc * Drb, 1), i2(WL, Dlk, d * anc * Drb, WL * d * anc * Drb), i1(Dlb, WL * Dlk), i1(WL * Dlk, 1));
+  push_bra_r(p, tb, dtype, bra_conj, d * anc * Drb, WL, Dlk, Dlb);
   return marked(std::move(p));
 }
 
@@ -1102,7 +1136,7 @@ inline int64_t ft_tmp_elems(const mpse_heff_ft& h, bool right_to_left = false) {
 
 // Left-to-right part shared by the matvec and the left environment update: T3 = W_2 W_1 (L . C); *up / *down receive
 // the labels of the two legs in T3, *kr the order in which the last product runs over (j, g, i).
-inline View ft_chain_l(Plan& p, int dtype, const mpse_heff_ft& h, char* up, char* down, std::string* kr) {
+inline View ft_chain_l(Plan& p, int dtype, const mpse_heff_ft& h, char* up, char* down, const char** kr) {
   const int64_t Dl = h.Dl, Dr = h.Dr, du = h.d_up, dv = h.d_down;
   View L(B_L, h.l_dtype, {{'a', Dl}, {'b', h.wl1}, {'c', h.wl2}, {'d', Dl}});
   View C(B_C, dtype, {{'a', Dl}, {'u', du}, {'v', dv}, {'j', Dr}});
@@ -1145,12 +1179,12 @@ inline Plan plan_heff_ft(int dtype, const mpse_heff_ft& h) {
   Plan p;
   if ((p.error = ft_check(h))) return p;
   p.tmp_elems[0] = p.tmp_elems[1] = p.tmp_elems[2] = ft_tmp_elems(h);
-  char up, down;
-  std::string kr;
-  View T3 = ft_chain_l(p, dtype, h, &up, &down, &kr);
+  char dud[4] = "d";     // (d, up, down): the rows of the last product
+  const char* kr;
+  View T3 = ft_chain_l(p, dtype, h, &dud[1], &dud[2], &kr);
   View R(B_R, h.r_dtype, {{'j', h.Dr}, {'g', h.wr1}, {'i', h.wr2}, {'k', h.Dr}});
-  View O(B_OUT, dtype, {{'d', h.Dl}, {up, h.d_up}, {down, h.d_down}, {'k', h.Dr}});
-  contract(p, T3, R, O, std::string("d") + up + down, kr, "k");
+  View O(B_OUT, dtype, {{'d', h.Dl}, {dud[1], h.d_up}, {dud[2], h.d_down}, {'k', h.Dr}});
+  contract(p, T3, R, O, dud, kr, "k");
   return marked(std::move(p));
 }
 
@@ -1167,12 +1201,12 @@ inline Plan plan_env_ft(int dtype, int domain, const mpse_heff_ft& h, int env_dt
   if (domain == MPSE_DOMAIN_L) {
     mpse_heff_ft hl = h;
     hl.l_dtype = env_dtype;
-    char up, down;
-    std::string kr;
-    View T3 = ft_chain_l(p, dtype, hl, &up, &down, &kr);
-    View BRA(B_BRA, dtype, {{'d', Dl}, {up, du}, {down, dv}, {'k', Dr}});
+    char dud[4] = "d";
+    const char* kr;
+    View T3 = ft_chain_l(p, dtype, hl, &dud[1], &dud[2], &kr);
+    View BRA(B_BRA, dtype, {{'d', Dl}, {dud[1], du}, {dud[2], dv}, {'k', Dr}});
     View O(B_OUT, dtype, {{'j', Dr}, {'g', h.wr1}, {'i', h.wr2}, {'k', Dr}});
-    contract(p, BRA, T3, O, "k", std::string("d") + up + down, kr, "", "", conj);
+    contract(p, BRA, T3, O, "k", dud, kr, "", "", conj);
     return marked(std::move(p));
   }
   if (domain != MPSE_DOMAIN_R) {
