@@ -729,6 +729,67 @@ int mpse_mps_rdm2_stats(mpse_ctx* ctx, int64_t* counts, int n);
  * 12 and 13 are 0 for a table or a selection that is refused.  No context, no device work. */
 int mpse_mps_rdm2_plan(int nsite, const int64_t* dims, int nsel, const int* sel, int any_complex, int64_t* info, int n);
 
+/* ------------------------------- one-site transition density matrices of selected sites of two chains */
+
+/* T_i[p, p'] = sum_{b,k,g,b',k'} op(B_i)[b,p,g,b'] L_i[b,k] K_i[k,p',g,k'] R_i[b',k'] for every selected site i of TWO
+ * chains, a bra B and a ket K, in one call: L_i and R_i the overlap environments of the sites left and right of i (bra
+ * index first: Db rows, Dk columns), the ancilla leg g traced, op the complex conjugate when conj_bra != 0, exactly the
+ * convention of mpse_mps_overlap.  sum_p T_i[p, p] = <bra|ket> for every i; with bra == ket and conj_bra = 1, T_i is
+ * rho_i of mpse_mps_rdm1 with the same index order; traced against a one-site operator O (first index on the bra side),
+ * <bra| O_i |ket> = sum_{p,p'} O[p,p'] T_i[p,p'], which replaces the per-operator windows, closing products and host
+ * reads of expectations(opers, bra) (transport/spectral_function.py:106-117: G_i(t) = <gs| a_i |ket(t)> / 1j):
+ *   bra[i], ket[i] : device site tensors, contiguous (Db_l, d, danc, Db_r) resp. (Dk_l, d, danc, Dk_r), each MPSE_F64
+ *                    or MPSE_C128 (bra_dtype[i], ket_dtype[i]; any mixture, across the two chains as well)
+ *   dims           : nsite rows (Db_l, Dk_l, d, danc, Db_r, Dk_r), host
+ *   sel            : nsel site indices, strictly ascending, host
+ *   out_host       : the nsel matrices one after the other, each d x d row-major complex pairs: 2 * sum_k d_k^2 doubles
+ * Refusals as mpse_mps_rdm1, with the same codes and in the same order: null pointers, an empty selection, a null site
+ * and unknown dtypes: MPSE_ERR_ARG; a selection that is not strictly ascending inside [0, nsite), rows with an extent <
+ * 1, neighbours whose bonds differ or a first / last bond != 1 in the bond columns of either chain: MPSE_ERR_SHAPE
+ * before any device work.  A refused call counts nothing, enqueues nothing and leaves out_host as it was.  Chains that
+ * pass mpse_mps_trdm1_plan run as TWO launches with no host read between them: k_trdm1_envs (two workgroups; one walks
+ * from the right with R in LDS, the other from the left with L in LDS, and each leaves its environment of every
+ * selected site in pooled memory) and k_trdm1_sites (one workgroup per selected site closes the two environments around
+ * the site; each p of T[p, p'] is summed by one wave with lane shuffles); no flag, spin wait or atomic between
+ * workgroups.  Every other chain runs the same contractions as products of the contraction kernel, all temporaries
+ * pooled (MPSE_ERR_OOM when they do not fit; the context stays usable).  The working dtype is complex as soon as any
+ * tensor of either chain is; two real chains return zero imaginary parts.  A fixed summation order: the same inputs
+ * give the same bits on every call (the two paths sum in different orders and agree to rounding).  MPSE_TRDM1_CHAIN=0 in
+ * the environment sends every chain through the enqueued products, =1 every chain whose launches fit through the
+ * kernels, above the bond limits of the rule as well (both for measurements).  Synchronous, one host read at the end;
+ * refused while a deferred list is being recorded. */
+int mpse_mps_trdm1(mpse_ctx* ctx, int nsite, const void* const* bra, const int* bra_dtype, const void* const* ket,
+                   const int* ket_dtype, const int64_t* dims /* nsite x 6 */, int conj_bra, int nsel, const int* sel,
+                   double* out_host);
+/* counts[i], i < n, cumulative:  0 calls taken by the chain kernels, 1 calls taken by the enqueued path, 2 sites walked
+ * (nsite per call), 3 matrices produced (nsel per call).  A refused call counts nothing.  Diagnostics for tests; no
+ * device work. */
+int mpse_mps_trdm1_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims table and the number of selected sites alone: returns 1 when the chain kernels take the
+ * call, else 0 (also for a table mpse_mps_trdm1 refuses).  LDS plan of either launch, in working elements of 8 (real)
+ * or 16 bytes (complex when any_complex != 0), rows padded to an odd length (x | 1) against bank conflicts:
+ *   region E  the largest of Db * (Dk | 1) over the bonds and Db_l * Db_r over the sites (the environment of the walks;
+ *             the intermediate of the closing, which contracts the ket first and is Db_l x Db_r whatever the bonds)
+ *   region T  the largest of Db_l * (Dk_r | 1) and Dk_l * (Db_r | 1) over the sites (one (sigma, ancilla) slice of the
+ *             walk from the left resp. from the right)
+ * The launches FIT when (E + T) elements lie within info[1] bytes, Db * Dk <= info[11] at every bond (one accumulator
+ * per entry of an environment), d, danc and d * danc <= info[10], every site tensor of either chain has fewer than 2^31
+ * elements (32-bit offsets) and nsel >= 1: there is no cap on a single bond, a bra of bond 1 against a ket of bond 256
+ * fits and so does the reverse.  The kernels TAKE a call that fits when the largest bond of either chain is <= info[0],
+ * or when every bond of the bra is 1 and the largest bond of the ket is <= info[13] (profiles/trdm1.md).  info[i], i <
+ * n (may be NULL):
+ *    0  the bond limit of the rule
+ *    1  LDS bytes a workgroup may use (the 160 KiB of a gfx950 compute unit)
+ *    2  LDS bytes of either launch (0: not taken)    3  its elements of region E (0: does not fit)
+ *    4  its elements of region T    5  threads of a workgroup
+ *    6  the largest bond of the bra (0: refused)    7  the largest bond of the ket (0: refused)
+ *    8  1 when the table is a chain    9  the cap on nsel (0: none, one workgroup per selected site)
+ *   10  the largest d * danc the kernels take   11  the largest Db * Dk of a bond they take
+ *   12  LDS bytes of either launch when it fits, whatever the rule says (0: does not fit)
+ *   13  the bond limit of the rule for the ket of a call whose bra has bond 1 throughout
+ * No context, no device work. */
+int mpse_mps_trdm1_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

@@ -1,11 +1,13 @@
-// What the chain calls with a site selection share beyond mpse_chain.h (mpse_corr.hip, mpse_rdm1.hip, mpse_rdm2.hip; no
-// other file includes this).  The three take dims rows (D_l, d, danc, D_r) of ONE chain and a strictly ascending
-// selection, and walk the chain with the identity transfer matrix: the environment in LDS, one (sigma, ancilla) slice
-// of a site at a time.  Here are the two stages of that transfer, once per direction, the moves of an environment
-// between LDS and pooled memory, the sizing of the launches, the checks of the entry points and what the
-// enqueued passes share.  A call keeps its descriptor row, its loop over the slices and what it does with the sums.
-// In all three a workgroup reads only what the launch before it wrote (no flag, no spin wait, no atomic), the host reads
-// once, at the end, and the order of every sum is fixed: the same inputs give the same bits.
+// What the chain calls with a site selection share beyond mpse_chain.h (mpse_corr.hip, mpse_rdm1.hip, mpse_rdm2.hip,
+// mpse_trdm1.hip; no other file includes this).  The first three take dims rows (D_l, d, danc, D_r) of ONE chain and a
+// strictly ascending selection, and walk the chain with the identity transfer matrix: the environment in LDS, one (sigma,
+// ancilla) slice of a site at a time.  mpse_trdm1.hip walks TWO chains with rectangular environments: its stages are
+// the walk2_* ones below, next to the square ones, which it leaves alone.  Here are the two stages of that transfer,
+// once per direction, the moves of an environment between LDS and pooled memory, the sizing of the launches, the
+// checks of the entry points and what the enqueued passes share.  A call keeps its descriptor row, its loop over the
+// slices and what it does with the sums.  In all four a workgroup reads only what the launch before it wrote (no flag,
+// no spin wait, no atomic), the host reads once, at the end, and the order of every sum is fixed: the same inputs give
+// the same bits.
 #pragma once
 #include "mpse_chain.h"
 
@@ -210,6 +212,124 @@ __device__ void chain_walk_left(const Row* __restrict__ sites, int last, ChainT<
       __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of L is done as well
     }
     walk_acc_store<CPLX>(acc, s.Dr, E);
+  }
+}
+
+// ------------------------------------------------------------------------------------------- device side, two chains
+// The same two stages for a bra B (Db_l, d, danc, Db_r) and a ket K (Dk_l, d, danc, Dk_r) that differ: an environment at
+// a bond is Db rows of chain_pitch(Dk) elements, bra index first.  `Row`: a descriptor row that starts with Chain2Row.
+// `krow` / `brow`: the elements of K / B per index of its left bond, d danc Dk_r / d danc Db_r; a slice is named by the
+// elements before it in such a row, `ket` = (sigma danc + a) Dk_r in K and `bra` = (sigma danc + a) Db_r in B.  op(B) is
+// the conjugate when the row says so (bra_cj: the call conjugates the bra and this tensor is complex).
+struct Chain2Row {   // what a descriptor row of a two-chain call begins with (56 bytes)
+  const void* bra;
+  const void* ket;
+  int Dbl, Dkl, d, danc, Dbr, Dkr;
+  int bra_c, ket_c;    // the side's tensor is complex128
+  int bra_cj;          // conjugate the bra tensor
+  int sel;             // position in the selection, -1: not selected
+};
+
+template <bool CPLX, class Row>
+__device__ __forceinline__ ChainT<CPLX> walk2_ld_bra(const Row& s, int i) {
+  const ChainT<CPLX> v = ChainEl<CPLX>::ld(s.bra, s.bra_c, i);
+  return s.bra_cj ? ChainEl<CPLX>::cj(v) : v;
+}
+
+// Leftwards (the walk from the left), first stage: T[b, k'] = sum_k E[b, k] K[k, ket, k'] with rows of E `pe` and rows
+// of T `pt` elements apart; ends with the barrier behind which T is read
+template <bool CPLX, class Row>
+__device__ __forceinline__ void walk2_left_slice(const Row& s, int krow, int ket, const ChainT<CPLX>* E, int pe,
+                                                 ChainT<CPLX>* Ts, int pt) {
+  using El = ChainEl<CPLX>;
+  using T = typename El::T;
+  const int Dkl = s.Dkl, Dkr = s.Dkr, nT = s.Dbl * Dkr;
+  for (int o = threadIdx.x; o < nT; o += CHAIN_THREADS) {
+    const int b = o / Dkr, kk = o - b * Dkr;
+    const T* e_row = E + b * pe;
+    const int k0 = ket + kk;
+    T sum = El::zero();
+#pragma unroll 4
+    for (int k = 0; k < Dkl; ++k) El::fma(sum, e_row[k], El::ld(s.ket, s.ket_c, k * krow + k0));
+    Ts[b * pt + kk] = sum;
+  }
+  __syncthreads();
+}
+
+// Leftwards, second stage: S = sum_b op(B[b, bra, b']) T[b, k'] of the entry o = b' Dk_r + k' of the new environment
+// (Db_r x Dk_r), rows of T `pt` apart.  Owners take o = tid + j * CHAIN_THREADS, k' fastest.
+template <bool CPLX, class Row>
+__device__ __forceinline__ void walk2_left_sum(const Row& s, int brow, int bra, int o, const ChainT<CPLX>* Ts, int pt,
+                                               ChainT<CPLX>& S) {
+  using El = ChainEl<CPLX>;
+  const int Dbl = s.Dbl, Dkr = s.Dkr;
+  const int bb = o / Dkr, kk = o - bb * Dkr;
+  const int b0 = bra + bb;
+  S = El::zero();
+#pragma unroll 4
+  for (int b = 0; b < Dbl; ++b) El::fma(S, walk2_ld_bra<CPLX>(s, b * brow + b0), Ts[b * pt + kk]);
+}
+
+// Rightwards (the walk from the right), first stage: T[k, b'] = sum_k' K[k, ket, k'] R[b', k'] into LDS, R with rows
+// of chain_pitch(Dk_r), T (Dk_l rows) with rows of chain_pitch(Db_r); ends with the barrier behind which T is read
+template <bool CPLX, class Row>
+__device__ __forceinline__ void walk2_right_slice(const Row& s, int krow, int ket, const ChainT<CPLX>* R,
+                                                  ChainT<CPLX>* Ts) {
+  using El = ChainEl<CPLX>;
+  using T = typename El::T;
+  const int Dbr = s.Dbr, Dkr = s.Dkr, pr = Dkr | 1, pt = Dbr | 1, nT = s.Dkl * Dbr;
+  for (int o = threadIdx.x; o < nT; o += CHAIN_THREADS) {
+    const int k = o / Dbr, bp = o - k * Dbr;
+    const T* r_row = R + bp * pr;
+    const int k0 = k * krow + ket;
+    T sum = El::zero();
+#pragma unroll 4
+    for (int kp = 0; kp < Dkr; ++kp) El::fma(sum, El::ld(s.ket, s.ket_c, k0 + kp), r_row[kp]);
+    Ts[k * pt + bp] = sum;
+  }
+  __syncthreads();
+}
+
+// Rightwards, second stage: S = sum_b' op(B[b, bra, b']) T[k, b'] of the entry o = b Dk_l + k of the new environment
+// (Db_l x Dk_l).  Owners take o = tid + j * CHAIN_THREADS: B[b, ..] is one address per b group.
+template <bool CPLX, class Row>
+__device__ __forceinline__ void walk2_right_sum(const Row& s, int brow, int bra, int o, const ChainT<CPLX>* Ts,
+                                                ChainT<CPLX>& S) {
+  using El = ChainEl<CPLX>;
+  const int Dkl = s.Dkl, Dbr = s.Dbr;
+  const int b = o / Dkl, k = o - b * Dkl;
+  const int b0 = b * brow + bra;
+  const ChainT<CPLX>* t_row = Ts + k * (Dbr | 1);
+  S = El::zero();
+#pragma unroll 4
+  for (int bp = 0; bp < Dbr; ++bp) El::fma(S, walk2_ld_bra<CPLX>(s, b0 + bp), t_row[bp]);
+}
+
+// The accumulators of the owners become the rows x cols environment in LDS; barriers as walk_acc_store
+template <bool CPLX>
+__device__ __forceinline__ void walk2_acc_store(const ChainT<CPLX> (&acc)[CHAIN_OUT_PER_THREAD], int rows, int cols,
+                                                ChainT<CPLX>* E) {
+  const int pitch = cols | 1;
+#pragma unroll
+  for (int j = 0; j < CHAIN_OUT_PER_THREAD; ++j) {
+    const int o = threadIdx.x + j * CHAIN_THREADS;
+    if (o < rows * cols) {
+      const int r = o / cols, c = o - r * cols;
+      E[r * pitch + c] = acc[j];
+    }
+  }
+  __syncthreads();
+}
+
+// the rows x cols environment in LDS to rows cols packed elements of pooled memory, as it is or transposed (cols x rows)
+template <bool CPLX, bool TRANSPOSED>
+__device__ __forceinline__ void walk2_env_to_pool(const ChainT<CPLX>* E, int rows, int cols, ChainT<CPLX>* P) {
+  const int pitch = cols | 1;
+  for (int o = threadIdx.x; o < rows * cols; o += CHAIN_THREADS) {
+    int r, c;
+    if (TRANSPOSED) c = o / rows, r = o - c * rows;
+    else r = o / cols, c = o - r * cols;
+    P[o] = E[r * pitch + c];
   }
 }
 

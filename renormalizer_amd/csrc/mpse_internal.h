@@ -169,6 +169,9 @@ struct mpse_ctx {
   // mpse_mps_rdm2 (mpse_mps_rdm2_stats; the order of include/mpsengine.h)
   enum Rdm2Stat { RD2_CHAIN, RD2_ENQUEUED, RD2_SITES, RD2_PAIRS, RD2_COUNT };
   long long rdm2_stats[RD2_COUNT] = {0};
+  // mpse_mps_trdm1 (mpse_mps_trdm1_stats; the order of include/mpsengine.h)
+  enum Trdm1Stat { TR_CHAIN, TR_ENQUEUED, TR_SITES, TR_MATRICES, TR_COUNT };
+  long long trdm1_stats[TR_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

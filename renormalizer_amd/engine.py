@@ -195,6 +195,10 @@ _SIGNATURES = {
                       _dblp],
     "mpse_mps_rdm2_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_mps_rdm2_plan": [C.c_int, _i64p, C.c_int, C.POINTER(C.c_int), C.c_int, _i64p, C.c_int],
+    "mpse_mps_trdm1": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                       C.POINTER(C.c_int), _i64p, C.c_int, C.c_int, C.POINTER(C.c_int), _dblp],
+    "mpse_mps_trdm1_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_trdm1_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -294,6 +298,19 @@ def mps_rdm2_plan(dims, sel, any_complex, lib=None):
     sel = [int(k) for k in sel]
     return _chain_plan((lib or load_library()).mpse_mps_rdm2_plan, dims, 4, "D_l, d, danc, D_r", RDM2_PLAN_INFO,
                        len(sel), (C.c_int * max(len(sel), 1))(*sel), int(bool(any_complex)))
+
+
+TRDM1_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond_bra",
+                   "max_bond_ket", "valid", "nsel_limit", "p_limit", "acc_limit", "lds_fit_bytes", "bond_limit_bra1")
+
+
+def mps_trdm1_plan(dims, nsel, any_complex, lib=None):
+    """Which path ``Engine.mps_trdm1`` takes for two chains, from their ``dims`` rows (Db_l, Dk_l, d, danc, Db_r, Dk_r)
+    and the number of selected sites alone (``mpse_mps_trdm1_plan``; needs the built library, no GPU).  Returns (chain
+    kernels?, {info name: value}); ``acc_limit``: the largest Db * Dk of a bond the launches take, ``bond_limit_bra1``:
+    the rule's limit for the ket when every bond of the bra is 1."""
+    return _chain_plan((lib or load_library()).mpse_mps_trdm1_plan, dims, 6, "Db_l, Dk_l, d, danc, Db_r, Dk_r",
+                       TRDM1_PLAN_INFO, int(nsel), int(bool(any_complex)))
 
 
 def check_selection(call, sel, nsite):
@@ -921,6 +938,51 @@ class Engine:
         ends = np.cumsum(sizes)
         return {(k, l): out[e - sz:e].reshape(rows[k][1], rows[k][1], rows[l][1], rows[l][1])
                 for (k, l), sz, e in zip(pairs, sizes, ends)}
+
+    # -- one-site transition density matrices of two chains
+    TRDM1_STATS = ("chain_kernel", "enqueued", "sites", "matrices")
+
+    def mps_trdm1_stats(self):
+        """{name: count} of the ``mps_trdm1`` calls of this context, cumulative (``mpse_mps_trdm1_stats``): calls taken
+        by the chain kernels, calls taken by the enqueued products, sites walked, matrices produced."""
+        return self._stats_dict(self.lib.mpse_mps_trdm1_stats, self.TRDM1_STATS)
+
+    @staticmethod
+    def trdm1_dims(bra_sites, ket_sites):
+        """The ``dims`` rows (Db_l, Dk_l, d, danc, Db_r, Dk_r) of two chains of site tensors (D_l, d[, danc], D_r);
+        ValueError when the two do not describe the same sites.  Needs no context."""
+        n = len(bra_sites)
+        if n == 0 or n != len(ket_sites):
+            raise ValueError(f"mps_trdm1: {n} bra sites, {len(ket_sites)} ket sites")
+        rows = []
+        for i, (b, k) in enumerate(zip(bra_sites, ket_sites)):
+            if b.ndim not in (3, 4) or k.ndim not in (3, 4):
+                raise ValueError(f"mps_trdm1: site {i} has shapes {b.shape} and {k.shape}")
+            pb = (b.shape[1], b.shape[2] if b.ndim == 4 else 1)
+            pk = (k.shape[1], k.shape[2] if k.ndim == 4 else 1)
+            if pb != pk:
+                raise ValueError(f"mps_trdm1: site {i} has physical and ancilla extents {pb} in the bra, {pk} in the ket")
+            rows.append([b.shape[0], k.shape[0], pb[0], pb[1], b.shape[-1], k.shape[-1]])
+        return rows
+
+    def mps_trdm1(self, bra_sites, ket_sites, sel, conj_bra):
+        """T_i[p, p'] = sum op(B)[b,p,g,b'] L_i[b,k] K[k,p',g,k'] R_i[b',k'] for the sites ``sel`` (strictly ascending)
+        of two chains of device site tensors (D_l, d[, danc], D_r), bra and ket, in one engine call
+        (``mpse_mps_trdm1``); L_i and R_i are the overlap environments of the other sites, the ancilla leg of
+        density-operator sites is traced.  ``conj_bra``: conjugate the bra inside the contraction, as in
+        ``mps_overlap``.  Real and complex sites may be mixed.  Returns a list of (d, d) complex128 arrays, one per
+        selected site; the trace of each is <bra|ket>."""
+        rows = self.trdm1_dims(bra_sites, ket_sites)
+        n = len(rows)
+        sel = check_selection("mps_trdm1", sel, n)
+        dims = (C.c_int64 * (6 * n))(*[int(x) for r in rows for x in r])
+        sizes = [rows[k][2] ** 2 for k in sel]
+        out = np.zeros(sum(sizes), dtype=np.complex128)
+        self._check(self.lib.mpse_mps_trdm1(
+            self.ctx, n, *_site_args(bra_sites), *_site_args(ket_sites), dims, int(bool(conj_bra)), len(sel),
+            (C.c_int * len(sel))(*sel), out.ctypes.data_as(_dblp)))
+        ends = np.cumsum(sizes)
+        return [out[e - sz:e].reshape(rows[k][2], rows[k][2]) for k, sz, e in zip(sel, sizes, ends)]
 
     def block_qr_stats(self):
         """(block QR calls, of which through the Cholesky-QR kernels, of which redone by Householder) of this context."""

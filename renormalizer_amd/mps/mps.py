@@ -682,6 +682,39 @@ class Mps:
                                                 [("n", dof) for dof in self.model.v_dofs])
         return e_occ, ph_occ
 
+    def transition_rdms(self, ket: "Mps", idx=None, self_is_conj=True) -> Dict[int, np.ndarray]:
+        """The one-site transition density matrices T_i[p, p'] = <self| (|p><p'| at site i) |ket> of the sites ``idx``
+        (a site, a list of sites or None for all) as ONE engine call (``Engine.mps_trdm1`` -> ``mpse_mps_trdm1``): both
+        environment passes over the two chains and the closing products of every requested site run inside the engine,
+        and the host reads once.  ``self`` is the bra exactly as in ``overlap`` and ``matrix_element``: it holds the
+        already-conjugated bra unless ``self_is_conj=False``, which conjugates inside the contraction.  The trace of
+        every matrix is ``self.overlap(ket, self_is_conj)``; with ``ket`` the same state and ``self_is_conj=False`` they
+        are the matrices of ``site_rdms``.  Always complex128.  Works for ``Mps`` and ``MpDm`` (the ancilla leg is
+        traced); the ``coeff`` factors are not included."""
+        assert len(self) == len(ket)
+        sel = self._pair_selection(idx)
+        mats = get_engine().mps_trdm1(self._mp, ket._mp, sel, conj_bra=not self_is_conj)
+        return dict(zip(sel, mats))
+
+    def transition_elements(self, symbol, dofs, ket: "Mps", self_is_conj=True) -> np.ndarray:
+        """<self| Op(symbol, dof) |ket> of a one-site operator for every dof of ``dofs``, each as sum(O * T_site) with
+        the site's transition density matrix from ONE engine call over the sites that carry a requested dof
+        (``transition_rdms``); dofs on one site share its matrix.  ``self`` is the bra as in ``matrix_element``.  The
+        values of ``ket.expectations([Mpo(model, Op(symbol, dof)) for dof in dofs], self)`` resp. ``..., self.conj())``
+        without the conjugated copy and without an operator window, a closing product and a host read per dof;
+        ``expectations`` itself stays as it is, the two sum in different orders and agree to rounding.  Always
+        complex.  ValueError for an operator that is not a one-site operator.  The ``coeff`` factors are not
+        included."""
+        local = []
+        for dof in dofs:
+            if isinstance(dof, list) or dof not in self.model.dof_to_siteidx:
+                raise ValueError(f"Op({symbol!r}, {dof!r}) is not a one-site operator on a dof of the model")
+            local.append(self._local_matrix(symbol, dof))
+        if not local:
+            return np.zeros(0, dtype=np.complex128)
+        mats = self.transition_rdms(ket, [site for site, _ in local], self_is_conj)
+        return np.array([np.sum(mat * mats[site]) for site, mat in local], dtype=np.complex128)
+
     def site_entropies(self) -> Dict[int, float]:
         """The values of ``calc_entropy("1site")``, the von Neumann entropy of every one-site reduced density matrix,
         from ``site_rdms()``: one engine call for the whole chain.  ``calc_entropy`` itself stays as it is; the two
