@@ -790,6 +790,51 @@ int mpse_mps_trdm1_stats(mpse_ctx* ctx, int64_t* counts, int n);
  * No context, no device work. */
 int mpse_mps_trdm1_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
 
+/* ------------------------------- Schmidt weights of selected bonds */
+
+/* The Schmidt weights p = sigma^2 of selected bonds of ONE chain in one call, without a canonical form, a quantum-number
+ * table or a copy of the state (replaces, for the weights and the entropies, the two sweeps of
+ * mps/mps.py:1759-1773 calc_bond_singular_values).  Bond k lies between the sites k and k + 1, 0 <= k <= nsite - 2, and
+ * has the dimension D_k = dims[k][3].  With L_k (D_k x D_k) the identity-operator environment of the sites 0 .. k and
+ * R_k that of the sites k + 1 .. nsite - 1 (first index from the conjugated tensor, as in mpse_mps_rdm1), the non-zero
+ * weights are the eigenvalues of L^(1/2) R^T L^(1/2): with L = U Lambda U^H, of the Hermitian matrix
+ *   M = Lambda^(1/2) U^H R^T U Lambda^(1/2).
+ * No inverse appears: a rank-deficient bond is no special case.
+ *   sites, dtype, dims : as for mpse_mps_rdm1 (the ancilla leg of density-operator sites is traced with the bonds)
+ *   sel                : nsel bond indices, strictly ascending inside [0, nsite - 1), host
+ *   out_host           : packed, for every selected bond D_k doubles: its weights in descending order, negative
+ *                        rounding noise clamped to 0; not normalised (they sum to <psi|psi>): sum_k D_k doubles
+ * The weights are exact to about eps * (the largest weight), not relatively: singular values below sqrt(eps) of the
+ * largest are not resolved.  Refusals as mpse_mps_rdm1, with the same codes and in the same order; a chain of one site
+ * has no bond and is refused like an empty selection (MPSE_ERR_ARG).  A refused call counts nothing, enqueues nothing
+ * and leaves out_host as it was.  Chains that pass mpse_mps_bond_spectra_plan run as TWO launches with no host read
+ * between them: k_bondspec_envs (two workgroups, the walks of k_rdm1_envs; the one from the left leaves L_k of every
+ * selected bond in pooled memory, the one from the right R_k) and k_bondspec_eig (one workgroup per selected bond: a
+ * cyclic two-sided Jacobi for Hermitian matrices in LDS, round-robin ordering, first on L with the vectors, then on M
+ * for the values; the stopping decision is taken on the device, a solve that reaches its sweep cap fails the call with
+ * MPSE_ERR_NOCONV and a message, no weight is returned); no flag, spin wait or atomic between workgroups.  Every other
+ * chain runs the two passes as products of the contraction kernel and the two solves of a bond through mpse_block_svd
+ * (a Hermitian positive semidefinite matrix has its eigenvalues as singular values), with a host read per solve; no
+ * speed is claimed for it.  A fixed summation order: the same inputs give the same bits on every call.
+ * MPSE_BOND_SPECTRA_CHAIN=0 / =1 as MPSE_RDM1_CHAIN.  Synchronous; refused while a deferred list is being recorded. */
+int mpse_mps_bond_spectra(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype,
+                          const int64_t* dims /* nsite x 4 */, int nsel, const int* sel, double* out_host);
+/* counts[i], i < n, cumulative:  0 calls taken by the chain kernels, 1 calls taken by the enqueued path, 2 sites walked
+ * (nsite per call), 3 bonds returned (nsel per call), 4 the largest number of Jacobi sweeps any solve of k_bondspec_eig
+ * has taken on this context (the sweep that finds nothing to rotate included).  A refused call counts nothing.
+ * Diagnostics for tests; no device work. */
+int mpse_mps_bond_spectra_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims table and the number of selected bonds alone: returns 1 when the chain kernels take the
+ * call, else 0 (also for a table mpse_mps_bond_spectra refuses, a chain of one site and nsel < 1).  The launches FIT
+ * under the conditions of mpse_mps_rdm1_plan; the kernels TAKE a call that fits when every bond is also <= info[0]
+ * (profiles/bond_spectra.md).  info[i], i < n (may be NULL): 0 to 11 as for mpse_mps_rdm1_plan, with 2 and 11 the larger
+ * of the two launches, then
+ *   12  LDS elements of k_bondspec_eig: 2 D (D | 1) + D, the matrix, the vectors and a strip for Lambda and the
+ *       rotations, at the largest bond D of the table (the selection is no argument here; 0: does not fit)
+ *   13  the sweep cap of a solve
+ * No context, no device work. */
+int mpse_mps_bond_spectra_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

@@ -30,6 +30,9 @@ def __getattr__(name):
     if name in ("ChargeDiffusionDynamics", "InitElectron", "EDGE_THRESHOLD", "calc_r_square"):
         from . import transport as _transport
         return getattr(_transport, name)
+    if name == "SpinBosonDynamics":
+        from .sbm import SpinBosonDynamics
+        return SpinBosonDynamics
     if name == "backend":
         from .mps.backend import backend
         return backend

@@ -1,6 +1,7 @@
 // What the chain calls with a site selection share beyond mpse_chain.h (mpse_corr.hip, mpse_rdm1.hip, mpse_rdm2.hip,
-// mpse_trdm1.hip; no other file includes this).  The first three take dims rows (D_l, d, danc, D_r) of ONE chain and a
-// strictly ascending selection, and walk the chain with the identity transfer matrix: the environment in LDS, one (sigma,
+// mpse_trdm1.hip, mpse_bondspec.hip; no other file includes this).  The first three and the last (whose selection names
+// bonds) take dims rows (D_l, d, danc, D_r) of ONE chain and a strictly ascending selection, and walk the chain with
+// the identity transfer matrix: the environment in LDS, one (sigma,
 // ancilla) slice of a site at a time.  mpse_trdm1.hip walks TWO chains with rectangular environments: its stages are
 // the walk2_* ones below, next to the square ones, which it leaves alone.  Here are the two stages of that transfer,
 // once per direction, the moves of an environment between LDS and pooled memory, the sizing of the launches, the
@@ -420,7 +421,8 @@ static inline int chain_sel_plan_out(const ChainSelPlan& pl, bool valid, int64_t
 }
 
 static_assert(mpse_ctx::CR_SITES == 2 && mpse_ctx::RD_SITES == 2 && mpse_ctx::RD2_SITES == 2 &&
-              mpse_ctx::CR_ENTRIES == 3 && mpse_ctx::RD_MATRICES == 3 && mpse_ctx::RD2_PAIRS == 3,
+              mpse_ctx::BS_SITES == 2 && mpse_ctx::CR_ENTRIES == 3 && mpse_ctx::RD_MATRICES == 3 &&
+              mpse_ctx::RD2_PAIRS == 3 && mpse_ctx::BS_BONDS == 3,
               "chain_sel_done: chain, enqueued, sites, results");
 // Tail of an entry point: counts the call (stats: by path, sites walked, results) and hands the result to the caller
 static inline int chain_sel_done(long long* stats, bool chain, int nsite, long long results,
@@ -441,16 +443,18 @@ static inline void chain_sel_plan_switch(const char* name, ChainSelPlan* pl) {
 // What an entry point refuses before any device work, in this order: a null argument (`rest`: the pointer arguments of
 // the call beyond `a` are all there) or fewer than nsel_min selected sites, a null site or an unknown dtype, a
 // selection that is not strictly ascending, a table that is no chain, a deferred list being recorded.  *cplx: some
-// tensor is complex128.
+// tensor is complex128.  `sel_end`: the selection lies in [0, sel_end); -1: in [0, nsite), a selection of sites (the
+// bonds of mpse_bondspec.hip end one earlier).
 static inline int chain_sel_prologue(mpse_ctx* ctx, const char* call, const ChainSelArgs& a, int nsel_min, bool rest,
-                                     bool* cplx) {
+                                     bool* cplx, int sel_end = -1) {
   if (!ctx) return MPSE_ERR_ARG;
   if (a.nsite < 1 || !a.sites || !a.dtype || !a.dims || a.nsel < nsel_min || !a.sel || !rest)
     return mpse_fail(ctx, MPSE_ERR_ARG, "%s: null argument, no sites or %s", call,
                      nsel_min > 1 ? "fewer than two selected sites" : "no selection");
   MPSE_TRY(chain_scan_sites(ctx, call, a.nsite, {a.sites}, {a.dtype}, cplx));
-  if (!chain_sel_ok(a.nsite, a.nsel, a.sel))
-    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: the selection is not strictly ascending inside [0, %d)", call, a.nsite);
+  if (sel_end < 0) sel_end = a.nsite;
+  if (!chain_sel_ok(sel_end, a.nsel, a.sel))
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: the selection is not strictly ascending inside [0, %d)", call, sel_end);
   if (!chain_sel_table_ok(a.nsite, a.dims))
     return mpse_fail(ctx, MPSE_ERR_SHAPE,
                      "%s: dims is not a chain (extents >= 1, matching neighbours, first and last bond 1)", call);

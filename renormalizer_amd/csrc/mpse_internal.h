@@ -172,6 +172,9 @@ struct mpse_ctx {
   // mpse_mps_trdm1 (mpse_mps_trdm1_stats; the order of include/mpsengine.h)
   enum Trdm1Stat { TR_CHAIN, TR_ENQUEUED, TR_SITES, TR_MATRICES, TR_COUNT };
   long long trdm1_stats[TR_COUNT] = {0};
+  // mpse_mps_bond_spectra (mpse_mps_bond_spectra_stats; the order of include/mpsengine.h)
+  enum BondSpecStat { BS_CHAIN, BS_ENQUEUED, BS_SITES, BS_BONDS, BS_MAX_SWEEPS, BS_COUNT };
+  long long bondspec_stats[BS_COUNT] = {0};
 };
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
 

@@ -199,6 +199,10 @@ _SIGNATURES = {
                        C.POINTER(C.c_int), _i64p, C.c_int, C.c_int, C.POINTER(C.c_int), _dblp],
     "mpse_mps_trdm1_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_mps_trdm1_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
+    "mpse_mps_bond_spectra": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p, C.c_int,
+                              C.POINTER(C.c_int), _dblp],
+    "mpse_mps_bond_spectra_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_bond_spectra_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -311,6 +315,19 @@ def mps_trdm1_plan(dims, nsel, any_complex, lib=None):
     the rule's limit for the ket when every bond of the bra is 1."""
     return _chain_plan((lib or load_library()).mpse_mps_trdm1_plan, dims, 6, "Db_l, Dk_l, d, danc, Db_r, Dk_r",
                        TRDM1_PLAN_INFO, int(nsel), int(bool(any_complex)))
+
+
+BOND_SPECTRA_PLAN_INFO = RDM1_PLAN_INFO + ("eig_elems", "sweep_cap")
+
+
+def mps_bond_spectra_plan(dims, nsel, any_complex, lib=None):
+    """Which path ``Engine.mps_bond_spectra`` takes for a chain, from its ``dims`` rows (D_l, d, danc, D_r) and the
+    number of selected bonds alone (``mpse_mps_bond_spectra_plan``; needs the built library, no GPU).  Returns (chain
+    kernels?, {info name: value}); ``eig_elems``: the LDS elements of the eigensolver launch, 2 D (D | 1) + D at the
+    largest bond D of the table, ``sweep_cap``: the sweeps after which a Jacobi solve fails the call; ``lds_bytes`` and
+    ``lds_fit_bytes`` are those of the larger of the two launches."""
+    return _chain_plan((lib or load_library()).mpse_mps_bond_spectra_plan, dims, 4, "D_l, d, danc, D_r",
+                       BOND_SPECTRA_PLAN_INFO, int(nsel), int(bool(any_complex)))
 
 
 def check_selection(call, sel, nsite):
@@ -913,8 +930,36 @@ class Engine:
         ends = np.cumsum(sizes)
         return [out[e - sz:e].reshape(rows[k][1], rows[k][1]) for k, sz, e in zip(sel, sizes, ends)]
 
+    # -- Schmidt weights of bonds
+    BOND_SPECTRA_STATS = ("chain_kernel", "enqueued", "sites", "bonds", "max_sweeps")
+
+    def mps_bond_spectra_stats(self):
+        """{name: count} of the ``mps_bond_spectra`` calls of this context, cumulative
+        (``mpse_mps_bond_spectra_stats``): calls taken by the chain kernels, calls taken by the enqueued path, sites
+        walked, bonds returned, and the largest number of sweeps a Jacobi solve of the chain kernels has taken."""
+        return self._stats_dict(self.lib.mpse_mps_bond_spectra_stats, self.BOND_SPECTRA_STATS)
+
+    def mps_bond_spectra(self, sites, sel):
+        """The Schmidt weights sigma^2 of the bonds ``sel`` (strictly ascending; bond k lies between the sites k and
+        k + 1) of a chain of device site tensors (D_l, d[, danc], D_r), in one engine call
+        (``mpse_mps_bond_spectra``): from the two identity-operator environments of each bond, without a canonical
+        form; the ancilla leg of density-operator sites is traced.  Returns a list of float64 arrays, one per selected
+        bond, each the D_k weights in descending order, not normalised."""
+        rows = self.corr_dims(sites)
+        n = len(rows)
+        if n < 2:
+            raise ValueError(f"mps_bond_spectra: a chain of {n} site(s) has no bond")
+        sel = check_selection("mps_bond_spectra", sel, n - 1)
+        dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
+        sizes = [rows[k][3] for k in sel]
+        out = np.zeros(sum(sizes), dtype=np.float64)
+        self._check(self.lib.mpse_mps_bond_spectra(
+            self.ctx, n, *_site_args(sites), dims, len(sel), (C.c_int * len(sel))(*sel), out.ctypes.data_as(_dblp)))
+        ends = np.cumsum(sizes)
+        return [out[e - sz:e] for sz, e in zip(sizes, ends)]
+
     # -- two-site reduced density matrices
-    RDM2_STATS = ("chain_kernel", "enqueued", "sites", "pairs")
+    RDM2_STATS =("chain_kernel", "enqueued", "sites", "pairs")
 
     def mps_rdm2_stats(self):
         """{name: count} of the ``mps_rdm2`` calls of this context, cumulative (``mpse_mps_rdm2_stats``): calls taken by

@@ -1,15 +1,18 @@
 """Spin-boson model construction: spectral densities, adiabatic renormalisation, bath discretisation.
 
 Counterpart of renormalizer/sbm/lib.py (``SpectralDensityFunction`` / ``OhmicSDF`` :38-139, ``DebyeSDF`` :18-35,
-``ColeDavidsonSDF`` :142-202, ``param2mollist`` :205-217) - the producer of BASELINE config 2's model.  Host-side
-only; the dynamics are plain ``Mps.evolve`` calls (examples/sbm.py)."""
+``ColeDavidsonSDF`` :142-202, ``param2mollist`` :205-217) - the producer of BASELINE config 2's model, host-side
+only - and of renormalizer/sbm/sbm.py: the job ``SpinBosonDynamics``, which loads the engine when it is constructed
+(examples/sbm_dynamics.py; examples/sbm.py is the same dynamics as plain ``Mps.evolve`` calls)."""
 import logging
 
 import numpy as np
 import scipy.integrate
 
 from .model import Phonon, SpinBosonModel
-from .utils import Quantity
+from .mps.mpo import Mpo
+from .utils import CompressConfig, Quantity
+from .utils.tdmps import TdMpsJob
 
 logger = logging.getLogger("renormalizer_amd")
 
@@ -129,3 +132,59 @@ def param2model(alpha, raw_delta, omega_c, renormalization_p, n_phonons, n_phys_
     omega_list, dis_list = sdf.post_process(omega, c2)
     ph_list = [Phonon.simple_phonon(o, d, n_phys_dim) for o, d in zip(omega_list, dis_list)]
     return SpinBosonModel(Quantity(0), Quantity(delta), ph_list), delta
+
+
+class SpinBosonDynamics(TdMpsJob):
+    """Real-time dynamics of the spin-boson model (renormalizer/sbm/sbm.py:13-92): the spin starts up, every mode in
+    its vacuum, a Hartree product state; with a thermofield model (``model.thermofield``) the same job runs at finite
+    temperature.  model: a spin-boson ``Model``; auto_expand: under TDVP, pad the bonds of the product state with
+    ``expand_bond_dimension(coef=1e-16, include_ex=False)``; compress_config / evolve_config: of the state; dump_dir /
+    dump_mps / job_name: as ``TdMpsJob``.
+
+    Recorded per step: ``sigma_x``, ``sigma_z``, ``rho`` (the spin's one-site density matrix) and ``bond_entropy``
+    (N - 1 values).  ``rho`` comes from ``Mps.site_rdms`` and the entropies from ``Mps.bond_entropies``: two engine
+    calls and two host reads per step, the state stays untouched (the reference takes ``calc_1site_rdm`` and
+    ``calc_entropy("bond")``, a copy of the state and two sweeps of blocked decompositions)."""
+
+    def __init__(self, model, auto_expand: bool = True, compress_config=None, evolve_config=None, dump_dir=None,
+                 dump_mps=None, job_name=None):
+        self.model = model
+        self.h_mpo = Mpo(model)
+        self.auto_expand = auto_expand
+        self.compress_config = CompressConfig() if compress_config is None else compress_config
+        self.spin_site = next(i for i, b in enumerate(model.basis) if b.is_spin)
+        self.sigma_x = []
+        self.sigma_z = []
+        self.rho = []
+        self.bond_entropy = []
+        super().__init__(evolve_config=evolve_config, dump_dir=dump_dir, dump_mps=dump_mps, job_name=job_name)
+
+    def init_mps(self):
+        from .mps.mps import Mps
+        logger.debug(f"mpo bond and physical dimension: {self.h_mpo.bond_dims}, {self.h_mpo.pbond_list}")
+        init_mps = Mps.ground_state(self.model, False)
+        init_mps.compress_config = self.compress_config
+        init_mps.evolve_config = self.evolve_config
+        if self.evolve_config.is_tdvp and self.auto_expand:
+            init_mps = init_mps.expand_bond_dimension(self.h_mpo, coef=1e-16, include_ex=False)
+        return init_mps
+
+    def process_mps(self, mps):
+        rho = mps.site_rdms(self.spin_site)[self.spin_site]
+        self.rho.append(rho)
+        self.sigma_z.append(float((rho[0, 0] - rho[1, 1]).real))
+        self.sigma_x.append(float((rho[0, 1] + rho[1, 0]).real))
+        logger.info(f"sigma_z: {self.sigma_z[-1]}. sigma_x: {self.sigma_x[-1]}")
+        self.bond_entropy.append(mps.bond_entropies())
+
+    def evolve_single_step(self, evolve_dt):
+        return self.latest_mps.evolve(self.h_mpo, evolve_dt)
+
+    def get_dump_dict(self):
+        dump_dict = dict()
+        dump_dict["time series"] = self.evolve_times
+        dump_dict["sigma_x"] = self.sigma_x
+        dump_dict["sigma_z"] = self.sigma_z
+        dump_dict["rho"] = self.rho
+        dump_dict["bond_entropy"] = self.bond_entropy
+        return dump_dict
