@@ -339,6 +339,24 @@ int mpse_env_update_ft(mpse_ctx* ctx, int dtype, int domain, const mpse_heff_ft*
  * tn < ceil(N / 64); nbytes = ceil(N / 64) * nkw * 8.  A mask of another size is ignored.  The mask must mark every
  * tile that holds a non-zero (a superset is fine, a missing tile drops its contribution). */
 int mpse_expm_centre_mask(mpse_ctx* ctx, const void* mask_dev, int64_t nbytes);
+/* Optional, for the NEXT mpse_expm_lanczos on this context only (a pending key is left alone by
+ * mpse_expm_lanczos_batch, like the centre mask): a non-zero key that names this solve among the solves the caller
+ * repeats - in a sweep, (site or bond, direction, site-or-bond solve).  The context keeps the launch plan of the fused
+ * bond / two-level-site matvec of a keyed solve in a slot of that key; the next solve under the key re-uses it when
+ * nothing it was built from differs: shapes and MPO terms are compared on the host, the tile-occupancy flags of the
+ * environments and the centre mask on the device by the scan that computes them anyway.  Whatever differs, the plan is
+ * rebuilt before the first matvec, so the key never changes a result: every solve is bitwise its keyless self.  Key 0
+ * (or no call): no slot.  MPSE_PLAN_REUSE=0 in the environment: keys are ignored.  The key serves the asynchronous solve
+ * (the one that runs the fused matvec); a solve that takes or falls back to the synchronous path runs without it. */
+int mpse_solve_slot(mpse_ctx* ctx, int64_t key);
+/* Byte budget of the slots (default 64 MiB); beyond it the least recently used slots go, at once and whenever a slot
+ * grows.  A hook for tests, not part of the integration surface. */
+int mpse_plan_store_budget(mpse_ctx* ctx, int64_t bytes);
+/* Cumulative counts[i], i < n (zeros beyond 6): 0 keyed solves, 1 of them whose slot matched on the host, 2 host-side
+ * mismatches (shape, MPO terms, plan parameters), 3 slots evicted, 4 rebuilds of the fused matvec's plan decided on the
+ * device (first builds included), 5 rebuilds of launch orders (none is kept yet: 0).  Reads two device words back:
+ * synchronous, diagnostics only. */
+int mpse_plan_reuse_stats(mpse_ctx* ctx, int64_t* counts, int n);
 
 int mpse_expm_lanczos(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im,
                       const void* C, void* out, double rtol, double atol, int max_dim, int* nvec);

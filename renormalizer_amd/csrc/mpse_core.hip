@@ -174,7 +174,85 @@ int defer_replay(mpse_ctx* ctx, int status) {
   return status;
 }
 
+// ---- plan store (mpse_internal.h) ---------------------------------------------------------------------------------
+
+static bool plan_reuse_on() {
+  static const bool on = [] {
+    const char* e = getenv("MPSE_PLAN_REUSE");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+int plan_words(mpse_ctx* ctx) {
+  if (ctx->plan_words_dev) return MPSE_OK;
+  void* p = nullptr;
+  MPSE_TRY(mpse_malloc(ctx, 16, &p));
+  ctx->plan_words_dev = static_cast<int*>(p);
+  return device_zero(ctx, ctx->plan_words_dev, 16);
+}
+
+void SolveScope::borrow_slot(long long key) {
+  if (slot || key == 0 || !plan_reuse_on()) return;
+  ++ctx->plan_stats[mpse_ctx::PR_KEYED];
+  mpse_ctx::PlanSlot* s = ctx->plan_store.find(key);
+  if (!s) s = ctx->plan_store.insert(key);
+  if (s->borrowed) return;
+  s->borrowed = true;
+  slot = s;
+}
+
+int plan_slot_buffer(mpse_ctx* ctx, mpse_ctx::PlanSlot* slot, size_t bytes, bool* ok) {
+  *ok = false;
+  if (slot->data.buf) {
+    mpse_free(ctx, slot->data.buf);
+    slot->data = mpse_ctx::PlanSlotData();
+    ctx->plan_store.charge(slot, 0);
+  }
+  int ev = 0;
+  const bool room = ctx->plan_store.make_room(bytes, slot, [ctx](mpse_ctx::PlanSlotData& d) {
+    if (d.buf) mpse_free(ctx, d.buf);
+  }, &ev);
+  ctx->plan_stats[mpse_ctx::PR_EVICT] += ev;
+  if (!room) return MPSE_OK;
+  MPSE_TRY(plan_words(ctx));
+  void* p = nullptr;
+  MPSE_TRY(mpse_malloc(ctx, bytes, &p));
+  slot->data.buf = p;
+  ctx->plan_store.charge(slot, bytes);
+  MPSE_TRY(device_zero(ctx, p, 16));
+  *ok = true;
+  return MPSE_OK;
+}
+
 extern "C" {
+
+int mpse_solve_slot(mpse_ctx* ctx, int64_t key) {
+  if (!ctx) return MPSE_ERR_ARG;
+  ctx->slot_pending = key;
+  return MPSE_OK;
+}
+
+int mpse_plan_store_budget(mpse_ctx* ctx, int64_t bytes) {
+  if (!ctx || bytes < 0) return MPSE_ERR_ARG;
+  ctx->plan_store.budget = (size_t)bytes;
+  int ev = 0;     // slots beyond the new budget go now, least recently used first
+  ctx->plan_store.make_room(0, nullptr, [ctx](mpse_ctx::PlanSlotData& d) {
+    if (d.buf) mpse_free(ctx, d.buf);
+  }, &ev);
+  ctx->plan_stats[mpse_ctx::PR_EVICT] += ev;
+  return MPSE_OK;
+}
+
+int mpse_plan_reuse_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  MPSE_BIND(ctx);
+  int v[4] = {0, 0, 0, 0};
+  if (ctx->plan_words_dev) MPSE_TRY(mpse_memcpy_d2h(ctx, v, ctx->plan_words_dev, 16));
+  for (int i = 0; i < n; ++i)
+    counts[i] = i < mpse_ctx::PR_COUNT ? ctx->plan_stats[i] : i < mpse_ctx::PR_COUNT + 2 ? v[i - mpse_ctx::PR_COUNT] : 0;
+  return MPSE_OK;
+}
 
 int mpse_prof_enable(mpse_ctx* ctx, int on) {
   if (!ctx) return MPSE_ERR_ARG;
@@ -318,6 +396,9 @@ int mpse_ctx_destroy(mpse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   prof_drain(ctx);
+  ctx->plan_store.clear([ctx](mpse_ctx::PlanSlotData& d) {
+    if (d.buf) mpse_free(ctx, d.buf);
+  });
   for (auto e : ctx->prof_free_events) (void)hipEventDestroy(e);
   for (auto& kv : ctx->free_blocks) (void)hipFree(kv.second);
   for (auto& kv : ctx->live) (void)hipFree(kv.first);

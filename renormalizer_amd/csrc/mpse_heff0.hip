@@ -90,8 +90,10 @@ __device__ __forceinline__ void f0_transpose(double2* __restrict__ rt, const dou
 
 // flags of the 16 x 16 tiles of an environment E (D, w, D) viewed per channel: F[(rt * w + b) * nt + ct] = any non-zero in
 // rows [16 rt, 16 rt + 16), channel b, columns [16 ct, 16 ct + 16).  One block of 256 threads = one tile row (rt, b).
+// changed (a keyed solve, else null): F holds the flags of the solve before under this key - a byte that comes out
+// different raises the word (every lane that sees one stores the same 1).
 __device__ __forceinline__ void f0_flags(const double2* __restrict__ E, int D, int w, int nt, unsigned char* __restrict__ F,
-                                         int rt, int b) {
+                                         int rt, int b, int* changed) {
   __shared__ int s_f[64];
   const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
   if (threadIdx.x < 64) s_f[threadIdx.x] = 0;
@@ -102,29 +104,71 @@ __device__ __forceinline__ void f0_flags(const double2* __restrict__ E, int D, i
     if (v.x != 0.0 || v.y != 0.0) s_f[ct] = 1;
   }
   __syncthreads();
-  if ((int)threadIdx.x < nt) F[((long long)rt * w + b) * nt + threadIdx.x] = s_f[threadIdx.x] ? 1 : 0;
+  if ((int)threadIdx.x < nt) {
+    const long long i = ((long long)rt * w + b) * nt + threadIdx.x;
+    const unsigned char v = s_f[threadIdx.x] ? 1 : 0;
+    if (changed && F[i] != v) *changed = 1;
+    F[i] = v;
+  }
 }
 
 // Per-solve preparation in ONE launch (three before): blocks [0, ntl wl) flag the tiles of L, the next ntr wr blocks those
 // of R, the rest transpose R - the three jobs do not depend on each other, and a launch at the head of a solve is ~8 us
 // of latency in front of its first matvec.
+// A keyed solve (changed != null) validates the plan kept in its slot on the way: the flag blocks compare what they
+// write with what the slot holds, and nfc more blocks (in front of the transposing ones) compare the fc_bytes bytes of
+// the caller's centre mask FC with the slot's copy FCs and renew it.
 __global__ __launch_bounds__(256) void k_f0_prepare(const double2* __restrict__ L, const double2* __restrict__ R,
                                                      double2* __restrict__ rt, unsigned char* __restrict__ FL,
                                                      unsigned char* __restrict__ FR, int Dl, int Dr, int wl, int wr, int ntl,
-                                                     int ntr, const int* __restrict__ skip) {
+                                                     int ntr, const int* __restrict__ skip, int* changed,
+                                                     const unsigned char* __restrict__ FC, unsigned char* __restrict__ FCs,
+                                                     int fc_bytes, int nfc) {
   if (skip && *skip) return;
   int blk = blockIdx.x;
   if (blk < ntl * wl) {
-    f0_flags(L, Dl, wl, ntl, FL, blk / wl, blk % wl);
+    f0_flags(L, Dl, wl, ntl, FL, blk / wl, blk % wl, changed);
     return;
   }
   blk -= ntl * wl;
   if (blk < ntr * wr) {
-    f0_flags(R, Dr, wr, ntr, FR, blk / wr, blk % wr);
+    f0_flags(R, Dr, wr, ntr, FR, blk / wr, blk % wr, changed);
     return;
   }
   blk -= ntr * wr;
-  f0_transpose(rt, R, Dr, wr, blk, (int)gridDim.x - ntl * wl - ntr * wr);
+  if (blk < nfc) {
+    for (int i = blk * 256 + threadIdx.x; i < fc_bytes; i += nfc * 256) {
+      const unsigned char v = FC[i];
+      if (FCs[i] != v) *changed = 1;
+      FCs[i] = v;
+    }
+    return;
+  }
+  blk -= nfc;
+  f0_transpose(rt, R, Dr, wr, blk, (int)gridDim.x - ntl * wl - ntr * wr - nfc);
+}
+
+// Head and tail of the two planners below for a keyed solve (changed != null; slot data of mpse_ctx::plan_store).  The
+// scan in front of the planner on the stream raised *changed if one flag byte differs from what the slot's plan was built
+// from; `force`: the host already knows that the plan must be rebuilt (fresh slot, other shape or term table).
+// f0_plan_kept: true = the slot holds this launch's output, return.  A launch that the solve's skip word turns off passes a
+// forced rebuild on to the next solve under the key.
+__device__ __forceinline__ bool f0_plan_kept(const int* skip, int* changed, int force) {
+  if (skip && *skip) {
+    if (changed && force && threadIdx.x == 0) *changed = 1;
+    return true;
+  }
+  return changed && !force && *changed == 0;
+}
+// f0_plan_done: count the rebuild, then - last - clear the word
+__device__ __forceinline__ void f0_plan_done(int* changed, int* recomputes) {
+  if (!changed) return;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(recomputes, 1);
+    __threadfence();
+    *changed = 0;
+  }
 }
 
 // which parts hold which output tile: bit s = f * nkc + kc of the word of (bra tile row at, l tile lt) is set when step 1
@@ -134,8 +178,9 @@ __global__ __launch_bounds__(1024) void k_f0_valid(const unsigned char* __restri
                                                     const unsigned char* __restrict__ FR, const F0Term* __restrict__ terms,
                                                     const int* __restrict__ nterm, int wl, int wr, int d, int ntl, int ntr,
                                                     int nkc, int fc_pitch, unsigned long long* __restrict__ mask,
-                                                    const int* __restrict__ skip) {
-  if (skip && *skip) return;
+                                                    const int* __restrict__ skip, int* changed, int force,
+                                                    int* recomputes) {
+  if (f0_plan_kept(skip, changed, force)) return;
   __shared__ unsigned long long s1[64], s2[64];    // per bra tile row / per l tile: bit s
   const int nparts = wr * nkc, tid = threadIdx.x;
   if (tid < 64) s1[tid] = s2[tid] = 0;
@@ -164,6 +209,7 @@ __global__ __launch_bounds__(1024) void k_f0_valid(const unsigned char* __restri
     const int row = t / ntr, lt = t - row * ntr;
     mask[t] = s1[row / d] & s2[lt];
   }
+  f0_plan_done(changed, recomputes);
 }
 
 // Part mask AND launch order of the units of a solve in one launch (one workgroup, once per solve like the flags;
@@ -182,8 +228,9 @@ __global__ __launch_bounds__(1024) void k_f0_plan(const unsigned char* __restric
                                                    const unsigned char* __restrict__ FR, const F0Term* __restrict__ terms,
                                                    const int* __restrict__ nterm, int wl, int wr, int d, int ntl, int ntr,
                                                    int nkc, int fc_pitch, unsigned long long* __restrict__ mask, int n_cu,
-                                                   F0Info* __restrict__ info, int compact, const int* __restrict__ skip) {
-  if (skip && *skip) return;
+                                                   F0Info* __restrict__ info, int compact, const int* __restrict__ skip,
+                                                   int* changed, int force, int* recomputes) {
+  if (f0_plan_kept(skip, changed, force)) return;
   // (the caller guarantees ntl, ntr <= 64, wl, wr <= 16 and at most MROWS flag rows of each kind: heff0_fused_parts)
   constexpr int WMAX = 256, MROWS = 1024;
   __shared__ unsigned long long s1[64], s2[64];    // per bra tile row / per l tile: bit s
@@ -300,6 +347,7 @@ __global__ __launch_bounds__(1024) void k_f0_plan(const unsigned char* __restric
     if (rank >= n_cu && rank < nw) pos = n_cu + (nw - 1 - rank);
     info[pos] = I;
   }
+  f0_plan_done(changed, recomputes);
 }
 
 // A unit = (bra tile row, part, value x of the physical index of the result - 0 for a bond matrix): the terms of the other
@@ -711,50 +759,88 @@ int heff0_fused_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C,
   char* base = nullptr;
   const bool hit = fc.buf && fc.L == h->L && fc.R == h->R && fc.W == h->W0 && fc.cmask == (const void*)FC && fc.Dl == Dl &&
                    fc.Dr == Dr && fc.w == wr && fc.nsite == h->nsite;
-  const size_t o_fl = rt_bytes, o_fr = o_fl + fl_bytes, o_tm = o_fr + fr_bytes, o_nt = o_tm + tm_bytes, o_mk = o_nt + nt_bytes;
-  const size_t o_od = o_mk + mk_bytes, tot_bytes = o_od + od_bytes;
+  // the plan data (offsets from `plan`): in the solve's own buffer behind Rt, or - a keyed solve - in the slot's buffer
+  // behind its word, followed there by the slot's copy of the centre mask
+  const size_t o_fl = 0, o_fr = o_fl + fl_bytes, o_tm = o_fr + fr_bytes, o_nt = o_tm + tm_bytes, o_mk = o_nt + nt_bytes;
+  const size_t o_od = o_mk + mk_bytes, o_fc = o_od + od_bytes;
+  const size_t fc_bytes = FC ? size_t(sc->cmask.bytes) : 0, plan_bytes = o_fc + ((fc_bytes + 15) & ~size_t(15));
   // MPSE_F0_ORDER=0: launch positions in plain unit order (as before round 6)
   static const bool order_on = [] {
     const char* e = getenv("MPSE_F0_ORDER");
     return !(e && e[0] == '0');
   }();
-  if (hit) {
-    base = static_cast<char*>(fc.buf);
-  } else {
-    void* p = nullptr;
+  if (!hit) {
     if (fc.buf) mpse_free(ctx, fc.buf);
     fc = SolveScope::F0Cache();
-    MPSE_TRY(mpse_malloc(ctx, tot_bytes, &p));
-    fc.buf = p, fc.L = h->L, fc.R = h->R, fc.W = h->W0, fc.cmask = FC, fc.Dl = Dl, fc.Dr = Dr, fc.w = wr, fc.nsite = h->nsite;
-    base = static_cast<char*>(p);
-    {   // terms | term counts: adjacent in the buffer, one upload
-      std::vector<char> up(tm_bytes + nt_bytes, 0);
-      memcpy(up.data(), terms.data(), tm_bytes);
-      memcpy(up.data() + tm_bytes, nterm.data(), size_t(wr) * sizeof(int));
-      MPSE_TRY(stage_h2d(ctx, base + o_tm, up.data(), up.size()));
+    // terms | term counts: adjacent in the buffer, one upload
+    std::vector<char> up(tm_bytes + nt_bytes, 0);
+    memcpy(up.data(), terms.data(), tm_bytes);
+    memcpy(up.data() + tm_bytes, nterm.data(), size_t(wr) * sizeof(int));
+    // a keyed solve: the plan data are the slot's when the host finds nothing different (mpse_plan_store.h); the device
+    // compares the rest.  Any mismatch renews the slot and forces the planner.
+    const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+    char* plan = nullptr;
+    int* changed = nullptr;
+    int force = 1;
+    mpse_ctx::PlanSlotData* renew = nullptr;     // the slot's host record to bring up to date once the launches are out
+    mpse_store::F0Sig renew_sig;
+    // (the first plan of the solve only: a solve whose operands alternate - C inside and outside the Krylov range, so
+    // that the centre mask comes and goes - would otherwise replace the slot's plan at every turn and never re-use it;
+    // its later plans are the scope's own, as without a key)
+    if (mpse_ctx::PlanSlot* slot = sc->slot_f0_taken ? nullptr : sc->slot) {
+      sc->slot_f0_taken = true;
+      mpse_ctx::PlanSlotData& sd = slot->data;
+      const mpse_store::F0Sig sig{Dl, Dr, wl, wr, d, h->nsite, n_cu, compact ? 1 : 0, fc_pitch, (int)fc_bytes, order_on ? 1 : 0};
+      const mpse_store::F0Match m = mpse_store::f0_match(sd.have_f0, sd.sig, sd.terms, sig, up.data(), up.size());
+      bool have = sd.buf != nullptr;
+      if (m == mpse_store::F0_FRESH || m == mpse_store::F0_SHAPE) MPSE_TRY(plan_slot_buffer(ctx, slot, 16 + plan_bytes, &have));
+      if (have) {
+        plan = static_cast<char*>(sd.buf) + 16;
+        changed = static_cast<int*>(sd.buf);
+        if (m == mpse_store::F0_HIT) {
+          force = 0;
+          ++ctx->plan_stats[mpse_ctx::PR_HITS];
+        } else {
+          if (m != mpse_store::F0_FRESH) ++ctx->plan_stats[mpse_ctx::PR_MISMATCH];
+          sd.have_f0 = false;      // (until the upload and the forced planner are enqueued: an error in between
+          renew = &sd, renew_sig = sig;   //  must not leave a record that matches data that never arrived)
+        }
+      }
     }
+    void* p = nullptr;
+    MPSE_TRY(mpse_malloc(ctx, rt_bytes + (plan ? 0 : plan_bytes), &p));
+    fc.buf = p, fc.L = h->L, fc.R = h->R, fc.W = h->W0, fc.cmask = FC, fc.Dl = Dl, fc.Dr = Dr, fc.w = wr, fc.nsite = h->nsite;
+    fc.plan = plan ? plan : static_cast<char*>(p) + rt_bytes;
+    char* const pl = static_cast<char*>(fc.plan);
+    if (force) MPSE_TRY(stage_h2d(ctx, pl + o_tm, up.data(), up.size()));
     const long long nel = (long long)wr * Dr * Dr;
     int nb = (int)((nel + 255) / 256);
     if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(k_f0_prepare, dim3(ntl * wl + ntr * wr + nb), dim3(256), 0, ctx->stream,
-                       static_cast<const double2*>(h->L), static_cast<const double2*>(h->R), reinterpret_cast<double2*>(base),
-                       reinterpret_cast<unsigned char*>(base + o_fl), reinterpret_cast<unsigned char*>(base + o_fr), Dl, Dr, wl,
-                       wr, ntl, ntr, skip);
+    const int nfc = changed && FC ? 1 : 0;
+    hipLaunchKernelGGL(k_f0_prepare, dim3(ntl * wl + ntr * wr + nfc + nb), dim3(256), 0, ctx->stream,
+                       static_cast<const double2*>(h->L), static_cast<const double2*>(h->R), static_cast<double2*>(p),
+                       reinterpret_cast<unsigned char*>(pl + o_fl), reinterpret_cast<unsigned char*>(pl + o_fr), Dl, Dr, wl,
+                       wr, ntl, ntr, skip, changed, FC, reinterpret_cast<unsigned char*>(pl + o_fc), (int)fc_bytes, nfc);
     if (order_on)
-      hipLaunchKernelGGL(k_f0_plan, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const unsigned char*>(base + o_fl), FC,
-                         reinterpret_cast<const unsigned char*>(base + o_fr), reinterpret_cast<const F0Term*>(base + o_tm),
-                         reinterpret_cast<const int*>(base + o_nt), wl, wr, d, ntl, ntr, nkc, fc_pitch,
-                         reinterpret_cast<unsigned long long*>(base + o_mk), ctx->n_cu > 0 ? ctx->n_cu : 256,
-                         reinterpret_cast<F0Info*>(base + o_od), compact ? 1 : 0, skip);
+      hipLaunchKernelGGL(k_f0_plan, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const unsigned char*>(pl + o_fl), FC,
+                         reinterpret_cast<const unsigned char*>(pl + o_fr), reinterpret_cast<const F0Term*>(pl + o_tm),
+                         reinterpret_cast<const int*>(pl + o_nt), wl, wr, d, ntl, ntr, nkc, fc_pitch,
+                         reinterpret_cast<unsigned long long*>(pl + o_mk), n_cu, reinterpret_cast<F0Info*>(pl + o_od),
+                         compact ? 1 : 0, skip, changed, force, ctx->plan_words_dev);
     else
-      hipLaunchKernelGGL(k_f0_valid, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const unsigned char*>(base + o_fl), FC,
-                         reinterpret_cast<const unsigned char*>(base + o_fr), reinterpret_cast<const F0Term*>(base + o_tm),
-                         reinterpret_cast<const int*>(base + o_nt), wl, wr, d, ntl, ntr, nkc, fc_pitch,
-                         reinterpret_cast<unsigned long long*>(base + o_mk), skip);
+      hipLaunchKernelGGL(k_f0_valid, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const unsigned char*>(pl + o_fl), FC,
+                         reinterpret_cast<const unsigned char*>(pl + o_fr), reinterpret_cast<const F0Term*>(pl + o_tm),
+                         reinterpret_cast<const int*>(pl + o_nt), wl, wr, d, ntl, ntr, nkc, fc_pitch,
+                         reinterpret_cast<unsigned long long*>(pl + o_mk), skip, changed, force, ctx->plan_words_dev);
+    if (renew) {
+      MPSE_HIP(ctx, hipGetLastError());
+      renew->have_f0 = true, renew->sig = renew_sig, renew->terms = up;
+    }
   }
+  base = static_cast<char*>(fc.plan);
   F0Args g{};
   g.L = static_cast<const double*>(h->L);
-  g.Rt = reinterpret_cast<const double*>(base);
+  g.Rt = static_cast<const double*>(fc.buf);
   g.C = static_cast<const double*>(C);
   g.parts = static_cast<double*>(pr.ptr);
   g.FL = reinterpret_cast<const unsigned char*>(base + o_fl);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/mpsengine.h"
+#include "mpse_plan_store.h"
 
 struct mpse_ctx {
   int device = 0;
@@ -114,6 +115,26 @@ struct mpse_ctx {
     const void* ptr = nullptr;
     long long bytes = 0;
   } cmask_pending;
+  // Plan store: device data of a local solve that the NEXT solve under the same caller's key (mpse_solve_slot) finds
+  // unchanged when the tile structure of its operands is unchanged - the plan of the fused matvec (mpse_heff0.hip: tile
+  // flags, term table, part mask, launch records).  A slot owns one device buffer, [0, 16) of it the word `changed`
+  // that the scan kernels raise and the planner clears; the host remembers what it compares itself (mpse_plan_store.h).
+  // Slots go least recently used first under plan_store.budget bytes, and with the context.  slot_pending waits for the
+  // next mpse_expm_lanczos like cmask_pending.  MPSE_PLAN_REUSE=0: keys are ignored.
+  struct PlanSlotData {
+    void* buf = nullptr;
+    bool have_f0 = false;
+    mpse_store::F0Sig sig;
+    std::vector<char> terms;       // term table | term counts as uploaded
+  };
+  using PlanSlot = mpse_store::Table<PlanSlotData>::Slot;
+  mpse_store::Table<PlanSlotData> plan_store;
+  long long slot_pending = 0;
+  // two device words, bumped by the planners when they do run: [0] k_f0_plan / k_f0_valid of keyed solves (diagnostics,
+  // mpse_plan_reuse_stats; context-wide, so that the sum outlives evicted slots); allocated by plan_words()
+  int* plan_words_dev = nullptr;
+  enum PlanStat { PR_KEYED, PR_HITS, PR_MISMATCH, PR_EVICT, PR_COUNT };
+  long long plan_stats[PR_COUNT] = {0};
   // Debug: per-workgroup timeline of the contraction kernel (MPSE_GEMM_TRACE=<file>): every workgroup appends one
   // record (grid, K tiles multiplied, s_memtime stamps of its phases); mpse_prof_get writes the file.
   unsigned long long* gemm_trace = nullptr;   // [1 + GEMM_TRACE_CAP * GEMM_TRACE_WORDS] words: counter, then records
@@ -176,7 +197,17 @@ struct mpse_ctx {
   enum BondSpecStat { BS_CHAIN, BS_ENQUEUED, BS_SITES, BS_BONDS, BS_MAX_SWEEPS, BS_COUNT };
   long long bondspec_stats[BS_COUNT] = {0};
 };
+// What the caller of mpse_expm_lanczos said about the one solve that follows (mpse_expm_centre_mask, mpse_solve_slot):
+// taken out of the context on entry and handed down as an argument to the scope of the asynchronous solve
+struct SolveHints {
+  mpse_ctx::CMask cmask;
+  long long slot_key = 0;
+};
 int qr_words(mpse_ctx* ctx);     // allocate + zero ctx->qr_words_dev once (mpse_qr.hip)
+int plan_words(mpse_ctx* ctx);   // allocate + zero ctx->plan_words_dev once (mpse_core.hip)
+// The slot's device buffer becomes one of `bytes` bytes (its first 16 the zeroed word `changed`): room is made under the
+// budget by evicting other slots; *ok = false when that cannot be done (the caller goes on as without a key).
+int plan_slot_buffer(mpse_ctx* ctx, mpse_ctx::PlanSlot* slot, size_t bytes, bool* ok);
 
 int mpse_fail(mpse_ctx* ctx, int code, const char* fmt, ...);
 // Makes ctx->device the calling thread's current HIP device (a new thread starts on device 0; allocations and
@@ -302,9 +333,15 @@ static inline mpse_index idx2(int64_t hi_ext, int64_t lo_ext, int64_t s_hi, int6
 // handed by pointer to every matvec of it; null outside a solve.  The scope owns the device data that the matvecs of its
 // solve compute once and share - masks, launch orders, the transposed right environment, the data of the fused matvec:
 // a matvec fills them through the pointer it was given, and the end of the scope frees exactly these and nothing else.
-// The context keeps none of it, so scopes do not see each other's data.
+// The context keeps one thing across solves: the plan data of a KEYED solve (mpse_solve_slot), in the slot of that key
+// (mpse_ctx::plan_store).  The scope borrows the slot for its lifetime and hands it back, never frees it.  A stale slot
+// cannot be observed: what the plan was built from is compared again at every solve - shapes and term table on the
+// host, every flag byte on the device by the scan that writes it - and the planner, next on the stream, rebuilds the
+// plan before the first matvec whenever one of them differs.  Without a key the scope keeps everything itself, as before.
 struct SolveScope {
   mpse_ctx* ctx;
+  mpse_ctx::PlanSlot* slot = nullptr;   // borrowed (borrow_slot), null: keyless
+  bool slot_f0_taken = false;           // the slot serves the FIRST fused-matvec plan of the solve (mpse_heff0.hip)
   // device word that turns every contraction launch into a no-op once it is non-zero: the asynchronous Lanczos solve,
   // whose iterations are enqueued ahead of the convergence decision
   const int* skip = nullptr;
@@ -348,6 +385,7 @@ struct SolveScope {
   // operands replace it
   struct F0Cache {
     void* buf = nullptr;
+    void* plan = nullptr;      // flags, terms, part mask, launch records: inside buf, or the slot's buffer past its word
     const void *L = nullptr, *R = nullptr, *W = nullptr, *cmask = nullptr;
     int Dl = 0, Dr = 0, w = 0, nsite = -1;
   } f0;
@@ -360,7 +398,10 @@ struct SolveScope {
     for (auto& e : perm_cache) mpse_free(ctx, e.perm);
     if (f0.buf) mpse_free(ctx, f0.buf);
     if (small_rt.rt) mpse_free(ctx, small_rt.rt);
+    if (slot) slot->borrowed = false;
   }
+  // takes the slot of `key` for this solve (0, MPSE_PLAN_REUSE=0 or a slot in use: none); mpse_core.hip
+  void borrow_slot(long long key);
   bool in_env(const void* p) const {
     const char* c = static_cast<const char*>(p);
     return keeps_env_masks && ((c >= env_lo[0] && c < env_hi[0]) || (c >= env_lo[1] && c < env_hi[1]));

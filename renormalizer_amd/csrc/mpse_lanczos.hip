@@ -794,9 +794,10 @@ void keep_env_masks(SolveScope& sc, const mpse_heff* h) {
 constexpr int LZ_FALLBACK = -77;   // internal: the asynchronous solve hands the problem to the synchronous one
 constexpr int LZ_BADSTART = -78;   // internal: |C|^2 outside [LZ_N2_MIN, LZ_N2_MAX) (expm_lanczos_solve decides)
 
-// cmask: the caller's structural mask of the centre (empty: none); it describes the Krylov vectors of this solve
+// hints: the caller's structural mask of the centre (empty: none; it describes the Krylov vectors of this solve) and its
+// key of the solve's plan slot (0: none).  Only this solve uses them: the synchronous one it may hand over to has neither.
 int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::complex<double> dt, const void* Cin, void* out,
-                       double rtol, double atol, int max_dim, int* nvec, int64_t n, mpse_ctx::CMask cmask) {
+                       double rtol, double atol, int max_dim, int* nvec, int64_t n, const SolveHints& hints) {
   const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
   const int64_t nd = n * (cplx ? 2 : 1);
@@ -831,7 +832,8 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
   SolveScope scope(ctx);
   scope.skip = done;
   keep_env_masks(scope, h);
-  scope.cmask = cmask;
+  scope.cmask = hints.cmask;
+  scope.borrow_slot(hints.slot_key);
 
   // the structural mask of the centre also serves the vector kernels of this solve (square operators on complex vectors
   // whose rows are whole multiples of 64 elements)
@@ -1177,10 +1179,10 @@ int expm_lanczos_sync(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::complex
 // One attempt at C as it is: the asynchronous solve where it applies, behind it the synchronous one.  LZ_BADSTART: |C|^2
 // is outside what the recurrence takes (expm_lanczos_solve decides); the arguments are checked there.
 int lanczos_attempt(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin, void* out,
-                    double rtol, double atol, int max_dim, int* nvec, int64_t n, bool async_first, mpse_ctx::CMask cmask) {
+                    double rtol, double atol, int max_dim, int* nvec, int64_t n, bool async_first, const SolveHints& hints) {
   const std::complex<double> dt(dt_re, dt_im);
   if (async_first && lanczos_async_enabled() && n > 256) {
-    const int st = expm_lanczos_async(ctx, dtype, h, dt, Cin, out, rtol, atol, max_dim, nvec, n, cmask);
+    const int st = expm_lanczos_async(ctx, dtype, h, dt, Cin, out, rtol, atol, max_dim, nvec, n, hints);
     if (st != LZ_FALLBACK) return st;
   }
   return expm_lanczos_sync(ctx, dtype, h, dt, Cin, out, rtol, atol, max_dim, nvec, n);
@@ -1190,9 +1192,9 @@ int lanczos_attempt(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, 
 // cannot take as it is (LZ_BADSTART) is zero or not finite - an error - or a nonzero C whose squared norm is subnormal or
 // beyond 1e300.  That one is solved as 2^e C, its largest element in [1, 2), with atol scaled alike, and the result scaled
 // back by 2^-e: the same stopping decisions, exact scalings.  Rare, and outside every iteration: C goes through the host once.
-// cmask: the caller's structural mask of the centre for this solve (empty: none) - both attempts receive it.
+// hints: the caller's centre mask and slot key for this solve (SolveHints; empty: none) - both attempts receive them.
 int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re, double dt_im, const void* Cin, void* out,
-                       double rtol, double atol, int max_dim, int* nvec, mpse_ctx::CMask cmask, bool async_first = true) {
+                       double rtol, double atol, int max_dim, int* nvec, const SolveHints& hints, bool async_first = true) {
   const bool cplx = dtype == MPSE_C128;
   if (!cplx && dt_im != 0.0)
     return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: complex time step needs a complex128 centre tensor");
@@ -1211,7 +1213,7 @@ int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_r
     if (o0 != c0 && o0 < c0 + bytes && c0 < o0 + bytes)
       return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: out overlaps C without being C");
   }
-  int st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, n, async_first, cmask);
+  int st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, n, async_first, hints);
   if (st != LZ_BADSTART) return st;
   const int64_t nd = n * (cplx ? 2 : 1);
   std::vector<double> hv(static_cast<size_t>(nd));
@@ -1228,7 +1230,7 @@ int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_r
   MPSE_TRY(S.alloc(size_t(nd) * sizeof(double)));
   MPSE_TRY(mpse_memcpy_h2d(ctx, S.p, hv.data(), size_t(nd) * sizeof(double)));
   ++ctx->lz_paths[mpse_ctx::LP_RESCALE];
-  st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, S.p, out, rtol, std::ldexp(atol, e), max_dim, nvec, n, true, cmask);
+  st = lanczos_attempt(ctx, dtype, h, dt_re, dt_im, S.p, out, rtol, std::ldexp(atol, e), max_dim, nvec, n, true, hints);
   if (st == LZ_BADSTART) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: start vector out of range after scaling");
   if (st == MPSE_OK || st == MPSE_ERR_NOCONV) {   // (NOCONV leaves its last estimate in out as well)
     hipLaunchKernelGGL((k_scal<false>), dim3(ew_blocks(nd)), dim3(256), 0, ctx->stream, (double*)out, (long long)nd,
@@ -1397,7 +1399,7 @@ int expm_lanczos_batch_set(mpse_ctx* ctx, int dtype, const BatchSet& bs, const m
     const int i = bs.idx[m];
     int nv = 0;
     const int st = expm_lanczos_solve(ctx, dtype, &hs[i], dt.real(), dt.imag(), member_ptr(vec(0), m, mstride), outs[i],
-                                      rtol, atol, max_dim, &nv, mpse_ctx::CMask(), hc[m].bad != 0);
+                                      rtol, atol, max_dim, &nv, SolveHints(), hc[m].bad != 0);
     if (nvec) nvec[i] = nv;
     st_out[i] = st;
     if (st != MPSE_OK) msg[i] = ctx->err;
@@ -1427,8 +1429,10 @@ int mpse_expm_lanczos(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_re
   // calls recorded by the caller for the time the result exists (QR of the new centre, environment update, absorption
   // of a bond factor) are issued here, before control goes back to the host language
   // a mask is good for the one solve it was set for, whatever path that takes: it leaves the context here
-  const mpse_ctx::CMask cmask = std::exchange(ctx->cmask_pending, mpse_ctx::CMask());
-  const int st = expm_lanczos_solve(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, cmask);
+  SolveHints hints;
+  hints.cmask = std::exchange(ctx->cmask_pending, mpse_ctx::CMask());
+  hints.slot_key = std::exchange(ctx->slot_pending, 0LL);    // (the same rule for the key of the solve, mpse_solve_slot)
+  const int st = expm_lanczos_solve(ctx, dtype, h, dt_re, dt_im, Cin, out, rtol, atol, max_dim, nvec, hints);
   return defer_replay(ctx, st);
 }
 
@@ -1509,7 +1513,7 @@ int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff
       continue;
     }
     int nv = 0;
-    st[i] = expm_lanczos_solve(ctx, dtype, &h[i], dt_re, dt_im, C[i], out[i], rtol, atol, max_dim, &nv, mpse_ctx::CMask());
+    st[i] = expm_lanczos_solve(ctx, dtype, &h[i], dt_re, dt_im, C[i], out[i], rtol, atol, max_dim, &nv, SolveHints());
     if (nvec) nvec[i] = nv;
     if (st[i] != MPSE_OK) msg[i] = ctx->err;
   }

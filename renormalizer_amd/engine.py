@@ -134,6 +134,9 @@ _SIGNATURES = {
     "mpse_nrm2": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, _dblp],
     "mpse_scaled_rms": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, _dblp],
     "mpse_expm_centre_mask": [C.c_void_p, C.c_void_p, C.c_int64],
+    "mpse_solve_slot": [C.c_void_p, C.c_int64],
+    "mpse_plan_store_budget": [C.c_void_p, C.c_int64],
+    "mpse_plan_reuse_stats": [C.c_void_p, C.POINTER(C.c_int64), C.c_int],
     "mpse_defer_begin": [C.c_void_p, C.c_int],
     "mpse_defer_end": [C.c_void_p],
     "mpse_defer_arm": [C.c_void_p, C.c_int],
@@ -1048,6 +1051,13 @@ class Engine:
         """{path: count}: how the contraction kernel was launched by this context, cumulative
         (``mpse_gemm_path_stats``; the names follow the order of include/mpsengine.h)."""
         return self._stats_dict(self.lib.mpse_gemm_path_stats, self.GEMM_PATHS)
+
+    PLAN_REUSE = ("keyed", "hits", "mismatches", "evictions", "fused_rebuilds", "order_rebuilds")
+
+    def plan_reuse_stats(self):
+        """{name: count} of ``mpse_plan_reuse_stats``: keyed solves (``mpse_solve_slot``), how their slots matched, and
+        how often the device rebuilt a kept plan; cumulative, reads the device (synchronous)."""
+        return self._stats_dict(self.lib.mpse_plan_reuse_stats, self.PLAN_REUSE)
 
     def wfold_path_stats(self):
         """{"grouped_mix": grouped launches that formed their beta term in the epilogue from blocks of the MPO site,

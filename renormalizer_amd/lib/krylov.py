@@ -30,6 +30,8 @@ def expm_krylov(Afunc, dt, vstart, block_size=50, rtol=1e-5, atol=1e-8, out=None
         nv = C.c_int()
         if Afunc.cmask is not None:
             eng._check(eng.lib.mpse_expm_centre_mask(eng.ctx, Afunc.cmask.ptr, Afunc.cmask.nbytes))
+        if Afunc.slot:
+            eng._check(eng.lib.mpse_solve_slot(eng.ctx, Afunc.slot))
         eng._check(eng.lib.mpse_expm_lanczos(eng.ctx, v.code, C.byref(Afunc.heff), dt.real, dt.imag, v.ptr, out.ptr,
                                              rtol, atol, 0, C.byref(nv)))
         return out, nv.value

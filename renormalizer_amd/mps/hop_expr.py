@@ -23,6 +23,7 @@ class Hop:
         self.nsite = nsite
         self.cshape = cshape
         self.cmask = None          # optional structural tile mask of the centre (centre_tile_mask), used by expm_krylov
+        self.slot = 0              # optional key of the solve among those its caller repeats (mpse_solve_slot), used by expm_krylov
         self.l = eng.asdevice(ltensor)
         self.r = eng.asdevice(rtensor)
         if self.twolayer:

@@ -1673,6 +1673,13 @@ class Mps:
         return sw.finish()
 
 
+def _solve_slot(imps, to_right, bond):
+    """Key of a local solve of the TDVP-PS sweep for ``mpse_solve_slot``: the solve of site ``imps`` (or of the bond
+    factor split off it) in one sweep direction recurs once per evolve with the same tile structure as long as the
+    bonds' quantum numbers stay, and the engine then re-uses its launch plans.  Non-zero."""
+    return 1 + ((int(imps) * 2 + (1 if to_right else 0)) * 2 + (1 if bond else 0))
+
+
 class _PsSweep:
     """One trajectory's TDVP-PS step (``Mps._evolve_tdvp_ps_sweeps``): the working copy of the state, its environments and
     QR notes, and the per-site pieces of a sweep - ``prepare`` / ``split_site`` / ``absorb`` / ``note_qr``.  The single
@@ -1720,6 +1727,7 @@ class _PsSweep:
         mps, eng, n = self.mps, self.eng, self.n
         hop = hop_expr(self.environ.read("L", imps - 1), self.environ.read("R", imps + 1), [self.mpo.device(imps, eng)],
                        shape)
+        hop.slot = _solve_slot(imps, mps.to_right, False)
         split = (not mps.to_right and imps != 0) or (mps.to_right and imps != n - 1)
         qnbigl = qnbigr = plan = None
         if split:
@@ -1753,6 +1761,7 @@ class _PsSweep:
             mps.qnidx = imps - 1
             r_array = environ.GetLR("R", imps, mps, mpo, itensor=r_array, method="System", canonical=True)
             hop_b = hop_expr(l_array, r_array, [], u.shape)
+            hop_b.slot = _solve_slot(imps, mps.to_right, True)
             if self.use_cmask and u.shape[0] * u.shape[1] >= (1 << 14):
                 # structural tile mask of the bond factor (rows: the left bond, columns: the new bond's states)
                 hop_b.cmask = centre_tile_mask(eng, qnbigl, np.array(qnrset, dtype=int).reshape(-1, q), mps.qntot,
@@ -1763,6 +1772,7 @@ class _PsSweep:
         mps.qnidx = imps + 1
         l_array = environ.GetLR("L", imps, mps, mpo, itensor=l_array, method="System", canonical=True)
         hop_b = hop_expr(l_array, r_array, [], vt.shape)
+        hop_b.slot = _solve_slot(imps, mps.to_right, True)
         if self.use_cmask and vt.shape[0] * vt.shape[1] >= (1 << 14):
             hop_b.cmask = centre_tile_mask(eng, np.array(qnlset, dtype=int).reshape(-1, q), qnbigr, mps.qntot,
                                            vt.shape)
