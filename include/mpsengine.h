@@ -853,6 +853,53 @@ int mpse_mps_bond_spectra_stats(mpse_ctx* ctx, int64_t* counts, int n);
  * No context, no device work. */
 int mpse_mps_bond_spectra_plan(int nsite, const int64_t* dims, int nsel, int any_complex, int64_t* info, int n);
 
+/* ------------------------------- expectation values of a list of MPOs against one chain */
+
+/* out[m] = <psi| O_m |psi>, m < nop, for MPOs O_m against ONE chain (the bra is the conjugate of the ket) in one call
+ * with one host read; replaces the loop of mps/mp.py expectations.  O_m is the identity outside its window
+ * [first[m], last[m]] and is given by the MPO sites of the window alone.
+ *   sites, dtype, dims  : as mpse_mps_rdm1 (rows D_l, d, danc, D_r; the ancilla leg of density-operator sites is traced)
+ *   first, last         : nop windows, 0 <= first[m] <= last[m] < nsite; windows may repeat and overlap
+ *   W, w_dtype          : the device MPO sites (wl, d, d, wr) of the windows, one window after the other (sum of the
+ *                         window lengths entries); the first physical leg meets the conjugated tensor
+ *   wdims               : (wl, wr) per MPO site; per window a chain of bonds that starts and ends at 1
+ *   out_host            : 2 nop doubles, (re, im) per operator
+ * An operator that is the identity everywhere is passed as a window of one site holding the identity and returns
+ * <psi|psi>.  Null pointers, nop < 1 and unknown dtypes: MPSE_ERR_ARG; a window outside the chain or with first > last,
+ * MPO bonds that do not match, a table that is no chain: MPSE_ERR_SHAPE; all before any device work, out_host as it
+ * was.  Calls that pass mpse_mps_expect_many_plan run as TWO kernels with no host read between them: k_expect_envs (two
+ * workgroups, the walks of k_bondspec_envs; they leave the identity environments L and R of every distinct window edge
+ * in pooled memory; the edges of the chain are the 1 x 1 sentinel) and k_expect_windows (one workgroup per operator: L
+ * into LDS as the transfer tensor (D, 1, D), the site step of k_sandwich_chain over the window, the closing against R
+ * as a block sum in a fixed order; launched again within the call when there are more operators than info[8]).  Every
+ * other call runs the same environments as enqueued products, each window as the environment updates that
+ * mpse_mps_sandwich enqueues and every closing as a product into one device result.  Working dtype complex as soon as
+ * any tensor is; an all-real call returns exact zero imaginary parts.  No atomics, no flags, a fixed summation order:
+ * the same inputs give the same bits on every call (the two paths sum in different orders and agree to rounding).
+ * MPSE_EXPECT_CHAIN=0 / =1 as MPSE_CORR_CHAIN.  Synchronous; refused while a deferred list is being recorded. */
+int mpse_mps_expect_many(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype,
+                         const int64_t* dims /* nsite x 4 */, int nop, const int* first, const int* last,
+                         const void* const* W, const int* w_dtype, const int64_t* wdims /* MPO sites x 2 */,
+                         double* out_host);
+/* counts[i], i < n, cumulative:  0 calls taken by the chain kernels, 1 calls taken by the enqueued path, 2 sites walked
+ * (nsite per call), 3 values returned (nop per call).  A refused call counts nothing.  Diagnostics for tests; no device
+ * work. */
+int mpse_mps_expect_many_stats(mpse_ctx* ctx, int64_t* counts, int n);
+/* The path rule, on the dims tables alone: returns 1 when the chain kernels take the call, else 0 (also for tables
+ * mpse_mps_expect_many refuses).  The launches FIT when the walks fit (mpse_mps_rdm1_plan), every MPO bond is
+ * <= info[15], the widest window site needs at most info[17] accumulators per thread, info[15] * ceil(D_r D_r /
+ * info[5]), and E (D w rows of D | 1 elements, the largest over the window bonds) plus the largest slice of T (D_l wl
+ * D_r) plus a word per wave are within info[1] bytes in the working dtype; the kernels TAKE a call that fits when every
+ * bond of the state is also <= info[0] (profiles/expect_many.md).  info[i], i < n (may be NULL): 0 to 11 as for
+ * mpse_mps_rdm1_plan (7: table AND windows are valid; 8: the workgroups of one k_expect_windows launch; 2 and 11 the
+ * larger of the two launches), then
+ *   12  LDS elements of E in k_expect_windows    13  of its slice of T    14  the largest MPO bond
+ *   15  MPO channels a thread holds    16  accumulators the widest window site needs    17  accumulators a thread has
+ *   18  bytes of a working element (8 or 16)
+ * No context, no device work. */
+int mpse_mps_expect_many_plan(int nsite, const int64_t* dims, int nop, const int* first, const int* last,
+                              const int64_t* wdims, int any_complex, int64_t* info, int n);
+
 /* Which renormalised basis states to keep, replaces select_basis of mps/lib.py:253-322 (the index selection; the
  * column copies are mpse_gather_cols / mpse_gather_rows): an equal quota int(m_max * percent / nblocks) per
  * quantum-number block (ascending block id, descending weight inside a block), the remaining slots by descending

@@ -24,12 +24,15 @@ def __getattr__(name):
     if name == "optimize_mps":
         from .mps.gs import optimize_mps
         return optimize_mps
-    if name in ("MpDm", "thermal_state", "BraKetPair"):
+    if name in ("MpDm", "thermal_state", "ThermalProp", "BraKetPair"):
         from . import mps as _mps
         return getattr(_mps, name)
     if name in ("ChargeDiffusionDynamics", "InitElectron", "EDGE_THRESHOLD", "calc_r_square"):
         from . import transport as _transport
         return getattr(_transport, name)
+    if name in ("Property", "property"):
+        from . import property as _property
+        return _property if name == "property" else _property.Property
     if name == "SpinBosonDynamics":
         from .sbm import SpinBosonDynamics
         return SpinBosonDynamics

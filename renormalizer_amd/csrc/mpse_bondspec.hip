@@ -9,7 +9,7 @@
 // No inverse: a rank-deficient L (a padded bond) only puts zero rows and columns into M.  Two paths, chosen from the dims
 // table alone (bondspec_plan):
 //   chain      two launches, for chains whose bonds are at most BS_BOND_MAX.  k_bondspec_envs: the two walks of
-//              k_rdm1_envs; workgroup 0 walks right to left and leaves R of every selected bond in pooled memory,
+//              k_rdm1_envs as mpse_chain_walk.h has them for bonds (walk_bonds_right / walk_bonds_left); workgroup 0 walks right to left and leaves R of every selected bond in pooled memory,
 //              workgroup 1 left to right and leaves L.  k_bondspec_eig: one workgroup per selected bond, two Hermitian
 //              eigensolves in LDS by a cyclic two-sided Jacobi (bs_jacobi).
 //   enqueued   the two passes as products of the contraction kernel, the two solves of a bond through the block SVD
@@ -69,49 +69,6 @@ BsPlan bondspec_plan(int nsite, const int64_t* dims, int nsel, bool cplx) {
   return pl;
 }
 
-// Workgroup 0 of k_bondspec_envs.  R behind the last site is 1.  Per site from the right down to the one right of the
-// first selected bond, the transfer of rd_walk_right (mpse_rdm1.hip); R of a selected bond goes to the pooled buffer as
-// it is.
-template <bool CPLX>
-__device__ void bs_walk_right(const BsSite* __restrict__ sites, int nsite, int first, ChainT<CPLX>* R, ChainT<CPLX>* Ts,
-                              ChainT<CPLX>* pool) {
-  walk_env_one<CPLX>(R);
-  for (int i = nsite - 1; i > first; --i) {
-    const BsSite s = sites[i];
-    const int p = s.d * s.danc, row = p * s.Dr, nE = s.Dl * s.Dl;
-    ChainT<CPLX> acc[CHAIN_OUT_PER_THREAD];
-    walk_acc_zero<CPLX>(acc);
-    for (int sa = 0; sa < p; ++sa) {
-      walk_right_slice<CPLX>(s, row, sa * s.Dr, R, Ts);
-      walk_acc_add<CPLX, false>(s, row, sa * s.Dr, Ts, nE, acc);
-      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of R is done as well
-    }
-    walk_acc_store<CPLX>(acc, s.Dl, R);
-    if (s.rsel >= 0) walk_env_to_pool<CPLX, false>(R, s.Dl, pool + s.roff);
-  }
-}
-
-// Workgroup 1: the sibling of chain_walk_left that leaves L BEHIND a site (the bond right of it) and ends behind site
-// `last`, the one left of the last selected bond
-template <bool CPLX>
-__device__ void bs_walk_left(const BsSite* __restrict__ sites, int last, ChainT<CPLX>* E, ChainT<CPLX>* Ts,
-                             ChainT<CPLX>* pool) {
-  walk_env_one<CPLX>(E);
-  for (int i = 0; i <= last; ++i) {
-    const BsSite s = sites[i];
-    const int p = s.d * s.danc, row = p * s.Dr, nE = s.Dr * s.Dr;
-    ChainT<CPLX> acc[CHAIN_OUT_PER_THREAD];
-    walk_acc_zero<CPLX>(acc);
-    for (int sa = 0; sa < p; ++sa) {
-      walk_left_slice<CPLX>(s, row, sa * s.Dr, E, s.Dl | 1, Ts, s.Dr);
-      walk_acc_add<CPLX, true>(s, row, sa * s.Dr, Ts, nE, acc);
-      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of L is done as well
-    }
-    walk_acc_store<CPLX>(acc, s.Dr, E);
-    if (s.sel >= 0) walk_env_to_pool<CPLX, false>(E, s.Dr, pool + s.loff);
-  }
-}
-
 template <bool CPLX>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_bondspec_envs(const BsSite* __restrict__ sites, int nsite, int first,
                                                                  int last, int e_elems, void* pool) {
@@ -120,9 +77,9 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_bondspec_envs(const BsSite* _
   T* E = reinterpret_cast<T*>(bs_lds);
   T* Ts = E + e_elems;
   if (blockIdx.x == 0)
-    bs_walk_right<CPLX>(sites, nsite, first, E, Ts, static_cast<T*>(pool));
+    walk_bonds_right<CPLX>(sites, nsite, first, E, Ts, static_cast<T*>(pool));
   else
-    bs_walk_left<CPLX>(sites, last, E, Ts, static_cast<T*>(pool));
+    walk_bonds_left<CPLX>(sites, last, E, Ts, static_cast<T*>(pool));
 }
 
 // ------------------------------------------------------------------------------------------ the Hermitian eigensolver

@@ -1,6 +1,7 @@
-// What the "whole chain in one engine call" entry points share (mpse_overlap.hip and mpse_sandwich.hip include this; the
-// calls with a selection, mpse_corr.hip, mpse_rdm1.hip, mpse_rdm2.hip, mpse_trdm1.hip and mpse_bondspec.hip, include it
-// through mpse_chain_walk.h, which adds the walks that those five share; no other file includes either).  Each call walks a
+// What the "whole chain in one engine call" entry points share (mpse_overlap.hip includes this, mpse_sandwich.hip through
+// mpse_sandwich_step.h, the site step it shares with mpse_expect.hip; the calls with a selection, mpse_corr.hip,
+// mpse_rdm1.hip, mpse_rdm2.hip, mpse_trdm1.hip, mpse_bondspec.hip and mpse_expect.hip, include it through
+// mpse_chain_walk.h, which adds the walks that those six share; no other file includes any of the three).  Each call walks a
 // chain of site tensors either with its own one-workgroup kernel(s), the environment in LDS, or as products enqueued
 // back to back; which one, its plan decides from the dims table alone.  A call supplies its descriptor row, its plan
 // (the sizing behind chain_table_ok), its kernel(s) with their loop nests and its enqueued fallback; the element type,

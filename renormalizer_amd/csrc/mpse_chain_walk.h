@@ -1,6 +1,6 @@
 // What the chain calls with a site selection share beyond mpse_chain.h (mpse_corr.hip, mpse_rdm1.hip, mpse_rdm2.hip,
-// mpse_trdm1.hip, mpse_bondspec.hip; no other file includes this).  The first three and the last (whose selection names
-// bonds) take dims rows (D_l, d, danc, D_r) of ONE chain and a strictly ascending selection, and walk the chain with
+// mpse_trdm1.hip, mpse_bondspec.hip, mpse_expect.hip; no other file includes this).  The first three and
+// mpse_bondspec.hip (whose selection names bonds) take dims rows (D_l, d, danc, D_r) of ONE chain and a strictly ascending selection, and walk the chain with
 // the identity transfer matrix: the environment in LDS, one (sigma,
 // ancilla) slice of a site at a time.  mpse_trdm1.hip walks TWO chains with rectangular environments: its stages are
 // the walk2_* ones below, next to the square ones, which it leaves alone.  Here are the two stages of that transfer,
@@ -214,6 +214,70 @@ __device__ void chain_walk_left(const Row* __restrict__ sites, int last, ChainT<
     }
     walk_acc_store<CPLX>(acc, s.Dr, E);
   }
+}
+
+// The walks that leave the identity environments of selected BONDS in pooled memory: the two workgroups of
+// k_bondspec_envs (mpse_bondspec.hip) and of k_expect_envs (mpse_expect.hip).  `Row` has, beyond ChainSelRow, rsel (the
+// bond LEFT of the site is selected: leave R there), roff and loff (working elements before that R, and before L of the
+// bond RIGHT of the site, which `sel` selects, in `pool`).
+// From the right: R behind the last site is 1.  Per site from the right down to the one right of the first selected
+// bond, the transfer of rd_walk_right (mpse_rdm1.hip); R of a selected bond goes to the pooled buffer as it is.
+template <bool CPLX, class Row>
+__device__ void walk_bonds_right(const Row* __restrict__ sites, int nsite, int first, ChainT<CPLX>* R, ChainT<CPLX>* Ts,
+                                 ChainT<CPLX>* pool) {
+  walk_env_one<CPLX>(R);
+  for (int i = nsite - 1; i > first; --i) {
+    const Row s = sites[i];
+    const int p = s.d * s.danc, row = p * s.Dr, nE = s.Dl * s.Dl;
+    ChainT<CPLX> acc[CHAIN_OUT_PER_THREAD];
+    walk_acc_zero<CPLX>(acc);
+    for (int sa = 0; sa < p; ++sa) {
+      walk_right_slice<CPLX>(s, row, sa * s.Dr, R, Ts);
+      walk_acc_add<CPLX, false>(s, row, sa * s.Dr, Ts, nE, acc);
+      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of R is done as well
+    }
+    walk_acc_store<CPLX>(acc, s.Dl, R);
+    if (s.rsel >= 0) walk_env_to_pool<CPLX, false>(R, s.Dl, pool + s.roff);
+  }
+}
+
+// From the left: the sibling of chain_walk_left that leaves L BEHIND a site (the bond right of it) and ends behind
+// site `last`, the one left of the last selected bond
+template <bool CPLX, class Row>
+__device__ void walk_bonds_left(const Row* __restrict__ sites, int last, ChainT<CPLX>* E, ChainT<CPLX>* Ts,
+                                ChainT<CPLX>* pool) {
+  walk_env_one<CPLX>(E);
+  for (int i = 0; i <= last; ++i) {
+    const Row s = sites[i];
+    const int p = s.d * s.danc, row = p * s.Dr, nE = s.Dr * s.Dr;
+    ChainT<CPLX> acc[CHAIN_OUT_PER_THREAD];
+    walk_acc_zero<CPLX>(acc);
+    for (int sa = 0; sa < p; ++sa) {
+      walk_left_slice<CPLX>(s, row, sa * s.Dr, E, s.Dl | 1, Ts, s.Dr);
+      walk_acc_add<CPLX, true>(s, row, sa * s.Dr, Ts, nE, acc);
+      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of L is done as well
+    }
+    walk_acc_store<CPLX>(acc, s.Dr, E);
+    if (s.sel >= 0) walk_env_to_pool<CPLX, false>(E, s.Dr, pool + s.loff);
+  }
+}
+
+// sum of v over the workgroup in a fixed order: down the lanes of each wave, then a tree over the waves through LDS;
+// the value is valid in thread 0 (k_corr_rows of mpse_corr.hip, k_expect_windows of mpse_expect.hip)
+template <bool CPLX>
+__device__ ChainT<CPLX> cr_block_sum(ChainT<CPLX> v, ChainT<CPLX>* red, int tid) {
+  using El = ChainEl<CPLX>;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) El::add(v, El::shfl_down(v, off));
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  for (int st = CHAIN_WAVES / 2; st > 0; st >>= 1) {
+    if (tid < st) El::add(red[tid], red[tid + st]);
+    __syncthreads();
+  }
+  const ChainT<CPLX> r = red[0];
+  __syncthreads();   // red is written again by the next sum
+  return r;
 }
 
 // ------------------------------------------------------------------------------------------- device side, two chains

@@ -14,7 +14,7 @@
 
 namespace {
 
-// the regions of mpse_chain_walk.h plus one word per wave for cr_block_sum
+// the regions of mpse_chain_walk.h plus one word per wave for cr_block_sum (mpse_chain_walk.h)
 static_assert(chain_walk_lds(CHAIN_BOND_FIT, 16, CHAIN_WAVES) <= CHAIN_LDS_MAX,
               "2 x 64 x 65 complex128 + 16 = 130 KB of 160 KB");
 // Largest bond up to which the two launches are faster than the enqueued products: measured with tools/corr_bench.py,
@@ -99,24 +99,6 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_corr_right(const CrSite* __re
     }
     walk_acc_store<CPLX>(acc_r, s.Dl, R);
   }
-}
-
-// sum of v over the workgroup in a fixed order: down the lanes of each wave, then a tree over the waves through LDS;
-// the value is valid in thread 0
-template <bool CPLX>
-__device__ ChainT<CPLX> cr_block_sum(ChainT<CPLX> v, ChainT<CPLX>* red, int tid) {
-  using El = ChainEl<CPLX>;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) El::add(v, El::shfl_down(v, off));
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  for (int st = CHAIN_WAVES / 2; st > 0; st >>= 1) {
-    if (tid < st) El::add(red[tid], red[tid + st]);
-    __syncthreads();
-  }
-  const ChainT<CPLX> r = red[0];
-  __syncthreads();   // red is written again by the next sum
-  return r;
 }
 
 // Workgroup k: E_0 = 1, then from site 0 to the last selected site.  At a selected site l >= k first the closing

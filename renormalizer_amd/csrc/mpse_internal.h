@@ -196,6 +196,9 @@ struct mpse_ctx {
   // mpse_mps_bond_spectra (mpse_mps_bond_spectra_stats; the order of include/mpsengine.h)
   enum BondSpecStat { BS_CHAIN, BS_ENQUEUED, BS_SITES, BS_BONDS, BS_MAX_SWEEPS, BS_COUNT };
   long long bondspec_stats[BS_COUNT] = {0};
+  // mpse_mps_expect_many (mpse_mps_expect_many_stats; the order of include/mpsengine.h)
+  enum ExpectStat { EX_CHAIN, EX_ENQUEUED, EX_SITES, EX_ENTRIES, EX_COUNT };
+  long long expect_stats[EX_COUNT] = {0};
 };
 // What the caller of mpse_expm_lanczos said about the one solve that follows (mpse_expm_centre_mask, mpse_solve_slot):
 // taken out of the context on entry and handed down as an argument to the scope of the asynchronous solve

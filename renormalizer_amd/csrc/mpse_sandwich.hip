@@ -6,30 +6,15 @@
 //   enqueued          the environment-update plan of mpse_env_update (left domain, no unit channel) site after site on
 //                     two pooled environments, enqueued back to back from here
 // Either way the host reads once, at the end.  No atomics, a fixed summation order: the same inputs give the same bits.
-#include "mpse_chain.h"
+#include "mpse_sandwich_step.h"
 
 namespace {
 
-// entries of the new E a thread accumulates in registers over (sigma, a): SW_PLANES entries (b', k') of the plane
-// Dbr x Dkr, each in all of the up to SW_CHANNELS outgoing MPO channels g'
-constexpr int SW_PLANES = 2;
-constexpr int SW_CHANNELS = 8;
-constexpr int SW_ACC = SW_PLANES * SW_CHANNELS;
 constexpr int64_t SW_SITE_ELEMS_MAX = 1ll << 30;   // elements of one site tensor: offsets stay inside 32 bits
 // Multiply-adds (of the working type) of the heaviest site above which the enqueued products are faster than one
 // workgroup although the chain still fits: measured with tools/sandwich_bench.py, profiles/sandwich.md
 constexpr int64_t SW_WORK_MAX = 1ll << 62;
 constexpr int64_t SW_WORK_CLAMP = INT64_MAX;   // what the work of an absurd table is reported as
-
-struct SwSite {   // one row of the descriptor table (72 bytes, uploaded once per call)
-  const void* bra;
-  const void* ket;
-  const void* w;
-  int Dbl, Dkl, wl, d, danc, Dbr, Dkr, wr;
-  int bra_c, ket_c, w_c;   // the tensor is complex128
-  int pad;
-};
-static_assert(sizeof(SwSite) == 72, "descriptor rows are copied as 8-byte words");
 
 struct SwPlan {
   bool chain;         // the chain kernel takes it
@@ -86,16 +71,9 @@ SwPlan sandwich_plan(int nsite, const int64_t* dims, bool cplx) {
   return pl;
 }
 
-// E_0 = 1 (1 x 1 x 1).  Per site and per (sigma, a) in ascending order:
-//   T[b, g, k'] = sum_k E[b, g, k] K[k, sigma, a, k']                                     (into LDS)
-//   for every (sigma', g) whose row W[g, sigma', sigma, :] holds a non-zero entry:
-//     S[b', k']       = sum_b op(B[b, sigma', a, b']) T[b, g, k']                          (register of the owner)
-//     E'[b', g', k'] += W[g, sigma', sigma, g'] S[b', k']   for the non-zero entries g'    (registers of the owner)
-// E' replaces E in LDS after the last (sigma, a).  A thread owns the entries (b', k') = tid + jj * CHAIN_THREADS, jj <
-// SW_PLANES, of every channel g' < SW_CHANNELS: SW_ACC accumulators, all indexed statically (sandwich_plan).  (b', k')
-// runs with k' fastest: the reads of K are contiguous, those of T conflict free, B[b, sigma', a, b'] is one address per
-// b' group.  The result E_N[0, 0, 0] goes to out[0..1] and, when pub is set, to the mapped host buffer followed by the
-// sequence number (publish_collect).
+// E_0 = 1 (1 x 1 x 1), then the site step of mpse_sandwich_step.h (sw_site_step) site after site.  The result
+// E_N[0, 0, 0] goes to out[0..1] and, when pub is set, to the mapped host buffer followed by the sequence number
+// (publish_collect).
 template <bool CPLX>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_sandwich_chain(const SwSite* __restrict__ sites, int nsite,
                                                                   int conj_bra, int e_elems, double* out, double* pub,
@@ -110,76 +88,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_sandwich_chain(const SwSite* 
   __syncthreads();
   for (int i = 0; i < nsite; ++i) {
     const SwSite s = sites[i];
-    const int Dbl = s.Dbl, Dkl = s.Dkl, wl = s.wl, d = s.d, danc = s.danc, Dbr = s.Dbr, Dkr = s.Dkr, wr = s.wr;
-    const int pe = Dkl | 1, pe_new = Dkr | 1;
-    const int nT = Dbl * wl * Dkr, P = Dbr * Dkr;
-    const int p = d * danc;
-    const int k_row = p * Dkr, b_row = p * Dbr, t_row = wl * Dkr;   // element strides of the left bond in K, B and T
-    const bool cj = conj_bra != 0 && s.bra_c != 0;
-    T acc[SW_PLANES][SW_CHANNELS];
-#pragma unroll
-    for (int jj = 0; jj < SW_PLANES; ++jj)
-#pragma unroll
-      for (int gp = 0; gp < SW_CHANNELS; ++gp) acc[jj][gp] = El::zero();
-    for (int sa = 0; sa < p; ++sa) {
-      const int sg = sa / danc, a = sa - sg * danc;
-      for (int o = tid; o < nT; o += CHAIN_THREADS) {
-        const int r = o / Dkr, kk = o - r * Dkr;
-        const T* e_row = E + r * pe;
-        const int k0 = sa * Dkr + kk;
-        T sum = El::zero();
-#pragma unroll 4
-        for (int k = 0; k < Dkl; ++k) El::fma(sum, e_row[k], El::ld(s.ket, s.ket_c, k * k_row + k0));
-        Ts[o] = sum;
-      }
-      __syncthreads();
-      for (int sp = 0; sp < d; ++sp) {
-        for (int g = 0; g < wl; ++g) {
-          const int w0 = ((g * d + sp) * d + sg) * wr;
-          bool any = false;
-          for (int gp = 0; gp < wr; ++gp) any = any || El::nz(El::ldc(s.w, s.w_c, w0 + gp));
-          if (!any) continue;
-          const int b_base = (sp * danc + a) * Dbr;
-#pragma unroll
-          for (int jj = 0; jj < SW_PLANES; ++jj) {
-            const int o = tid + jj * CHAIN_THREADS;
-            if (jj * CHAIN_THREADS >= P) break;
-            T S = El::zero();
-            if (o < P) {
-              const int bb = o / Dkr, kk = o - bb * Dkr;
-              const T* t_col = Ts + g * Dkr + kk;
-              const int b0 = b_base + bb;
-#pragma unroll 2
-              for (int b = 0; b < Dbl; ++b) {
-                T v = El::ld(s.bra, s.bra_c, b * b_row + b0);
-                if (cj) v = El::cj(v);
-                El::fma(S, v, t_col[b * t_row]);
-              }
-            }
-#pragma unroll
-            for (int gp = 0; gp < SW_CHANNELS; ++gp) {
-              if (gp < wr) {
-                const T w = El::ldc(s.w, s.w_c, w0 + gp);
-                if (El::nz(w)) El::fma(acc[jj][gp], w, S);
-              }
-            }
-          }
-        }
-      }
-      __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of E is done as well
-    }
-#pragma unroll
-    for (int jj = 0; jj < SW_PLANES; ++jj) {
-      const int o = tid + jj * CHAIN_THREADS;
-      if (o < P) {
-        const int bb = o / Dkr, kk = o - bb * Dkr;
-        T* e_new = E + bb * wr * pe_new + kk;
-#pragma unroll
-        for (int gp = 0; gp < SW_CHANNELS; ++gp)
-          if (gp < wr) e_new[gp * pe_new] = acc[jj][gp];
-      }
-    }
-    __syncthreads();
+    sw_site_step<CPLX>(s, conj_bra, E, Ts);
   }
   if (tid == 0) chain_publish2(out, pub, seq_slot, seq, El::re(E[0]), El::im(E[0]));
 }

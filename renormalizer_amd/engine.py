@@ -206,6 +206,12 @@ _SIGNATURES = {
                               C.POINTER(C.c_int), _dblp],
     "mpse_mps_bond_spectra_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_mps_bond_spectra_plan": [C.c_int, _i64p, C.c_int, C.c_int, _i64p, C.c_int],
+    "mpse_mps_expect_many": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p, C.c_int,
+                             C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int), _i64p,
+                             _dblp],
+    "mpse_mps_expect_many_stats": [C.c_void_p, _i64p, C.c_int],
+    "mpse_mps_expect_many_plan": [C.c_int, _i64p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _i64p, C.c_int,
+                                  _i64p, C.c_int],
     "mpse_truncate_select": [_dblp, _i64p, C.c_int64, C.c_int64, C.c_double, _i64p, _i64p],
     "mpse_block_qr": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64],
@@ -331,6 +337,33 @@ def mps_bond_spectra_plan(dims, nsel, any_complex, lib=None):
     ``lds_fit_bytes`` are those of the larger of the two launches."""
     return _chain_plan((lib or load_library()).mpse_mps_bond_spectra_plan, dims, 4, "D_l, d, danc, D_r",
                        BOND_SPECTRA_PLAN_INFO, int(nsel), int(bool(any_complex)))
+
+
+EXPECT_MANY_PLAN_INFO = ("bond_limit", "lds_budget", "lds_bytes", "e_elems", "t_elems", "threads", "max_bond", "valid",
+                         "grid_cap", "p_limit", "bond_fit_limit", "lds_fit_bytes", "win_e_elems", "win_t_elems", "w_max",
+                         "channel_limit", "acc_needed", "acc_per_thread", "elem_bytes")
+
+
+def _window_args(windows):
+    """(nop, first array, last array, wdims array) of ``windows``: one (first site, [(wl, wr) per MPO site]) per
+    operator"""
+    nop = len(windows)
+    first = [int(f) for f, _ in windows]
+    last = [int(f) + len(w) - 1 for f, w in windows]
+    flat = [int(x) for _, w in windows for pair in w for x in pair]
+    return (nop, (C.c_int * max(nop, 1))(*first), (C.c_int * max(nop, 1))(*last),
+            (C.c_int64 * max(len(flat), 2))(*flat))
+
+
+def mps_expect_many_plan(dims, windows, any_complex, lib=None):
+    """Which path ``Engine.mps_expect_many`` takes, from the ``dims`` rows (D_l, d, danc, D_r) of the chain and the
+    ``windows`` of the operators alone, one (first site, [(wl, wr) per MPO site of the window]) each
+    (``mpse_mps_expect_many_plan``; needs the built library, no GPU).  Returns (chain kernels?, {info name: value});
+    ``valid``: the table is a chain AND every window lies inside it with MPO bonds from 1 to 1 (a window without sites
+    stands for first > last), ``grid_cap``: the workgroups of one launch of the window kernel, ``lds_bytes`` and
+    ``lds_fit_bytes``: the larger of the two launches."""
+    return _chain_plan((lib or load_library()).mpse_mps_expect_many_plan, dims, 4, "D_l, d, danc, D_r",
+                       EXPECT_MANY_PLAN_INFO, *_window_args(windows), int(bool(any_complex)))
 
 
 def check_selection(call, sel, nsite):
@@ -960,6 +993,43 @@ class Engine:
             self.ctx, n, *_site_args(sites), dims, len(sel), (C.c_int * len(sel))(*sel), out.ctypes.data_as(_dblp)))
         ends = np.cumsum(sizes)
         return [out[e - sz:e] for sz, e in zip(sizes, ends)]
+
+    # -- expectation values of a list of MPOs
+    EXPECT_MANY_STATS = ("chain_kernel", "enqueued", "sites", "entries")
+
+    def mps_expect_many_stats(self):
+        """{name: count} of the ``mps_expect_many`` calls of this context, cumulative (``mpse_mps_expect_many_stats``):
+        calls taken by the chain kernels, calls taken by the enqueued path, sites walked (the chain's once per call),
+        values returned."""
+        return self._stats_dict(self.lib.mpse_mps_expect_many_stats, self.EXPECT_MANY_STATS)
+
+    def mps_expect_many(self, sites, operators):
+        """<psi| O_m |psi> for a list of MPOs against ONE chain of device site tensors (D_l, d[, danc], D_r), in one
+        engine call with one host read (``mpse_mps_expect_many``).  ``operators``: one (first site, [device MPO sites
+        (wl, d, d, wr) of the window]) per operator, which is the identity outside its window; the first physical leg
+        of an MPO site meets the conjugated tensor, the ancilla leg of density-operator sites is traced.  Real and
+        complex tensors may be mixed.  Returns a complex128 array of len(operators) values."""
+        rows = self.corr_dims(sites)
+        n = len(rows)
+        if n == 0 or len(operators) == 0:
+            raise ValueError(f"mps_expect_many: {n} sites, {len(operators)} operators")
+        wsites, windows = [], []
+        for m, (first, ws) in enumerate(operators):
+            first, ws = int(first), list(ws)
+            if not ws or first < 0 or first + len(ws) > n:
+                raise ValueError(f"mps_expect_many: operator {m} has {len(ws)} MPO sites from site {first} of {n}")
+            for i, w in enumerate(ws, first):
+                if w.ndim != 4 or w.shape[1] != rows[i][1] or w.shape[2] != rows[i][1]:
+                    raise ValueError(f"mps_expect_many: operator {m} has shape {w.shape} at site {i}, d = {rows[i][1]}")
+            wsites.extend(ws)
+            windows.append((first, [(w.shape[0], w.shape[3]) for w in ws]))
+        dims = (C.c_int64 * (4 * n))(*[int(x) for r in rows for x in r])
+        nop, first, last, wdims = _window_args(windows)
+        out = np.zeros(nop, dtype=np.complex128)
+        self._check(self.lib.mpse_mps_expect_many(
+            self.ctx, n, *_site_args(sites), dims, nop, first, last, *_site_args(wsites), wdims,
+            out.ctypes.data_as(_dblp)))
+        return out
 
     # -- two-site reduced density matrices
     RDM2_STATS =("chain_kernel", "enqueued", "sites", "pairs")

@@ -3,4 +3,4 @@ from .mpo import Mpo
 from .mps import BraKetPair, Mps
 from .batch import evolve_batch
 from .mpdm import MpDm
-from .thermalprop import thermal_state
+from .thermalprop import ThermalProp, thermal_state

@@ -519,6 +519,30 @@ class Mps:
             out.append(float(prod.real) if np.isclose(prod.imag, 0) else prod)
         return np.array(out)
 
+    def mpo_expectations(self, mpos) -> np.ndarray:
+        """The array ``expectations(mpos)`` returns as ONE engine call (``Engine.mps_expect_many`` ->
+        ``mpse_mps_expect_many``): every MPO is cut to its window of sites that are not the exact identity (scaled
+        identities are part of the window; an MPO that is the identity everywhere keeps its first site), the identity
+        environments of all window edges are built once inside the engine, every window is walked there and the host
+        reads once, instead of one chain of per-site calls and one read per operator.  The bra is the conjugate of the
+        state.  Same conventions as ``expectations``: real entries where the imaginary part is negligible, the
+        ``coeff`` factor not included.  ``expectation`` and ``expectations`` stay as they are (their values are pinned
+        bit for bit); the two routes sum in different orders and agree to rounding.  Works for ``Mps`` and ``MpDm``
+        (the ancilla leg is traced)."""
+        mpos = [Mpo(self.model, m) if isinstance(m, (Op, OpSum)) else m for m in mpos]
+        if not mpos:
+            return np.array([])
+        eng = get_engine()
+        n = len(self)
+        operators = []
+        for m in mpos:
+            assert len(m) == n
+            nontrivial = [i for i in range(n) if not _is_identity_site(m[i])]
+            first, last = (nontrivial[0], nontrivial[-1]) if nontrivial else (0, 0)
+            operators.append((first, [m.device(i, eng) for i in range(first, last + 1)]))
+        vals = eng.mps_expect_many(self._mp, operators)
+        return np.array([float(v.real) if np.isclose(v.imag, 0) else complex(v) for v in vals])
+
     @property
     def e_occupations(self):
         """mps/mps.py:600-609"""

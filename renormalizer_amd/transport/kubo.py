@@ -87,13 +87,15 @@ class TransportKubo(TdMpsJob):
     ``model.e_dofs`` (default: a periodic one-dimensional chain); insteps / ievolve_config: steps and configuration of
     the imaginary-time propagation to beta / 2; compress_config: of the states (the product j rho is compressed with
     it); evolve_config: of the real-time propagation; thermal_dump_path: where the thermal state is read from when the
-    file exists and written to when it does not (default ``<dump_dir>/<job_name>_impdm.npz``).  ``properties`` is not
-    supported."""
+    file exists and written to when it does not (default ``<dump_dir>/<job_name>_impdm.npz``); properties: a
+    ``Property`` whose ``calc_properties_braketpair`` is called on the (bra, ket) pair after every step of a job without
+    phonon-assisted hopping (where the reference calls it) and whose results are dumped."""
 
     def __init__(self, model, temperature, distance_matrix=None, insteps=1, ievolve_config=None, compress_config=None,
                  evolve_config=None, dump_dir=None, job_name=None, thermal_dump_path=None, properties=None):
-        if properties is not None:
-            raise NotImplementedError("TransportKubo: `properties` is not supported")
+        if properties is not None and not callable(getattr(properties, "calc_properties_braketpair", None)):
+            raise NotImplementedError("TransportKubo: `properties` is a Property (calc_properties_braketpair and "
+                                      f"prop_res); {type(properties).__name__} objects are not supported")
         if temperature == 0:
             raise ValueError("Can't set temperature to 0.")
         self.model = model
@@ -120,7 +122,7 @@ class TransportKubo(TdMpsJob):
         else:
             self.thermal_dump_path = None
         self.thermal_state_loaded = False
-        self.properties = None
+        self.properties = properties
         self._auto_corr = []
         self._auto_corr_decomposition = []
         super().__init__(evolve_config=evolve_config, dump_dir=dump_dir, job_name=job_name)
@@ -178,6 +180,8 @@ class TransportKubo(TdMpsJob):
         # the negative sign: both current operators are kept real, each lacks a factor -i
         if self.j_oper2 is None:
             self._auto_corr.append(-mps.ft)
+            if self.properties is not None:
+                self.properties.calc_properties_braketpair(mps)
             return
         bra, ket, ket2 = self._states(mps)
         ft1 = -mps[0].ft                                          # <j_1(t) j_1(0)>
@@ -216,6 +220,10 @@ class TransportKubo(TdMpsJob):
         return mobility_in_au, mobility_in_au / mobility2au
 
     def get_dump_dict(self):
-        return {"mol list": self.model.to_dict(), "temperature": self.temperature.as_au(),
+        dump = {"mol list": self.model.to_dict(), "temperature": self.temperature.as_au(),
                 "time series": self.evolve_times, "auto correlation": self.auto_corr,
                 "auto correlation decomposition": self.auto_corr_decomposition, "mobility": self.calc_mobility()[1]}
+        if self.properties is not None:
+            for name, res in self.properties.prop_res.items():
+                dump[name] = res
+        return dump
