@@ -9,8 +9,8 @@
 // No inverse: a rank-deficient L (a padded bond) only puts zero rows and columns into M.  Two paths, chosen from the dims
 // table alone (bondspec_plan):
 //   chain      two launches, for chains whose bonds are at most BS_BOND_MAX.  k_bondspec_envs: the two walks of
-//              k_rdm1_envs as mpse_chain_walk.h has them for bonds (walk_bonds_right / walk_bonds_left); workgroup 0 walks right to left and leaves R of every selected bond in pooled memory,
-//              workgroup 1 left to right and leaves L.  k_bondspec_eig: one workgroup per selected bond, two Hermitian
+//              k_rdm1_envs as mpse_chain_walk.h has them for bonds (walk_envs with AT_BOND); workgroup 0 walks right to
+//              left and leaves R of every selected bond in pooled memory, workgroup 1 left to right and leaves L.  k_bondspec_eig: one workgroup per selected bond, two Hermitian
 //              eigensolves in LDS by a cyclic two-sided Jacobi (bs_jacobi).
 //   enqueued   the two passes as products of the contraction kernel, the two solves of a bond through the block SVD
 //              (a Hermitian positive semidefinite matrix has its eigenvalues as singular values and the eigenvectors of
@@ -72,14 +72,7 @@ BsPlan bondspec_plan(int nsite, const int64_t* dims, int nsel, bool cplx) {
 template <bool CPLX>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_bondspec_envs(const BsSite* __restrict__ sites, int nsite, int first,
                                                                  int last, int e_elems, void* pool) {
-  using T = ChainT<CPLX>;
-  extern __shared__ __attribute__((aligned(16))) double bs_lds[];
-  T* E = reinterpret_cast<T*>(bs_lds);
-  T* Ts = E + e_elems;
-  if (blockIdx.x == 0)
-    walk_bonds_right<CPLX>(sites, nsite, first, E, Ts, static_cast<T*>(pool));
-  else
-    walk_bonds_left<CPLX>(sites, last, E, Ts, static_cast<T*>(pool));
+  walk_envs<CPLX, true>(sites, nsite, first, last, e_elems, pool);
 }
 
 // ------------------------------------------------------------------------------------------ the Hermitian eigensolver
@@ -402,8 +395,8 @@ int bondspec_enqueued(mpse_ctx* ctx, const ChainSelArgs& a, bool cplx, double* o
   for (int i = a.nsite - 1; i > first; --i) {
     const int64_t* d = a.dims + 4 * i;
     const int64_t Dl = d[0], p = d[1] * d[2], Dr = d[3];
-    MPSE_TRY(q.a_r(Dl * p, Dr, q.site[i], at(rbuf, i), x1.p));
-    MPSE_TRY(q.ca_y(Dl, p * Dr, q.site[i], x1.p, at(rbuf, i - 1)));
+    MPSE_TRY(q.a_r(Dl * p, Dr, Dr, q.site[i], at(rbuf, i), x1.p));
+    MPSE_TRY(q.ca_y(Dl, Dl, p * Dr, q.site[i], x1.p, at(rbuf, i - 1)));
   }
   // ---- left pass: L of bond i from L of bond i - 1 and site i (bond -1 shares the parity of bond 1: scratch[1])
   MPSE_TRY(stage_h2d(ctx, scratch[1], one, es));
@@ -411,8 +404,8 @@ int bondspec_enqueued(mpse_ctx* ctx, const ChainSelArgs& a, bool cplx, double* o
     const int64_t* d = a.dims + 4 * i;
     const int64_t Dl = d[0], p = d[1] * d[2], Dr = d[3];
     const void* L = i == 0 ? scratch[1] : at(lbuf, i - 1);
-    MPSE_TRY(q.l_a(1, Dl, p * Dr, L, q.site[i], x1.p));
-    MPSE_TRY(q.ca_x(1, Dl * p, Dr, q.site[i], x1.p, at(lbuf, i)));
+    MPSE_TRY(q.l_a(1, Dl, Dl, p * Dr, L, q.site[i], x1.p));
+    MPSE_TRY(q.ca_x(1, Dl * p, Dr, Dr, q.site[i], x1.p, at(lbuf, i)));
   }
   // ---- the two solves of every selected bond
   std::vector<double> s_host((size_t)d_max), root((size_t)d_max);
@@ -427,7 +420,7 @@ int bondspec_enqueued(mpse_ctx* ctx, const ChainSelArgs& a, bool cplx, double* o
     MPSE_TRY(mpse_gather_cols(ctx, q.dt, us.p, u.p, D, D, cols.data(), root.data(), D));
     MPSE_TRY(q.gemm(0, idx1(D, 1), idx1(D, D), idx1(D, D), idx1(D, 1), idx1(D, D), idx1(D, 1), 1, 0, 0, 0, R, us.p,
                     t1.p));
-    MPSE_TRY(q.ca_x(1, D, D, us.p, t1.p, m.p));
+    MPSE_TRY(q.ca_x(1, D, D, D, us.p, t1.p, m.p));
     MPSE_TRY(bs_psd_svd(ctx, q.dt, D, m.p, u.p, vt.p, s_host.data()));
     for (int64_t i = 0; i < D; ++i) out_host[ooff[k] + i] = s_host[i] > 0.0 ? s_host[i] : 0.0;
   }

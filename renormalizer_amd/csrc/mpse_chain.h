@@ -1,11 +1,12 @@
 // What the "whole chain in one engine call" entry points share (mpse_overlap.hip includes this, mpse_sandwich.hip through
-// mpse_sandwich_step.h, the site step it shares with mpse_expect.hip; the calls with a selection, mpse_corr.hip,
-// mpse_rdm1.hip, mpse_rdm2.hip, mpse_trdm1.hip, mpse_bondspec.hip and mpse_expect.hip, include it through
-// mpse_chain_walk.h, which adds the walks that those six share; no other file includes any of the three).  Each call walks a
-// chain of site tensors either with its own one-workgroup kernel(s), the environment in LDS, or as products enqueued
-// back to back; which one, its plan decides from the dims table alone.  A call supplies its descriptor row, its plan
-// (the sizing behind chain_table_ok), its kernel(s) with their loop nests and its enqueued fallback; the element type,
-// the limits of a launch, the publishing tail, the staging, the dispatch and the bookkeeping of the exports are here.
+// mpse_sandwich_step.h, the site step it shares with mpse_expect.hip; the calls with a selection include it through
+// mpse_chain_walk.h, which adds the stages and walks that those six share: mpse_corr.hip, mpse_rdm2.hip,
+// mpse_bondspec.hip and mpse_expect.hip directly, mpse_rdm1.hip and mpse_trdm1.hip through mpse_chain_sites.h, the one
+// call those two are; no other file includes any of the four).  Each call walks a chain of site tensors either with its
+// own one-workgroup kernel(s), the environment in LDS, or as products enqueued back to back; which one, its plan decides
+// from the dims table alone.  A call supplies its descriptor row, its plan (the sizing behind chain_table_ok), its
+// kernel(s) with their loop nests and its enqueued fallback; the element type, the limits of a launch, the publishing
+// tail, the staging, the dispatch and the bookkeeping of the exports are here.
 #pragma once
 #include <algorithm>
 #include <initializer_list>
@@ -202,21 +203,5 @@ static inline int widen_site(mpse_ctx* ctx, TmpBuf& buf, const void** site, int6
   if (!buf.p) MPSE_TRY(buf.alloc((size_t)cap * 16));
   MPSE_TRY(mpse_cast_f64_to_c128(ctx, buf.p, *site, n));
   *site = buf.p;
-  return MPSE_OK;
-}
-
-// The sites of a chain call with dims rows (D_l, d, danc, D_r) in ONE working dtype: (*site)[i] is sites[i], or, for a
-// real site of a complex call, its widened copy in a pooled buffer of `wide`, which lives as long as its owner
-static inline int chain_widen_sites(mpse_ctx* ctx, int nsite, const void* const* sites, const int* dtype,
-                                    const int64_t* dims, bool cplx, std::vector<std::unique_ptr<TmpBuf>>* wide,
-                                    std::vector<const void*>* site) {
-  site->assign(sites, sites + nsite);
-  for (int i = 0; i < nsite; ++i) {
-    if (!cplx || dtype[i] == MPSE_C128) continue;
-    const int64_t* d = dims + 4 * i;
-    const int64_t n = d[0] * d[1] * d[2] * d[3];
-    wide->emplace_back(new TmpBuf(ctx));
-    MPSE_TRY(widen_site(ctx, *wide->back(), &(*site)[i], n, n));
-  }
   return MPSE_OK;
 }

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_corr_right(const CrSite* __re
         }
       }
     }
-    walk_acc_store<CPLX>(acc_r, s.Dl, R);
+    walk_acc_store<CPLX>(acc_r, s.Dl, s.Dl, R);
   }
 }
 
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_corr_rows(const CrSite* __res
       }
       __syncthreads();   // T is overwritten by the next (sigma, a); after the last one every read of E is done as well
     }
-    walk_acc_store<CPLX>(acc, Dr, E);
+    walk_acc_store<CPLX>(acc, Dr, Dr, E);
   }
 }
 
@@ -263,17 +263,17 @@ int corr_enqueued(mpse_ctx* ctx, const CrArgs& a, bool cplx, double* out_host) {
     for (int i = a.nsite - 1; i >= first; --i) {
       const int64_t* d = a.dims + 4 * i;
       const int64_t Dl = d[0], dd = d[1], Dr = d[3], p = dd * d[2];
-      MPSE_TRY(q.a_r(Dl * p, Dr, q.site[i], R, y1.p));
+      MPSE_TRY(q.a_r(Dl * p, Dr, Dr, q.site[i], R, y1.p));
       if (k >= 0 && a.sel[k] == i) {
         // which = 1: Y -> G (not needed for the first selected site), 2: Z -> Gd
         for (int which = (k == 0 ? 2 : 1); which <= 2; ++which) {
           MPSE_TRY(mix(d, M + (size_t)(moff[k] + which * dd * dd) * es, y1.p, y2.p));
-          MPSE_TRY(q.ca_y(Dl, p * Dr, q.site[i], y2.p, G + (size_t)(goff[k] + (which == 2 ? Dl * Dl : 0)) * es));
+          MPSE_TRY(q.ca_y(Dl, Dl, p * Dr, q.site[i], y2.p, G + (size_t)(goff[k] + (which == 2 ? Dl * Dl : 0)) * es));
         }
         --k;
       }
       if (i == first) break;
-      MPSE_TRY(q.ca_y(Dl, p * Dr, q.site[i], y1.p, Rn));
+      MPSE_TRY(q.ca_y(Dl, Dl, p * Dr, q.site[i], y1.p, Rn));
       std::swap(R, Rn);
     }
   }
@@ -301,12 +301,12 @@ int corr_enqueued(mpse_ctx* ctx, const CrArgs& a, bool cplx, double* out_host) {
         if (i == last) break;
       }
       const int64_t nrow = n_open + 1;
-      MPSE_TRY(q.l_a(nrow, Dl, p * Dr, S, q.site[i], X1));
+      MPSE_TRY(q.l_a(nrow, Dl, Dl, p * Dr, S, q.site[i], X1));
       if (is_sel) {
         MPSE_TRY(mix(d, M + (size_t)moff[n_open] * es, X1, X1 + (size_t)(nrow * Dl * p * Dr) * es));
         ++n_open;
       }
-      MPSE_TRY(q.ca_x(n_open + 1, Dl * p, Dr, q.site[i], X1, Sn));
+      MPSE_TRY(q.ca_x(n_open + 1, Dl * p, Dr, Dr, q.site[i], X1, Sn));
       std::swap(S, Sn);
     }
   }

@@ -119,14 +119,7 @@ ExPlan expect_plan(int nsite, const int64_t* dims, int nop, const int* first, co
 template <bool CPLX>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_expect_envs(const ExSite* __restrict__ sites, int nsite, int first,
                                                                int last, int e_elems, void* pool) {
-  using T = ChainT<CPLX>;
-  extern __shared__ __attribute__((aligned(16))) double ex_lds[];
-  T* E = reinterpret_cast<T*>(ex_lds);
-  T* Ts = E + e_elems;
-  if (blockIdx.x == 0)
-    walk_bonds_right<CPLX>(sites, nsite, first, E, Ts, static_cast<T*>(pool));
-  else
-    walk_bonds_left<CPLX>(sites, last, E, Ts, static_cast<T*>(pool));
+  walk_envs<CPLX, true>(sites, nsite, first, last, e_elems, pool);
 }
 
 // Launch 2.  Workgroup x takes operator op0 + x: L of its first bond from pooled memory into E (D rows of D | 1
@@ -255,14 +248,14 @@ int expect_enqueued(mpse_ctx* ctx, const ExArgs& a, bool cplx, double* out_host)
   for (int i = a.nsite - 1; i >= e.min_r; --i) {
     const int64_t* d = a.dims + 4 * i;
     const int64_t Dl = d[0], p = d[1] * d[2], Dr = d[3];
-    MPSE_TRY(q.a_r(Dl * p, Dr, q.site[i], R(i + 1), x1.p));
-    MPSE_TRY(q.ca_y(Dl, p * Dr, q.site[i], x1.p, R(i)));
+    MPSE_TRY(q.a_r(Dl * p, Dr, Dr, q.site[i], R(i + 1), x1.p));
+    MPSE_TRY(q.ca_y(Dl, Dl, p * Dr, q.site[i], x1.p, R(i)));
   }
   for (int i = 0; i < e.max_l; ++i) {
     const int64_t* d = a.dims + 4 * i;
     const int64_t Dl = d[0], p = d[1] * d[2], Dr = d[3];
-    MPSE_TRY(q.l_a(1, Dl, p * Dr, L(i), q.site[i], x1.p));
-    MPSE_TRY(q.ca_x(1, Dl * p, Dr, q.site[i], x1.p, L(i + 1)));
+    MPSE_TRY(q.l_a(1, Dl, Dl, p * Dr, L(i), q.site[i], x1.p));
+    MPSE_TRY(q.ca_x(1, Dl * p, Dr, Dr, q.site[i], x1.p, L(i + 1)));
   }
   row = 0;
   for (int m = 0; m < a.nop; ++m) {

@@ -7,7 +7,7 @@
 // paths, chosen from the dims table and the selection alone (rdm2_plan):
 //   chain      two launches, for chains whose bonds are at most RD2_BOND_MAX.  k_rdm2_envs: workgroup 0 walks right to
 //              left with R in LDS and leaves, at every selected site l but the first, the d_l^2 closed environments
-//              G_l^{qq'}[b, c] in pooled memory; workgroup 1 walks left to right (chain_walk_left) and leaves L_k at
+//              G_l^{qq'}[b, c] in pooled memory; workgroup 1 walks left to right (walk_left) and leaves L_k at
 //              every selected site but the last.  k_rdm2_rows: one workgroup per unit (k, p, p') starts at sel[k] from
 //              L_k, opens with the slices sigma = p' and the bra rows sigma' = p, carries E to the right and closes
 //              against all G_l^{qq'} at every later selected site.
@@ -129,7 +129,7 @@ __device__ void rd2_walk_right(const Rd2Site* __restrict__ sites, int nsite, int
       __syncthreads();   // T is overwritten by the next (q', g); after the last one every read of R is done as well
     }
     if (i == stop) break;
-    walk_acc_store<CPLX>(acc, s.Dl, R);
+    walk_acc_store<CPLX>(acc, s.Dl, s.Dl, R);
   }
 }
 
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_rdm2_envs(const Rd2Site* __re
   if (blockIdx.x == 0)
     rd2_walk_right<CPLX>(sites, nsite, stop, E, Ts, static_cast<T*>(pool));
   else
-    chain_walk_left<CPLX>(sites, last, E, Ts, static_cast<T*>(pool));
+    walk_left<CPLX, false>(sites, last, E, Ts, static_cast<T*>(pool));
 }
 
 // Workgroup u: the row |p><p'| opened at site sel[k] = units[u].site.  E = L_k from the pooled buffer, then from that
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_rdm2_rows(const Rd2Site* __re
       walk_acc_add<CPLX, true>(s, row, bra, Ts, nE, acc);
       __syncthreads();   // T is overwritten by the next slice; after the last one every read of E is done as well
     }
-    walk_acc_store<CPLX>(acc, Dr, E);
+    walk_acc_store<CPLX>(acc, Dr, Dr, E);
   }
 }
 
@@ -266,7 +266,7 @@ int64_t rd2_stack_bytes() {
 }
 
 // The same contractions as products of the contraction kernel, in one dtype: complex as soon as any site is (real sites
-// are widened into pooled copies first, chain_widen_sites).  The plain products: ChainSelEnq of mpse_chain_walk.h.
+// are widened into pooled copies first).  The plain products: ChainSelEnq of mpse_chain_walk.h.
 //   right pass, site i from the last one down to sel[1], R (D_r, D_r) = [b', c']:  Y1 = A . R,  R' = conj(A) . Y1
 //     selected:  G_i[(b, c), (q, q')] = sum_(g, b') conj(A[b, q, (g, b')]) Y1[c, q', (g, b')]      (one product)
 //   left pass, site i from 0 to sel[nsel - 2] - 1, L (D_l, D_l) = [b, c]:  X1 = L . A,  L' = conj(A) . X1; L of a
@@ -332,13 +332,13 @@ int rdm2_enqueued(mpse_ctx* ctx, const ChainSelArgs& a, bool cplx, int64_t out_e
     for (int i = a.nsite - 1; i >= a.sel[1]; --i) {
       const int64_t* d = a.dims + 4 * i;
       const int64_t Dl = d[0], dd = d[1], da = d[2], Dr = d[3], p = dd * da;
-      MPSE_TRY(q.a_r(Dl * p, Dr, q.site[i], R, xl.p));
+      MPSE_TRY(q.a_r(Dl * p, Dr, Dr, q.site[i], R, xl.p));
       if (q.pos[i] >= 0)
         MPSE_TRY(q.gemm(1, idx1(Dl * dd, da * Dr), idx1(da * Dr, 1), idx1(da * Dr, 1), idx1(Dl * dd, da * Dr),
                         idx2(Dl, dd, Dl * dd * dd, dd), idx2(Dl, dd, dd * dd, 1), 1, 0, 0, 0, q.site[i], xl.p,
                         G + (size_t)goff[q.pos[i]] * es));
       if (i == a.sel[1]) break;
-      MPSE_TRY(q.ca_y(Dl, p * Dr, q.site[i], xl.p, Rn));
+      MPSE_TRY(q.ca_y(Dl, Dl, p * Dr, q.site[i], xl.p, Rn));
       std::swap(R, Rn);
     }
   }
@@ -351,8 +351,8 @@ int rdm2_enqueued(mpse_ctx* ctx, const ChainSelArgs& a, bool cplx, int64_t out_e
   for (int i = 0; i < a.sel[nsel - 2]; ++i) {
     const int64_t* d = a.dims + 4 * i;
     const int64_t Dl = d[0], p = d[1] * d[2], Dr = d[3];
-    MPSE_TRY(q.l_a(1, Dl, p * Dr, l_at(i), q.site[i], xl.p));
-    MPSE_TRY(q.ca_x(1, Dl * p, Dr, q.site[i], xl.p, l_at(i + 1)));
+    MPSE_TRY(q.l_a(1, Dl, Dl, p * Dr, l_at(i), q.site[i], xl.p));
+    MPSE_TRY(q.ca_x(1, Dl * p, Dr, Dr, q.site[i], xl.p, l_at(i + 1)));
   }
   // ---- open rows, chunk by chunk
   struct Run {   // rows [r0, r0 + n) of the opening site sel[k] lie behind `before` rows of the stack
@@ -381,14 +381,14 @@ int rdm2_enqueued(mpse_ctx* ctx, const ChainSelArgs& a, bool cplx, int64_t out_e
       }
       if (i == last) break;
       if (nrow > 0) {
-        MPSE_TRY(q.l_a(nrow, Dl, p * Dr, S, q.site[i], x1.p));
-        MPSE_TRY(q.ca_x(nrow, Dl * p, Dr, q.site[i], x1.p, Sn));
+        MPSE_TRY(q.l_a(nrow, Dl, Dl, p * Dr, S, q.site[i], x1.p));
+        MPSE_TRY(q.ca_x(nrow, Dl * p, Dr, Dr, q.site[i], x1.p, Sn));
       }
       if (k >= ch.k0 && k <= ch.k1) {
         const bool part = ch.r1 > ch.r0;
         const int64_t ra = part ? ch.r0 : 0, rb = part ? ch.r1 : dd * dd;
         char* dest = Sn + (size_t)(nrow * Dr * Dr) * es;
-        MPSE_TRY(q.l_a(1, Dl, p * Dr, l_at(i), q.site[i], xl.p));
+        MPSE_TRY(q.l_a(1, Dl, Dl, p * Dr, l_at(i), q.site[i], xl.p));
         // the rows (p, p') of [ra, rb): for every p its range [lo, hi) of p'; M = (p, b'), K = (a, g), N = (p', c')
         for (int64_t pr = ra / dd; pr * dd < rb; ++pr) {
           int64_t np = 1, lo = std::max(ra, pr * dd) - pr * dd, hi = std::min(rb, (pr + 1) * dd) - pr * dd;

@@ -129,6 +129,38 @@ def test_empty_selection():
     assert not mps_trdm1_plan(tab, -1, True)[0]
 
 
+def test_square_tables_are_sized_as_one_chain():
+    """ONE chain is the case bra = ket of two: on seeded random square tables ``mps_rdm1_plan`` of the rows (D_l, d,
+    danc, D_r) and ``mps_trdm1_plan`` of the same rows written with six columns agree on the path, the LDS bytes and
+    elements, the largest bond and ``valid``.  1 .. 7 sites, bonds up to 128, d up to 70000, real and complex, so that
+    tables the kernels take, tables that only fit and tables that do not fit all occur."""
+    from renormalizer_amd.engine import mps_rdm1_plan
+    rng = np.random.default_rng(20240611)
+    taken = fit_only = no_fit = 0
+    for _ in range(400):
+        nsite = int(rng.integers(1, 8))
+        cap = int(rng.choice((1, 4, 16, 64, 128)))
+        bonds = [1] + [int(rng.integers(1, cap + 1)) for _ in range(nsite - 1)] + [1]
+        dims4 = []
+        for i in range(nsite):
+            d = int(rng.choice((65536, 70000))) if rng.random() < 0.05 else int(rng.integers(1, 9))
+            dims4.append([bonds[i], d, int(rng.integers(1, 3)), bonds[i + 1]])
+        if rng.random() < 0.05:
+            dims4[0][0] = 2                                              # no chain: both report valid = 0
+        dims6 = [[r[0], r[0], r[1], r[2], r[3], r[3]] for r in dims4]
+        nsel, cplx = int(rng.integers(0, nsite + 1)), bool(rng.integers(0, 2))
+        ok1, one = mps_rdm1_plan(dims4, nsel, cplx)
+        ok2, two = mps_trdm1_plan(dims6, nsel, cplx)
+        assert ok1 == ok2, (dims4, nsel, cplx)
+        for name in ("lds_bytes", "lds_fit_bytes", "e_elems", "t_elems", "valid"):
+            assert one[name] == two[name], (name, dims4, nsel, cplx)
+        assert one["max_bond"] == two["max_bond_bra"] == two["max_bond_ket"], (dims4, nsel, cplx)
+        taken += ok1
+        fit_only += (not ok1) and one["lds_fit_bytes"] > 0
+        no_fit += one["valid"] == 1 and one["lds_fit_bytes"] == 0
+    assert taken > 0 and fit_only > 0 and no_fit > 0, (taken, fit_only, no_fit)
+
+
 def test_binding_refuses_before_the_library():
     def z(*shape):
         return np.zeros(shape)
