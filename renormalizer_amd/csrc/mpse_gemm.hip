@@ -29,8 +29,10 @@
 //     others with their tile columns skewed by the tile row.  (tools/gemm_balance.py on MPSE_GEMM_TRACE timelines.)
 //   * accumulation order over k is fixed and independent of the launch order => bitwise reproducible results.
 #include <cstdlib>
+#include <type_traits>
 
 #include "mpse_device.h"
+#include "mpse_gemm_tiles.h"
 #include "mpse_internal.h"
 #include "mpse_plans.h"
 
@@ -163,6 +165,25 @@ __device__ __forceinline__ long long idx_off(const IdxMap& m, int i) {
   return (long long)hi * m.s_hi + (long long)l * m.s_lo;
 }
 
+// One element of the result, shared by the kernel's epilogue and the split-K reduction: o = alpha x, o += beta c0
+__device__ __forceinline__ double2 alpha_times(const GemmArgs& g, double xr, double xi) {
+  double2 o;
+  o.x = g.alpha_re * xr - g.alpha_im * xi;
+  o.y = g.alpha_re * xi + g.alpha_im * xr;
+  return o;
+}
+__device__ __forceinline__ void add_beta(const GemmArgs& g, double2& o, double2 c0) {
+  o.x += g.beta_re * c0.x - g.beta_im * c0.y;
+  o.y += g.beta_re * c0.y + g.beta_im * c0.x;
+}
+
+// one element of an operand or of a partial sum: complex as one 16-byte load, real with a zero imaginary part
+template <bool CPLX>
+__device__ __forceinline__ double2 load_elem(const double* p) {
+  if constexpr (CPLX) return *reinterpret_cast<const double2*>(p);
+  return make_double2(*p, 0.0);
+}
+
 // one record of the debug timeline (MPSE_GEMM_TRACE), written by one thread of a workgroup as it leaves the kernel
 __device__ __forceinline__ void trace_record(const GemmArgs& g, bool ca, bool cb, unsigned long long t0,
                                              unsigned long long rt0, unsigned long long t1, unsigned long long t2,
@@ -185,26 +206,39 @@ __device__ __forceinline__ void trace_record(const GemmArgs& g, bool ca, bool cb
   r[9] = __builtin_amdgcn_s_memrealtime();
 }
 
-#ifndef MPSE_GEMM_3M
-#define MPSE_GEMM_3M 1
-#endif
 constexpr int BM = 64, BN = 64, BK = 16, LDK = BK + 1;   // BM x BN: granularity of the tile-occupancy masks
 
+// The MFMAs of one 16 x 16 sub-tile on one k-group (4 of K).  complex x complex uses the 3M scheme (three real products
+// per complex product instead of four):
+//   T1 = Ar Br, T2 = Ai Bi, T3 = (Ar + Ai)(Br + Bi)  =>  re = T1 - T2, im = T3 - T1 - T2
+// re holds T1, im holds T3, t2 holds T2 until the epilogue combines them; as / bs: the sums, formed once per k-group.
+// complex x real: two products, real x real: one.
+template <bool CA, bool CB>
+__device__ __forceinline__ void mfma_subtile(const double& ar, const double& ai, const double& br, const double& bi,
+                                             const double& as, const double& bs, v4d& re, v4d& im, v4d& t2) {
+  re = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, re, 0, 0, 0);
+  if constexpr (CA && CB) {
+    t2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bi, t2, 0, 0, 0);
+    im = __builtin_amdgcn_mfma_f64_16x16x4f64(as, bs, im, 0, 0, 0);
+  } else if constexpr (CA) {
+    im = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, im, 0, 0, 0);
+  } else if constexpr (CB) {
+    im = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi, im, 0, 0, 0);
+  }
+}
+
 // KS: both K maps are single level -> no integer division in the K loop
-// WS: waves per side of the workgroup tile.  WS = 2: 256 threads own 64 x 64 (the workhorse); WS = 1: ONE wave owns
-// 32 x 32 - for products whose 64 x 64 tiles cannot fill the chip, four times as many workgroups instead of slicing K
-// into partial sums that a second kernel has to add up.
-// WI: 16-row blocks of the output tile per wave.  2: four waves of 32 x 32 (the default).  1 (WS = 2 only): eight
-// waves of 16 x 32 on the same 64 x 64 tile - for launches that put ONE workgroup on a compute unit, so that every
+// WI: 16-row blocks of the 64 x 64 output tile per wave.  2: four waves of 32 x 32 (the default).  1: eight
+// waves of 16 x 32 on the same tile - for launches that put ONE workgroup on a compute unit, so that every
 // SIMD still has two waves to overlap fragment reads, staging and address arithmetic with the other's MFMAs.
 // GRP: grouped launch (GemmGroups; batch == 1, unsplit, KS, K a multiple of BK, M a multiple of the tile height).
-template <bool CA, bool CB, bool KS, int WS, int WI = 2, bool GRP = false>
-__global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 : ((CA && CB) ? 2 : 3)) void k_gemm(const GemmArgs g) {
-  static_assert(!GRP || (KS && WS == 2), "grouped launches use the single-level 64 x 64 kernel");
-  constexpr int TBM = 32 * WS, TBN = 32 * WS, NT = 64 * WS * WS * (2 / WI);
-  static_assert(WI == 2 || (WI == 1 && WS == 2), "eight-wave form only for 64 x 64 tiles");
-  constexpr int LD = WS == 2 ? 80 : 48;          // [k][i] panel rows; LD mod 32 == 16 keeps the fragment reads conflict free
-  constexpr int NLD = TBM * BK / NT;             // staged elements per thread and operand (panel = BK*LD >= TBM*LDK doubles)
+template <bool CA, bool CB, bool KS, int WI = 2, bool GRP = false>
+__global__ __launch_bounds__(256 * (2 / WI), WI == 1 ? 4 : ((CA && CB) ? 2 : 3)) void k_gemm(const GemmArgs g) {
+  static_assert(!GRP || KS, "grouped launches use the single-level kernel");
+  static_assert(WI == 1 || WI == 2, "four or eight waves");
+  constexpr int NT = 256 * (2 / WI);
+  constexpr int LD = 80;                         // [k][i] panel rows; LD mod 32 == 16 keeps the fragment reads conflict free
+  constexpr int NLD = BM * BK / NT;              // staged elements per thread and operand (panel = BK*LD >= BM*LDK doubles)
   constexpr bool CC = CA || CB;
   constexpr int EA = CA ? 2 : 1, EB = CB ? 2 : 1, EC = CC ? 2 : 1;
   // one LDS object: [Are | Aim? | Bre | Bim?], each BK x LD doubles
@@ -221,50 +255,20 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  const int wm = WS == 2 ? wave >> 1 : 0, wn = WS == 2 ? wave & 1 : 0;   // WI == 1: wm = 0 .. 3
+  const int wm = wave >> 1, wn = wave & 1;   // WI == 1: wm = 0 .. 3
   constexpr int WROWS = 16 * WI;         // rows of the output tile per wave
 
   const int ntile = g.tiles_m * g.tiles_n;
   const int bid = blockIdx.x;
-  // launch position -> (batch, K slice, tile): tile-fastest, or - split products of one batch element - slice-fastest:
-  // the die of a workgroup is its launch position mod 8, so with the slice running fastest a die works on one (or a
-  // few) K slices of every tile and its L2 sees 1/8 of both operands instead of most of them
-  int bs = bid / ntile;                  // (batch, k-slice)
-  int t = bid - bs * ntile;
-  int half = 0;                          // grouped launch with split2: which half of the tile's K tiles
-  if constexpr (GRP) {
-    if (g.gg.split2) {
-      // Launch position -> (tile, half).  Positions go to the dies round robin and, on a die, to its compute units in
-      // order: the first cpd positions of a die get a unit each, the next cpd join them.  The 2 m halves of the die's m
-      // tiles, by decreasing weight, are laid out so that the unit that receives the q-th heaviest half in the first
-      // round receives the q-th lightest in the second.
-      if ((ntile & 7) == 0) {
-        const int m2 = 2 * (ntile >> 3), r = bid >> 3, cpd = g.gg.cpd;
-        const int q = (r < cpd || m2 <= cpd) ? r : (m2 - 1) - (r - cpd);
-        half = q & 1;
-        t = ((q >> 1) << 3) | (bid & 7);
-      } else {
-        half = bid & 1;
-        t = bid >> 1;
-      }
-      bs = half;       // (slot of the dot partials: half * tiles + tile)
-    }
-  }
-  if (g.slice_fast) {
-    t = bid / g.ksplit;
-    bs = bid - t * g.ksplit;
-  }
+  // ---- tile of this position: launch position -> (batch, K slice, tile, half of a halved tile), mpse_gemm_tiles.h
+  int bs, t, half;
+  mpse_tiles::launch_position(g, GRP, bid, ntile, bs, t, half);
   const int b = bs / g.ksplit;
   const int ks_id = bs - b * g.ksplit;
-  // heaviest tiles first (k_tile_order); the odd slices of a split product run through the order backwards, so that
-  // the compute unit that receives a heavy tile's slice in one round receives a light one in the next
   bool dead = false;                     // grouped launch with a result mask: nobody reads this tile
-  if (g.perm) {
-    t = g.perm[(ks_id & 1) ? ntile - 1 - t : t];
-    if constexpr (GRP) {
-      dead = t < 0;
-      t = dead ? ~t : t;
-    }
+  if (g.perm) {                          // heaviest tiles first (k_tile_order)
+    t = g.perm[mpse_tiles::order_index(t, ks_id, ntile)];
+    if constexpr (GRP) mpse_tiles::order_decode(t, t, dead);
   }
   int tm = t / g.tiles_n;
   int tn = t - tm * g.tiles_n;
@@ -281,29 +285,14 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
       return;
     }
   }
-  // unsplit products without a sorted order: all tiles of a tile row (die_group 1) or tile column (2) on one die -
-  // position p runs on die p mod 8, so die x takes rows x, x + 8, .. with every column: the larger operand's panels are
-  // fetched into one L2 instead of into all eight
-  if (g.die_group == 1) {
-    const int x = t & 7, j = t >> 3;
-    tm = x + 8 * (j / g.tiles_n);
-    tn = j % g.tiles_n;
-  } else if (g.die_group == 2) {
-    const int x = t & 7, j = t >> 3;
-    tn = x + 8 * (j / g.tiles_m);
-    tm = j % g.tiles_m;
-  }
-  // Workgroups go to the eight dies round robin (die = blockIdx mod 8) and the number of tile columns is a multiple
-  // of eight, so without the skew a die would own whole tile columns: with block-sparse operands (quantum-number
-  // sectors are column ranges) some dies got three times the K tiles of others (tools/gemm_balance.py).
-  if (g.skew && !g.perm && !g.die_group) tn = (tn + tm) % g.tiles_n;
-
+  MPSE_TILES_PLACE(g, t, tm, tn);       // die groups, skew
   // grouped launch: the tile row picks the group, the rest of the kernel sees the group's own rows
   int grp = 0;
   if constexpr (GRP) {
-    grp = tm / g.gg.tiles_m_grp;
+    grp = mpse_tiles::group_of_row(tm, g.gg.tiles_m_grp);
     tm -= grp * g.gg.tiles_m_grp;
   }
+  // ---- operands of the batch element / of the group
   const GGrp& gp = g.gg.g[grp];          // (kernel-argument memory; touched by GRP instantiations only)
   const double* A = GRP ? gp.seg[0].A : g.A + (long long)b * g.sbA * EA;
   const double* B = GRP ? gp.seg[0].B : g.B + (long long)b * g.sbB * EB;
@@ -319,64 +308,26 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
       ak[r] = tid % BK;
       ai[r] = tid / BK + (NT / BK) * r;
     } else {
-      ai[r] = tid % TBM;
-      ak[r] = tid / TBM + (NT / TBM) * r;
+      ai[r] = tid % BM;
+      ak[r] = tid / BM + (NT / BM) * r;
     }
     if (g.b_kfast) {
       bk[r] = tid % BK;
       bj[r] = tid / BK + (NT / BK) * r;
     } else {
-      bj[r] = tid % TBN;
-      bk[r] = tid / TBN + (NT / TBN) * r;
+      bj[r] = tid % BN;
+      bk[r] = tid / BN + (NT / BN) * r;
     }
     // rows / columns past the edge read a clamped (valid) address: they only feed outputs that
     // are never stored, so no predication is needed and every load below is unconditional
-    int gi = min(tm * TBM + ai[r], g.M - 1);
-    int gj = min(tn * TBN + bj[r], g.N - 1);
+    int gi = min(tm * BM + ai[r], g.M - 1);
+    int gj = min(tn * BN + bj[r], g.N - 1);
     aoff[r] = idx_off(g.mA, gi);
     boff[r] = idx_off(g.nB, gj);
   }
 
   double2 ra[NLD], rb[NLD];
   bool ka_in[NLD], kb_in[NLD];
-  // generic tile load: two-level K maps and the (only possibly partial) last K tile
-  auto load_edge = [&](int kt) {
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      {
-        const int k = kt * BK + ak[r];
-        const bool kin = k < g.K;
-        const int kc = kin ? k : g.K - 1;
-        const long long ko = KS ? (long long)kc * g.kA.s_lo : idx_off(g.kA, kc);
-        const double* p = A + (aoff[r] + ko) * EA;
-        double2 v;
-        if constexpr (CA) {
-          v = *reinterpret_cast<const double2*>(p);
-        } else {
-          v.x = *p;
-          v.y = 0.0;
-        }
-        ra[r] = v;       // zeroing of k >= K happens at LDS-write time: nothing here consumes the load,
-        ka_in[r] = kin;  // so the waitcnt for it lands after the MFMA block of the current tile
-      }
-      {
-        const int k = kt * BK + bk[r];
-        const bool kin = k < g.K;
-        const int kc = kin ? k : g.K - 1;
-        const long long ko = KS ? (long long)kc * g.kB.s_lo : idx_off(g.kB, kc);
-        const double* p = B + (boff[r] + ko) * EB;
-        double2 v;
-        if constexpr (CB) {
-          v = *reinterpret_cast<const double2*>(p);
-        } else {
-          v.x = *p;
-          v.y = 0.0;
-        }
-        rb[r] = v;
-        kb_in[r] = kin;
-      }
-    }
-  };
   const int nkt_seg = GRP ? g.gg.nkt_seg : 0;
   const int nkt_all = GRP ? gp.nseg * nkt_seg : (g.K + BK - 1) / BK;
   int kt_begin = GRP ? 0 : ks_id * g.kt_per_split;
@@ -400,7 +351,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
       }
       return best;
     };
-    const long long a0 = tile_min(g.mA, tm * TBM, TBM, g.M), b0 = tile_min(g.nB, tn * TBN, TBN, g.N);
+    const long long a0 = tile_min(g.mA, tm * BM, BM, g.M), b0 = tile_min(g.nB, tn * BN, BN, g.N);
     a_row0 = reinterpret_cast<const char*>(A + a0 * EA);
     b_col0 = reinterpret_cast<const char*>(B + b0 * EB);
 #pragma unroll
@@ -425,31 +376,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   auto seg_pick = [&](const char* const(&arr)[GMAX_SEG], int q) {
     return q == 0 ? arr[0] : q == 1 ? arr[1] : q == 2 ? arr[2] : arr[3];
   };
-  // FULL: every k of the tile is < K.  Otherwise (at most the last K tile of a GEMM) lanes past K skip the
-  // load and stage zeros.
-  auto load_ks = [&](int kt, bool full) {
-    const char* at = a_row0 + (long long)kt * step_a;
-    const char* bt = b_col0 + (long long)kt * step_b;
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const bool ina = full || kt * BK + ak[r] < g.K;
-      const bool inb = full || kt * BK + bk[r] < g.K;
-      ra[r] = make_double2(0.0, 0.0);
-      rb[r] = make_double2(0.0, 0.0);
-      if (ina) {
-        if constexpr (CA)
-          ra[r] = *reinterpret_cast<const double2*>(at + loa[r]);
-        else
-          ra[r].x = *reinterpret_cast<const double*>(at + loa[r]);
-      }
-      if (inb) {
-        if constexpr (CB)
-          rb[r] = *reinterpret_cast<const double2*>(bt + lob[r]);
-        else
-          rb[r].x = *reinterpret_cast<const double*>(bt + lob[r]);
-      }
-    }
-  };
+  // every k of the tile is < K
   auto load_full = [&](int kt) {
     const char* at = a_row0 + (long long)kt * step_a;
     const char* bt = b_col0 + (long long)kt * step_b;
@@ -474,24 +401,77 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
       }
     }
   };
+  // ---- loader: K tile kt of both operands -> staging registers
   auto load_tile = [&](int kt) {
     if constexpr (GRP) {
       load_full(kt);
     } else if constexpr (KS) {
-      if ((kt + 1) * BK <= g.K)
+      if ((kt + 1) * BK <= g.K) {
         load_full(kt);
-      else
-        load_ks(kt, false);
-    } else {
-      load_edge(kt);
+      } else {   // (at most the last K tile of a product) lanes past K skip the load and stage zeros
+        const char* at = a_row0 + (long long)kt * step_a;
+        const char* bt = b_col0 + (long long)kt * step_b;
+#pragma unroll
+        for (int r = 0; r < NLD; ++r) {
+          const bool ina = kt * BK + ak[r] < g.K, inb = kt * BK + bk[r] < g.K;
+          ra[r] = make_double2(0.0, 0.0);
+          rb[r] = make_double2(0.0, 0.0);
+          if (ina) {
+            if constexpr (CA)
+              ra[r] = *reinterpret_cast<const double2*>(at + loa[r]);
+            else
+              ra[r].x = *reinterpret_cast<const double*>(at + loa[r]);
+          }
+          if (inb) {
+            if constexpr (CB)
+              rb[r] = *reinterpret_cast<const double2*>(bt + lob[r]);
+            else
+              rb[r].x = *reinterpret_cast<const double*>(bt + lob[r]);
+          }
+        }
+      }
+    } else {     // general maps: an offset per element, also for the (only possibly partial) last K tile
+#pragma unroll
+      for (int r = 0; r < NLD; ++r) {
+        {
+          const int k = kt * BK + ak[r];
+          const bool kin = k < g.K;
+          const int kc = kin ? k : g.K - 1;
+          const long long ko = idx_off(g.kA, kc);
+          const double* p = A + (aoff[r] + ko) * EA;
+          double2 v;
+          if constexpr (CA) {
+            v = *reinterpret_cast<const double2*>(p);
+          } else {
+            v.x = *p;
+            v.y = 0.0;
+          }
+          ra[r] = v;       // zeroing of k >= K happens at LDS-write time: nothing here consumes the load,
+          ka_in[r] = kin;  // so the waitcnt for it lands after the MFMA block of the current tile
+        }
+        {
+          const int k = kt * BK + bk[r];
+          const bool kin = k < g.K;
+          const int kc = kin ? k : g.K - 1;
+          const long long ko = idx_off(g.kB, kc);
+          const double* p = B + (boff[r] + ko) * EB;
+          double2 v;
+          if constexpr (CB) {
+            v = *reinterpret_cast<const double2*>(p);
+          } else {
+            v.x = *p;
+            v.y = 0.0;
+          }
+          rb[r] = v;
+          kb_in[r] = kin;
+        }
+      }
     }
   };
   const double sgn_a = g.conjA ? -1.0 : 1.0, sgn_b = g.conjB ? -1.0 : 1.0;
 
-  // complex x complex uses the 3M scheme (three real products per complex product instead of four):
-  //   T1 = Ar Br, T2 = Ai Bi, T3 = (Ar + Ai)(Br + Bi)  =>  re = T1 - T2, im = T3 - T1 - T2
-  // acc_re holds T1, acc_im holds T3, acc_t2 holds T2 until the epilogue combines them.
-  constexpr bool M3 = CA && CB && MPSE_GEMM_3M;
+  // accumulators (complex x complex: the three products of the 3M scheme, mfma_subtile)
+  constexpr bool M3 = CA && CB;
   v4d acc_re[WI][2], acc_im[WI][2], acc_t2[WI][2];
 #pragma unroll
   for (int i = 0; i < WI; ++i)
@@ -502,8 +482,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
       acc_t2[i][j] = v4d{0, 0, 0, 0};
     }
 
-  // next K tile >= from (and < kt_end) whose A and B tiles both hold non-zeros; kt_end if there is none.
-  // The flag words of this workgroup's tile row / column are fetched into LDS once (up to MASKW words each): read
+  // ---- flags into LDS.  The flag words of this workgroup's tile row / column are fetched once (up to MASKW words each): read
   // from global memory inside the K loop they put an L2 round trip in front of every tile's loads.
   constexpr int MASKW = 64;
   __shared__ unsigned long long s_mask[2][MASKW];
@@ -544,28 +523,10 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
       // this workgroup's half: occupied K tiles [n half / 2, n (half + 1) / 2) of the tile (every thread walks the
       // same flag words); without masks the K range itself is halved
       if (mlds) {
-        auto word_of = [&](int w) {
-          unsigned long long x = s_mask[0][w] & 0x0101010101010101ull;
-          const int valid = nkt_all - 8 * w;
-          if (valid < 8) x &= valid > 0 ? (1ull << (8 * valid)) - 1ull : 0ull;
-          return x;
-        };
+        auto word_at = [&](int w) { return mpse_tiles::trim_flags(s_mask[0][w], w, nkt_all); };
         int n = 0;
-        for (int w = 0; w < g.nkw; ++w) n += __popcll(word_of(w));
-        auto pos_of = [&](int i) {      // position of the i-th occupied tile (i >= n: the end of the range)
-          if (i >= n) return nkt_all;
-          int seen = 0;
-          for (int w = 0; w < g.nkw; ++w) {
-            unsigned long long x = word_of(w);
-            const int c = __popcll(x);
-            if (seen + c > i) {
-              for (int skip = i - seen; skip > 0; --skip) x &= x - 1;
-              return (w << 3) + (__builtin_ctzll(x) >> 3);
-            }
-            seen += c;
-          }
-          return nkt_all;
-        };
+        for (int w = 0; w < g.nkw; ++w) n += __popcll(word_at(w));
+        const mpse_tiles::FlaggedPos<decltype(word_at)> pos_of{n, g.nkw, nkt_all, word_at};
         kt_begin = half == 0 ? 0 : pos_of(n / 2);
         kt_end = half == 0 ? pos_of(n / 2) : nkt_all;
       } else {
@@ -575,8 +536,8 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     }
   } else if constexpr (KS) {
     // masks are kept per 64 rows / columns whatever the workgroup tile
-    if (g.amask) am = g.amask + ((long long)b * g.mtiles_m + (tm * TBM) / BM) * g.nkw;
-    if (g.bmask) bm = g.bmask + ((long long)b * g.mtiles_n + (tn * TBN) / BN) * g.nkw;
+    if (g.amask) am = g.amask + ((long long)b * g.mtiles_m + tm) * g.nkw;
+    if (g.bmask) bm = g.bmask + ((long long)b * g.mtiles_n + tn) * g.nkw;
     if ((am || bm) && g.nkw <= MASKW) {
       if (tid < g.nkw) {
         s_mask[0][tid] = am ? am[tid] : 0x0101010101010101ull;
@@ -588,29 +549,20 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   }
   auto next_kt = [&](int from) -> int {
     if (!am && !bm) return from;
-    while (from < kt_end) {
-      const int w = from >> 3;                      // 8 byte flags per word
-      unsigned long long word = 0x0101010101010101ull;
+    return mpse_tiles::next_flagged(from, kt_end, [&](int w) {
+      unsigned long long word = mpse_tiles::FLAGS_ALL;
       if (mlds) {
         word &= s_mask[0][w] & s_mask[1][w];
       } else {
         if (am) word &= am[w];
         if (bm) word &= bm[w];
       }
-      word &= ~0ull << ((from & 7) * 8);
-      if (word) {
-        const int kt = (w << 3) + (__builtin_ctzll(word) >> 3);
-        return kt < kt_end ? kt : kt_end;
-      }
-      from = (w + 1) << 3;
-    }
-    return kt_end;
+      return word;
+    });
   };
   int kt = next_kt(kt_begin);
   if (g.trace) tr1 = __builtin_readcyclecounter();
-  if (kt < kt_end) {
-    load_tile(kt);
-  }
+  if (kt < kt_end) load_tile(kt);
   const int frow = lane & 15, fk = lane >> 4;
   // LDS strides (in doubles) of element (i, k) of each panel
   const int sai = g.a_kfast ? LDK : 1, sak = g.a_kfast ? 1 : LD;
@@ -630,74 +582,37 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   // operand fragments of one k-group (4 of K): double buffered so that the ds_reads of group kk+1 are in
   // flight under the 16 MFMAs of group kk
   double f_ar[2][WI], f_ai[2][WI], f_br[2][2], f_bi[2][2];
-  constexpr int lds_set = 0;
   auto read_frag = [&](int buf, int kk) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       if (i < WI) {
-        f_ar[buf][i] = sAr[lds_set + rofa[i] + kk * 4 * sak];
-        if constexpr (CA) f_ai[buf][i] = sAi[lds_set + rofa[i] + kk * 4 * sak];
+        f_ar[buf][i] = sAr[rofa[i] + kk * 4 * sak];
+        if constexpr (CA) f_ai[buf][i] = sAi[rofa[i] + kk * 4 * sak];
       }
-      f_br[buf][i] = sBr[lds_set + rofb[i] + kk * 4 * sbk];
-      if constexpr (CB) f_bi[buf][i] = sBi[lds_set + rofb[i] + kk * 4 * sbk];
+      f_br[buf][i] = sBr[rofb[i] + kk * 4 * sbk];
+      if constexpr (CB) f_bi[buf][i] = sBi[rofb[i] + kk * 4 * sbk];
     }
   };
-  // staged registers -> LDS panels of set `off`
-  auto stage_to_lds = [&](int off) {
+  // staged registers -> LDS panels
+  auto stage_to_lds = [&]() {
 #pragma unroll
     for (int r = 0; r < NLD; ++r) {
-      if constexpr (KS) {  // out-of-range k were staged as zeros by load_ks
-        sAr[off + wofa[r]] = ra[r].x;
-        if constexpr (CA) sAi[off + wofa[r]] = sgn_a * ra[r].y;
-        sBr[off + wofb[r]] = rb[r].x;
-        if constexpr (CB) sBi[off + wofb[r]] = sgn_b * rb[r].y;
+      if constexpr (KS) {  // out-of-range k were staged as zeros by load_tile
+        sAr[wofa[r]] = ra[r].x;
+        if constexpr (CA) sAi[wofa[r]] = sgn_a * ra[r].y;
+        sBr[wofb[r]] = rb[r].x;
+        if constexpr (CB) sBi[wofb[r]] = sgn_b * rb[r].y;
       } else {
-        sAr[off + wofa[r]] = ka_in[r] ? ra[r].x : 0.0;
-        if constexpr (CA) sAi[off + wofa[r]] = ka_in[r] ? sgn_a * ra[r].y : 0.0;
-        sBr[off + wofb[r]] = kb_in[r] ? rb[r].x : 0.0;
-        if constexpr (CB) sBi[off + wofb[r]] = kb_in[r] ? sgn_b * rb[r].y : 0.0;
+        sAr[wofa[r]] = ka_in[r] ? ra[r].x : 0.0;
+        if constexpr (CA) sAi[wofa[r]] = ka_in[r] ? sgn_a * ra[r].y : 0.0;
+        sBr[wofb[r]] = kb_in[r] ? rb[r].x : 0.0;
+        if constexpr (CB) sBi[wofb[r]] = kb_in[r] ? sgn_b * rb[r].y : 0.0;
       }
     }
   };
-  // the 16 (x3 / x4 / x2 / x1) MFMAs of k-group kk on fragment buffer cb
-  auto mfma_group = [&](int cb) {
-    if constexpr (M3) {
-      double as[WI], bs[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (i < WI) as[i] = f_ar[cb][i] + f_ai[cb][i];
-        bs[i] = f_br[cb][i] + f_bi[cb][i];
-      }
-#pragma unroll
-      for (int i = 0; i < WI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc_re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_br[cb][j], acc_re[i][j], 0, 0, 0);
-          acc_t2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ai[cb][i], f_bi[cb][j], acc_t2[i][j], 0, 0, 0);
-          acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], acc_im[i][j], 0, 0, 0);
-        }
-    } else {
-#pragma unroll
-      for (int i = 0; i < WI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc_re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_br[cb][j], acc_re[i][j], 0, 0, 0);
-          if constexpr (CA && CB) {
-            acc_re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f_ai[cb][i], f_bi[cb][j], acc_re[i][j], 0, 0, 0);
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_bi[cb][j], acc_im[i][j], 0, 0, 0);
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ai[cb][i], f_br[cb][j], acc_im[i][j], 0, 0, 0);
-          } else if constexpr (CA) {
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ai[cb][i], f_br[cb][j], acc_im[i][j], 0, 0, 0);
-          } else if constexpr (CB) {
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_bi[cb][j], acc_im[i][j], 0, 0, 0);
-          }
-        }
-    }
-  };
-
-  // the last k-group of a tile with the staging stores of the next tile between its MFMAs (one register of each
-  // operand per output sub-tile; KS variants)
-  auto mfma_group_staging = [&](int cb) {
+  // The 16 (x3 / x2 / x1) MFMAs of a k-group on fragment buffer cb.  `staging` (the last k-group of a tile, KS
+  // variants): with the staging stores of the next tile between them, one register of each operand per output sub-tile.
+  auto mfma_group = [&](int cb, auto staging) {
     double as[WI], bs[2];
     if constexpr (M3) {
 #pragma unroll
@@ -710,46 +625,34 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     for (int i = 0; i < WI; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        if constexpr (M3) {
-          acc_re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_br[cb][j], acc_re[i][j], 0, 0, 0);
-          acc_t2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ai[cb][i], f_bi[cb][j], acc_t2[i][j], 0, 0, 0);
-          acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], acc_im[i][j], 0, 0, 0);
-        } else {
-          acc_re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_br[cb][j], acc_re[i][j], 0, 0, 0);
-          if constexpr (CA && CB) {
-            acc_re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(-f_ai[cb][i], f_bi[cb][j], acc_re[i][j], 0, 0, 0);
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_bi[cb][j], acc_im[i][j], 0, 0, 0);
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ai[cb][i], f_br[cb][j], acc_im[i][j], 0, 0, 0);
-          } else if constexpr (CA) {
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ai[cb][i], f_br[cb][j], acc_im[i][j], 0, 0, 0);
-          } else if constexpr (CB) {
-            acc_im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f_ar[cb][i], f_bi[cb][j], acc_im[i][j], 0, 0, 0);
-          }
-        }
-        constexpr int PER = NLD / 4 > 0 ? NLD / 4 : 1;
+        mfma_subtile<CA, CB>(f_ar[cb][i], f_ai[cb][i], f_br[cb][j], f_bi[cb][j], as[i], bs[j], acc_re[i][j], acc_im[i][j],
+                             acc_t2[i][j]);
+        if constexpr (decltype(staging)::value) {
+          constexpr int PER = NLD / 4 > 0 ? NLD / 4 : 1;
 #pragma unroll
-        for (int q = 0; q < PER; ++q) {
-          const int r = (2 * i + j) * PER + q;
-          if (r < NLD) {
+          for (int q = 0; q < PER; ++q) {
+            const int r = (2 * i + j) * PER + q;
+            if (r < NLD) {
             sAr[wofa[r]] = ra[r].x;
             if constexpr (CA) sAi[wofa[r]] = sgn_a * ra[r].y;
             sBr[wofb[r]] = rb[r].x;
             if constexpr (CB) sBi[wofb[r]] = sgn_b * rb[r].y;
+            }
           }
+          // pin the interleave: the MFMAs of this sub-tile, then its staging stores (left alone the scheduler issues
+          // the MFMAs first and the stores in a block behind them)
+          constexpr int NM = M3 ? 3 : (CA || CB) ? 2 : 1;
+          __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
+          __builtin_amdgcn_sched_group_barrier(0x200, (2 + (CA ? 1 : 0) + (CB ? 1 : 0)) * PER, 0);
         }
-        // pin the interleave: the MFMAs of this sub-tile, then its staging stores (left alone the scheduler issues
-        // the MFMAs first and the stores in a block behind them)
-        constexpr int NM = M3 ? 3 : (CA && CB) ? 4 : (CA || CB) ? 2 : 1;
-        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, (2 + (CA ? 1 : 0) + (CB ? 1 : 0)) * PER, 0);
       }
   };
+  constexpr std::false_type plain{};
+  constexpr std::true_type with_staging{};
 
-#ifndef MPSE_GEMM_PIPE
-#define MPSE_GEMM_PIPE 1
-#endif
+  // ---- K loop
   int kt_done = 0;
-  if constexpr (KS && MPSE_GEMM_PIPE) {
+  if constexpr (KS) {
     // Software-pipelined K loop.  A wave issues in order: every instruction that is not an MFMA and sits between the
     // last MFMA of one K tile and the first of the next (barrier, staging stores, barrier, mask look-up, pointer
     // updates, loads, first fragment reads) is time the matrix pipe idles unless a second workgroup on the CU fills it
@@ -758,11 +661,9 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     // tile; the loads of the tile after that are issued under the first k-group of the next iteration.
     int nk = kt_end;
     if (kt < kt_end) {
-      stage_to_lds(0);
+      stage_to_lds();
       nk = next_kt(kt + 1);
-      if (nk < kt_end) {
-        load_tile(nk);
-      }
+      if (nk < kt_end) load_tile(nk);
       lds_barrier();
       if (g.trace) tr2 = __builtin_readcyclecounter();
       read_frag(0, 0);
@@ -771,13 +672,13 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     while (nk < kt_end) {          // tile kt has a successor (single-exit loop: an exit in the middle made the
       ++kt_done;                   // compiler keep two copies of the accumulators and spill)
       read_frag(1, 1);
-      mfma_group(0);
+      mfma_group(0, plain);
       read_frag(0, 2);
-      mfma_group(1);
+      mfma_group(1, plain);
       read_frag(1, 3);
-      mfma_group(0);
+      mfma_group(0, plain);
       lds_barrier();               // every wave holds its last fragments: the panels may be overwritten
-      mfma_group_staging(1);       // the MFMAs of the last k-group, the staging stores of tile nk between them
+      mfma_group(1, with_staging); // the MFMAs of the last k-group, the staging stores of tile nk between them
       // the tile after nk (mask words in LDS: no global load is waited for); its loads stay in flight across the
       // barrier (lds_barrier does not wait for them) and across the next iteration's MFMAs
       const int after = next_kt(nk + 1);
@@ -790,24 +691,22 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     if (any) {                     // last tile: nothing left to stage
       ++kt_done;
       read_frag(1, 1);
-      mfma_group(0);
+      mfma_group(0, plain);
       read_frag(0, 2);
-      mfma_group(1);
+      mfma_group(1, plain);
       read_frag(1, 3);
-      mfma_group(0);
-      mfma_group(1);
+      mfma_group(0, plain);
+      mfma_group(1, plain);
     }
   } else {
   while (kt < kt_end) {
     ++kt_done;
     __syncthreads();
     if (g.trace && kt_done == 1) tr2 = __builtin_readcyclecounter();
-    stage_to_lds(0);
+    stage_to_lds();
     __syncthreads();
     const int nk = next_kt(kt + 1);
-    if (nk < kt_end) {
-      load_tile(nk);
-    }
+    if (nk < kt_end) load_tile(nk);
     kt = nk;
 
     read_frag(0, 0);
@@ -815,7 +714,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     for (int kk = 0; kk < BK / 4; ++kk) {
       const int cb = kk & 1;
       if (kk + 1 < BK / 4) read_frag(cb ^ 1, kk + 1);
-      mfma_group(cb);
+      mfma_group(cb, plain);
     }
   }
   }
@@ -831,7 +730,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     }
   } trace_end{g, tr0, rt0, tr1, tr2, tr3, tid, kt_done};
   if (g.kt_counter && tid == 0 && kt_done) atomicAdd(g.kt_counter, (unsigned long long)kt_done);
-  if constexpr (M3) {
+  if constexpr (M3) {   // ---- 3M combine
 #pragma unroll
     for (int i = 0; i < WI; ++i)
 #pragma unroll
@@ -840,19 +739,19 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
         acc_re[i][j] = acc_re[i][j] - acc_t2[i][j];
       }
   }
-  // ---- epilogue: lane holds rows (lane>>4)+4r, column lane&15 of each 16x16 tile
+  // ---- epilogue (split-K store, or: beta source, store with dot and hand-off, block dot): lane holds rows (lane>>4)+4r, column lane&15 of each 16x16 tile
   if (g.ksplit > 1) {
     // raw partial sums; alpha/beta and the strided store happen in k_splitk_reduce
     double* wsb = g.ws + (long long)bs * g.M * g.N * EC;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int gj = tn * TBN + wn * 32 + j * 16 + (lane & 15);
+      const int gj = tn * BN + wn * 32 + j * 16 + (lane & 15);
       if (gj >= g.N) continue;
 #pragma unroll
       for (int i = 0; i < WI; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int gi = tm * TBM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r;
+          const int gi = tm * BM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r;
           if (gi >= g.M) continue;
           double* p = wsb + ((long long)gi * g.N + gj) * EC;
           if constexpr (CC)
@@ -905,12 +804,12 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
         double2 v[WI][2][4];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const int gj = min(tn * TBN + wn * 32 + j * 16 + (lane & 15), g.N - 1);
+          const int gj = min(tn * BN + wn * 32 + j * 16 + (lane & 15), g.N - 1);
 #pragma unroll
           for (int i = 0; i < WI; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const int gi = tm * TBM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r + delta;
+              const int gi = tm * BM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r + delta;
               const int gc = min(max(gi, 0), g.M - 1);
               v[i][j][r] = *reinterpret_cast<const double2*>(src + ((long long)gc * g.gg.mix_ld + gj) * 2);
             }
@@ -933,14 +832,14 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   if (PRE && (need_c || need_y)) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int gj = min(tn * TBN + wn * 32 + j * 16 + (lane & 15), g.N - 1);     // clamped: never stored past the edge
+      const int gj = min(tn * BN + wn * 32 + j * 16 + (lane & 15), g.N - 1);     // clamped: never stored past the edge
       const long long coffn = idx_off(g.nC, gj);
       const long long cinn = g.Cin ? idx_off(g.nCin, gj) : 0;
 #pragma unroll
       for (int i = 0; i < WI; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int gi = min(tm * TBM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r, g.M - 1);
+          const int gi = min(tm * BM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r, g.M - 1);
           const long long co = idx_off(g.mC, gi) + coffn;
           if (need_c && !mix_on) {
             const double* pin = g.Cin ? g.Cin + (idx_off(g.mCin, gi) + cinn) * EC : C + co * EC;
@@ -971,7 +870,7 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int gj = tn * TBN + wn * 32 + j * 16 + (lane & 15);
+    const int gj = tn * BN + wn * 32 + j * 16 + (lane & 15);
     if (gj >= g.N) continue;
     if constexpr (HAND) {
       if (hand) {
@@ -984,24 +883,21 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
     for (int i = 0; i < WI; ++i) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int gi = tm * TBM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r;
+        const int gi = tm * BM + wm * WROWS + i * 16 + (lane >> 4) + 4 * r;
         if (gi >= g.M) continue;
         const long long co = idx_off(g.mC, gi) + coffn;
         double* p = C + co * EC;
         const double xr = acc_re[i][j][r];
         if constexpr (CC) {
           const double xi = acc_im[i][j][r];
-          double2 o;
-          o.x = g.alpha_re * xr - g.alpha_im * xi;
-          o.y = g.alpha_re * xi + g.alpha_im * xr;
+          double2 o = alpha_times(g, xr, xi);
           if (need_c) {
             double2 c0;
             if constexpr (PRE)
               c0 = pre_c[i][j][r];
             else
               c0 = *reinterpret_cast<const double2*>(g.Cin ? g.Cin + (idx_off(g.mCin, gi) + idx_off(g.nCin, gj)) * EC : C + co * EC);
-            o.x += g.beta_re * c0.x - g.beta_im * c0.y;
-            o.y += g.beta_re * c0.y + g.beta_im * c0.x;
+            add_beta(g, o, c0);
           }
           *reinterpret_cast<double2*>(p) = o;
           if (need_y) {
@@ -1033,28 +929,26 @@ __global__ __launch_bounds__(64 * WS * WS * (2 / WI), WS == 1 ? 1 : WI == 1 ? 4 
   if constexpr (HAND) {
     if (hand && !(wm & 1)) dre = dim = 0.0;
   }
-  if constexpr (WS == 2) {
-    if (g.dot_y) {   // workgroup-uniform
-      // (block-wide sum for NT threads, totals to every thread; fixed order)
-      __shared__ double s_dot[2 * (NT / 64)];
-      dre = wave_sum(dre);
-      dim = wave_sum(dim);
-      if (lane == 0) {
-        s_dot[2 * wave] = dre;
-        s_dot[2 * wave + 1] = dim;
-      }
-      __syncthreads();
-      dre = dim = 0.0;
+  if (g.dot_y) {   // workgroup-uniform
+    // (block-wide sum for NT threads, totals to every thread; fixed order)
+    __shared__ double s_dot[2 * (NT / 64)];
+    dre = wave_sum(dre);
+    dim = wave_sum(dim);
+    if (lane == 0) {
+      s_dot[2 * wave] = dre;
+      s_dot[2 * wave + 1] = dim;
+    }
+    __syncthreads();
+    dre = dim = 0.0;
 #pragma unroll
-      for (int w = 0; w < NT / 64; ++w) {
-        dre += s_dot[2 * w];
-        dim += s_dot[2 * w + 1];
-      }
-      if (tid == 0) {   // slot = the tile, not the launch position: the sum order does not depend on the tile order
-        const long long slot = (long long)bs * ntile + (long long)tm * g.tiles_n + tn;
-        g.dot_part[2 * slot] = dre;
-        g.dot_part[2 * slot + 1] = dim;
-      }
+    for (int w = 0; w < NT / 64; ++w) {
+      dre += s_dot[2 * w];
+      dim += s_dot[2 * w + 1];
+    }
+    if (tid == 0) {   // slot = the tile, not the launch position: the sum order does not depend on the tile order
+      const long long slot = (long long)bs * ntile + (long long)tm * g.tiles_n + tn;
+      g.dot_part[2 * slot] = dre;
+      g.dot_part[2 * slot + 1] = dim;
     }
   }
 }
@@ -1109,7 +1003,7 @@ __global__ __launch_bounds__(1024) void k_tile_order(const unsigned long long* _
     if (i < ntile) {
       const int tm = i / tiles_n, tn = i - tm * tiles_n;
       if (gg.ngrp > 0) {   // grouped launch: the segments of the tile row's group, byte flags per operand
-        const int grp = tm / gg.tiles_m_grp, tml = tm - grp * gg.tiles_m_grp;
+        const int grp = mpse_tiles::group_of_row(tm, gg.tiles_m_grp), tml = tm - grp * gg.tiles_m_grp;
         const GGrp& G = gg.g[grp];
         // a tile outside the result mask (one group): no flags - weight 0, last in the order - and marked there
         const bool off = gg.omask && !mpse_plan::out_tile_live(gg.omask, gg.om_pitch, gg.om_d, om_N, om_M, tm, tn);
@@ -1163,7 +1057,7 @@ __global__ __launch_bounds__(1024) void k_tile_order(const unsigned long long* _
   for (int i = tid; i < ntile; i += 1024) {
     const int s = part ? (7 - (i & 7)) * per_die + (i >> 3) : i;
     const int t = 0xFFFF - (int)(key[s] & 0xFFFFu);
-    perm[i] = dead[t] ? ~t : t;
+    perm[i] = dead[t] ? ~t : t;           // (mpse_tiles::order_decode reads it)
   }
 }
 
@@ -1187,47 +1081,23 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const GemmArgs g, int bat
       int s = 0;
       // four slices in flight per thread (the loads are independent, the additions keep their fixed order)
       for (; s + 4 <= g.ksplit; s += 4) {
-        if constexpr (CC) {
-          const double2 v0 = *reinterpret_cast<const double2*>(w + (long long)s * mn * EC);
-          const double2 v1 = *reinterpret_cast<const double2*>(w + (long long)(s + 1) * mn * EC);
-          const double2 v2 = *reinterpret_cast<const double2*>(w + (long long)(s + 2) * mn * EC);
-          const double2 v3 = *reinterpret_cast<const double2*>(w + (long long)(s + 3) * mn * EC);
-          xr += v0.x;
-          xi += v0.y;
-          xr += v1.x;
-          xi += v1.y;
-          xr += v2.x;
-          xi += v2.y;
-          xr += v3.x;
-          xi += v3.y;
-        } else {
-          const double v0 = w[(long long)s * mn], v1 = w[(long long)(s + 1) * mn];
-          const double v2 = w[(long long)(s + 2) * mn], v3 = w[(long long)(s + 3) * mn];
-          xr += v0;
-          xr += v1;
-          xr += v2;
-          xr += v3;
-        }
+        const double2 v0 = load_elem<CC>(w + (long long)s * mn * EC), v1 = load_elem<CC>(w + (long long)(s + 1) * mn * EC);
+        const double2 v2 = load_elem<CC>(w + (long long)(s + 2) * mn * EC), v3 = load_elem<CC>(w + (long long)(s + 3) * mn * EC);
+        xr += v0.x, xi += v0.y;
+        xr += v1.x, xi += v1.y;
+        xr += v2.x, xi += v2.y;
+        xr += v3.x, xi += v3.y;
       }
       for (; s < g.ksplit; ++s) {
-        if constexpr (CC) {
-          const double2 v = *reinterpret_cast<const double2*>(w + (long long)s * mn * EC);
-          xr += v.x;
-          xi += v.y;
-        } else {
-          xr += w[(long long)s * mn];
-        }
+        const double2 v = load_elem<CC>(w + (long long)s * mn * EC);
+        xr += v.x, xi += v.y;
       }
       const long long co = idx_off(g.nC, j);
       double* p = crow + co * EC;
       const double* pin = g.Cin ? g.Cin + (idx_off(g.mCin, i) + idx_off(g.nCin, j)) * EC : p;
       if constexpr (CC) {
-        double2 o = make_double2(g.alpha_re * xr - g.alpha_im * xi, g.alpha_re * xi + g.alpha_im * xr);
-        if (g.use_beta) {
-          const double2 c0 = *reinterpret_cast<const double2*>(pin);
-          o.x += g.beta_re * c0.x - g.beta_im * c0.y;
-          o.y += g.beta_re * c0.y + g.beta_im * c0.x;
-        }
+        double2 o = alpha_times(g, xr, xi);
+        if (g.use_beta) add_beta(g, o, *reinterpret_cast<const double2*>(pin));
         *reinterpret_cast<double2*>(p) = o;
         if (g.dot_y) dot_acc(dre, dim, o, reinterpret_cast<const double2*>(g.dot_y)[idx_off(g.mC, i) + co]);
       } else {
@@ -1484,14 +1354,14 @@ void launch_gemm(mpse_ctx* ctx, const GemmArgs& g, long long nwg, bool ca, bool 
                  dim3 rgrid = dim3(0), int batch = 1) {
   using Kern = void (*)(const GemmArgs);
   static const Kern plain[4][3] = {   // [complex operands first][eight waves, four waves, general]
-      {k_gemm<true, true, true, 2, 1>, k_gemm<true, true, true, 2>, k_gemm<true, true, false, 2>},
-      {k_gemm<true, false, true, 2, 1>, k_gemm<true, false, true, 2>, k_gemm<true, false, false, 2>},
-      {k_gemm<false, true, true, 2, 1>, k_gemm<false, true, true, 2>, k_gemm<false, true, false, 2>},
-      {k_gemm<false, false, true, 2, 1>, k_gemm<false, false, true, 2>, k_gemm<false, false, false, 2>}};
+      {k_gemm<true, true, true, 1>, k_gemm<true, true, true>, k_gemm<true, true, false>},
+      {k_gemm<true, false, true, 1>, k_gemm<true, false, true>, k_gemm<true, false, false>},
+      {k_gemm<false, true, true, 1>, k_gemm<false, true, true>, k_gemm<false, true, false>},
+      {k_gemm<false, false, true, 1>, k_gemm<false, false, true>, k_gemm<false, false, false>}};
   static void (*const reduce[2])(const GemmArgs, int) = {k_splitk_reduce<true>, k_splitk_reduce<false>};
   static const Kern groups[2][2] = {   // [complex first operand first][eight waves, four waves]
-      {k_gemm<true, true, true, 2, 1, true>, k_gemm<true, true, true, 2, 2, true>},
-      {k_gemm<false, true, true, 2, 1, true>, k_gemm<false, true, true, 2, 2, true>}};
+      {k_gemm<true, true, true, 1, true>, k_gemm<true, true, true, 2, true>},
+      {k_gemm<false, true, true, 1, true>, k_gemm<false, true, true, 2, true>}};
   const int form = fast && wide ? 0 : fast ? 1 : 2;
   const Kern k = grouped ? groups[ca ? 0 : 1][form] : plain[(ca ? 0 : 2) + (cb ? 0 : 1)][form];
   hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(form == 0 ? 512 : 256), 0, ctx->stream, g);
