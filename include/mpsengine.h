@@ -985,6 +985,56 @@ int mpse_gather_cols(mpse_ctx* ctx, int dtype, void* out, const void* in, int64_
 int mpse_gather_rows(mpse_ctx* ctx, int dtype, void* out, const void* in, int64_t ncol,
                      const int64_t* rows_host, const double* scale_host, int64_t nrow_out);
 
+/* ------------------------------------------- tangent-space (TDA) excited states */
+
+/* The Hamiltonian projected onto the first-order tangent space of a matrix product state, replaces the closures hop and
+ * hdiag of mps/tda.py:152-247 (TDA.kernel).  With B_j the right-canonical sites of the normalised state, A_j the
+ * left-canonical sites of the left-to-right SVD sweep (tda.py:98-121), U_j (Dl, d, n_j) the trailing columns of the full
+ * left factor of site j (absent where n_j = 0) and T_j = U_j X_j, one application is
+ *   L_0 = 1, L_{j+1} = updL(L_j; A_j, W_j, A_j);  R_N = 1, R_j = updR(R_{j+1}; B_j, W_j, B_j)        (once per handle)
+ *   F_0 = 0, F_{j+1} = updL(F_j; A_j, W_j, B_j) + updL(L_j; A_j, W_j, T_j)                           j = 0 .. N-2
+ *   G_N = 0, G_j     = updR(G_{j+1}; B_j, W_j, A_j) + updR(R_{j+1}; B_j, W_j, T_j)                   j = N-1 .. 1
+ *   O_j = heff(L_j, W_j, R_{j+1}) T_j + heff(F_j, W_j, R_{j+1}) B_j + heff(L_j, W_j, G_{j+1}) A_j
+ *   Y_j[l, r] = sum_{a, s} conj(U_j[a, s, l]) O_j[a, s, r]
+ * (upd(E; bra, W, ket) = mpse_env_update with the bra conjugated, heff = the one-site mpse_heff_apply): 4 (N - 1)
+ * environment updates and 3 N effective-Hamiltonian applications at most, where the reference rebuilds an environment
+ * chain per site that carries coefficients (about N^2 updates).  Terms that vanish (F_0, G_N, T_j of a site without U_j)
+ * are not issued.  The vector x is the concatenation, over the sites that have a U_j, of X_j (n_j, Dr_j), row major
+ * (the reference's reshape_x); its element type is the handle's working dtype: MPSE_C128 as soon as any operand is
+ * complex, MPSE_F64 otherwise.
+ *
+ * mpse_tda_create: the handle borrows the caller's device pointers - they must stay valid and unchanged while it lives -
+ *   A[i], B[i] (Dl, d, Dr), U[i] (Dl, d, n) or NULL, W[i] (wl, d, d, wr), each MPSE_F64 or MPSE_C128 (u_dtype[i] of an
+ *   absent U[i] is not read), dims: nsite rows (Dl, d, Dr, wl, wr, n), host; n == 0 <=> U[i] == NULL.
+ *   Rows with an extent < 1 (n < 0), neighbours whose bonds or MPO bonds differ, a first / last bond or MPO bond != 1, or
+ *   n > Dl d: MPSE_ERR_SHAPE before any device work; null sites or dtypes out of range: MPSE_ERR_ARG.  It owns L_j, R_j
+ *   (one enqueued update each; their unit channels are looked up once with mpse_env_unit_channel), widened copies of
+ *   real sites of a complex handle, the offsets of x and the work buffers F, G, T, O.  *xsize_out = sum_j n_j Dr_j,
+ *   *dtype_out = the working dtype (either may be NULL).  An empty tangent space (xsize == 0) is MPSE_ERR_SHAPE.
+ * mpse_tda_apply: y = P^H H P x, enqueued on the context stream, no host synchronisation; x is not modified and must
+ *   not overlap y.
+ * mpse_tda_hdiag: out_f64[xsize] = Re diag(P^H H P) (tda.py:154-170, "abc,ded,bghe,agl,chl->ld"), per site
+ *   X[b,c,(g,l)] = sum_a L[a,b,c] conj(U[a,(g,l)]) as a product, Q[(b,g,h),l] = sum_c X[b,c,g,l] U[c,h,l] by the
+ *   column-wise dot kernel k_tda_qdiag, then the products with W and with the strided diagonal of R; the columns l are
+ *   walked in chunks that keep X under 256 MiB (MPSE_TDA_X_BYTES in the environment overrides the bound, read per call).
+ * mpse_tda_davidson: mpse_davidson with the handle as the operator, on vectors of xsize elements of the working dtype
+ *   (`dtype` must be it): same iteration, arguments, limits and results; no mask.  Synchronous.
+ * mpse_tda_stats: counts[i], i < n, cumulative:  0 handles created, 1 applications, 2 environment updates and 3
+ *   effective-Hamiltonian applications issued by applications, 4 sites through k_tda_qdiag, 5 Davidson calls.
+ *   Diagnostics for tests; no device work. */
+typedef struct mpse_tda mpse_tda;
+int mpse_tda_create(mpse_ctx* ctx, int nsite, const void* const* A, const int* a_dtype, const void* const* B,
+                    const int* b_dtype, const void* const* U, const int* u_dtype, const void* const* W,
+                    const int* w_dtype, const int64_t* dims /* nsite x 6 */, mpse_tda** out, int64_t* xsize_out,
+                    int* dtype_out);
+int mpse_tda_destroy(mpse_ctx* ctx, mpse_tda* h);
+int mpse_tda_apply(mpse_ctx* ctx, mpse_tda* h, const void* x, void* y);
+int mpse_tda_hdiag(mpse_ctx* ctx, mpse_tda* h, void* out_f64);
+int mpse_tda_davidson(mpse_ctx* ctx, int dtype, mpse_tda* h, const void* hdiag_f64, int nroots, int nguess,
+                      const void* guess, double tol, int max_cycle, int max_space, double lindep, double shift,
+                      double* e_host, void* x_out, int* ncycle, int* nmatvec);
+int mpse_tda_stats(mpse_ctx* ctx, int64_t* counts, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ def __getattr__(name):
     if name == "optimize_mps":
         from .mps.gs import optimize_mps
         return optimize_mps
-    if name in ("MpDm", "thermal_state", "ThermalProp", "BraKetPair"):
+    if name in ("MpDm", "thermal_state", "ThermalProp", "BraKetPair", "TDA"):
         from . import mps as _mps
         return getattr(_mps, name)
     if name in ("ChargeDiffusionDynamics", "InitElectron", "EDGE_THRESHOLD", "calc_r_square"):

@@ -3,7 +3,7 @@
 set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
-SRCS="mpse_core.hip mpse_gemm.hip mpse_contract.hip mpse_small.hip mpse_heff0.hip mpse_vec.hip mpse_lanczos.hip mpse_qr.hip mpse_qr2.hip mpse_cholqr.hip mpse_svd.hip mpse_davidson.hip mpse_pcg.hip mpse_small2.hip mpse_overlap.hip mpse_sandwich.hip mpse_corr.hip mpse_rdm1.hip mpse_rdm2.hip mpse_trdm1.hip mpse_bondspec.hip mpse_expect.hip"
+SRCS="mpse_core.hip mpse_gemm.hip mpse_contract.hip mpse_small.hip mpse_heff0.hip mpse_vec.hip mpse_lanczos.hip mpse_qr.hip mpse_qr2.hip mpse_cholqr.hip mpse_svd.hip mpse_davidson.hip mpse_pcg.hip mpse_small2.hip mpse_overlap.hip mpse_sandwich.hip mpse_corr.hip mpse_rdm1.hip mpse_rdm2.hip mpse_trdm1.hip mpse_bondspec.hip mpse_expect.hip mpse_tda.hip"
 OBJS=""
 PIDS=""
 for s in $SRCS; do

@@ -232,9 +232,7 @@ struct Dav {
   mpse_ctx* ctx;
   int dtype;
   bool cplx;
-  const mpse_heff* h;
-  SolveScope* scope;
-  int twolayer;
+  DavOp op;       // the operator: y = H x (mpse_davidson: the effective Hamiltonian; mpse_tda_davidson: the handle)
   const void* mask;
   int64_t n;
   size_t es;
@@ -251,10 +249,7 @@ struct Dav {
 
   int apply(const void* x, void* y) {
     ++nmatvec;
-    if (twolayer)
-      MPSE_TRY(mpse_heff_apply2(ctx, dtype, h, x, y));
-    else
-      MPSE_TRY(heff_apply(ctx, dtype, h, x, y, scope, nullptr));
+    MPSE_TRY(op.fn(op.self, x, y));
     if (mask) MPSE_TRY(mpse_mul_real(ctx, dtype, y, mask, n));
     return MPSE_OK;
   }
@@ -330,6 +325,20 @@ struct Dav {
   }
 };
 
+// the operator of mpse_davidson: the effective Hamiltonian inside the scope of the solve
+struct HeffOp {
+  mpse_ctx* ctx;
+  int dtype;
+  const mpse_heff* h;
+  SolveScope* scope;
+  int twolayer;
+  static int apply(void* self, const void* x, void* y) {
+    HeffOp* o = static_cast<HeffOp*>(self);
+    if (o->twolayer) return mpse_heff_apply2(o->ctx, o->dtype, o->h, x, y);
+    return heff_apply(o->ctx, o->dtype, o->h, x, y, o->scope, nullptr);
+  }
+};
+
 }  // namespace
 
 extern "C" int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, const void* hdiag_f64,
@@ -349,6 +358,15 @@ extern "C" int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int t
   int64_t n = s.Dl_ket * s.Dr_ket * s.d0 * anc;
   if (h->nsite == 2) n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
   if (n <= 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "davidson: empty centre tensor");
+  HeffOp op{ctx, dtype, h, &scope, twolayer};
+  return davidson_solve(ctx, dtype, n, DavOp{&HeffOp::apply, &op}, hdiag_f64, mask_f64, nroots, nguess, guess, tol,
+                        max_cycle, max_space, lindep, shift, e_host, x_out, ncycle, nmatvec);
+}
+
+// The iteration of mpse_davidson on vectors of n elements under any operator (mpse_internal.h)
+int davidson_solve(mpse_ctx* ctx, int dtype, int64_t n, const DavOp& op, const void* hdiag_f64, const void* mask_f64,
+                   int nroots, int nguess, const void* guess, double tol, int max_cycle, int max_space, double lindep,
+                   double shift, double* e_host, void* x_out, int* ncycle, int* nmatvec) {
   if (max_space <= 0) max_space = 12 + (nroots - 1) * 3;
   if (max_space + nroots + 1 > DV_MAX)
     return mpse_fail(ctx, MPSE_ERR_ARG, "davidson: max_space too large (max_space + nroots + 1 = %d > %d)",
@@ -366,7 +384,7 @@ extern "C" int mpse_davidson(mpse_ctx* ctx, int dtype, const mpse_heff* h, int t
   MPSE_TRY(VB.alloc(size_t(cap) * n * es));
   MPSE_TRY(WB.alloc(size_t(cap) * n * es));
   Dav d;
-  d.ctx = ctx, d.dtype = dtype, d.cplx = cplx, d.h = h, d.scope = &scope, d.twolayer = twolayer, d.mask = mask_f64;
+  d.ctx = ctx, d.dtype = dtype, d.cplx = cplx, d.op = op, d.mask = mask_f64;
   d.n = n, d.es = es;
   d.nb = dv_blocks(n * (cplx ? 2 : 1));
   MPSE_TRY(PB.alloc(size_t(DV_MAX) * d.nb * 2 * sizeof(double)));

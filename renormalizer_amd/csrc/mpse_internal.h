@@ -199,6 +199,9 @@ struct mpse_ctx {
   // mpse_mps_expect_many (mpse_mps_expect_many_stats; the order of include/mpsengine.h)
   enum ExpectStat { EX_CHAIN, EX_ENQUEUED, EX_SITES, EX_ENTRIES, EX_COUNT };
   long long expect_stats[EX_COUNT] = {0};
+  // mpse_tda_* (mpse_tda_stats; the order of include/mpsengine.h)
+  enum TdaStat { TD_HANDLES, TD_APPLIES, TD_ENV_UPDATES, TD_HEFF_APPLIES, TD_QDIAG_SITES, TD_DAVIDSON, TD_COUNT };
+  long long tda_stats[TD_COUNT] = {0};
 };
 // What the caller of mpse_expm_lanczos said about the one solve that follows (mpse_expm_centre_mask, mpse_solve_slot):
 // taken out of the context on entry and handed down as an argument to the scope of the asynchronous solve
@@ -615,6 +618,19 @@ struct PublishAt {
 __attribute__((visibility("hidden"))) PublishAt publish_target(mpse_ctx* ctx, bool wait_here, int slot);
 __attribute__((visibility("hidden"))) int publish_collect(mpse_ctx* ctx, const PublishAt& at, const void* dsrc, size_t stride,
                                                           int B, int W, int slot, void* host_out);
+
+// The Davidson iteration of mpse_davidson (mpse_davidson.hip) on vectors of n elements of `dtype` under an operator the
+// caller supplies: fn(self, x, y) enqueues y = H x on the context stream.  Everything else - arguments, limits, results -
+// as mpse_davidson documents it.
+struct DavOp {
+  int (*fn)(void* self, const void* x, void* y);
+  void* self;
+};
+__attribute__((visibility("hidden"))) int davidson_solve(mpse_ctx* ctx, int dtype, int64_t n, const DavOp& op,
+                                                         const void* hdiag_f64, const void* mask_f64, int nroots,
+                                                         int nguess, const void* guess, double tol, int max_cycle,
+                                                         int max_space, double lindep, double shift, double* e_host,
+                                                         void* x_out, int* ncycle, int* nmatvec);
 
 // reductions (mpse_vec.hip): results land in ctx->pinned after a stream sync
 int dotc_sync(mpse_ctx* ctx, int dtype, const void* x, const void* y, int64_t n, double* re, double* im);

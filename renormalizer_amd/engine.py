@@ -221,6 +221,15 @@ _SIGNATURES = {
                             _i64p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _dblp, C.c_int64],
     "mpse_gather_cols": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _i64p, _dblp, C.c_int64],
     "mpse_gather_rows": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _dblp, C.c_int64],
+    "mpse_tda_create": [C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p), C.POINTER(C.c_int)] * 4 +
+                       [_i64p, C.POINTER(C.c_void_p), _i64p, C.POINTER(C.c_int)],
+    "mpse_tda_destroy": [C.c_void_p, C.c_void_p],
+    "mpse_tda_apply": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpse_tda_hdiag": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpse_tda_davidson": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                          C.c_int, C.c_int, C.c_double, C.c_double, _dblp, C.c_void_p, C.POINTER(C.c_int),
+                          C.POINTER(C.c_int)],
+    "mpse_tda_stats": [C.c_void_p, _i64p, C.c_int],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["mpse_last_error", "mpse_version"])
 
@@ -569,6 +578,81 @@ class DeviceTensor:
         out = (C.c_double * 2)()
         self.eng._check(self.eng.lib.mpse_dotc(self.eng.ctx, self.code, self.ptr, other.ptr, self.size, out))
         return complex(out[0], out[1]) if self.is_complex else float(out[0])
+
+
+class TdaOperator:
+    """The Hamiltonian projected onto the first-order tangent space of a matrix product state (``mpse_tda_*``,
+    include/mpsengine.h): ``a``, ``b`` the left- / right-canonical device sites (Dl, d, Dr), ``u`` the tangent factors
+    (Dl, d, n) or None, ``w`` the MPO sites (wl, d, d, wr).  The engine handle borrows the tensors; this object keeps
+    them alive.  ``dtype`` is the working dtype of the vectors, ``xsize`` their length."""
+
+    def __init__(self, eng, a, b, u, w):
+        n = len(a)
+        if not (len(b) == len(u) == len(w) == n) or n < 1:
+            raise ValueError("TdaOperator: a, b, u, w must list the same sites")
+        self.eng = eng
+        self.handle = None
+        self._keep = (list(a), list(b), list(u), list(w))
+        rows = []
+        for i in range(n):
+            if a[i].ndim != 3 or w[i].ndim != 4 or a[i].shape != b[i].shape:
+                raise ValueError(f"TdaOperator: site {i}: A {a[i].shape}, B {b[i].shape}, W {w[i].shape}")
+            if u[i] is not None and (u[i].ndim != 3 or u[i].shape[:2] != a[i].shape[:2]):
+                raise ValueError(f"TdaOperator: site {i}: U {u[i].shape} on a site {a[i].shape}")
+            rows += [a[i].shape[0], a[i].shape[1], a[i].shape[2], w[i].shape[0], w[i].shape[3],
+                     0 if u[i] is None else u[i].shape[2]]
+            if w[i].shape[1:3] != (a[i].shape[1],) * 2:
+                raise ValueError(f"TdaOperator: site {i}: W {w[i].shape} on a site {a[i].shape}")
+        self.xshape = [None if u[i] is None else (u[i].shape[2], b[i].shape[2]) for i in range(n)]
+        uptr = (C.c_void_p * n)(*[None if t is None else t.ptr for t in u])
+        ucode = (C.c_int * n)(*[0 if t is None else t.code for t in u])
+        h, xs, dt = C.c_void_p(), C.c_int64(), C.c_int()
+        eng._check(eng.lib.mpse_tda_create(eng.ctx, n, *_site_args(a), *_site_args(b), uptr, ucode, *_site_args(w),
+                                           (C.c_int64 * len(rows))(*rows), C.byref(h), C.byref(xs), C.byref(dt)))
+        self.handle = h.value
+        self.xsize = int(xs.value)
+        self.dtype = np.dtype(np.complex128 if dt.value == C128 else np.float64)
+
+    def close(self):
+        if self.handle and self.eng.ctx is not None:
+            self.eng.lib.mpse_tda_destroy(self.eng.ctx, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, x, y=None):
+        """y = P^H H P x for a device vector of ``xsize`` elements of ``dtype``; enqueued, no host synchronisation"""
+        if x.dtype != self.dtype or x.size != self.xsize:
+            raise ValueError(f"TdaOperator.apply: x {x.shape} {x.dtype}, the operator takes {self.xsize} of {self.dtype}")
+        if y is None:
+            y = self.eng.empty((self.xsize,), self.dtype)
+        self.eng._check(self.eng.lib.mpse_tda_apply(self.eng.ctx, self.handle, x.ptr, y.ptr))
+        return y
+
+    def hdiag(self):
+        """Re diag(P^H H P) as a float64 device vector (the Davidson preconditioner)"""
+        out = self.eng.empty((self.xsize,), np.float64)
+        self.eng._check(self.eng.lib.mpse_tda_hdiag(self.eng.ctx, self.handle, out.ptr))
+        return out
+
+    def davidson(self, guesses, hdiag, nroots, tol=1e-12, max_cycle=100, max_space=None, lindep=1e-14, shift=1e-4):
+        """The ``nroots`` lowest eigenpairs by the engine's Davidson (``mpse_tda_davidson``); ``guesses``: host arrays of
+        ``xsize`` elements.  Returns (e (nroots,), x (nroots, xsize) host array, ncycle, nmatvec)."""
+        eng = self.eng
+        g = eng.asdevice(np.ascontiguousarray(np.stack([np.asarray(v).reshape(-1) for v in guesses]), dtype=self.dtype))
+        if g.shape[1] != self.xsize:
+            raise ValueError(f"TdaOperator.davidson: guesses of {g.shape[1]} elements, the operator takes {self.xsize}")
+        out = eng.empty((nroots, self.xsize), self.dtype)
+        e = (C.c_double * nroots)()
+        ncyc, nmv = C.c_int(), C.c_int()
+        eng._check(eng.lib.mpse_tda_davidson(eng.ctx, g.code, self.handle, hdiag.ptr, nroots, g.shape[0], g.ptr, tol,
+                                             max_cycle, 0 if max_space is None else max_space, lindep, shift, e,
+                                             out.ptr, C.byref(ncyc), C.byref(nmv)))
+        return np.array([float(v) for v in e]), out.to_host(), ncyc.value, nmv.value
 
 
 class Engine:
@@ -1030,6 +1114,19 @@ class Engine:
             self.ctx, n, *_site_args(sites), dims, nop, first, last, *_site_args(wsites), wdims,
             out.ctypes.data_as(_dblp)))
         return out
+
+    # -- tangent-space (TDA) operator
+    TDA_STATS = ("handles", "applies", "env_updates", "heff_applies", "qdiag_sites", "davidson")
+
+    def tda_stats(self):
+        """{name: count} of the ``mpse_tda_*`` calls of this context, cumulative (``mpse_tda_stats``): handles created,
+        applications, the environment updates and effective-Hamiltonian applications they issued, sites through
+        k_tda_qdiag, Davidson calls."""
+        return self._stats_dict(self.lib.mpse_tda_stats, self.TDA_STATS)
+
+    def tda_operator(self, a, b, u, w):
+        """``TdaOperator`` on lists of device tensors (``mpse_tda_create``)"""
+        return TdaOperator(self, a, b, u, w)
 
     # -- two-site reduced density matrices
     RDM2_STATS =("chain_kernel", "enqueued", "sites", "pairs")
