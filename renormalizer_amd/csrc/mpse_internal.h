@@ -68,11 +68,12 @@ struct mpse_ctx {
     PIN_SCALAR2 = 0,       // [0, 2): read_scalar2 (dot products, norms)
     PIN_FLAG = 8,          // [8, 9): Lanczos closeness flag; block SVD: done words of nblk blocks, (nblk + 1) / 2 doubles
     PIN_LZ_SCAL = 16,      // [16, 540): recurrence scalars of the synchronous Lanczos solve, up to 4 + 4 * 130 doubles
-    PIN_LZ_CTL = 24,       // [24, 28): LzCtl of the asynchronous Lanczos solve
     PIN_ENV_UNIT = 32,        // [32, 32 + w): deviation from the unit per MPO channel of an environment, w <= 2048
     PIN_PCG_CTL = 40,      // [40, 48): PcgCtl of mpse_pcg / mpse_pcg_sum
     PIN_DAVIDSON = 64,     // [64, 64 + count): subspace products and norms of the Davidson solver, count <= 1024
-    PIN_BATCH_CTL = 3700,  // [3700, 3956): control blocks of a batched solve, 64 x LzCtl or 32 x PcgCtl (never both at once)
+    // [3700, 3956): control blocks of a launch set, up to 64 x LzCtl (the asynchronous Lanczos solve, single or batched)
+    // or 32 x PcgCtl (the batched PCG), never both at once
+    PIN_BATCH_CTL = 3700,
     PIN_QR_STATUS = 3990,  // [3990, 3991): breakdown word of the Cholesky-QR
     PIN_SLOTS_END = 4000,  // slots of publish_and_wait end here
     PIN_DOUBLES = 4096,
@@ -348,8 +349,9 @@ struct SolveScope {
   mpse_ctx* ctx;
   mpse_ctx::PlanSlot* slot = nullptr;   // borrowed (borrow_slot), null: keyless
   bool slot_f0_taken = false;           // the slot serves the FIRST fused-matvec plan of the solve (mpse_heff0.hip)
-  // device word that turns every contraction launch into a no-op once it is non-zero: the asynchronous Lanczos solve,
-  // whose iterations are enqueued ahead of the convergence decision
+  // device word that turns every contraction launch into a no-op once it is non-zero: the stop word of the asynchronous
+  // Lanczos solve (LzCtl::stop: decision fallen, or the host has to take over), whose iterations are enqueued ahead of
+  // the convergence decision
   const int* skip = nullptr;
   // Lanczos: the environments [env_lo, env_hi), constant over the solve - the tile-occupancy masks of operands inside
   // them are scanned once and kept (occ_cache), and so are the launch orders built on such masks (perm_cache)
@@ -481,7 +483,9 @@ int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, 
                    MatvecReq* mv, bool* taken);
 
 // Batched small-centre Krylov solves (mpse_expm_lanczos_batch, mpse_lanczos.hip): what differs between the members of one
-// launch set beyond their slab (vectors, scalars, partials and control block at member-0 addresses + m * mstride bytes)
+// launch set beyond their region of the slab (mpse_lanczos_plan.h: vectors, scalars, partials, flag word and control
+// block at member-0 addresses + m * mstride bytes).  The kernels of the asynchronous solve take the table as a nullable
+// pointer: a single solve is a launch set of one member that passes its C and out directly and uploads no table.
 struct BatchMember {
   const void* L;    // environments and MPO site of the member's effective Hamiltonian
   const void* R;

@@ -7,9 +7,20 @@
 #include <utility>
 
 #include "mpse_internal.h"
+#include "mpse_lanczos_plan.h"
 #include "mpse_vec_kernels.h"
 
 namespace {
+
+// member_ptr (mpse_internal.h) for the kernels of this file, as pointer arithmetic.  Through member_ptr's round trip
+// over an integer the compiler no longer knows that a kernel argument points to global memory and issues flat loads and
+// stores: with it the merged kernels were slower than the single forms they replace (k_lincomb_dev +13 %,
+// k_lanczos_update_u +5 % at the headline's sizes, profiles/lanczos_one_driver.md).  Null stays null.
+template <class T>
+__device__ __forceinline__ T* lz_member(T* p, unsigned m, long long mstride) {
+  using Byte = std::conditional_t<std::is_const<T>::value, const char, char>;
+  return p ? reinterpret_cast<T*>(reinterpret_cast<Byte*>(p) + (long long)m * mstride) : p;
+}
 
 // dst = src / sqrt(b2) where b2 = sum of the nb partials of the preceding norm kernel; block 0 also stores b2
 // (and the unused imaginary slot) to b2_out for the host and for the next recurrence step.
@@ -120,7 +131,7 @@ __device__ __forceinline__ void lanczos_update_u(double* __restrict__ u_next, co
                                                  const double* __restrict__ a_partial, int a_nb, double* __restrict__ a_out,
                                                  const double* __restrict__ cur_partial, int cur_nb,
                                                  double* __restrict__ cur_out, const double* __restrict__ prev2,
-                                                 double* __restrict__ partial, const int* __restrict__ done,
+                                                 double* __restrict__ partial, const int* __restrict__ stop,
                                                  const unsigned long long* __restrict__ pmask, int prow, int ptiles,
                                                  const unsigned char* __restrict__ cmask, int crow, int ckw) {
   // pmask (complex vectors, VEC): the parts hold only some 16 x 16 tiles of the result viewed as rows of prow elements
@@ -130,7 +141,7 @@ __device__ __forceinline__ void lanczos_update_u(double* __restrict__ u_next, co
   // crow elements, crow a multiple of 64, byte [(column / 64) * ckw + row / 16]): every vector of the solve is exactly
   // zero in the tiles it leaves out - nothing is read there and zeros are written (a wave works on 64 consecutive
   // elements of one row: the test is uniform over the wave)
-  if (done && *done) return;
+  if (*stop) return;
   // The first pair of elements of this thread is requested BEFORE the scalars of the step are summed: its loads (mask
   // word, parts, U_j, U_{j-1}) do not depend on them, and the two block reductions of sum_partials otherwise stand in
   // front of every trip to memory of a kernel that is nothing but such trips.  Same arithmetic, same order.
@@ -241,43 +252,27 @@ __device__ __forceinline__ void lanczos_update_u(double* __restrict__ u_next, co
     partial[2 * blockIdx.x + 1] = 0.0;
   }
 }
+// Member blockIdx.y of a launch set (a single solve: one member): every per-member pointer at its member-0 address +
+// blockIdx.y * mstride bytes (one slab per launch set).  The part and centre masks are the same for all members.
 template <bool VEC>
-__global__ __launch_bounds__(RED_THREADS) void k_lanczos_update_u(double* __restrict__ u_next,
-                                                                  const double* __restrict__ y, int nparts,
-                                                                  long long part_stride,
-                                                                  const double* __restrict__ u1,
-                                                                  const double* __restrict__ u0, long long n_doubles,
-                                                                  const double* __restrict__ a_partial, int a_nb,
-                                                                  double* __restrict__ a_out,
-                                                                  const double* __restrict__ cur_partial, int cur_nb,
-                                                                  double* __restrict__ cur_out,
-                                                                  const double* __restrict__ prev2,
-                                                                  double* __restrict__ partial,
-                                                                  const int* __restrict__ done,
+__global__ __launch_bounds__(RED_THREADS) void k_lanczos_update_u(double* u_next, const double* y, int nparts,
+                                                                  long long part_stride, const double* u1,
+                                                                  const double* u0, long long n_doubles,
+                                                                  const double* a_partial, int a_nb, double* a_out,
+                                                                  const double* cur_partial, int cur_nb,
+                                                                  double* cur_out, const double* prev2,
+                                                                  double* partial, const int* stop,
                                                                   const unsigned long long* __restrict__ pmask,
                                                                   int prow, int ptiles,
                                                                   const unsigned char* __restrict__ cmask, int crow,
-                                                                  int ckw) {
-  lanczos_update_u<VEC>(u_next, y, nparts, part_stride, u1, u0, n_doubles, a_partial, a_nb, a_out, cur_partial, cur_nb,
-                        cur_out, prev2, partial, done, pmask, prow, ptiles, cmask, crow, ckw);
-}
-// Batched form (mpse_expm_lanczos_batch): member blockIdx.y, every pointer at its member-0 address + blockIdx.y * mstride
-// bytes (one slab per launch set); no part or centre masks
-template <bool VEC>
-__global__ __launch_bounds__(RED_THREADS) void k_lanczos_update_u_b(double* u_next, const double* y, int nparts,
-                                                                    long long part_stride, const double* u1,
-                                                                    const double* u0, long long n_doubles,
-                                                                    const double* a_partial, int a_nb, double* a_out,
-                                                                    const double* cur_partial, int cur_nb,
-                                                                    double* cur_out, const double* prev2,
-                                                                    double* partial, const int* done, long long mstride) {
+                                                                  int ckw, long long mstride) {
   const unsigned m = blockIdx.y;
-  lanczos_update_u<VEC>(member_ptr(u_next, m, mstride), member_ptr(y, m, mstride), nparts, part_stride,
-                        member_ptr(u1, m, mstride), member_ptr(u0, m, mstride), n_doubles,
-                        member_ptr(a_partial, m, mstride), a_nb, member_ptr(a_out, m, mstride),
-                        member_ptr(cur_partial, m, mstride), cur_nb, member_ptr(cur_out, m, mstride),
-                        member_ptr(prev2, m, mstride), member_ptr(partial, m, mstride), member_ptr(done, m, mstride),
-                        nullptr, 0, 0, nullptr, 0, 0);
+  lanczos_update_u<VEC>(lz_member(u_next, m, mstride), lz_member(y, m, mstride), nparts, part_stride,
+                        lz_member(u1, m, mstride), lz_member(u0, m, mstride), n_doubles,
+                        lz_member(a_partial, m, mstride), a_nb, lz_member(a_out, m, mstride),
+                        lz_member(cur_partial, m, mstride), cur_nb, lz_member(cur_out, m, mstride),
+                        lz_member(prev2, m, mstride), lz_member(partial, m, mstride), lz_member(stop, m, mstride),
+                        pmask, prow, ptiles, cmask, crow, ckw);
 }
 
 struct Coefs {
@@ -378,21 +373,26 @@ void expm_coefs(int m, const std::vector<double>& alpha, const std::vector<doubl
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Asynchronous solve: the host enqueues Lanczos iterations ahead of the convergence decision.  The small-matrix
-// exponential, the closeness test of successive estimates and the decision itself run on the device; once the
-// decision has fallen every later launch of the solve (contractions included, SolveScope::skip) returns at once.
-// The host waits once per solve (when its guess of the Krylov dimension, taken from the last solve of the same
-// problem class, was right), instead of twice per convergence check.
+// Asynchronous solve: the host enqueues Lanczos iterations ahead of the convergence decision, for a launch set of B
+// members of one shape (a single solve: B = 1; mpse_expm_lanczos_batch: up to LZB_MAX, every launch of the chain covering
+// all of them, blockIdx.y = member).  The small-matrix exponential, the closeness test of successive estimates and the
+// decision itself run on the device; once a member's decision has fallen every later launch of that member
+// (contractions included, SolveScope::skip) returns at once.  The host waits once per solve (when its guess of the
+// Krylov dimension, taken from the last solve of the same problem class, was right), instead of twice per convergence
+// check, and then for the control blocks of all members at once.
 struct LzCtl {
-  int done;       // decision has fallen: later launches do nothing
+  int done;       // decision has fallen
   int nvec;       // Krylov dimension of the answer
   int which;      // 0: answer in `out`, 1: in the spare buffer
   int bad;        // zero / non-finite start vector
   int need_host;  // |dt| * spectral bound too large for the on-device exponential: the host takes this check over
   int forced_m;   // breakdown: the estimate of this check is final, with this many vectors
-  int pad[2];
+  int stop;       // done || need_host || bad, raised by k_lz_decide: every later kernel of the member returns at once
+  int pad;
 };
-constexpr int LZ_MAXM = 64;   // one wavefront holds the Krylov coefficients
+using mpse_lz::LZ_MAXM;
+static_assert(sizeof(LzCtl) == mpse_lz::LZ_CTL_DOUBLES * sizeof(double), "control block as the layout counts it");
+static_assert(mpse_lz::LZ_NORM_CAP == RED_MAX_BLOCKS, "norm partials of the vector kernels fit their areas");
 // |C|^2 of a start vector the unnormalised recurrence takes as it is: a normal double below 1e300 (1 / |C|^2 and the
 // squares of the matvec stay finite and keep all their digits); other nonzero vectors are scaled by a power of two first
 constexpr double LZ_N2_MIN = 2.2250738585072014e-308, LZ_N2_MAX = 1e300;
@@ -407,7 +407,6 @@ constexpr double LZ_N2_MIN = 2.2250738585072014e-308, LZ_N2_MAX = 1e300;
 // is no estimate before it, so it is evaluated together with the second one).
 __device__ __forceinline__ void lz_coefs(double* __restrict__ scal, int j, double dt_re, double dt_im, double tiny,
                                          double* __restrict__ coef, LzCtl* ctl, const double* __restrict__ part, int nb) {
-  if (ctl->done) return;
   const int lane = threadIdx.x;
   if (gridDim.x == 2 && blockIdx.x == 0) {   // the earlier check: its beta^2 is in scal already (summed by the update
     j -= 2;                                  // kernel of iteration j - 1)
@@ -504,64 +503,41 @@ __device__ __forceinline__ void lz_coefs(double* __restrict__ scal, int j, doubl
     coef[LZ_MAXM + lane] = lane < m ? yi * sc : 0.0;
   }
 }
-__global__ __launch_bounds__(64) void k_lz_coefs(double* __restrict__ scal, int j, double dt_re, double dt_im,
-                                                 double tiny, double* __restrict__ coef, LzCtl* ctl,
-                                                 const double* __restrict__ part, int nb) {
-  lz_coefs(scal, j, dt_re, dt_im, tiny, coef, ctl, part, nb);
-}
-// Batched form: member blockIdx.y (blockIdx.x / gridDim.x keep their meaning); a member whose kernels stopped
-// (LzCtl::pad[0], k_lz_decide_b) does nothing
-__global__ __launch_bounds__(64) void k_lz_coefs_b(double* scal, int j, double dt_re, double dt_im, double tiny,
-                                                   double* coef, LzCtl* ctl, const double* part, int nb,
-                                                   long long mstride) {
+// Member blockIdx.y (blockIdx.x / gridDim.x keep their meaning)
+__global__ __launch_bounds__(64) void k_lz_coefs(double* scal, int j, double dt_re, double dt_im, double tiny,
+                                                 double* coef, LzCtl* ctl, const double* part, int nb,
+                                                 long long mstride) {
   const unsigned m = blockIdx.y;
-  LzCtl* c = member_ptr(ctl, m, mstride);
-  if (c->pad[0]) return;
-  lz_coefs(member_ptr(scal, m, mstride), j, dt_re, dt_im, tiny, member_ptr(coef, m, mstride), c,
-           member_ptr(part, m, mstride), nb);
+  LzCtl* c = lz_member(ctl, m, mstride);
+  if (c->stop) return;
+  lz_coefs(lz_member(scal, m, mstride), j, dt_re, dt_im, tiny, lz_member(coef, m, mstride), c,
+           lz_member(part, m, mstride), nb);
 }
 
-// the decision of the check at iteration j (its estimate went to buffer `which`).  ``pub`` != null: the host waits at this
-// check - the control block goes to the mapped pinned buffer and the sequence number after it (a k_publish launch did
-// that before: one launch and its latency less per wait).
-__device__ __forceinline__ void lz_decide(LzCtl* ctl, const unsigned int* flag, unsigned int gen, int has_prev, int j,
-                                          int which, double* pub, volatile double* seq_slot, double seq) {
-  if (!(ctl->done || ctl->need_host)) {
-    if (ctl->forced_m > 0) {
-      ctl->done = 1;
-      ctl->nvec = ctl->forced_m;
-      ctl->which = which;
-    } else if (has_prev && *flag != gen) {
-      ctl->done = 1;
-      ctl->nvec = j + 1;
-      ctl->which = which;
-    }
-  }
-  if (pub) {
-    const double* src = reinterpret_cast<const double*>(ctl);
-    for (int i = 0; i < int(sizeof(LzCtl) / sizeof(double)); ++i) pub[i] = src[i];
-    __threadfence_system();
-    *seq_slot = seq;
-    __threadfence_system();
-  }
-}
-__global__ void k_lz_decide(LzCtl* ctl, const unsigned int* __restrict__ flag, unsigned int gen, int has_prev, int j,
-                            int which, double* pub, volatile double* seq_slot, double seq) {
-  lz_decide(ctl, flag, gen, has_prev, j, which, pub, seq_slot, seq);
-}
-// Batched form: one lane per member (B <= 64).  A member whose decision has fallen, or that needs the host
-// (need_host, bad), raises its skip word LzCtl::pad[0]: every later kernel of that member returns at once.  ``pub``
-// != null: all B control blocks go to pub + 4 m, then one sequence number.
-__global__ __launch_bounds__(64) void k_lz_decide_b(LzCtl* ctl, const unsigned int* flag, unsigned int gen, int has_prev,
-                                                    int j, int which, int B, long long mstride, double* pub,
-                                                    volatile double* seq_slot, double seq) {
+// The decisions of the check at iteration j (the estimates went to buffer `which`), one lane per member (B <= 64).  A
+// member whose decision has fallen, or that needs the host (need_host, bad), raises its stop word.  ``pub`` != null: the
+// host waits at this check - all B control blocks go to the mapped pinned buffer at pub + 4 m, then one sequence number
+// (a k_publish launch did that before: one launch and its latency less per wait).
+__global__ __launch_bounds__(64) void k_lz_decide(LzCtl* ctl, const unsigned int* flag, unsigned int gen, int has_prev,
+                                                  int j, int which, int B, long long mstride, double* pub,
+                                                  volatile double* seq_slot, double seq) {
   const int m = threadIdx.x;
   constexpr int W = int(sizeof(LzCtl) / sizeof(double));
   if (m < B) {
-    LzCtl* c = member_ptr(ctl, m, mstride);
-    if (!c->pad[0]) {
-      lz_decide(c, member_ptr(flag, m, mstride), gen, has_prev, j, which, nullptr, nullptr, 0.0);
-      if (c->done || c->need_host || c->bad) c->pad[0] = 1;
+    LzCtl* c = lz_member(ctl, m, mstride);
+    if (!c->stop) {
+      if (!(c->done || c->need_host)) {     // (raised by k_lz_coefs of this check)
+        if (c->forced_m > 0) {
+          c->done = 1;
+          c->nvec = c->forced_m;
+          c->which = which;
+        } else if (has_prev && *lz_member(flag, m, mstride) != gen) {
+          c->done = 1;
+          c->nvec = j + 1;
+          c->which = which;
+        }
+      }
+      if (c->done || c->need_host || c->bad) c->stop = 1;
     }
     if (pub) {
       const double* src = reinterpret_cast<const double*>(c);
@@ -591,6 +567,7 @@ __device__ __forceinline__ void lincomb_dev(double* __restrict__ res, const doub
                                             const LzCtl* __restrict__ ctl, int m_early,
                                             const unsigned char* __restrict__ cmask, int crow, int ckw) {
   // cmask: as in k_lanczos_update_u - the basis vectors (and the earlier estimate) are exactly zero outside it
+  // (a member that stopped has one of the two set; k_lz_coefs of this check may have raised them since)
   if (ctl->done || ctl->need_host) return;
   __shared__ double cr[LZ_MAXM], ci[LZ_MAXM], er[LZ_MAXM], ei[LZ_MAXM];
   if (threadIdx.x < LZ_MAXM) {
@@ -651,27 +628,20 @@ __device__ __forceinline__ void lincomb_dev(double* __restrict__ res, const doub
   }
   if ((prev || m_early > 0) && bad) atomicMax(flag, gen);
 }
+// Member blockIdx.y.  The estimate goes to the member's own result (res_sel 0: mem[m].out, or `out` itself when there is
+// no member table - a single solve uploads none) or to its spare buffer (1: spare + m * mstride); ``prev_sel`` names the
+// earlier estimate the same way (-1: none)
 template <bool CPLX>
-__global__ void k_lincomb_dev(double* __restrict__ res, const double* __restrict__ V, long long n, int m,
-                              const double* __restrict__ coef, const double* __restrict__ prev, double rtol, double atol,
-                              unsigned int* __restrict__ flag, unsigned int gen, const LzCtl* __restrict__ ctl,
-                              int m_early, const unsigned char* __restrict__ cmask, int crow, int ckw) {
-  lincomb_dev<CPLX>(res, V, n, m, coef, prev, rtol, atol, flag, gen, ctl, m_early, cmask, crow, ckw);
-}
-// Batched form: member blockIdx.y.  The estimate goes to the member's own result (res_sel 0: mem[m].out) or to its spare
-// buffer (1: spare + m * mstride); ``prev_sel`` names the earlier estimate the same way (-1: none)
-template <bool CPLX>
-__global__ void k_lincomb_dev_b(const BatchMember* __restrict__ mem, double* spare, int res_sel, int prev_sel,
-                                const double* V, long long n, int m, const double* coef, double rtol, double atol,
-                                unsigned int* flag, unsigned int gen, const LzCtl* ctl, int m_early, long long mstride) {
+__global__ void k_lincomb_dev(const BatchMember* __restrict__ mem, double* out, double* spare, int res_sel, int prev_sel,
+                              const double* V, long long n, int m, const double* coef, double rtol, double atol,
+                              unsigned int* flag, unsigned int gen, const LzCtl* ctl, int m_early,
+                              const unsigned char* __restrict__ cmask, int crow, int ckw, long long mstride) {
   const unsigned b = blockIdx.y;
-  const LzCtl* c = member_ptr(ctl, b, mstride);
-  if (c->pad[0]) return;
-  double* out = static_cast<double*>(mem[b].out);
-  double* sp = member_ptr(spare, b, mstride);
-  lincomb_dev<CPLX>(res_sel == 0 ? out : sp, member_ptr(V, b, mstride), n, m, member_ptr(coef, b, mstride),
-                    prev_sel < 0 ? nullptr : (prev_sel == 0 ? out : sp), rtol, atol, member_ptr(flag, b, mstride), gen,
-                    c, m_early, nullptr, 0, 0);
+  double* o = mem ? static_cast<double*>(mem[b].out) : out;
+  double* sp = lz_member(spare, b, mstride);
+  lincomb_dev<CPLX>(res_sel == 0 ? o : sp, lz_member(V, b, mstride), n, m, lz_member(coef, b, mstride),
+                    prev_sel < 0 ? nullptr : (prev_sel == 0 ? o : sp), rtol, atol, lz_member(flag, b, mstride), gen,
+                    lz_member(ctl, b, mstride), m_early, cmask, crow, ckw);
 }
 
 // Start of an asynchronous solve in one launch (three before: zero fill of the control block, copy of the start vector,
@@ -710,18 +680,16 @@ __device__ __forceinline__ void lz_start(double* __restrict__ u0, const double* 
     partial[2 * blockIdx.x + 1] = im;
   }
 }
+// Member blockIdx.y starts from mem[m].C (without a member table: from `c`); its flag word is cleared with its control
+// block (the region is fresh memory; lz_flag_stamp clears again only when the stamp wraps around)
 template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_lz_start(double* __restrict__ u0, const double* __restrict__ c, long long n,
-                                                          double* __restrict__ partial, LzCtl* ctl) {
-  lz_start<CPLX>(u0, c, n, partial, ctl);
-}
-// Batched form: member blockIdx.y starts from mem[m].C
-template <bool CPLX>
-__global__ __launch_bounds__(RED_THREADS) void k_lz_start_b(const BatchMember* __restrict__ mem, double* u0, long long n,
-                                                            double* partial, LzCtl* ctl, long long mstride) {
+__global__ __launch_bounds__(RED_THREADS) void k_lz_start(const BatchMember* __restrict__ mem, const double* c, double* u0,
+                                                          long long n, double* partial, LzCtl* ctl, unsigned int* flag,
+                                                          long long mstride) {
   const unsigned m = blockIdx.y;
-  lz_start<CPLX>(member_ptr(u0, m, mstride), static_cast<const double*>(mem[m].C), n, member_ptr(partial, m, mstride),
-                 member_ptr(ctl, m, mstride));
+  if (blockIdx.x == 0 && threadIdx.x == 0) *lz_member(flag, m, mstride) = 0;
+  lz_start<CPLX>(lz_member(u0, m, mstride), mem ? static_cast<const double*>(mem[m].C) : c, n,
+                 lz_member(partial, m, mstride), lz_member(ctl, m, mstride));
 }
 
 inline bool lanczos_async_enabled() {
@@ -733,38 +701,20 @@ inline bool lanczos_async_enabled() {
 }
 
 constexpr int LZ_CW = int(sizeof(LzCtl) / sizeof(double));
+constexpr int LZB_MAX = 64;            // members per launch set (one lane each in k_lz_decide)
+static_assert(mpse_ctx::PIN_BATCH_CTL + LZB_MAX * LZ_CW < mpse_ctx::PIN_QR_STATUS, "batch slot clear of the QR status word");
 
-// The schedule that the asynchronous and the batched solve share (a batched member returns the bits of its single solve):
-// how far the host runs ahead of the decision, how the basis grows, which iterations carry a check.
-struct LzSchedule {
-  unsigned long long key;   // problem class of the run-ahead hint (mpse_ctx::lz_hint)
-  int limit;                // iterations the decision on the device covers: one wavefront of coefficients
-  int wait_from;            // first wait at the check that can confirm the hinted dimension (or the first that can decide at all)
-  int cap;                  // capacity of the basis, vectors
-  LzSchedule(mpse_ctx* ctx, int nsite, int64_t n, bool cplx, int max_dim)
-      : key(((unsigned long long)nsite << 60) ^ ((unsigned long long)n << 1) ^ (cplx ? 1ull : 0ull)),
-        limit(max_dim < LZ_MAXM ? max_dim : LZ_MAXM) {
-    const auto it = ctx->lz_hint.find(key);
-    const int hint = it != ctx->lz_hint.end() ? it->second : 0;
-    wait_from = hint - 1 > 6 ? hint - 1 : 6;
-    cap = hint + 4 > 16 ? hint + 4 : 16;
-    if (cap > limit + 1) cap = limit + 1;
-  }
-  int grown() const { return cap * 2 < limit + 1 ? cap * 2 : limit + 1; }
-  // Iteration j: does it carry a check (krylov.py:76-81), is it the last one.  The first check of a solve (j = 4) cannot
-  // stop it - there is no earlier estimate to compare with - so it is evaluated together with the second one (j = 6,
-  // `merged`): one pass over the basis forms both estimates, and a solve has three small launches and ~25 us of
-  // dependent latency less.
-  struct Step {
-    bool check, last, merged;
-  };
-  Step at(int j, bool have_prev) const {
-    Step st{j > 3 && j % 2 == 0, j + 1 >= limit, false};
-    if (st.check && !have_prev && j == 4 && j + 3 < limit) st.check = false;   // (its turn comes at j = 6)
-    if (st.check && !have_prev && j == 6) st.merged = true;
-    return st;
-  }
-};
+// The schedule and the region layout are integer rules of their own (mpse_lanczos_plan.h, tested on the host).  The
+// run-ahead hint they start from is kept per problem class in the context (mpse_ctx::lz_hint)
+using mpse_lz::LZ_DOT_CAP;
+using LzSchedule = mpse_lz::Schedule;
+inline unsigned long long lz_hint_key(int nsite, int64_t n, bool cplx) {
+  return ((unsigned long long)nsite << 60) ^ ((unsigned long long)n << 1) ^ (cplx ? 1ull : 0ull);
+}
+inline int lz_hint(mpse_ctx* ctx, unsigned long long key) {
+  const auto it = ctx->lz_hint.find(key);
+  return it != ctx->lz_hint.end() ? it->second : 0;
+}
 
 // Generation stamp of a check that compares two estimates (0 for one that does not): the flag word is raised to the
 // stamp, so it never has to be cleared between checks - only when the stamp wraps around (B words, `pitch` bytes apart)
@@ -794,43 +744,211 @@ void keep_env_masks(SolveScope& sc, const mpse_heff* h) {
 constexpr int LZ_FALLBACK = -77;   // internal: the asynchronous solve hands the problem to the synchronous one
 constexpr int LZ_BADSTART = -78;   // internal: |C|^2 outside [LZ_N2_MIN, LZ_N2_MAX) (expm_lanczos_solve decides)
 
+// What lz_async_run works on: a launch set of B members (1 <= B <= LZB_MAX) of n elements each
+struct LzProblem {
+  int dtype;
+  int64_t n;
+  int B;
+  // start vectors and results: the device table of the members, or - null, B == 1 - the two pointers themselves (a
+  // single solve uploads no table: the upload would stand on the dependent chain of every solve)
+  const BatchMember* mem;
+  const void* C;
+  void* out;
+  std::complex<double> dt;
+  double rtol, atol;
+  bool vec16;                    // 16-byte accesses: every Krylov vector starts on a 16-byte boundary and has even length
+  // The structural mask of the centre (null: none): every vector of the solve is zero in the tiles it leaves out
+  // (k_lanczos_update_u); the same for all members
+  const unsigned char* vmask;
+  int vm_row, vm_kw;
+  int parts, dot_cap;            // result parts and dot partials the matvec may write (mpse_lz::layout)
+};
+// The set's areas: one slab, member m's region `lay.stride` doubles behind that of member m - 1.  The driver allocates
+// it and replaces it when the basis grows; the caller finds C (bitwise, basis vector 0) and the spare estimate there.
+struct LzSet {
+  TmpBuf slab;
+  mpse_lz::Layout lay{};
+  explicit LzSet(mpse_ctx* ctx) : slab(ctx) {}
+  double* at(int64_t off, int m = 0) { return slab.as<double>() + m * lay.stride + off; }
+  long long mstride() const { return lay.stride * (long long)sizeof(double); }
+};
+// The one point where the callers of lz_async_run differ - y = H U_j for every member, iteration j.  The matvec gets
+// member-0 addresses: U_j, the result parts, the dot partials, the members' stop word (its launches do nothing for a
+// member whose word is set), the basis' range.  It says how the result came: as the sum of `nparts` tensors n elements
+// apart (with `pmask`: tile-masked parts, MatvecReq::Parts), with a_nb partials of <H U_j, U_j>.
+struct LzIter {
+  int j;
+  const double* u;
+  double* parts;
+  double* dot;
+  const int* stop;
+  long long mstride;
+  const char *basis_lo, *basis_hi;
+};
+struct LzMatvecOut {
+  int nparts = 1, a_nb = 0;
+  const unsigned long long* pmask = nullptr;
+  int prow = 0, ptiles = 0;
+};
+struct LzOutcome {
+  enum Kind {
+    RUNNING,   // (inside the driver only)
+    DONE,      // the estimate with `nvec` vectors is the answer: in the member's `out` (which = 0) or in its spare area (1)
+    BAD,       // |C|^2 outside what the recurrence takes; nothing went to `out`
+    TO_SYNC    // the synchronous solve has to take over: need_host, or no decision within the 64-vector limit
+  } kind = RUNNING;
+  int which = 0, nvec = 0;
+  bool breakdown = false;        // DONE by the breakdown rule, not by convergence
+};
+// What happened on the way, in the terms of mpse_ctx::lz_paths (LP_WAITS, LP_MERGED, LP_GROW, LP_PARTS, LP_VMASK,
+// LP_UNVEC, LP_HOST_FIRST / LP_HOST_LATER, LP_LIMIT).  The driver reports, its callers count.
+struct LzTally {
+  long long paths[mpse_ctx::LP_COUNT] = {0};
+  bool estimates = false;        // a check was enqueued: estimates may have gone to `out`
+};
+
+// The asynchronous iteration for one launch set; one outcome per member at oc[0 .. B).
+template <class Matvec>
+int lz_async_run(mpse_ctx* ctx, const LzProblem& p, LzSchedule sch, LzSet& set, Matvec&& matvec, LzOutcome* oc,
+                 LzTally* tally) {
+  const int B = p.B;
+  const int64_t n = p.n;
+  const bool cplx = p.dtype == MPSE_C128;
+  const int64_t nd = n * (cplx ? 2 : 1);
+  const double tiny = 100.0 * double(n) * 2.220446049250313e-16;
+  const int nb = red_blocks(nd);
+  const double vbytes = double(B) * double(n) * double(dtype_size(p.dtype));   // (the profiler's algorithmic bytes, variant 4)
+  mpse_lz::Layout& L = set.lay;
+  L = mpse_lz::layout(n, cplx, p.parts, p.dot_cap, sch.cap);
+  MPSE_TRY(set.slab.alloc(size_t(B) * L.stride * sizeof(double)));
+  // member-0 addresses, read again after the slab has grown
+  auto vec = [&](int j) { return set.at(L.basis) + int64_t(j) * nd; };
+  auto ctl = [&] { return reinterpret_cast<LzCtl*>(set.at(L.ctl)); };
+  auto flag = [&] { return reinterpret_cast<unsigned int*>(set.at(L.flag)); };
+
+  // U_0 = C itself (the Krylov basis is kept unnormalised, k_lanczos_update_u); |C|^2 partials feed the first step
+  {
+    ProfScope ps(ctx, 4, 0.0, 3.0 * vbytes);
+    MPSE_LAUNCH_TF(ctx, cplx, k_lz_start, dim3(nb, B), dim3(RED_THREADS), p.mem, (const double*)p.C, vec(0), (long long)n,
+                   set.at(L.norm[0]), ctl(), flag(), set.mstride());
+    ps.end();
+  }
+  MPSE_HIP(ctx, hipGetLastError());
+
+  int prev_sel = -1;    // where the earlier estimate went: -1 none, 0 the result, 1 the spare area (the same for all)
+  bool waited = false;
+  std::vector<LzCtl> hc(B);
+  for (int m = 0; m < B; ++m) oc[m] = LzOutcome();
+  for (int j = 0;; ++j) {
+    if (j + 2 > sch.cap) {      // room for U_{j+1}: a new slab with a longer basis per member
+      // In front of the matvec: the result parts are dead here (the update of iteration j - 1 has read them) and stay
+      // behind; what lies in front of them and what lies behind them moves, section by section at the same offsets
+      const int ncap = sch.grown();
+      const mpse_lz::Layout G = mpse_lz::layout(n, cplx, p.parts, p.dot_cap, ncap);
+      ++tally->paths[mpse_ctx::LP_GROW];
+      TmpBuf s2(ctx);
+      MPSE_TRY(s2.alloc(size_t(B) * G.stride * sizeof(double)));
+      const int64_t span[2][2] = {{0, L.parts}, {L.spare, L.stride}};
+      for (const auto& r : span)
+        MPSE_HIP(ctx, hipMemcpy2DAsync(s2.as<double>() + r[0], size_t(G.stride) * 8, set.at(r[0]), size_t(L.stride) * 8,
+                                       size_t(r[1] - r[0]) * 8, size_t(B), hipMemcpyDeviceToDevice, ctx->stream));
+      std::swap(set.slab.p, s2.p);
+      L = G;
+      sch.cap = ncap;
+    }
+    const long long mstride = set.mstride();
+    double* scal = set.at(L.scal);
+    double* part_a = set.at(L.dot);
+    const int* stop0 = &ctl()->stop;
+    LzMatvecOut mv;
+    MPSE_TRY(matvec(LzIter{j, vec(j), set.at(L.parts), part_a, stop0, mstride, reinterpret_cast<const char*>(vec(0)),
+                           reinterpret_cast<const char*>(vec(sch.cap))},
+                    &mv));
+    // |U_j|^2 partials came from step j - 1 (or from |C|^2); this step's |w|^2 partials go to the other area
+    double* cur_part = set.at(L.norm[j & 1]);
+    double* new_part = set.at(L.norm[(j + 1) & 1]);
+    double* cur_out = j == 0 ? scal : scal + 6 + 4 * (j - 1);
+    const double* prev2 = j == 0 ? scal : (j == 1 ? scal : scal + 6 + 4 * (j - 2));
+    if (mv.nparts > 1 || mv.pmask) ++tally->paths[mpse_ctx::LP_PARTS];
+    if (!mv.pmask && p.vmask) ++tally->paths[mpse_ctx::LP_VMASK];
+    if (!p.vec16) ++tally->paths[mpse_ctx::LP_UNVEC];
+    {
+      ProfScope ps(ctx, 4, 0.0, (j > 0 ? 4.0 : 3.0) * vbytes + (mv.nparts - 1) * vbytes);
+      MPSE_LAUNCH_TF(ctx, p.vec16, k_lanczos_update_u, dim3(nb, B), dim3(RED_THREADS), vec(j + 1),
+                     (const double*)set.at(L.parts), mv.nparts, (long long)nd, (const double*)vec(j),
+                     j > 0 ? (const double*)vec(j - 1) : (const double*)nullptr, (long long)nd, (const double*)part_a,
+                     mv.a_nb, scal + 4 + 4 * j, (const double*)cur_part, nb, cur_out, prev2, new_part, stop0, mv.pmask,
+                     mv.prow, mv.ptiles, mv.pmask ? nullptr : p.vmask, p.vm_row, p.vm_kw, mstride);
+      ps.end();
+    }
+    const LzSchedule::Step step = sch.at(j, prev_sel >= 0);
+    const bool merged = step.merged, last = step.last;
+    if (step.check) {
+      if (merged) ++tally->paths[mpse_ctx::LP_MERGED];
+      hipLaunchKernelGGL(k_lz_coefs, dim3(merged ? 2 : 1, B), dim3(64), 0, ctx->stream, scal, j, p.dt.real(), p.dt.imag(),
+                         tiny, set.at(L.coef), ctl(), (const double*)new_part, nb, mstride);
+      // successive estimates alternate between `out` and the spare area (no copies between checks)
+      const int res_sel = prev_sel == 0 ? 1 : 0;
+      const bool compares = prev_sel >= 0 || merged;
+      unsigned int gen = 0;
+      MPSE_TRY(lz_flag_stamp(ctx, compares, flag(), size_t(mstride), B, &gen));
+      MPSE_LAUNCH_TF(ctx, cplx, k_lincomb_dev, dim3(ew_blocks(n), B), dim3(256), p.mem, (double*)p.out, set.at(L.spare),
+                     res_sel, prev_sel, (const double*)vec(0), (long long)n, j + 1, (const double*)set.at(L.coef), p.rtol,
+                     p.atol, flag(), gen, (const LzCtl*)ctl(), merged ? j - 1 : 0, p.vmask, p.vm_row, p.vm_kw, mstride);
+      const bool wait_here = j >= sch.wait_from || waited || last;
+      const PublishAt pa = publish_target(ctx, wait_here, mpse_ctx::PIN_BATCH_CTL);
+      hipLaunchKernelGGL(k_lz_decide, dim3(1), dim3(64), 0, ctx->stream, ctl(), (const unsigned int*)flag(), gen,
+                         compares ? 1 : 0, j, res_sel, B, mstride, pa.pub, pa.seq_slot, pa.seq);
+      prev_sel = res_sel;
+      tally->estimates = true;
+      MPSE_HIP(ctx, hipGetLastError());
+      if (wait_here) {
+        MPSE_TRY(publish_collect(ctx, pa, ctl(), size_t(mstride), B, LZ_CW, mpse_ctx::PIN_BATCH_CTL, hc.data()));
+        ++tally->paths[mpse_ctx::LP_WAITS];
+        bool all = true;
+        for (int m = 0; m < B; ++m) {
+          LzOutcome& o = oc[m];
+          if (o.kind != LzOutcome::RUNNING) continue;
+          if (hc[m].bad) {             // (done was raised with it: nothing went to `out`)
+            o.kind = LzOutcome::BAD;
+          } else if (hc[m].need_host) {
+            o.kind = LzOutcome::TO_SYNC;
+            ++tally->paths[waited ? mpse_ctx::LP_HOST_LATER : mpse_ctx::LP_HOST_FIRST];
+          } else if (hc[m].done) {
+            o.kind = LzOutcome::DONE;
+            o.which = hc[m].which, o.nvec = hc[m].nvec, o.breakdown = hc[m].forced_m > 0;
+          } else {
+            all = false;
+          }
+        }
+        waited = true;
+        if (all) return MPSE_OK;
+      }
+    }
+    if (last) {     // beyond one wavefront of coefficients (or no convergence): the synchronous solve decides
+      ++tally->paths[mpse_ctx::LP_LIMIT];
+      for (int m = 0; m < B; ++m)
+        if (oc[m].kind == LzOutcome::RUNNING) oc[m].kind = LzOutcome::TO_SYNC;
+      return MPSE_OK;
+    }
+  }
+}
+
+// The single solve: a launch set of one member with the general matvec.
 // hints: the caller's structural mask of the centre (empty: none; it describes the Krylov vectors of this solve) and its
 // key of the solve's plan slot (0: none).  Only this solve uses them: the synchronous one it may hand over to has neither.
 int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::complex<double> dt, const void* Cin, void* out,
                        double rtol, double atol, int max_dim, int* nvec, int64_t n, const SolveHints& hints) {
   const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
-  const int64_t nd = n * (cplx ? 2 : 1);
-  const double tiny = 100.0 * double(n) * 2.220446049250313e-16;
-  LzSchedule sch(ctx, h->nsite, n, cplx, max_dim);
-  int& cap = sch.cap;
-  TmpBuf V(ctx), W(ctx), RES(ctx), SCAL(ctx);
-  MPSE_TRY(V.alloc(size_t(cap) * n * es));
-  // the matvec result, with room for a second part (MatvecReq::parts: halved tiles)
-  long long wcap = (n <= 65536 ? 4 : 2) * n;   // (small centres: up to four slices, mpse_small.hip)
-  const int f0_parts = (cplx && (reinterpret_cast<uintptr_t>(Cin) & 15) == 0) ? heff0_fused_parts(h, dtype) : 0;
-  if ((long long)f0_parts * n > wcap) wcap = (long long)f0_parts * n;   // tile-masked parts of the fused 0-site matvec
-  MPSE_TRY(W.alloc(size_t(wcap) * es));
-  MPSE_TRY(RES.alloc(size_t(n) * es));
-  // scalars as in the synchronous solve: [0..1] |v|^2 ; per j: alpha at 4+4j, beta^2 at 6+4j ; then control + coefficients
-  const int SC_CTL = 4 + 4 * 130, SC_COEF = SC_CTL + 8;
-  MPSE_TRY(SCAL.alloc(size_t(SC_COEF + 4 * LZ_MAXM) * sizeof(double)));
-  double* scal = SCAL.as<double>();
-  LzCtl* ctl = reinterpret_cast<LzCtl*>(scal + SC_CTL);
-  double* coef = scal + SC_COEF;
-  const int* done = &ctl->done;
-  const int nb = red_blocks(nd);
-  // <H U_j, U_j> partials: room for 4096 producers (the fused bond / two-level-site matvec has up to
-  // (D / 16) w (D / 64) d workgroups per unit share, mpse_heff0.hip), above the areas of the norm partials
-  constexpr int DOT_CAP = 4096;
-  double* part_a = ctx->dscratch + 16 * RED_MAX_BLOCKS;
-  static_assert(16 * RED_MAX_BLOCKS + 2 * DOT_CAP < (1 << 16) - 8, "dot partials fit the device scratch");
+  const unsigned long long key = lz_hint_key(h->nsite, n, cplx);
   const bool vec16 = (cplx || n % 2 == 0) && (reinterpret_cast<uintptr_t>(Cin) & 15) == 0;
-  const double vbytes = double(n) * double(es);
-  auto vec = [&](int j) { return V.as<char>() + size_t(j) * n * es; };
+  // the matvec result, with room for a second part (MatvecReq::parts: halved tiles)
+  int parts = n <= 65536 ? 4 : 2;   // (small centres: up to four slices, mpse_small.hip)
+  const int f0_parts = (cplx && (reinterpret_cast<uintptr_t>(Cin) & 15) == 0) ? heff0_fused_parts(h, dtype) : 0;
+  if (f0_parts > parts) parts = f0_parts;   // tile-masked parts of the fused 0-site matvec
 
   SolveScope scope(ctx);
-  scope.skip = done;
   keep_env_masks(scope, h);
   scope.cmask = hints.cmask;
   scope.borrow_slot(hints.slot_key);
@@ -857,138 +975,69 @@ int expm_lanczos_async(mpse_ctx* ctx, int dtype, const mpse_heff* h, std::comple
     const char* e = getenv("MPSE_OUT_MASK");   // MPSE_OUT_MASK=0: the matvec writes every tile of its result
     return !(e && e[0] == '0');
   }();
-  // (the vector launches are bracketed for the profiler: variant 4, algorithmic bytes)
-  auto dot_partials = [&](const void* x, const void* y, double* dst) {
-    ProfScope ps(ctx, 4, 0.0, 2.0 * vbytes);
-    MPSE_LAUNCH_TF(ctx, cplx, k_dot_partial, dim3(nb), dim3(RED_THREADS), (const double*)x, (const double*)y, (long long)n,
-                   dst, done);
-    ps.end();
-  };
-  // U_0 = C itself (the Krylov basis is kept unnormalised, k_lanczos_update_u); |C|^2 partials feed the first step
-  double* part_b2[2] = {ctx->dscratch + 4 * RED_MAX_BLOCKS, ctx->dscratch + 8 * RED_MAX_BLOCKS};
-  {
-    ProfScope ps(ctx, 4, 0.0, 3.0 * vbytes);
-    MPSE_LAUNCH_TF(ctx, cplx, k_lz_start, dim3(nb), dim3(RED_THREADS), (double*)vec(0), (const double*)Cin, (long long)n,
-                   part_b2[0], ctl);
-    ps.end();
-  }
-  MPSE_HIP(ctx, hipGetLastError());
 
-  unsigned int* dflag = reinterpret_cast<unsigned int*>(ctx->dscratch + (size_t(1) << 16) - 8);
-  void* prev = nullptr;
-  // The synchronous solve restarts from Cin.  Estimates of this solve may have gone to `out` already: when `out` is
-  // Cin, C is put back from its copy U_0 first (bitwise C; U_0 is never written after k_lz_start).
-  auto handover = [&]() -> int {
-    if (prev && out == Cin) {
-      ++ctx->lz_paths[mpse_ctx::LP_ALIAS_RESTART];
-      MPSE_TRY(mpse_memcpy_d2d(ctx, out, vec(0), size_t(n) * es));
-    }
-    return LZ_FALLBACK;
-  };
-  bool waited = false;
-  LzCtl hc;
-  memset(&hc, 0, sizeof(hc));
-  for (int j = 0;; ++j) {
-    scope.krylov_lo = V.as<char>();   // (V moves when it grows)
-    scope.krylov_hi = V.as<char>() + size_t(cap) * n * es;
+  const int nb = red_blocks(n * (cplx ? 2 : 1));
+  auto matvec = [&](const LzIter& it, LzMatvecOut* r) -> int {
+    scope.skip = it.stop;
+    scope.krylov_lo = it.basis_lo;   // (the basis moves when it grows)
+    scope.krylov_hi = it.basis_hi;
     MatvecReq mv;
     // <H U_j, U_j> rides on the launch that completes H U_j; matvecs that cannot take it leave nb_out = 0 and the
     // reduction runs as a pass of its own
-    mv.dot.y = vec(j);
-    mv.dot.part = part_a;
-    mv.dot.cap = DOT_CAP;
-    // the result may come as W + W2 (the update below reads both): the last product of a large one-site matvec then
-    // runs as halved tiles, two workgroups per compute unit
-    mv.parts.ptr = W.p;
-    mv.parts.cap_elems = wcap;
+    mv.dot.y = it.u;
+    mv.dot.part = it.dot;
+    mv.dot.cap = LZ_DOT_CAP;
+    // the result may come as W + W2 (the update reads both): the last product of a large one-site matvec then runs as
+    // halved tiles, two workgroups per compute unit
+    mv.parts.ptr = it.parts;
+    mv.parts.cap_elems = (long long)parts * n;
     mv.parts.n = n;
     mv.parts.masked_ok = f0_parts > 0 && vec16;
-    // the update below reads the result only inside the structural mask (a matvec that answers with a part mask of its
-    // own is one that does not look at this request)
+    // the update reads the result only inside the structural mask (a matvec that answers with a part mask of its own is
+    // one that does not look at this request)
     if (vmask && omask_on) mv.out_mask.mask = vmask, mv.out_mask.row = vm_row, mv.out_mask.pitch = vm_kw;
-    MPSE_TRY(heff_apply(ctx, dtype, h, vec(j), W.p, &scope, &mv));
-    const unsigned long long* pmask = mv.parts.mask;
-    const int prow = mv.parts.mask_row, ptiles = mv.parts.mask_tiles;
+    MPSE_TRY(heff_apply(ctx, dtype, h, it.u, it.parts, &scope, &mv));
     const int used = mv.parts.used;
-    const int nparts = used > 0 ? used : (used == -2 ? 2 : 1);
-    const bool two = nparts > 1;
-    const bool dot_done = mv.dot.nb_out > 0;
-    const int a_nb = dot_done ? mv.dot.nb_out : nb;
-    if (!dot_done) {
-      if (two) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: a two-part matvec result without its dot partials");
-      dot_partials(W.p, vec(j), part_a);
-    }
-    if (j + 2 > cap) {      // room for U_{j+1}
-      const int ncap = sch.grown();
-      ++ctx->lz_paths[mpse_ctx::LP_GROW];
-      TmpBuf V2(ctx);
-      MPSE_TRY(V2.alloc(size_t(ncap) * n * es));
-      MPSE_TRY(mpse_memcpy_d2d(ctx, V2.p, V.p, size_t(cap) * n * es));
-      std::swap(V.p, V2.p);
-      cap = ncap;
-    }
-    // |U_j|^2 partials came from step j - 1 (or from |C|^2); this step's |w|^2 partials go to the other area
-    double* cur_part = part_b2[j & 1];
-    double* new_part = part_b2[(j + 1) & 1];
-    double* cur_out = j == 0 ? scal : scal + 6 + 4 * (j - 1);
-    const double* prev2 = j == 0 ? scal : (j == 1 ? scal : scal + 6 + 4 * (j - 2));
-    if (two || pmask) ++ctx->lz_paths[mpse_ctx::LP_PARTS];
-    if (!pmask && vmask) ++ctx->lz_paths[mpse_ctx::LP_VMASK];
-    if (!vec16) ++ctx->lz_paths[mpse_ctx::LP_UNVEC];
-    {
-      ProfScope ps(ctx, 4, 0.0, (j > 0 ? 4.0 : 3.0) * vbytes + (nparts - 1) * vbytes);
-      MPSE_LAUNCH_TF(ctx, vec16, k_lanczos_update_u, dim3(nb), dim3(RED_THREADS), (double*)vec(j + 1), W.as<const double>(),
-                     nparts, (long long)nd, (const double*)vec(j), j > 0 ? (const double*)vec(j - 1) : (const double*)nullptr,
-                     (long long)nd, (const double*)part_a, a_nb, scal + 4 + 4 * j, (const double*)cur_part, nb, cur_out,
-                     prev2, new_part, done, pmask, prow, ptiles, pmask ? nullptr : vmask, vm_row, vm_kw);
-      ps.end();
-    }
-    const LzSchedule::Step step = sch.at(j, prev != nullptr);
-    const bool merged = step.merged, last = step.last;
-    if (step.check) {
-      if (merged) ++ctx->lz_paths[mpse_ctx::LP_MERGED];
-      hipLaunchKernelGGL(k_lz_coefs, dim3(merged ? 2 : 1), dim3(64), 0, ctx->stream, scal, j, dt.real(), dt.imag(), tiny,
-                         coef, ctl, (const double*)new_part, nb);
-      void* dst = (prev == out) ? RES.p : out;
-      unsigned int gen = 0;
-      MPSE_TRY(lz_flag_stamp(ctx, prev || merged, dflag, 0, 1, &gen));
-      MPSE_LAUNCH_TF(ctx, cplx, k_lincomb_dev, dim3(ew_blocks(n)), dim3(256), (double*)dst, V.as<double>(), (long long)n,
-                     j + 1, (const double*)coef, (const double*)prev, rtol, atol, dflag, gen, (const LzCtl*)ctl,
-                     merged ? j - 1 : 0, vmask, vm_row, vm_kw);
-      const bool wait_here = j >= sch.wait_from || waited || last;
-      const PublishAt at = publish_target(ctx, wait_here, mpse_ctx::PIN_LZ_CTL);
-      hipLaunchKernelGGL(k_lz_decide, dim3(1), dim3(1), 0, ctx->stream, ctl, (const unsigned int*)dflag, gen,
-                         (prev || merged) ? 1 : 0, j, dst == out ? 0 : 1, at.pub, at.seq_slot, at.seq);
-      prev = dst;
-      MPSE_HIP(ctx, hipGetLastError());
-      if (wait_here) {
-        MPSE_TRY(publish_collect(ctx, at, ctl, 0, 1, LZ_CW, mpse_ctx::PIN_LZ_CTL, &hc));
-        ++ctx->lz_paths[mpse_ctx::LP_WAITS];
-        const bool waited_before = waited;
-        waited = true;
-        if (hc.bad) return LZ_BADSTART;    // (done was raised with it: nothing went to `out`)
-        if (hc.need_host) {
-          ++ctx->lz_paths[waited_before ? mpse_ctx::LP_HOST_LATER : mpse_ctx::LP_HOST_FIRST];
-          return handover();
-        }
-        if (hc.done) {
-          ++ctx->lz_paths[mpse_ctx::LP_ASYNC_DONE];
-          ++ctx->lz_paths[hc.forced_m > 0 ? mpse_ctx::LP_BD_ASYNC : mpse_ctx::LP_CONV];
-          // the answer sits in the spare buffer (an even number of estimates): copied now - the host knows; before, a
-          // conditional copy kernel was enqueued at every waited check
-          if (hc.which == 1) MPSE_TRY(mpse_memcpy_d2d(ctx, out, RES.p, size_t(n) * es));
-          break;
-        }
+    r->pmask = mv.parts.mask, r->prow = mv.parts.mask_row, r->ptiles = mv.parts.mask_tiles;
+    r->nparts = used > 0 ? used : (used == -2 ? 2 : 1);
+    r->a_nb = mv.dot.nb_out > 0 ? mv.dot.nb_out : nb;
+    if (mv.dot.nb_out > 0) return MPSE_OK;
+    if (r->nparts > 1) return mpse_fail(ctx, MPSE_ERR_ARG, "expm_lanczos: a two-part matvec result without its dot partials");
+    ProfScope ps(ctx, 4, 0.0, 2.0 * double(n) * double(es));
+    MPSE_LAUNCH_TF(ctx, cplx, k_dot_partial, dim3(nb), dim3(RED_THREADS), (const double*)it.parts, it.u, (long long)n,
+                   it.dot, it.stop);
+    ps.end();
+    return MPSE_OK;
+  };
+
+  const LzProblem p{dtype, n, 1, nullptr, Cin, out, dt, rtol, atol, vec16, vmask, vm_row, vm_kw, parts, LZ_DOT_CAP};
+  LzSet set(ctx);
+  LzOutcome oc;
+  LzTally tally;
+  const int st = lz_async_run(ctx, p, LzSchedule(lz_hint(ctx, key), max_dim), set, matvec, &oc, &tally);
+  for (int i = 0; i < mpse_ctx::LP_COUNT; ++i) ctx->lz_paths[i] += tally.paths[i];
+  MPSE_TRY(st);
+  switch (oc.kind) {
+    case LzOutcome::BAD:
+      return LZ_BADSTART;
+    case LzOutcome::DONE:
+      ++ctx->lz_paths[mpse_ctx::LP_ASYNC_DONE];
+      ++ctx->lz_paths[oc.breakdown ? mpse_ctx::LP_BD_ASYNC : mpse_ctx::LP_CONV];
+      // the answer sits in the spare area (an even number of estimates): copied now - the host knows; before, a
+      // conditional copy kernel was enqueued at every waited check
+      if (oc.which == 1) MPSE_TRY(mpse_memcpy_d2d(ctx, out, set.at(set.lay.spare), size_t(n) * es));
+      ctx->lz_hint[key] = oc.nvec;
+      if (nvec) *nvec = oc.nvec;
+      return MPSE_OK;
+    default:
+      // The synchronous solve restarts from Cin.  Estimates of this solve may have gone to `out` already: when `out` is
+      // Cin, C is put back from its copy U_0 first (bitwise C; U_0 is never written after k_lz_start).
+      if (tally.estimates && out == Cin) {
+        ++ctx->lz_paths[mpse_ctx::LP_ALIAS_RESTART];
+        MPSE_TRY(mpse_memcpy_d2d(ctx, out, set.at(set.lay.basis), size_t(n) * es));
       }
-    }
-    if (last) {     // beyond one wavefront of coefficients (or no convergence): the synchronous solve decides
-      ++ctx->lz_paths[mpse_ctx::LP_LIMIT];
-      return handover();
-    }
+      return LZ_FALLBACK;
   }
-  ctx->lz_hint[sch.key] = hc.nvec;
-  if (nvec) *nvec = hc.nvec;
-  return MPSE_OK;
 }
 
 // The synchronous solve: the host reads the recurrence scalars at every check and forms the coefficients itself.  It
@@ -1242,14 +1291,8 @@ int expm_lanczos_solve(mpse_ctx* ctx, int dtype, const mpse_heff* h, double dt_r
 
 // ------------------------------------------------------------------------------------------------------------
 // Batched solve (mpse_expm_lanczos_batch): B members of one shape whose matvec takes the one-launch small-centre path
-// run the asynchronous solve above in lock-step, every launch of the chain covering all of them (blockIdx.y / z =
-// member).  Each member does the arithmetic of its single solve in the same order - the batched kernels apply the member
-// offset and run the bodies of the single kernels, with the same grids per member - and stops its own kernels when
-// its decision has fallen (LzCtl::pad[0]).  The host waits once per check for all B control blocks.
-constexpr int LZB_MAX = 64;            // members per launch set (one lane each in k_lz_decide_b)
-constexpr int LZB_DOT_CAP = 4096;      // the dot request of expm_lanczos_async
-static_assert(mpse_ctx::PIN_BATCH_CTL + LZB_MAX * LZ_CW < mpse_ctx::PIN_QR_STATUS, "batch slot clear of the QR status word");
-
+// run as one launch set of lz_async_run.  Each member does the arithmetic of its single solve in the same order - the
+// same kernels with the same grids per member - and stops its own kernels when its decision has fallen (LzCtl::stop).
 struct BatchSet {
   const mpse_heff* h0;        // the shape (every member has the same nsite / dims / dtypes)
   std::vector<int> idx;       // member -> position in the caller's arrays
@@ -1265,24 +1308,9 @@ int expm_lanczos_batch_set(mpse_ctx* ctx, int dtype, const BatchSet& bs, const m
                            std::vector<char>& single, std::vector<int>& st_out, std::vector<std::string>& msg) {
   const int B = (int)bs.idx.size();
   const int64_t n = bs.n;
-  const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
-  const int64_t nd = n * (cplx ? 2 : 1);
-  const double tiny = 100.0 * double(n) * 2.220446049250313e-16;
-  LzSchedule sch(ctx, bs.h0->nsite, n, cplx, max_dim);
-  int& cap = sch.cap;
-  const int nb = red_blocks(nd);
-
-  // per-member region of the slab (doubles, 256-byte aligned sections; the Krylov basis last so that it can grow):
-  // [scalars, control block, coefficients][flag word][dot partials][norm partials x 2][result parts][spare][basis]
-  auto al = [](int64_t x) { return (x + 31) & ~int64_t(31); };
-  const int SC_CTL = 4 + 4 * 130, SC_COEF = SC_CTL + 8;
-  const int64_t o_flag = al(SC_COEF + 4 * LZ_MAXM), o_pa = o_flag + 32, o_pb0 = o_pa + al(2 * int64_t(bs.nb_dot));
-  const int64_t o_pb1 = o_pb0 + al(2 * int64_t(nb)), o_w = o_pb1 + al(2 * int64_t(nb));
-  const int64_t o_res = o_w + al(bs.nparts * nd), o_v = o_res + al(nd);
-  int64_t ms = o_v + al(cap * nd);
-  TmpBuf SLAB(ctx), RT(ctx), MEM(ctx);
-  MPSE_TRY(SLAB.alloc(size_t(B) * ms * sizeof(double)));
+  const unsigned long long key = lz_hint_key(bs.h0->nsite, n, dtype == MPSE_C128);
+  TmpBuf RT(ctx), MEM(ctx);
   MPSE_TRY(RT.alloc(size_t(B) * bs.rt_bytes));
   MPSE_TRY(MEM.alloc(size_t(B) * sizeof(BatchMember)));
   std::vector<BatchMember> mh(B);
@@ -1292,105 +1320,31 @@ int expm_lanczos_batch_set(mpse_ctx* ctx, int dtype, const BatchSet& bs, const m
   }
   MPSE_TRY(stage_h2d(ctx, MEM.p, mh.data(), mh.size() * sizeof(BatchMember)));
   const BatchMember* mem = MEM.as<const BatchMember>();
-  // the sections of member 0 (the others: + m * mstride bytes); placed again when the slab has grown
-  long long mstride;
-  double *scal, *coef, *part_a, *part_b2[2], *W, *RES;
-  LzCtl* ctl;
-  unsigned int* flag;
-  const int* skip0;
-  auto place = [&] {
-    double* base = SLAB.as<double>();
-    mstride = ms * (long long)sizeof(double);
-    scal = base;
-    ctl = reinterpret_cast<LzCtl*>(scal + SC_CTL);
-    coef = scal + SC_COEF;
-    flag = reinterpret_cast<unsigned int*>(base + o_flag);
-    skip0 = &ctl->pad[0];
-    part_a = base + o_pa;
-    part_b2[0] = base + o_pb0, part_b2[1] = base + o_pb1;
-    W = base + o_w;
-    RES = base + o_res;
+  auto matvec = [&](const LzIter& it, LzMatvecOut* r) -> int {
+    // (the transposed environments wait for k_lz_start: it clears the stop words their launch looks at)
+    if (it.j == 0) MPSE_TRY(heff_small_batch_rt(ctx, dtype, bs.h0, B, mem, it.stop, it.mstride));
+    r->nparts = bs.nparts, r->a_nb = bs.nb_dot;
+    return heff_small_batch_apply(ctx, dtype, bs.h0, B, mem, it.u, it.parts, n, it.dot, LZ_DOT_CAP, it.stop, it.mstride);
   };
-  place();
-  auto vec = [&](int j) { return SLAB.as<double>() + o_v + int64_t(j) * nd; };
-  const bool vec16 = true;   // (members are grouped only when every Krylov vector starts on a 16-byte boundary)
-  MPSE_HIP(ctx, hipMemset2DAsync(flag, size_t(mstride), 0, sizeof(unsigned int), size_t(B), ctx->stream));
-
-  MPSE_LAUNCH_TF_CHK(ctx, cplx, k_lz_start_b, dim3(nb, B), dim3(RED_THREADS), mem, vec(0), (long long)n, part_b2[0], ctl,
-                     mstride);
-  MPSE_TRY(heff_small_batch_rt(ctx, dtype, bs.h0, B, mem, skip0, mstride));
-
-  int prev_sel = -1;    // where the earlier estimate went: -1 none, 0 the result, 1 the spare buffer (the same for all)
-  bool waited = false;
-  std::vector<LzCtl> hc(B);
-  std::vector<char> fin(B, 0);
-  for (int j = 0;; ++j) {
-    MPSE_TRY(heff_small_batch_apply(ctx, dtype, bs.h0, B, mem, vec(j), W, n, part_a, LZB_DOT_CAP, skip0, mstride));
-    if (j + 2 > cap) {      // room for U_{j+1}: a new slab with a longer basis per member
-      const int ncap = sch.grown();
-      const int64_t nms = o_v + al(ncap * nd);
-      TmpBuf S2(ctx);
-      MPSE_TRY(S2.alloc(size_t(B) * nms * sizeof(double)));
-      MPSE_HIP(ctx, hipMemcpy2DAsync(S2.p, size_t(nms) * 8, SLAB.p, size_t(ms) * 8, size_t(ms) * 8, size_t(B),
-                                     hipMemcpyDeviceToDevice, ctx->stream));
-      std::swap(SLAB.p, S2.p);
-      ms = nms;
-      cap = ncap;
-      place();
-    }
-    double* cur_part = part_b2[j & 1];
-    double* new_part = part_b2[(j + 1) & 1];
-    double* cur_out = j == 0 ? scal : scal + 6 + 4 * (j - 1);
-    const double* prev2 = j == 0 ? scal : (j == 1 ? scal : scal + 6 + 4 * (j - 2));
-    hipLaunchKernelGGL(k_lanczos_update_u_b<vec16>, dim3(nb, B), dim3(RED_THREADS), 0, ctx->stream, vec(j + 1),
-                       (const double*)W, bs.nparts, (long long)nd, (const double*)vec(j),
-                       j > 0 ? (const double*)vec(j - 1) : (const double*)nullptr, (long long)nd, (const double*)part_a,
-                       bs.nb_dot, scal + 4 + 4 * j, (const double*)cur_part, nb, cur_out, prev2, new_part, skip0, mstride);
-    const LzSchedule::Step step = sch.at(j, prev_sel >= 0);
-    const bool merged = step.merged, last = step.last;
-    if (step.check) {
-      hipLaunchKernelGGL(k_lz_coefs_b, dim3(merged ? 2 : 1, B), dim3(64), 0, ctx->stream, scal, j, dt.real(), dt.imag(),
-                         tiny, coef, ctl, (const double*)new_part, nb, mstride);
-      const int res_sel = prev_sel == 0 ? 1 : 0;
-      unsigned int gen = 0;
-      MPSE_TRY(lz_flag_stamp(ctx, prev_sel >= 0 || merged, flag, size_t(mstride), B, &gen));
-      MPSE_LAUNCH_TF(ctx, cplx, k_lincomb_dev_b, dim3(ew_blocks(n), B), dim3(256), mem, RES, res_sel, prev_sel,
-                     (const double*)vec(0), (long long)n, j + 1, (const double*)coef, rtol, atol, flag, gen,
-                     (const LzCtl*)ctl, merged ? j - 1 : 0, mstride);
-      const bool wait_here = j >= sch.wait_from || waited || last;
-      const PublishAt at = publish_target(ctx, wait_here, mpse_ctx::PIN_BATCH_CTL);
-      hipLaunchKernelGGL(k_lz_decide_b, dim3(1), dim3(64), 0, ctx->stream, ctl, (const unsigned int*)flag, gen,
-                         (prev_sel >= 0 || merged) ? 1 : 0, j, res_sel, B, mstride, at.pub, at.seq_slot, at.seq);
-      prev_sel = res_sel;
-      MPSE_HIP(ctx, hipGetLastError());
-      if (wait_here) {
-        MPSE_TRY(publish_collect(ctx, at, ctl, size_t(mstride), B, LZ_CW, mpse_ctx::PIN_BATCH_CTL, hc.data()));
-        waited = true;
-        bool all = true;
-        for (int m = 0; m < B; ++m) {
-          if (hc[m].bad || hc[m].need_host) single[m] = 1;
-          else if (hc[m].done) fin[m] = 1;
-          else all = false;
-        }
-        if (all) break;
-      }
-    }
-    if (last) {     // beyond one wavefront of coefficients (or no convergence): the single solve decides
-      for (int m = 0; m < B; ++m)
-        if (!fin[m]) single[m] = 1;
-      break;
-    }
-  }
+  // (members are grouped only when every Krylov vector starts on a 16-byte boundary; no part or centre masks)
+  const LzProblem p{dtype, n, B, mem, nullptr, nullptr, dt, rtol, atol, true, nullptr, 0, 0, bs.nparts, bs.nb_dot};
+  LzSet set(ctx);
+  std::vector<LzOutcome> oc(B);
+  LzTally tally;   // (a batch counts its members, not their paths: mpse_expm_lanczos_batch_stats)
+  MPSE_TRY(lz_async_run(ctx, p, LzSchedule(lz_hint(ctx, key), max_dim), set, matvec, oc.data(), &tally));
   int best = 0;
   for (int m = 0; m < B; ++m) {
-    if (!fin[m]) continue;
-    if (hc[m].which == 1)
-      MPSE_TRY(mpse_memcpy_d2d(ctx, outs[bs.idx[m]], member_ptr(RES, m, mstride), size_t(n) * es));
-    if (nvec) nvec[bs.idx[m]] = hc[m].nvec;
-    if (hc[m].nvec > best) best = hc[m].nvec;
+    if (oc[m].kind != LzOutcome::DONE) {
+      single[m] = 1;
+      continue;
+    }
+    if (oc[m].which == 1)
+      MPSE_TRY(mpse_memcpy_d2d(ctx, outs[bs.idx[m]], set.at(set.lay.spare, m), size_t(n) * es));
+    if (nvec) nvec[bs.idx[m]] = oc[m].nvec;
+    if (oc[m].nvec > best) best = oc[m].nvec;
     st_out[bs.idx[m]] = MPSE_OK;
   }
-  if (best > 0) ctx->lz_hint[sch.key] = best;
+  if (best > 0) ctx->lz_hint[key] = best;
   // members the batch could not finish: the single solve from the copy of their start vector in the basis (bitwise C;
   // out may alias C).  Where their own asynchronous solve would hand over to the synchronous one (need_host, the vector
   // limit), that one runs directly - it starts from C and does not depend on the attempt before it
@@ -1398,14 +1352,15 @@ int expm_lanczos_batch_set(mpse_ctx* ctx, int dtype, const BatchSet& bs, const m
     if (!single[m]) continue;
     const int i = bs.idx[m];
     int nv = 0;
-    const int st = expm_lanczos_solve(ctx, dtype, &hs[i], dt.real(), dt.imag(), member_ptr(vec(0), m, mstride), outs[i],
-                                      rtol, atol, max_dim, &nv, SolveHints(), hc[m].bad != 0);
+    const int st = expm_lanczos_solve(ctx, dtype, &hs[i], dt.real(), dt.imag(), set.at(set.lay.basis, m), outs[i], rtol,
+                                      atol, max_dim, &nv, SolveHints(), oc[m].kind == LzOutcome::BAD);
     if (nvec) nvec[i] = nv;
     st_out[i] = st;
     if (st != MPSE_OK) msg[i] = ctx->err;
   }
   return MPSE_OK;
 }
+
 
 }  // namespace
 
@@ -1469,7 +1424,7 @@ int mpse_expm_lanczos_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff
       }
       size_t rtb = 0;
       int np = 0, nbd = 0;
-      if (!heff_small_batch_plan(&hi, dtype, n, LZB_DOT_CAP, &rtb, &np, &nbd)) continue;
+      if (!heff_small_batch_plan(&hi, dtype, n, LZ_DOT_CAP, &rtb, &np, &nbd)) continue;
       BatchSet* tgt = nullptr;
       for (auto& o : open) {
         const mpse_heff& h0 = *o.h0;

@@ -543,6 +543,50 @@ def test_batched_members_across_bands(eng):
     assert all(np.array_equal(a, b) for a, b in zip(outs, outs2))
 
 
+def test_batch_grows_and_member_leaves_at_limit(eng, long_problem):
+    """three members of LONG_DIMS under one dt whose single solves need 17 .. 32, 33 .. 63 and more than 64 vectors:
+    the slab of the batch grows (it starts at 16 vectors: a short solve of the class sets the run-ahead hint first),
+    two members finish at different checks and the third leaves at the 64-vector limit for the synchronous solve.
+    The members differ by an energy shift.  A shift alone cannot move the Krylov dimension under a real-time step
+    (exp(dt (H + E)) = exp(dt E) exp(dt H): the same Krylov space, estimates that differ by a phase), so the first two
+    also have their level spacings scaled by 0.12 and 0.4 (|dt| x spectral width 12 and 41 instead of 103; a host
+    Lanczos with the engine's checks gives 27 and 47 vectors); the third is the problem of test_vector_limit_handover."""
+    k3, hop3, c3, ex3 = long_problem
+    dt = -1j * LONG_TAU
+    base = [0.71, 0.43, 0.59, 0.37]
+    rng = np.random.default_rng(12)
+    ks = [kron_problem(300, LONG_DIMS, True, shift=7.0, spacing=[0.12 * s for s in base]),
+          kron_problem(300, LONG_DIMS, True, shift=3.0, spacing=[0.4 * s for s in base]), k3]
+    cs = [_rand(rng, (k3.n,), True), _rand(rng, (k3.n,), True), c3]
+    exs = [ks[0].expm(dt, cs[0]), ks[1].expm(dt, cs[1]), ex3]
+    hops = [_hop(ks[0]), _hop(ks[1]), hop3]
+    devs = [eng.asdevice(c) for c in cs]
+    singles = [_solve(eng, h, c, dt, *LONG_TOL) for h, c in zip(hops, devs)]
+    assert all(s[0] == 0 for s in singles)
+    assert 16 < singles[0][2] <= 32 and 32 < singles[1][2] < 64 and 64 < singles[2][2] <= 128, [s[2] for s in singles]
+    assert singles[2][3].get("limit") == 1 and singles[2][3].get("sync") == 1, singles[2][3]
+    cshort, _, _, _ = _eig_start(k3, 3, rng, True)
+
+    def short_solve():           # leaves the hint of the class at 3: the next solve starts with room for 16 vectors
+        st, _, nv, _ = _solve(eng, hop3, eng.asdevice(cshort), dt, 1e-14)
+        assert st == 0 and nv <= 8, (st, nv)
+
+    short_solve()
+    st, outs, nvs, d, (nb, ns) = _batch(eng, hops, devs, dt, *LONG_TOL)
+    assert st == 0 and nb == 2 and ns == 1, (st, nb, ns)
+    # the third member: the synchronous solve, straight from the batch (whose own loop counts no paths)
+    assert d.get("sync") == 1 and "limit" not in d and d.get("converged") == 1, d
+    for i, (s1, o, nv) in enumerate(zip(singles, outs, nvs)):
+        assert np.array_equal(s1[1], o) and s1[2] == nv, i
+        assert _relerr(o, exs[i]) < 1e-9, i
+    # out == C
+    short_solve()
+    devs2 = [eng.asdevice(c) for c in cs]
+    st, outs2, nvs2, _, (nb2, ns2) = _batch(eng, hops, devs2, dt, *LONG_TOL, outs=devs2)
+    assert st == 0 and nvs2 == nvs and (nb2, ns2) == (2, 1)
+    assert all(np.array_equal(a, b) for a, b in zip(outs, outs2))
+
+
 # =============================================================================================== 7. edges
 
 @pytest.mark.parametrize("path", ["sync", "async"])
