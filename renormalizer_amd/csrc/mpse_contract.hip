@@ -634,6 +634,126 @@ extern "C" int mpse_env_update_ft(mpse_ctx* ctx, int dtype, int domain, const mp
   return run_plan(ctx, dtype, p, bufs);
 }
 
+int ft_shape_ok(mpse_ctx* ctx, const mpse_heff_ft& h, const char* who) {
+  if (h.Dl <= 0 || h.Dr <= 0 || h.d_up <= 0 || h.d_down <= 0 || h.wl1 <= 0 || h.wr1 <= 0 || h.wl2 <= 0 || h.wr2 <= 0)
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: empty extent", who);
+  if ((h.leg1 != MPSE_LEG_UP && h.leg1 != MPSE_LEG_DOWN) || (h.leg2 != MPSE_LEG_UP && h.leg2 != MPSE_LEG_DOWN) ||
+      (h.leg1 == MPSE_LEG_DOWN && h.leg2 == MPSE_LEG_UP))
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: layers act up/up, down/down or up/down", who);
+  return MPSE_OK;
+}
+
+// ---- preconditioner of the summed solve: the diagonal of each term from the environment diagonals and a per-site factor
+namespace {
+
+// element of an MPO site W (wl, d, d, wr) that takes leg value `in` to `out` under the layer's transposition flag
+__device__ __forceinline__ double ft_w_elem(const double* W, int trans, long long d, long long wr, long long b, long long in,
+                                            long long out, long long f) {
+  return trans ? W[((b * d + in) * d + out) * wr + f] : W[((b * d + out) * d + in) * wr + f];
+}
+
+struct FtShape {
+  long long Dl, Dr, du, dv, wl1, wr1, wl2, wr2;
+  int leg1, leg2, trans1, trans2;
+};
+
+// S[b, c, u, v, g, i]: both layers on one leg: sum_x W1(leg -> x)[b, g] W2(x -> leg)[c, i]; one per leg: the two diagonals
+__global__ __launch_bounds__(256) void k_site_factor_ft(const FtShape h, const double* __restrict__ W1,
+                                                        const double* __restrict__ W2, double* __restrict__ S) {
+  const long long total = h.wl1 * h.wl2 * h.du * h.dv * h.wr1 * h.wr2;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  long long r = idx;
+  const long long i = r % h.wr2; r /= h.wr2;
+  const long long g = r % h.wr1; r /= h.wr1;
+  const long long v = r % h.dv; r /= h.dv;
+  const long long u = r % h.du; r /= h.du;
+  const long long c = r % h.wl2;
+  const long long b = r / h.wl2;
+  double acc = 0.0;
+  if (h.leg1 == h.leg2) {
+    const long long d = h.leg1 == MPSE_LEG_UP ? h.du : h.dv, e = h.leg1 == MPSE_LEG_UP ? u : v;
+    for (long long x = 0; x < d; ++x)
+      acc += ft_w_elem(W1, h.trans1, d, h.wr1, b, e, x, g) * ft_w_elem(W2, h.trans2, d, h.wr2, c, x, e, i);
+  } else {
+    acc = ft_w_elem(W1, h.trans1, h.du, h.wr1, b, u, u, g) * ft_w_elem(W2, h.trans2, h.dv, h.wr2, c, v, v, i);
+  }
+  S[idx] = acc;
+}
+
+// diag[a, u, v, j] (+)= weight * sum_{b, c, g, i} Re(L[a, b, c, a] R[j, g, i, j]) S[b, c, u, v, g, i]; one thread per entry
+template <bool LC, bool RC>
+__global__ __launch_bounds__(256) void k_diag_ft(const FtShape h, const double* __restrict__ L,
+                                                 const double* __restrict__ R, const double* __restrict__ S, double weight,
+                                                 double shift, int accumulate, double* __restrict__ diag) {
+  const long long total = h.Dl * h.du * h.dv * h.Dr;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  long long r = idx;
+  const long long j = r % h.Dr; r /= h.Dr;
+  const long long v = r % h.dv; r /= h.dv;
+  const long long u = r % h.du;
+  const long long a = r / h.du;
+  double acc = 0.0;
+  for (long long b = 0; b < h.wl1; ++b)
+    for (long long c = 0; c < h.wl2; ++c) {
+      const long long lo = ((a * h.wl1 + b) * h.wl2 + c) * h.Dl + a;
+      const double lr = LC ? L[2 * lo] : L[lo], li = LC ? L[2 * lo + 1] : 0.0;
+      for (long long g = 0; g < h.wr1; ++g)
+        for (long long i = 0; i < h.wr2; ++i) {
+          const long long ro = ((j * h.wr1 + g) * h.wr2 + i) * h.Dr + j;
+          const double rr = RC ? R[2 * ro] : R[ro], ri = RC ? R[2 * ro + 1] : 0.0;
+          acc += (lr * rr - li * ri) * S[((((b * h.wl2 + c) * h.du + u) * h.dv + v) * h.wr1 + g) * h.wr2 + i];
+        }
+    }
+  diag[idx] = (accumulate ? diag[idx] : shift) + weight * acc;
+}
+
+FtShape ft_shape(const mpse_heff_ft& h) {
+  return FtShape{h.Dl, h.Dr, h.d_up, h.d_down, h.wl1, h.wr1, h.wl2, h.wr2, h.leg1, h.leg2, h.trans1, h.trans2};
+}
+
+}  // namespace
+
+extern "C" int mpse_site_factor_ft(mpse_ctx* ctx, const mpse_heff_ft* h, void* S_f64) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (!h || !S_f64 || !h->W1 || !h->W2) return mpse_fail(ctx, MPSE_ERR_ARG, "site_factor_ft: null argument");
+  MPSE_BIND(ctx);
+  MPSE_TRY(ft_shape_ok(ctx, *h, "site_factor_ft"));
+  if (h->w_dtype != MPSE_F64) return mpse_fail(ctx, MPSE_ERR_ARG, "site_factor_ft: real MPO sites only");
+  const long long total = h->wl1 * h->wl2 * h->d_up * h->d_down * h->wr1 * h->wr2;
+  hipLaunchKernelGGL(k_site_factor_ft, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ft_shape(*h),
+                     static_cast<const double*>(h->W1), static_cast<const double*>(h->W2), static_cast<double*>(S_f64));
+  MPSE_HIP(ctx, hipGetLastError());
+  return MPSE_OK;
+}
+
+extern "C" int mpse_diag_ft(mpse_ctx* ctx, const mpse_heff_ft* h, const void* S_f64, double weight, double shift,
+                            int accumulate, void* diag_f64) {
+  if (!ctx) return MPSE_ERR_ARG;
+  if (!h || !S_f64 || !diag_f64 || !h->L || !h->R) return mpse_fail(ctx, MPSE_ERR_ARG, "diag_ft: null argument");
+  MPSE_BIND(ctx);
+  MPSE_TRY(ft_shape_ok(ctx, *h, "diag_ft"));
+  const long long total = h->Dl * h->d_up * h->d_down * h->Dr;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  const FtShape fs = ft_shape(*h);
+  const double *L = static_cast<const double*>(h->L), *R = static_cast<const double*>(h->R);
+  const double* S = static_cast<const double*>(S_f64);
+  double* dg = static_cast<double*>(diag_f64);
+  const bool lc = h->l_dtype == MPSE_C128, rc = h->r_dtype == MPSE_C128;
+  if (lc && rc)
+    hipLaunchKernelGGL((k_diag_ft<true, true>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  else if (lc)
+    hipLaunchKernelGGL((k_diag_ft<true, false>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  else if (rc)
+    hipLaunchKernelGGL((k_diag_ft<false, true>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  else
+    hipLaunchKernelGGL((k_diag_ft<false, false>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
+  MPSE_HIP(ctx, hipGetLastError());
+  if (!accumulate) ++ctx->pcg_sum_stats[mpse_ctx::PSS_DIAGS];
+  return MPSE_OK;
+}
+
 extern "C" int mpse_env_unit_channel(mpse_ctx* ctx, int dtype, const void* env, int64_t D, int64_t w, double tol,
                                      int64_t* unit_host) {
   if (!ctx || !env || !unit_host) return MPSE_ERR_ARG;

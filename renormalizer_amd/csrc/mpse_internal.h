@@ -69,10 +69,9 @@ struct mpse_ctx {
     PIN_FLAG = 8,          // [8, 9): Lanczos closeness flag; block SVD: done words of nblk blocks, (nblk + 1) / 2 doubles
     PIN_LZ_SCAL = 16,      // [16, 540): recurrence scalars of the synchronous Lanczos solve, up to 4 + 4 * 130 doubles
     PIN_ENV_UNIT = 32,        // [32, 32 + w): deviation from the unit per MPO channel of an environment, w <= 2048
-    PIN_PCG_CTL = 40,      // [40, 48): PcgCtl of mpse_pcg / mpse_pcg_sum
     PIN_DAVIDSON = 64,     // [64, 64 + count): subspace products and norms of the Davidson solver, count <= 1024
     // [3700, 3956): control blocks of a launch set, up to 64 x LzCtl (the asynchronous Lanczos solve, single or batched)
-    // or 32 x PcgCtl (the batched PCG), never both at once
+    // or 32 x PcgCtl (mpse_pcg, mpse_pcg_sum: one block; mpse_pcg_batch), never both at once
     PIN_BATCH_CTL = 3700,
     PIN_QR_STATUS = 3990,  // [3990, 3991): breakdown word of the Cholesky-QR
     PIN_SLOTS_END = 4000,  // slots of publish_and_wait end here
@@ -478,6 +477,8 @@ int heff_apply(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void
 int heff_apply2(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc);
 // One term of the finite-temperature correction-vector operator (mpse_heff_apply_ft), inside a solve (sc may be null)
 int heff_apply_ft(mpse_ctx* ctx, int dtype, const mpse_heff_ft* h, const void* C, void* out, SolveScope* sc);
+// extents and leg order of such a term; refuses with "<who>: ..." (hidden: the dynamic symbol table stays what it was)
+__attribute__((visibility("hidden"))) int ft_shape_ok(mpse_ctx* ctx, const mpse_heff_ft& h, const char* who);
 // One-launch matvec of small 0- / 1-site centres (mpse_small.hip); *taken says whether it ran (else: the plans)
 int heff_small_try(mpse_ctx* ctx, int dtype, const mpse_heff* h, const void* C, void* out, SolveScope* sc,
                    MatvecReq* mv, bool* taken);

@@ -19,13 +19,11 @@
 #include "mpse_cx.h"
 #include "mpse_device.h"
 #include "mpse_internal.h"
+#include "mpse_pcg_plan.h"
 
 namespace {
 
-constexpr int PCG_K = 4;        // the host reads the pinned control block every PCG_K iterations: at most PCG_K - 1
-                                // matvecs are enqueued past the decision
-
-enum { PCG_WHY_NONE = 0, PCG_WHY_TOL = 1, PCG_WHY_MAXITER = 2, PCG_WHY_CURVATURE = 3, PCG_WHY_DIAG = 4, PCG_WHY_ZERO_B = 5 };
+using namespace mpse_pcg_plan;   // PCG_K, PCG_CW, PCG_WHY_*, waits_at, default_max_iter, layout
 
 struct PcgCtl {
   int done;        // decision has fallen: later launches do nothing
@@ -37,8 +35,7 @@ struct PcgCtl {
   double bb;       // |mask * b|^2
   double pad[3];
 };
-static_assert(sizeof(PcgCtl) == 8 * sizeof(double), "control block = 8 doubles");
-constexpr int PCG_CW = int(sizeof(PcgCtl) / sizeof(double));
+static_assert(sizeof(PcgCtl) == PCG_CW * sizeof(double), "control block = PCG_CW doubles");
 
 __device__ __forceinline__ void pcg_publish(const PcgCtl* ctl, double* pub, volatile double* seq_slot, double seq) {
   const double* src = reinterpret_cast<const double*>(ctl);
@@ -385,212 +382,297 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_publish_b(const Pcg2Member*
   }
 }
 
-template <bool CPLX>
-int pcg_run(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const double* diag,
-            const double* mask, const double* b, double* x, double tol, int max_iter, int64_t n, PcgCtl* hc,
-            int nterms = 0, const mpse_heff_ft* terms = nullptr, const double* weights = nullptr) {
-  const size_t es = dtype_size(dtype);
-  const int64_t nd = n * (CPLX ? 2 : 1);
-  const int nb = red_blocks(nd);
-  // one slab: control block, five areas of partials (|b|^2; p^H q; r^H z twice, by iteration parity; b^H x), then y, q, r, p
-  // (a summed solve: one more y per further term, behind p)
-  const size_t head = size_t(PCG_CW + 5 * 2 * nb) * sizeof(double);
-  const size_t head_al = (head + 255) & ~size_t(255);
-  TmpBuf slab(ctx);
-  MPSE_TRY(slab.alloc(head_al + (4 + size_t(nterms > 1 ? nterms - 1 : 0)) * size_t(n) * es));
-  PcgCtl* ctl = slab.as<PcgCtl>();
-  double* part = slab.as<double>() + PCG_CW;
-  double *part_bb = part, *part_pq = part + 2 * nb, *part_bx = part + 4 * nb;
-  double* part_rz[2] = {part + 6 * nb, part + 8 * nb};
-  char* vecs = slab.as<char>() + head_al;
-  double* y = reinterpret_cast<double*>(vecs);
-  double* q = reinterpret_cast<double*>(vecs + size_t(n) * es);
-  double* r = reinterpret_cast<double*>(vecs + 2 * size_t(n) * es);
-  double* p = reinterpret_cast<double*>(vecs + 3 * size_t(n) * es);
+// ---- the host side: one driver (pcg_drive) for mpse_pcg, mpse_pcg_sum and the launch sets of mpse_pcg_batch
 
-  SolveScope scope(ctx);
-  scope.skip = &ctl->done;
-  // a single term of weight one is the plain solve on that term's result
-  const bool summed = nterms > 1 || (nterms == 1 && weights[0] != 1.0);
-  PcgTerms ts;
-  memset(&ts, 0, sizeof(ts));
-  ts.n = nterms;
-  for (int t = 0; t < nterms; ++t) {
-    ts.y[t] = t == 0 ? y : reinterpret_cast<double*>(vecs + (3 + size_t(t)) * size_t(n) * es);
-    ts.w[t] = weights[t];
+// A launch set: B >= 1 members of one shape.  mh[m] holds the caller's b, x, mask, diag and shift of member m and the
+// vectors, partials and control block of its region of the slab (mpse_pcg_plan::layout, regions `stride` bytes apart).
+// mem: the same table on the device, or null (B == 1): a single solve uploads nothing and launches the direct-pointer
+// kernels on mh[0] - its launches and its global accesses are what they always were.
+struct PcgSet {
+  int dtype;
+  int64_t n;
+  int nb, nbq;                   // partial pairs per reduction of the vector kernels / of p^H q
+  double tol;
+  int max_iter;
+  int B;
+  const Pcg2Member *mh, *mem;
+  size_t stride;
+  const char* who;
+};
+void pcg_place(Pcg2Member& mb, char* base, const Layout& l) {
+  auto at = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+  mb.ctl = base + l.ctl;
+  mb.part_bb = at(l.part_bb), mb.part_bx = at(l.part_bx), mb.part_pq = at(l.part_pq);
+  mb.part_rz0 = at(l.part_rz[0]), mb.part_rz1 = at(l.part_rz[1]);
+  mb.y = at(l.y), mb.q = at(l.q), mb.r = at(l.r), mb.p = at(l.p);
+}
+
+// The stages as launches, one method per stage: the table form when the set has a device table, else the direct form.
+struct PcgLaunch {
+  mpse_ctx* ctx;
+  const PcgSet& s;
+  const bool cplx = s.dtype == MPSE_C128;
+  const long long n = (long long)s.n;
+  const Pcg2Member& m = s.mh[0];
+  const dim3 grid{(unsigned)s.nb, 1, (unsigned)(s.mem ? s.B : 1)}, block{RED_THREADS};
+  PcgCtl* ctl() const { return static_cast<PcgCtl*>(m.ctl); }
+  double* rz(int k) const { return k & 1 ? m.part_rz1 : m.part_rz0; }      // r^H z partials by iteration parity
+
+  int prep() const {
+    if (s.mem)
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_prep_b, grid, block, s.mem, n);
+    else
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_prep, grid, block, m.x, m.b, m.mask, m.diag, n, m.part_bb, ctl());
+    return MPSE_OK;
   }
-  auto matvec = [&](const void* in) -> int {
-    if (nterms > 0) {
-      for (int t = 0; t < nterms; ++t)
-        MPSE_TRY(heff_apply_ft(ctx, dtype, &terms[t], in, const_cast<double*>(ts.y[t]), &scope));
-      return MPSE_OK;
+  int start() const {
+    if (s.mem)
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_start_b, grid, block, s.mem, n, s.nb);
+    else
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_start, grid, block, m.y, m.b, m.mask, m.diag, m.x, m.r, m.p, m.shift, n, m.part_bb,
+                         s.nb, m.part_rz0, m.part_bx, ctl());
+    return MPSE_OK;
+  }
+  // q and the partials of p^H q from the product in y, or from the results of the terms of a summed solve
+  int q(const PcgTerms* sum) const {
+    if (s.mem) return mpse_fail(ctx, MPSE_ERR_ARG, "%s: the q kernel has no table form", s.who);
+    if (sum)
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_q_sum, grid, block, *sum, m.p, m.mask, m.shift, m.q, n, m.part_pq, ctl());
+    else
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_q, grid, block, m.y, m.p, m.mask, m.shift, m.q, n, m.part_pq, ctl());
+    return MPSE_OK;
+  }
+  int step(int k) const {
+    if (s.mem)
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_step_b, grid, block, s.mem, n, s.nbq, s.nb, k);
+    else
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_step, grid, block, m.p, m.q, m.b, m.mask, m.diag, m.x, m.r, n, m.part_pq,
+                         rz(k - 1), rz(k), m.part_bx, s.nb, ctl());
+    return MPSE_OK;
+  }
+  // the direction update with the decision.  `at`: where the control blocks go when the host waits here - the direct
+  // form publishes by itself, the table form in a launch of one workgroup behind it
+  int dir(int k, const PublishAt& at) const {
+    const double tol2 = s.tol * s.tol;
+    if (s.mem) {
+      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_dir_b, grid, block, s.mem, n, s.nb, tol2, k, s.max_iter);
+      if (at.pub) hipLaunchKernelGGL(k_pcg_publish_b, dim3(1), block, 0, ctx->stream, s.mem, s.B, at.pub, at.seq_slot, at.seq);
+    } else {
+      MPSE_LAUNCH_TF(ctx, cplx, k_pcg_dir, grid, block, m.r, m.diag, m.p, n, rz(k), rz(k + 1), m.part_bx, s.nb, tol2, k,
+                     s.max_iter, ctl(), at.pub, at.seq_slot, at.seq);
     }
-    return twolayer ? heff_apply2(ctx, dtype, h, in, y, &scope) : heff_apply(ctx, dtype, h, in, y, &scope, nullptr);
-  };
-  const dim3 grid(nb), block(RED_THREADS);
-  const long long nn = (long long)n;
-  const double tol2 = tol * tol;
-  memset(hc, 0, sizeof(*hc));
-
-  hipLaunchKernelGGL(k_pcg_prep<CPLX>, grid, block, 0, ctx->stream, x, b, mask, diag, nn, part_bb, ctl);
-  MPSE_HIP(ctx, hipGetLastError());
-  MPSE_TRY(matvec(x));
-  if (summed) {
-    hipLaunchKernelGGL(k_pcg_combine<CPLX>, grid, block, 0, ctx->stream, ts, y, nn);
     MPSE_HIP(ctx, hipGetLastError());
+    return MPSE_OK;
   }
-  hipLaunchKernelGGL(k_pcg_start<CPLX>, grid, block, 0, ctx->stream, (const double*)y, b, mask, diag, x, r, p, shift, nn,
-                     (const double*)part_bb, nb, part_rz[0], part_bx, ctl);
-  MPSE_HIP(ctx, hipGetLastError());
-  for (int k = 0;; ++k) {
-    if (k > 0) {
-      MPSE_TRY(matvec(p));
-      ++ctx->pcg_stats[mpse_ctx::PS_MATVECS];
-      ctx->pcg_sum_stats[mpse_ctx::PSS_TERM_APPLIES] += nterms;
-      if (summed)
-        hipLaunchKernelGGL(k_pcg_q_sum<CPLX>, grid, block, 0, ctx->stream, ts, (const double*)p, mask, shift, q, nn,
-                           part_pq, (const PcgCtl*)ctl);
-      else
-        hipLaunchKernelGGL(k_pcg_q<CPLX>, grid, block, 0, ctx->stream, (const double*)y, (const double*)p, mask, shift, q,
-                           nn, part_pq, (const PcgCtl*)ctl);
-      MPSE_HIP(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_pcg_step<CPLX>, grid, block, 0, ctx->stream, (const double*)p, (const double*)q, b, mask, diag,
-                         x, r, nn, (const double*)part_pq, (const double*)part_rz[(k - 1) & 1], part_rz[k & 1], part_bx,
-                         nb, ctl);
-      MPSE_HIP(ctx, hipGetLastError());
-    }
-    const bool wait_here = (k % PCG_K == PCG_K - 1) || k >= max_iter;
-    const PublishAt at = publish_target(ctx, wait_here, mpse_ctx::PIN_PCG_CTL);
-    hipLaunchKernelGGL(k_pcg_dir<CPLX>, grid, block, 0, ctx->stream, (const double*)r, diag, p, nn,
-                       (const double*)part_rz[k & 1], (const double*)part_rz[(k + 1) & 1], (const double*)part_bx, nb,
-                       tol2, k, max_iter, ctl, at.pub, at.seq_slot, at.seq);
-    MPSE_HIP(ctx, hipGetLastError());
-    if (wait_here) {
-      // the control block that this k_pcg_dir published, or a copy of it
-      MPSE_TRY(publish_collect(ctx, at, ctl, 0, 1, PCG_CW, mpse_ctx::PIN_PCG_CTL, hc));
-      ++ctx->pcg_stats[mpse_ctx::PS_WAITS];
-      if (nterms > 0) ++ctx->pcg_sum_stats[mpse_ctx::PSS_WAITS];
-      if (hc->done) break;
-      if (k >= max_iter) return mpse_fail(ctx, MPSE_ERR_HIP, "pcg: no decision at the iteration limit");
-    }
-  }
-  return MPSE_OK;
-}
-template <class... A>
-int pcg_run_dtype(mpse_ctx* ctx, int dtype, A... a) {
-  return dtype == MPSE_C128 ? pcg_run<true>(ctx, dtype, a...) : pcg_run<false>(ctx, dtype, a...);
-}
-
-// ---- preconditioner of the summed solve: the diagonal of each term from the environment diagonals and a per-site factor
-// element of an MPO site W (wl, d, d, wr) that takes leg value `in` to `out` under the layer's transposition flag
-__device__ __forceinline__ double ft_w_elem(const double* W, int trans, long long d, long long wr, long long b, long long in,
-                                            long long out, long long f) {
-  return trans ? W[((b * d + in) * d + out) * wr + f] : W[((b * d + out) * d + in) * wr + f];
-}
-
-struct FtShape {
-  long long Dl, Dr, du, dv, wl1, wr1, wl2, wr2;
-  int leg1, leg2, trans1, trans2;
 };
 
-// S[b, c, u, v, g, i]: both layers on one leg: sum_x W1(leg -> x)[b, g] W2(x -> leg)[c, i]; one per leg: the two diagonals
-__global__ __launch_bounds__(256) void k_site_factor_ft(const FtShape h, const double* __restrict__ W1,
-                                                        const double* __restrict__ W2, double* __restrict__ S) {
-  const long long total = h.wl1 * h.wl2 * h.du * h.dv * h.wr1 * h.wr2;
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  long long r = idx;
-  const long long i = r % h.wr2; r /= h.wr2;
-  const long long g = r % h.wr1; r /= h.wr1;
-  const long long v = r % h.dv; r /= h.dv;
-  const long long u = r % h.du; r /= h.du;
-  const long long c = r % h.wl2;
-  const long long b = r / h.wl2;
-  double acc = 0.0;
-  if (h.leg1 == h.leg2) {
-    const long long d = h.leg1 == MPSE_LEG_UP ? h.du : h.dv, e = h.leg1 == MPSE_LEG_UP ? u : v;
-    for (long long x = 0; x < d; ++x)
-      acc += ft_w_elem(W1, h.trans1, d, h.wr1, b, e, x, g) * ft_w_elem(W2, h.trans2, d, h.wr2, c, x, e, i);
-  } else {
-    acc = ft_w_elem(W1, h.trans1, h.du, h.wr1, b, u, u, g) * ft_w_elem(W2, h.trans2, h.dv, h.wr2, c, v, v, i);
-  }
-  S[idx] = acc;
-}
+// what the driver enqueued, for the counters of its callers (valid also when the run fails part-way)
+struct PcgTally {
+  long long products = 0, waits = 0;
+};
 
-// diag[a, u, v, j] (+)= weight * sum_{b, c, g, i} Re(L[a, b, c, a] R[j, g, i, j]) S[b, c, u, v, g, i]; one thread per entry
-template <bool LC, bool RC>
-__global__ __launch_bounds__(256) void k_diag_ft(const FtShape h, const double* __restrict__ L,
-                                                 const double* __restrict__ R, const double* __restrict__ S, double weight,
-                                                 double shift, int accumulate, double* __restrict__ diag) {
-  const long long total = h.Dl * h.du * h.dv * h.Dr;
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  long long r = idx;
-  const long long j = r % h.Dr; r /= h.Dr;
-  const long long v = r % h.dv; r /= h.dv;
-  const long long u = r % h.du;
-  const long long a = r / h.du;
-  double acc = 0.0;
-  for (long long b = 0; b < h.wl1; ++b)
-    for (long long c = 0; c < h.wl2; ++c) {
-      const long long lo = ((a * h.wl1 + b) * h.wl2 + c) * h.Dl + a;
-      const double lr = LC ? L[2 * lo] : L[lo], li = LC ? L[2 * lo + 1] : 0.0;
-      for (long long g = 0; g < h.wr1; ++g)
-        for (long long i = 0; i < h.wr2; ++i) {
-          const long long ro = ((j * h.wr1 + g) * h.wr2 + i) * h.Dr + j;
-          const double rr = RC ? R[2 * ro] : R[ro], ri = RC ? R[2 * ro + 1] : 0.0;
-          acc += (lr * rr - li * ri) * S[((((b * h.wl2 + c) * h.du + u) * h.dv + v) * h.wr1 + g) * h.wr2 + i];
-        }
+// Runs a launch set to the decisions of all its members: hc[0 .. B).  The matvec is the one point where the callers
+// differ: mv.start() enqueues y = A x0 for every member, mv.product() the product with p of an iteration, which either
+// leaves q and the partials of p^H q (mv.makes_q) or y - then the q kernel follows, on mv.sum() when y is a sum of terms.
+template <class Matvec>
+int pcg_drive(mpse_ctx* ctx, const PcgSet& s, Matvec& mv, PcgCtl* hc, PcgTally* tally) {
+  const PcgLaunch go{ctx, s};
+  memset(hc, 0, size_t(s.B) * sizeof(PcgCtl));
+  MPSE_TRY(go.prep());
+  MPSE_TRY(mv.start());
+  MPSE_TRY(go.start());
+  for (int k = 0;; ++k) {
+    if (k > 0) {
+      MPSE_TRY(mv.product());
+      ++tally->products;
+      if (!mv.makes_q) MPSE_TRY(go.q(mv.sum()));
+      MPSE_TRY(go.step(k));
     }
-  diag[idx] = (accumulate ? diag[idx] : shift) + weight * acc;
+    const bool wait_here = waits_at(k, s.max_iter);
+    const PublishAt at = publish_target(ctx, wait_here, mpse_ctx::PIN_BATCH_CTL);
+    MPSE_TRY(go.dir(k, at));
+    if (!wait_here) continue;
+    // the control blocks that this launch published, or a copy of them
+    MPSE_TRY(publish_collect(ctx, at, s.mh[0].ctl, s.stride, s.B, PCG_CW, mpse_ctx::PIN_BATCH_CTL, hc));
+    ++tally->waits;
+    bool all = true;
+    for (int m = 0; m < s.B; ++m) all = all && hc[m].done;
+    if (all) return MPSE_OK;
+    if (k >= s.max_iter) return mpse_fail(ctx, MPSE_ERR_HIP, "%s: no decision at the iteration limit", s.who);
+  }
 }
 
-FtShape ft_shape(const mpse_heff_ft& h) {
-  return FtShape{h.Dl, h.Dr, h.d_up, h.d_down, h.wl1, h.wr1, h.wl2, h.wr2, h.leg1, h.leg2, h.trans1, h.trans2};
+// ---- the three matvecs
+// Heff or its two-layer form on the pointers of a single solve; contractions return at once after the decision
+struct PcgGeneral {
+  static constexpr bool makes_q = false;
+  mpse_ctx* ctx;
+  int dtype;
+  const mpse_heff* h;
+  int twolayer;
+  const Pcg2Member& m;
+  SolveScope scope{ctx};         // (the caller sets scope.skip to the control block's `done`)
+  int apply(const void* in) {
+    return twolayer ? heff_apply2(ctx, dtype, h, in, m.y, &scope) : heff_apply(ctx, dtype, h, in, m.y, &scope, nullptr);
+  }
+  int start() { return apply(m.x); }
+  int product() { return apply(m.p); }
+  const PcgTerms* sum() const { return nullptr; }
+};
+// a weighted sum of finite-temperature terms, each into a y of its own (ts.y: m.y, then the layout's further vectors);
+// a single term of weight one is the plain solve on that term's result
+struct PcgSummed {
+  static constexpr bool makes_q = false;
+  mpse_ctx* ctx;
+  const PcgSet& s;
+  const mpse_heff_ft* terms;
+  PcgTerms ts;
+  SolveScope scope{ctx};
+  int apply(const void* in) {
+    for (int t = 0; t < ts.n; ++t)
+      MPSE_TRY(heff_apply_ft(ctx, s.dtype, &terms[t], in, const_cast<double*>(ts.y[t]), &scope));
+    return MPSE_OK;
+  }
+  int start() {
+    MPSE_TRY(apply(s.mh[0].x));
+    if (sum())      // the start residual goes through k_pcg_start: the sum into the first term's vector
+      MPSE_LAUNCH_TF_CHK(ctx, s.dtype == MPSE_C128, k_pcg_combine, dim3(s.nb), dim3(RED_THREADS), ts, s.mh[0].y, (long long)s.n);
+    return MPSE_OK;
+  }
+  int product() { return apply(s.mh[0].p); }
+  const PcgTerms* sum() const { return ts.n > 1 || ts.w[0] != 1.0 ? &ts : nullptr; }
+};
+// the one-launch two-layer matvec of a launch set (mpse_small2.hip): members from the device table, q by itself
+struct PcgSmall2 {
+  static constexpr bool makes_q = true;
+  mpse_ctx* ctx;
+  const Small2Plan& pl;
+  const PcgSet& s;
+  int start() {
+    MPSE_TRY(small2_prep(ctx, s.dtype, pl, s.B, s.mem));
+    return small2_apply(ctx, s.dtype, pl, s.B, s.mem, 0);
+  }
+  int product() { return small2_apply(ctx, s.dtype, pl, s.B, s.mem, 1); }
+  const PcgTerms* sum() const { return nullptr; }
+};
+
+// a single solve (mpse_pcg, mpse_pcg_sum, a batch member outside the one-launch rule): its slab and its set of one
+struct PcgSingle {
+  TmpBuf slab;
+  Layout lay{};
+  Pcg2Member m{};
+  PcgSet set{};
+  explicit PcgSingle(mpse_ctx* ctx) : slab(ctx) {}
+  int init(int dtype, int64_t n, int extra_y, double shift, const void* diag, const void* mask, const void* b, void* x,
+           double tol, int max_iter) {
+    const bool cplx = dtype == MPSE_C128;
+    const int nb = red_blocks(n * (cplx ? 2 : 1));
+    lay = layout(n, cplx, nb, nb, extra_y);
+    MPSE_TRY(slab.alloc(lay.stride));
+    pcg_place(m, slab.as<char>(), lay);
+    m.diag = static_cast<const double*>(diag), m.mask = static_cast<const double*>(mask);
+    m.b = static_cast<const double*>(b), m.x = static_cast<double*>(x);
+    m.shift = shift;
+    set = PcgSet{dtype, n, nb, nb, tol, max_iter > 0 ? max_iter : default_max_iter(n), 1, &m, nullptr, 0, "pcg"};
+    return MPSE_OK;
+  }
+};
+
+// ---- argument rules shared by the entry points (`who` heads the message), and those of mpse_pcg
+int pcg_check_dtype(mpse_ctx* ctx, const char* who, int dtype) {
+  return dtype != MPSE_F64 && dtype != MPSE_C128 ? mpse_fail(ctx, MPSE_ERR_ARG, "%s: unknown dtype", who) : MPSE_OK;
 }
-int ft_shape_ok(mpse_ctx* ctx, const mpse_heff_ft& h, const char* who) {
-  if (h.Dl <= 0 || h.Dr <= 0 || h.d_up <= 0 || h.d_down <= 0 || h.wl1 <= 0 || h.wr1 <= 0 || h.wl2 <= 0 || h.wr2 <= 0)
-    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: empty extent", who);
-  if ((h.leg1 != MPSE_LEG_UP && h.leg1 != MPSE_LEG_DOWN) || (h.leg2 != MPSE_LEG_UP && h.leg2 != MPSE_LEG_DOWN) ||
-      (h.leg1 == MPSE_LEG_DOWN && h.leg2 == MPSE_LEG_UP))
-    return mpse_fail(ctx, MPSE_ERR_SHAPE, "%s: layers act up/up, down/down or up/down", who);
+int pcg_check_parts(mpse_ctx* ctx, const char* who, int dtype, int l_dtype, int r_dtype, int w_dtype) {
+  if (dtype != MPSE_C128 && (l_dtype == MPSE_C128 || r_dtype == MPSE_C128 || w_dtype == MPSE_C128))
+    return mpse_fail(ctx, MPSE_ERR_ARG, "%s: real vectors with complex operator parts", who);
   return MPSE_OK;
 }
+int pcg_check_tol_shift(mpse_ctx* ctx, const char* who, double tol, double shift) {
+  if (!(tol >= 0.0) || !std::isfinite(shift)) return mpse_fail(ctx, MPSE_ERR_ARG, "%s: tol must be >= 0 and shift finite", who);
+  return MPSE_OK;
+}
+int pcg_check_overlap(mpse_ctx* ctx, const char* who, int dtype, int64_t n, const void* b, const void* x) {
+  const size_t bytes = size_t(n) * dtype_size(dtype);
+  const char *xb = static_cast<const char*>(x), *bb = static_cast<const char*>(b);
+  return xb < bb + bytes && bb < xb + bytes ? mpse_fail(ctx, MPSE_ERR_ARG, "%s: x must not overlap b", who) : MPSE_OK;
+}
+// The rules of mpse_pcg in the order they fire; it touches nothing but the message, so that mpse_pcg_batch can ask for
+// a member's status without running it.  *n: the vector length of a member that passes.
+int pcg_check_member(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const void* b,
+                     const void* x, double tol, int64_t* n) {
+  if (!h || !b || !x || !h->L || !h->R || !h->W0) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: null argument");
+  MPSE_TRY(pcg_check_dtype(ctx, "pcg", dtype));
+  MPSE_TRY(pcg_check_parts(ctx, "pcg", dtype, h->l_dtype, h->r_dtype, h->w_dtype));
+  MPSE_TRY(pcg_check_tol_shift(ctx, "pcg", tol, shift));
+  const mpse_dims& s = h->dims;
+  if ((s.Dl_bra > 0 && s.Dl_bra != s.Dl_ket) || (s.Dr_bra > 0 && s.Dr_bra != s.Dr_ket))
+    return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg: the projected operator must be square (bra bonds == ket bonds)");
+  if (h->nsite != 1 && h->nsite != 2) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: one- or two-site centres");
+  if (twolayer && (s.danc > 1 || s.danc1 > 1)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: two-layer operators take no ancilla");
+  const int64_t anc = s.danc > 0 ? s.danc : 1;
+  *n = s.Dl_ket * s.Dr_ket * s.d0 * anc;
+  if (h->nsite == 2) *n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
+  if (*n <= 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg: empty centre tensor");
+  return pcg_check_overlap(ctx, "pcg", dtype, *n, b, x);
+}
 
-}  // namespace
-
-// counts a solve that reached its decision and turns the control block into outputs and status
-static int pcg_report(mpse_ctx* ctx, const PcgCtl& hc, bool masked, double tol, int* iters_host, double* relres_host,
-                      double* lvalue_host) {
-  ++ctx->pcg_stats[mpse_ctx::PS_SOLVES];
-  if (masked) ++ctx->pcg_stats[mpse_ctx::PS_MASKED];
-  ctx->pcg_stats[mpse_ctx::PS_ITERS] += hc.iters;
+// ---- outcomes: a control block as outputs and status (one without a decision is a failure of the engine)
+int pcg_outcome(const PcgCtl& hc, int* iters_host, double* relres_host, double* lvalue_host) {
   if (iters_host) *iters_host = hc.iters;
   if (relres_host) *relres_host = std::sqrt(hc.relres2);
   if (lvalue_host) *lvalue_host = hc.lvalue;
+  return hc.why == PCG_WHY_NONE ? MPSE_ERR_HIP : hc.status;
+}
+// in a batch these belong to the member; any other status fails the call
+bool pcg_members_own(int status) {
+  return status == MPSE_OK || status == MPSE_ERR_NOCONV || status == MPSE_ERR_ARG || status == MPSE_ERR_SHAPE;
+}
+// a single solve that reached its decision: counted, written out, with the message of one that failed
+int pcg_single_end(mpse_ctx* ctx, const PcgCtl& hc, bool masked, double tol, int* iters_host, double* relres_host,
+                   double* lvalue_host) {
+  const int st = pcg_outcome(hc, iters_host, relres_host, lvalue_host);
+  ++ctx->pcg_stats[mpse_ctx::PS_SOLVES];
+  if (masked) ++ctx->pcg_stats[mpse_ctx::PS_MASKED];
+  ctx->pcg_stats[mpse_ctx::PS_ITERS] += hc.iters;
   switch (hc.why) {
     case PCG_WHY_TOL:
     case PCG_WHY_ZERO_B:
       ++ctx->pcg_stats[mpse_ctx::PS_END_TOL];
-      return MPSE_OK;
+      return st;
     case PCG_WHY_MAXITER:
       ++ctx->pcg_stats[mpse_ctx::PS_END_MAXITER];
-      return mpse_fail(ctx, MPSE_ERR_NOCONV, "pcg: |r| / |b| = %.3e after %d iterations (tol %.3e)", std::sqrt(hc.relres2),
-                       hc.iters, tol);
+      return mpse_fail(ctx, st, "pcg: |r| / |b| = %.3e after %d iterations (tol %.3e)", std::sqrt(hc.relres2), hc.iters, tol);
     case PCG_WHY_CURVATURE:
       ++ctx->pcg_stats[mpse_ctx::PS_END_CURVATURE];
-      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: curvature p^H A p <= 0 (or not a number) after %d iterations: the operator "
+      return mpse_fail(ctx, st, "pcg: curvature p^H A p <= 0 (or not a number) after %d iterations: the operator "
                        "is not positive definite", hc.iters);
     case PCG_WHY_DIAG:
-      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: the preconditioner diagonal has entries that are not positive");
+      return mpse_fail(ctx, st, "pcg: the preconditioner diagonal has entries that are not positive");
     default:
-      return mpse_fail(ctx, MPSE_ERR_HIP, "pcg: control block without a decision");
+      return mpse_fail(ctx, st, "pcg: control block without a decision");
   }
 }
 
-// ---- mpse_pcg_batch: launch sets of members with one shape that takes the one-launch two-layer matvec
-namespace {
+// mpse_pcg behind its argument rules (n from pcg_check_member); also a batch member outside the one-launch rule
+int pcg_solve_general(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double shift, const void* diag,
+                      const void* mask, const void* b, void* x, double tol, int max_iter, int64_t n, int* iters_host,
+                      double* relres_host, double* lvalue_host) {
+  wsite_written(ctx, x, size_t(n) * dtype_size(dtype));
+  PcgSingle one(ctx);
+  MPSE_TRY(one.init(dtype, n, 0, shift, diag, mask, b, x, tol, max_iter));
+  PcgGeneral mv{ctx, dtype, h, twolayer, one.m};
+  mv.scope.skip = static_cast<const int*>(one.m.ctl);      // PcgCtl::done
+  PcgCtl hc;
+  PcgTally t;
+  const int st = pcg_drive(ctx, one.set, mv, &hc, &t);
+  ctx->pcg_stats[mpse_ctx::PS_MATVECS] += t.products;
+  ctx->pcg_stats[mpse_ctx::PS_WAITS] += t.waits;
+  if (st != MPSE_OK) return st;      // (allocation or runtime failure: no solve is counted)
+  if (twolayer) ++ctx->pcg_stats[mpse_ctx::PS_TWOLAYER];
+  return pcg_single_end(ctx, hc, mask != nullptr, tol, iters_host, relres_host, lvalue_host);
+}
 
+// ---- mpse_pcg_batch: launch sets of members with one shape that takes the one-launch two-layer matvec
 constexpr int PCGB_MAX = 32;         // members per launch set
 static_assert(mpse_ctx::PIN_BATCH_CTL + PCGB_MAX * PCG_CW < mpse_ctx::PIN_QR_STATUS, "batch slot clear of the QR status word");
 
@@ -603,42 +685,37 @@ bool pcg_batch_eligible(int dtype, const mpse_heff& h, int twolayer, Small2Plan*
   return small2_plan(dtype, s.Dl_ket, s.d0, s.Dr_ket, s.wl, s.wr, plan);
 }
 
-struct PcgSet {
+struct PcgGroup {
   Small2Plan plan;
   std::vector<int> idx;      // member -> position in the caller's arrays
 };
 
-int pcg_batch_set(mpse_ctx* ctx, int dtype, const PcgSet& ps, const mpse_heff* hs, const double* shifts,
+int pcg_batch_set(mpse_ctx* ctx, int dtype, const PcgGroup& ps, const mpse_heff* hs, const double* shifts,
                   const void* const* diags, const void* const* masks, const void* const* bs, void* const* xs, double tol,
-                  int max_iter, std::vector<PcgCtl>& hc) {
+                  int max_iter, PcgCtl* hc) {
   const int B = (int)ps.idx.size();
   const Small2Plan& pl = ps.plan;
   const bool cplx = dtype == MPSE_C128;
   const size_t es = dtype_size(dtype);
   const int64_t n = int64_t(pl.Dl) * pl.d * pl.Dr;
-  const int64_t nd = n * (cplx ? 2 : 1);
-  const int nb = red_blocks(nd), nbq = pl.Dl;
-  // per-member region of the slab (256-byte aligned sections): control block, partials (|b|^2; p^H q; b^H x; r^H z twice),
-  // y, q, r, p, the transposed left environment, the sparse W list
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t o_part = al(sizeof(PcgCtl));
-  const size_t o_vec = o_part + al(size_t(8 * nb + 2 * nbq) * sizeof(double));
-  const size_t vb = al(size_t(n) * es);
-  const size_t o_lt = o_vec + 4 * vb;
-  const size_t o_ptr = o_lt + al(size_t(pl.Dl) * pl.wl * pl.wl * pl.Dl * es);
+  const int nb = red_blocks(n * (cplx ? 2 : 1)), nbq = pl.Dl;
+  // behind the solver's sections of a member: the transposed left environment and the sparse W list of its matvec
+  Layout lay = layout(n, cplx, nb, nbq, 0);
   const size_t cap = size_t(pl.rows) * pl.pitch;
-  const size_t o_idx = o_ptr + al(size_t(pl.rows + 1) * sizeof(int));
-  const size_t o_val = o_idx + al(cap * sizeof(int));
-  const size_t ms = o_val + al(cap * sizeof(double));
+  const size_t o_lt = lay.end;
+  const size_t o_ptr = o_lt + align256(size_t(pl.Dl) * pl.wl * pl.wl * pl.Dl * es);
+  const size_t o_idx = o_ptr + align256(size_t(pl.rows + 1) * sizeof(int));
+  const size_t o_val = o_idx + align256(cap * sizeof(int));
+  lay.stride = o_val + align256(cap * sizeof(double));
   TmpBuf SLAB(ctx), MEM(ctx);
-  MPSE_TRY(SLAB.alloc(size_t(B) * ms));
+  MPSE_TRY(SLAB.alloc(size_t(B) * lay.stride));
   MPSE_TRY(MEM.alloc(size_t(B) * sizeof(Pcg2Member)));
   std::vector<Pcg2Member> mh(B);
   for (int m = 0; m < B; ++m) {
     const int i = ps.idx[m];
-    char* base = SLAB.as<char>() + size_t(m) * ms;
-    double* part = reinterpret_cast<double*>(base + o_part);
+    char* base = SLAB.as<char>() + size_t(m) * lay.stride;
     Pcg2Member& mb = mh[m];
+    pcg_place(mb, base, lay);
     mb.L = static_cast<const double*>(hs[i].L), mb.R = static_cast<const double*>(hs[i].R);
     mb.W = static_cast<const double*>(hs[i].W0);
     mb.Lt = reinterpret_cast<double*>(base + o_lt);
@@ -648,48 +725,19 @@ int pcg_batch_set(mpse_ctx* ctx, int dtype, const PcgSet& ps, const mpse_heff* h
     mb.diag = diags ? static_cast<const double*>(diags[i]) : nullptr;
     mb.b = static_cast<const double*>(bs[i]);
     mb.x = static_cast<double*>(xs[i]);
-    mb.y = reinterpret_cast<double*>(base + o_vec), mb.q = reinterpret_cast<double*>(base + o_vec + vb);
-    mb.r = reinterpret_cast<double*>(base + o_vec + 2 * vb), mb.p = reinterpret_cast<double*>(base + o_vec + 3 * vb);
-    mb.part_bb = part, mb.part_bx = part + 2 * nb, mb.part_rz0 = part + 4 * nb, mb.part_rz1 = part + 6 * nb;
-    mb.part_pq = part + 8 * nb;
-    mb.ctl = base;
     mb.shift = shifts[i];
     wsite_written(ctx, xs[i], size_t(n) * es);
   }
   MPSE_TRY(stage_h2d(ctx, MEM.p, mh.data(), mh.size() * sizeof(Pcg2Member)));
-  const Pcg2Member* mem = MEM.as<const Pcg2Member>();
-  const dim3 grid(nb, 1, B), block(RED_THREADS);
-  const long long nn = (long long)n;
-  const double tol2 = tol * tol;
-  if (max_iter <= 0) max_iter = int(10 * n);      // (n <= 64 * 16 * 64)
-
-  MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_prep_b, grid, block, mem, nn);
-  MPSE_TRY(small2_prep(ctx, dtype, pl, B, mem));
-  MPSE_TRY(small2_apply(ctx, dtype, pl, B, mem, 0));
-  MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_start_b, grid, block, mem, nn, nb);
+  const PcgSet set{dtype, n, nb, nbq, tol, max_iter > 0 ? max_iter : default_max_iter(n), B, mh.data(),
+                   MEM.as<const Pcg2Member>(), lay.stride, "pcg_batch"};
+  PcgSmall2 mv{ctx, pl, set};
+  PcgTally t;
+  const int st = pcg_drive(ctx, set, mv, hc, &t);
   ++ctx->pcg_batch_stats[mpse_ctx::PB_SETS];
-  for (int k = 0;; ++k) {
-    if (k > 0) {
-      MPSE_TRY(small2_apply(ctx, dtype, pl, B, mem, 1));
-      ++ctx->pcg_batch_stats[mpse_ctx::PB_MATVEC_LAUNCHES];
-      MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_step_b, grid, block, mem, nn, nbq, nb, k);
-    }
-    MPSE_LAUNCH_TF_CHK(ctx, cplx, k_pcg_dir_b, grid, block, mem, nn, nb, tol2, k, max_iter);
-    const bool wait_here = (k % PCG_K == PCG_K - 1) || k >= max_iter;
-    if (!wait_here) continue;
-    const PublishAt at = publish_target(ctx, true, mpse_ctx::PIN_BATCH_CTL);
-    if (at.pub) {
-      hipLaunchKernelGGL(k_pcg_publish_b, dim3(1), block, 0, ctx->stream, mem, B, at.pub, at.seq_slot, at.seq);
-      MPSE_HIP(ctx, hipGetLastError());
-    }
-    MPSE_TRY(publish_collect(ctx, at, SLAB.p, ms, B, PCG_CW, mpse_ctx::PIN_BATCH_CTL, hc.data()));
-    ++ctx->pcg_batch_stats[mpse_ctx::PB_WAITS];
-    bool all = true;
-    for (int m = 0; m < B; ++m) all = all && hc[m].done;
-    if (all) break;
-    if (k >= max_iter) return mpse_fail(ctx, MPSE_ERR_HIP, "pcg_batch: no decision at the iteration limit");
-  }
-  return MPSE_OK;
+  ctx->pcg_batch_stats[mpse_ctx::PB_MATVEC_LAUNCHES] += t.products;
+  ctx->pcg_batch_stats[mpse_ctx::PB_WAITS] += t.waits;
+  return st;
 }
 
 }  // namespace
@@ -703,23 +751,21 @@ int mpse_pcg_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff* h, int 
   if (!ctx) return MPSE_ERR_ARG;
   if (count < 0 || (count > 0 && (!h || !shift_host || !b || !x || !status_host)))
     return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_batch: null argument");
-  if (dtype != MPSE_F64 && dtype != MPSE_C128) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_batch: unknown dtype");
+  MPSE_TRY(pcg_check_dtype(ctx, "pcg_batch", dtype));
   if (!(tol >= 0.0)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_batch: tol must be >= 0");
   if (count == 0) return MPSE_OK;
   MPSE_BIND(ctx);
-  const size_t es = dtype_size(dtype);
-  // launch sets: eligible members of one shape, in the order of their first appearance, up to PCGB_MAX each
-  std::vector<PcgSet> sets, open;
+  auto out = [](auto* arr, int i) { return arr ? arr + i : nullptr; };
+  // launch sets: members that pass the rules of mpse_pcg and are eligible, of one shape, in the order of their first
+  // appearance, up to PCGB_MAX each
+  std::vector<PcgGroup> sets, open;
   std::vector<char> grouped(count, 0);
   for (int i = 0; i < count; ++i) {
-    const mpse_heff& hi = h[i];
     Small2Plan pl;
-    if (!b[i] || !x[i] || !hi.L || !hi.R || !hi.W0 || !std::isfinite(shift_host[i])) continue;   // (mpse_pcg refuses it)
-    if (!pcg_batch_eligible(dtype, hi, twolayer, &pl)) continue;
-    const size_t bytes = size_t(pl.Dl) * pl.d * pl.Dr * es;
-    const char *xb = static_cast<const char*>(x[i]), *bb = static_cast<const char*>(b[i]);
-    if (xb < bb + bytes && bb < xb + bytes) continue;
-    PcgSet* tgt = nullptr;
+    int64_t n;
+    if (pcg_check_member(ctx, dtype, &h[i], twolayer, shift_host[i], b[i], x[i], tol, &n) != MPSE_OK) continue;
+    if (!pcg_batch_eligible(dtype, h[i], twolayer, &pl)) continue;
+    PcgGroup* tgt = nullptr;
     for (auto& o : open)
       if (o.plan.Dl == pl.Dl && o.plan.d == pl.d && o.plan.Dr == pl.Dr && o.plan.wl == pl.wl && o.plan.wr == pl.wr) {
         tgt = &o;
@@ -730,37 +776,37 @@ int mpse_pcg_batch(mpse_ctx* ctx, int dtype, int count, const mpse_heff* h, int 
       tgt->idx.clear();
     }
     if (!tgt) {
-      open.push_back(PcgSet{pl, {}});
+      open.push_back(PcgGroup{pl, {}});
       tgt = &open.back();
     }
     tgt->idx.push_back(i);
     grouped[i] = 1;
   }
   for (auto& o : open) sets.push_back(o);
-  for (const PcgSet& ps : sets) {
-    std::vector<PcgCtl> hc(ps.idx.size());
+  PcgCtl hc[PCGB_MAX];
+  for (const PcgGroup& ps : sets) {
     MPSE_TRY(pcg_batch_set(ctx, dtype, ps, h, shift_host, diag_f64, mask_f64, b, x, tol, max_iter, hc));
     for (size_t m = 0; m < ps.idx.size(); ++m) {
       const int i = ps.idx[m];
+      status_host[i] = pcg_outcome(hc[m], out(iters_host, i), out(relres_host, i), out(lvalue_host, i));
+      if (!pcg_members_own(status_host[i])) return mpse_fail(ctx, status_host[i], "pcg_batch: control block without a decision");
       ++ctx->pcg_batch_stats[mpse_ctx::PB_MEMBERS];
-      if (iters_host) iters_host[i] = hc[m].iters;
-      if (relres_host) relres_host[i] = std::sqrt(hc[m].relres2);
-      if (lvalue_host) lvalue_host[i] = hc[m].lvalue;
-      status_host[i] = hc[m].status;
     }
   }
+  // the others one by one as mpse_pcg solves them; one that its rules refuse has that status, the message and zeros
   for (int i = 0; i < count; ++i) {
     if (grouped[i]) continue;
     ++ctx->pcg_batch_stats[mpse_ctx::PB_SINGLE];
-    int it = 0;
-    double rel = 0.0, lv = 0.0;
-    const int st = mpse_pcg(ctx, dtype, &h[i], twolayer, shift_host[i], diag_f64 ? diag_f64[i] : nullptr,
-                            mask_f64 ? mask_f64[i] : nullptr, b[i], x[i], tol, max_iter, &it, &rel, &lv);
-    if (st != MPSE_OK && st != MPSE_ERR_NOCONV && st != MPSE_ERR_ARG && st != MPSE_ERR_SHAPE) return st;
+    int64_t n;
+    int st = pcg_check_member(ctx, dtype, &h[i], twolayer, shift_host[i], b[i], x[i], tol, &n);
+    if (st == MPSE_OK)
+      st = pcg_solve_general(ctx, dtype, &h[i], twolayer, shift_host[i], diag_f64 ? diag_f64[i] : nullptr,
+                             mask_f64 ? mask_f64[i] : nullptr, b[i], x[i], tol, max_iter, n, out(iters_host, i),
+                             out(relres_host, i), out(lvalue_host, i));
+    else
+      pcg_outcome(PcgCtl{}, out(iters_host, i), out(relres_host, i), out(lvalue_host, i));
+    if (!pcg_members_own(st)) return st;
     status_host[i] = st;
-    if (iters_host) iters_host[i] = it;
-    if (relres_host) relres_host[i] = rel;
-    if (lvalue_host) lvalue_host[i] = lv;
   }
   return MPSE_OK;
 }
@@ -784,39 +830,15 @@ int mpse_pcg(mpse_ctx* ctx, int dtype, const mpse_heff* h, int twolayer, double 
              const void* mask_f64, const void* b, void* x, double tol, int max_iter, int* iters_host,
              double* relres_host, double* lvalue_host) {
   if (!ctx) return MPSE_ERR_ARG;
-  if (!h || !b || !x || !h->L || !h->R || !h->W0) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: null argument");
+  int64_t n;
+  MPSE_TRY(pcg_check_member(ctx, dtype, h, twolayer, shift, b, x, tol, &n));
   MPSE_BIND(ctx);
-  if (dtype != MPSE_F64 && dtype != MPSE_C128) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: unknown dtype");
-  if (dtype != MPSE_C128 && (h->l_dtype == MPSE_C128 || h->r_dtype == MPSE_C128 || h->w_dtype == MPSE_C128))
-    return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: real vectors with complex operator parts");
-  if (!(tol >= 0.0) || !std::isfinite(shift)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: tol must be >= 0 and shift finite");
-  const mpse_dims& s = h->dims;
-  if ((s.Dl_bra > 0 && s.Dl_bra != s.Dl_ket) || (s.Dr_bra > 0 && s.Dr_bra != s.Dr_ket))
-    return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg: the projected operator must be square (bra bonds == ket bonds)");
-  if (h->nsite != 1 && h->nsite != 2) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: one- or two-site centres");
-  if (twolayer && (s.danc > 1 || s.danc1 > 1)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: two-layer operators take no ancilla");
-  const int64_t anc = s.danc > 0 ? s.danc : 1;
-  int64_t n = s.Dl_ket * s.Dr_ket * s.d0 * anc;
-  if (h->nsite == 2) n *= s.d1 * (s.danc1 > 0 ? s.danc1 : anc);
-  if (n <= 0) return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg: empty centre tensor");
-  const size_t bytes = size_t(n) * dtype_size(dtype);
-  const char *xb = static_cast<const char*>(x), *bb = static_cast<const char*>(b);
-  if (xb < bb + bytes && bb < xb + bytes) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg: x must not overlap b");
-  if (max_iter <= 0) max_iter = n > (int64_t(1) << 27) ? (1 << 30) : int(10 * n);   // scipy's default, 10 n
-  wsite_written(ctx, x, bytes);
-
-  PcgCtl hc;
-  const double *diag = static_cast<const double*>(diag_f64), *mask = static_cast<const double*>(mask_f64);
-  const int st = pcg_run_dtype(ctx, dtype, h, twolayer, shift, diag, mask, static_cast<const double*>(b),
-                               static_cast<double*>(x), tol, max_iter, n, &hc);
-  if (st != MPSE_OK) return st;      // (allocation or runtime failure: no solve is counted)
-  if (twolayer) ++ctx->pcg_stats[mpse_ctx::PS_TWOLAYER];
-  return pcg_report(ctx, hc, mask_f64 != nullptr, tol, iters_host, relres_host, lvalue_host);
+  return pcg_solve_general(ctx, dtype, h, twolayer, shift, diag_f64, mask_f64, b, x, tol, max_iter, n, iters_host,
+                           relres_host, lvalue_host);
 }
 
 int mpse_pcg_stats(mpse_ctx* ctx, int64_t* counts, int n) {
-  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
-  for (int i = 0; i < n && i < mpse_ctx::PS_COUNT; ++i) counts[i] = ctx->pcg_stats[i];
+  MPSE_TRY(stats_out(ctx, &mpse_ctx::pcg_stats, counts, n));
   if (n > mpse_ctx::PS_COUNT) counts[mpse_ctx::PS_COUNT] = PCG_K;
   return MPSE_OK;
 }
@@ -828,76 +850,46 @@ int mpse_pcg_sum(mpse_ctx* ctx, int dtype, int nterms, const mpse_heff_ft* terms
   if (!terms || !weights_host || !b || !x) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: null argument");
   MPSE_BIND(ctx);
   if (nterms < 1 || nterms > 4) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: 1 to 4 terms, got %d", nterms);
-  if (dtype != MPSE_F64 && dtype != MPSE_C128) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: unknown dtype");
-  if (!(tol >= 0.0) || !std::isfinite(shift)) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: tol must be >= 0 and shift finite");
+  MPSE_TRY(pcg_check_dtype(ctx, "pcg_sum", dtype));
+  MPSE_TRY(pcg_check_tol_shift(ctx, "pcg_sum", tol, shift));
   for (int t = 0; t < nterms; ++t) {
     const mpse_heff_ft& h = terms[t];
     if (!h.L || !h.R || !h.W1 || !h.W2) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: null operator part in term %d", t);
     MPSE_TRY(ft_shape_ok(ctx, h, "pcg_sum"));
     if (!std::isfinite(weights_host[t])) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: weight %d is not finite", t);
-    if (dtype != MPSE_C128 && (h.l_dtype == MPSE_C128 || h.r_dtype == MPSE_C128 || h.w_dtype == MPSE_C128))
-      return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: real vectors with complex operator parts");
+    MPSE_TRY(pcg_check_parts(ctx, "pcg_sum", dtype, h.l_dtype, h.r_dtype, h.w_dtype));
     if (h.Dl != terms[0].Dl || h.Dr != terms[0].Dr || h.d_up != terms[0].d_up || h.d_down != terms[0].d_down)
       return mpse_fail(ctx, MPSE_ERR_SHAPE, "pcg_sum: term %d acts on another centre shape", t);
   }
   const int64_t n = terms[0].Dl * terms[0].d_up * terms[0].d_down * terms[0].Dr;
-  const size_t bytes = size_t(n) * dtype_size(dtype);
-  const char *xb = static_cast<const char*>(x), *bb = static_cast<const char*>(b);
-  if (xb < bb + bytes && bb < xb + bytes) return mpse_fail(ctx, MPSE_ERR_ARG, "pcg_sum: x must not overlap b");
-  if (max_iter <= 0) max_iter = n > (int64_t(1) << 27) ? (1 << 30) : int(10 * n);
-  wsite_written(ctx, x, bytes);
+  MPSE_TRY(pcg_check_overlap(ctx, "pcg_sum", dtype, n, b, x));
+  wsite_written(ctx, x, size_t(n) * dtype_size(dtype));
 
+  PcgSingle one(ctx);
+  MPSE_TRY(one.init(dtype, n, nterms - 1, shift, diag_f64, mask_f64, b, x, tol, max_iter));
+  PcgSummed mv{ctx, one.set, terms};
+  mv.scope.skip = static_cast<const int*>(one.m.ctl);
+  memset(&mv.ts, 0, sizeof(mv.ts));
+  mv.ts.n = nterms;
+  for (int t = 0; t < nterms; ++t) {
+    mv.ts.y[t] = t == 0 ? one.m.y : reinterpret_cast<double*>(one.slab.as<char>() + one.lay.extra_y + size_t(t - 1) * one.lay.vec);
+    mv.ts.w[t] = weights_host[t];
+  }
   PcgCtl hc;
-  const double *diag = static_cast<const double*>(diag_f64), *mask = static_cast<const double*>(mask_f64);
-  const int st = pcg_run_dtype(ctx, dtype, nullptr, 0, shift, diag, mask, static_cast<const double*>(b),
-                               static_cast<double*>(x), tol, max_iter, n, &hc, nterms, terms, weights_host);
+  PcgTally t;
+  const int st = pcg_drive(ctx, one.set, mv, &hc, &t);
+  ctx->pcg_stats[mpse_ctx::PS_MATVECS] += t.products;
+  ctx->pcg_stats[mpse_ctx::PS_WAITS] += t.waits;
+  ctx->pcg_sum_stats[mpse_ctx::PSS_TERM_APPLIES] += t.products * nterms;
+  ctx->pcg_sum_stats[mpse_ctx::PSS_WAITS] += t.waits;
   if (st != MPSE_OK) return st;
   ++ctx->pcg_sum_stats[mpse_ctx::PSS_SOLVES];
   ctx->pcg_sum_stats[mpse_ctx::PSS_ITERS] += hc.iters;
-  return pcg_report(ctx, hc, mask_f64 != nullptr, tol, iters_host, relres_host, lvalue_host);
+  return pcg_single_end(ctx, hc, mask_f64 != nullptr, tol, iters_host, relres_host, lvalue_host);
 }
 
 int mpse_pcg_sum_stats(mpse_ctx* ctx, int64_t* counts, int n) {
   return stats_out(ctx, &mpse_ctx::pcg_sum_stats, counts, n);
-}
-
-int mpse_site_factor_ft(mpse_ctx* ctx, const mpse_heff_ft* h, void* S_f64) {
-  if (!ctx) return MPSE_ERR_ARG;
-  if (!h || !S_f64 || !h->W1 || !h->W2) return mpse_fail(ctx, MPSE_ERR_ARG, "site_factor_ft: null argument");
-  MPSE_BIND(ctx);
-  MPSE_TRY(ft_shape_ok(ctx, *h, "site_factor_ft"));
-  if (h->w_dtype != MPSE_F64) return mpse_fail(ctx, MPSE_ERR_ARG, "site_factor_ft: real MPO sites only");
-  const long long total = h->wl1 * h->wl2 * h->d_up * h->d_down * h->wr1 * h->wr2;
-  hipLaunchKernelGGL(k_site_factor_ft, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ft_shape(*h),
-                     static_cast<const double*>(h->W1), static_cast<const double*>(h->W2), static_cast<double*>(S_f64));
-  MPSE_HIP(ctx, hipGetLastError());
-  return MPSE_OK;
-}
-
-int mpse_diag_ft(mpse_ctx* ctx, const mpse_heff_ft* h, const void* S_f64, double weight, double shift, int accumulate,
-                 void* diag_f64) {
-  if (!ctx) return MPSE_ERR_ARG;
-  if (!h || !S_f64 || !diag_f64 || !h->L || !h->R) return mpse_fail(ctx, MPSE_ERR_ARG, "diag_ft: null argument");
-  MPSE_BIND(ctx);
-  MPSE_TRY(ft_shape_ok(ctx, *h, "diag_ft"));
-  const long long total = h->Dl * h->d_up * h->d_down * h->Dr;
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  const FtShape fs = ft_shape(*h);
-  const double *L = static_cast<const double*>(h->L), *R = static_cast<const double*>(h->R);
-  const double* S = static_cast<const double*>(S_f64);
-  double* dg = static_cast<double*>(diag_f64);
-  const bool lc = h->l_dtype == MPSE_C128, rc = h->r_dtype == MPSE_C128;
-  if (lc && rc)
-    hipLaunchKernelGGL((k_diag_ft<true, true>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
-  else if (lc)
-    hipLaunchKernelGGL((k_diag_ft<true, false>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
-  else if (rc)
-    hipLaunchKernelGGL((k_diag_ft<false, true>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
-  else
-    hipLaunchKernelGGL((k_diag_ft<false, false>), grid, block, 0, ctx->stream, fs, L, R, S, weight, shift, accumulate, dg);
-  MPSE_HIP(ctx, hipGetLastError());
-  if (!accumulate) ++ctx->pcg_sum_stats[mpse_ctx::PSS_DIAGS];
-  return MPSE_OK;
 }
 
 }  // extern "C"

@@ -784,17 +784,25 @@ class Engine:
         ``diag`` (float64 device tensor, ``shift`` included) the preconditioner, ``mask`` (float64 0/1) the
         symmetry-allowed entries.  Returns ``PcgResult(status, iters, relres, lvalue)``; status 3 (not converged
         within ``max_iter``) is returned, any other failure raises unless ``check`` is False."""
-        n = int(np.prod(hop.cshape))
-        assert b.size == n and x.size == n and b.dtype == x.dtype, (b.shape, x.shape, hop.cshape)
-        assert diag is None or (diag.size == n and diag.dtype == np.float64)
-        assert mask is None or (mask.size == n and mask.dtype == np.float64)
+        self._pcg_operands(int(np.prod(hop.cshape)), b, x, diag, mask)
         it, rel, lv = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
         st = self.lib.mpse_pcg(self.ctx, x.code, C.byref(hop.heff), int(hop.twolayer), float(shift),
                                None if diag is None else diag.ptr, None if mask is None else mask.ptr, b.ptr, x.ptr,
                                float(tol), int(max_iter), C.byref(it), C.byref(rel), C.byref(lv))
+        return self._pcg_result(st, it.value, rel.value, lv.value, check)
+
+    @staticmethod
+    def _pcg_operands(n, b, x, diag, mask):
+        """the operands of one conjugate-gradient system against its length ``n``"""
+        assert b.size == n and x.size == n and b.dtype == x.dtype, (b.shape, x.shape, n)
+        assert diag is None or (diag.size == n and diag.dtype == np.float64)
+        assert mask is None or (mask.size == n and mask.dtype == np.float64)
+
+    def _pcg_result(self, st, iters, relres, lvalue, check=False):
+        """``PcgResult`` from the outputs of a solve; ``check``: any status but 0 and 3 (not converged) raises"""
         if check and st not in (0, 3):
             self._check(st)
-        return PcgResult(int(st), it.value, rel.value, lv.value)
+        return PcgResult(int(st), int(iters), float(relres), float(lvalue))
 
     PCG_BATCH_STATS = ("batched_members", "single_members", "launch_sets", "matvec_launches", "host_waits",
                        "set_limit")
@@ -820,11 +828,8 @@ class Engine:
         assert len(diags) == cnt and len(masks) == cnt
         code, two = xs[0].code, bool(hops[0].twolayer)
         for hop, b, x, dg, mk in zip(hops, bs, xs, diags, masks):
-            n = int(np.prod(hop.cshape))
-            assert bool(hop.twolayer) == two and x.code == code and b.dtype == x.dtype
-            assert b.size == n and x.size == n, (b.shape, x.shape, hop.cshape)
-            assert dg is None or (dg.size == n and dg.dtype == np.float64)
-            assert mk is None or (mk.size == n and mk.dtype == np.float64)
+            assert bool(hop.twolayer) == two and x.code == code
+            self._pcg_operands(int(np.prod(hop.cshape)), b, x, dg, mk)
         harr = (mpse_heff * cnt)(*[hop.heff for hop in hops])
         ptrs = lambda ts: (C.c_void_p * cnt)(*[None if t is None else t.ptr for t in ts])
         sh = (C.c_double * cnt)(*[float(v) for v in shifts])
@@ -832,7 +837,7 @@ class Engine:
         rel, lv = (C.c_double * cnt)(), (C.c_double * cnt)()
         self._check(self.lib.mpse_pcg_batch(self.ctx, code, cnt, harr, int(two), sh, ptrs(diags), ptrs(masks), ptrs(bs),
                                             ptrs(xs), float(tol), int(max_iter), st, it, rel, lv))
-        return [PcgResult(int(st[i]), int(it[i]), float(rel[i]), float(lv[i])) for i in range(cnt)]
+        return [self._pcg_result(st[i], it[i], rel[i], lv[i]) for i in range(cnt)]
 
     # -- two MPO layers on a two-leg centre: the terms of the finite-temperature correction-vector operator
     def ft_term(self, w1, w2, leg1, leg2, trans1, trans2, shape, L=None, R=None):
@@ -897,17 +902,12 @@ class Engine:
         nt = len(terms)
         arr = (mpse_heff_ft * nt)(*terms)
         w = (C.c_double * nt)(*[float(v) for v in weights])
-        n = x.size
-        assert b.size == n and b.dtype == x.dtype
-        assert diag is None or (diag.size == n and diag.dtype == np.float64)
-        assert mask is None or (mask.size == n and mask.dtype == np.float64)
+        self._pcg_operands(x.size, b, x, diag, mask)
         it, rel, lv = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
         st = self.lib.mpse_pcg_sum(self.ctx, x.code, nt, arr, w, float(shift), None if diag is None else diag.ptr,
                                    None if mask is None else mask.ptr, b.ptr, x.ptr, float(tol), int(max_iter),
                                    C.byref(it), C.byref(rel), C.byref(lv))
-        if check and st not in (0, 3):
-            self._check(st)
-        return PcgResult(int(st), it.value, rel.value, lv.value)
+        return self._pcg_result(st, it.value, rel.value, lv.value, check)
 
     # -- overlap of two chains
     OVERLAP_STATS = ("chain_kernel", "enqueued", "sites")

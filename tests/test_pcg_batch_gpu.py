@@ -148,7 +148,9 @@ def test_exact_every_member(eng, dims, w, real_ok, masked, cplx):
 
 
 def test_handed_to_pcg_bitwise(eng):
-    """a shape outside the rule, a one-layer member and a two-site member run through mpse_pcg: bitwise Engine.pcg"""
+    """a shape outside the rule, a one-layer member and a two-site member run as mpse_pcg runs them: bitwise Engine.pcg,
+    and every counter of ``pcg_stats`` moves as it does over that call"""
+    moved = lambda a, b: {k: b[k] - a[k] for k in b if k != "wait_interval"}       # (wait_interval is no count)
     outside = Member(eng, 5, (5, SM2_DMAX + 1, 4), 3, False, True)
     cases = [(outside.p, outside.b, outside.x0, outside.diag)]
     for dims, two in (((9, 5, 11), False), ((6, 3, 4, 5), True)):
@@ -159,12 +161,16 @@ def test_handed_to_pcg_bitwise(eng):
         dev = lambda: (eng.asdevice(b.reshape(p.shape)), eng.asdevice(x0.reshape(p.shape)),
                        eng.asdevice(dg.reshape(p.shape)))
         db, dx, dd = dev()
+        c0 = eng.pcg_stats()
         one = eng.pcg(p.hop, db, dx, diag=dd, mask=p.dmask, shift=p.shift, tol=TOL)
+        c1 = eng.pcg_stats()
         db2, dx2, dd2 = dev()
         s0 = eng.pcg_batch_stats()
         got = eng.pcg_batch([p.hop], [db2], [dx2], [dd2], [p.dmask], [p.shift], TOL)[0]
         s1 = eng.pcg_batch_stats()
+        c2 = eng.pcg_stats()
         assert s1["single_members"] - s0["single_members"] == 1 and s1["batched_members"] == s0["batched_members"]
+        assert moved(c1, c2) == moved(c0, c1) and moved(c0, c1)["solves"] == 1
         assert tuple(got) == tuple(one) and one.status == OK
         assert np.array_equal(dx.to_host(), dx2.to_host())
 
