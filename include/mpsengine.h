@@ -977,6 +977,22 @@ int mpse_block_svd_full(mpse_ctx* ctx, int dtype, const void* coef, int64_t nrow
                         const int64_t* col_idx_host, const int64_t* col_off_host, const int64_t* extra_host,
                         void* U, int64_t KU, void* Vt, int64_t KV, double* S_host, int64_t K);
 
+/* Which block step ran the Jacobi sweeps of the mpse_block_svd / mpse_block_svd_full calls of this context, cumulative:
+ * the column kernel (pairs of 8-column blocks in LDS) takes a call whose widest block fits the dynamic LDS the runtime
+ * grants it - 512 bytes per complex column, 256 per real one: 300 / 600 columns at 150 KB - the Gram-matrix kernel every
+ * other call and, with MPSE_SVD_GRAM=2 in the environment, every call.  counts[i], i < n, receives (zeros beyond the
+ * last entry)
+ *    0  decompositions that reached the sweeps (a call refused for its arguments or shapes counts nothing)
+ *    1  of those, sweeps run by the column kernel
+ *    2  of those, sweeps run by the Gram kernel
+ *    3  sweeps
+ *    4  launches of the two sweep kernels
+ *    5  not a count: the row slabs per pair of column blocks (gram_R) of the most recent Gram decomposition, 0: none yet
+ *    6  not a count: bytes of dynamic LDS the column kernel may use in this process (150 KB, or 64 KB where the runtime
+ *       refused the attribute); 0 before the first decomposition of the context
+ * Diagnostics for tests; no device work.  No reference counterpart. */
+int mpse_block_svd_stats(mpse_ctx* ctx, int64_t* counts, int n);
+
 /* out[:, j] = in[:, cols_host[j]] * scale_host[j]  (column gather of a row-major matrix,
  * replaces the per-column copies of mps/lib.py:303-316 select_basis; scale_host may be NULL). */
 int mpse_gather_cols(mpse_ctx* ctx, int dtype, void* out, const void* in, int64_t nrow, int64_t ncol_in,

@@ -148,6 +148,10 @@ struct mpse_ctx {
   long long gemm_paths[GP_COUNT] = {0};
   // mpse_block_qr: decompositions that took the Cholesky-QR path / that fell back from it to Householder
   long long qr_chol_calls = 0, qr_chol_fallbacks = 0, qr_calls = 0;
+  // mpse_block_svd[_full]: which block step ran the sweeps (mpse_block_svd_stats; the order of include/mpsengine.h).
+  // The last two are no counts: gram_R of the latest Gram decomposition, the dynamic LDS granted to the column kernel
+  enum SvdStat { SV_DECOMP, SV_COLUMN, SV_GRAM, SV_SWEEPS, SV_LAUNCHES, SV_GRAM_R, SV_COL_LDS, SV_COUNT };
+  long long svd_stats[SV_COUNT] = {0};
   // optimistic mode of the Cholesky-QR path (mpse_block_qr_optimistic): breakdowns raise this sticky device word
   // instead of being read back per decomposition
   bool qr_optimistic = false;

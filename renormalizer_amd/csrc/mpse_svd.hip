@@ -111,7 +111,8 @@ __global__ void k_sweep_end(int nblk, int* nrot, int* done) {
 // for 256 columns, each of them dozens of dependent rotations deep (a launch per rotation step costs ~6 us on this
 // part whatever it does).  The pairs INSIDE a block are rotated in the first launch of a sweep only (full inner round
 // robin over the 2 JB_COLS columns); the other launches rotate the JB_COLS x JB_COLS cross pairs (JB_COLS inner
-// steps).  Needs 2 x 2 JB_COLS x nn elements of LDS: nn <= 256 (complex) / 512 (real).
+// steps).  Needs 2 x 2 JB_COLS x nn elements of LDS (512 bytes per complex column, 256 per real one): whatever fits the
+// dynamic LDS the runtime grants - nn <= 300 (complex) / 600 (real) at 150 KB, 128 / 256 at the default 64 KB.
 constexpr int JB_COLS = 8;
 constexpr int JB_KEEP = 4;          // x 64 rows of a column pair kept in registers through an inner step
 template <bool CPLX>
@@ -284,7 +285,8 @@ __global__ __launch_bounds__(64 * JB_COLS) void k_jacobi_block(double* ws, doubl
 
 // Block step on the Gram matrix (round 6): a pair of JG-column blocks of X and V is rotated through its 2 JG x 2 JG Gram
 // matrix instead of through its columns - the step for blocks too wide for the column kernel above (its LDS holds
-// 4 JB_COLS columns of nn rows: nn <= 256 complex), where the alternative was one launch per rotation step.
+// 4 JB_COLS columns of nn rows: nn <= 300 complex / 600 real in 150 KB), where the alternative was one launch per
+// rotation step.
 //   1. G = Y^H Y of the 2 JG = 32 columns Y of the pair, on MFMA straight from memory (rows dealt to the 4 waves, partial
 //      sums added through LDS in a fixed order).  Only the first launch of a sweep forms all three tiles: the diagonal
 //      tiles of a column block travel with it (dgin / dgout: what the rotations of the previous launch made of them),
@@ -954,8 +956,9 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
     MPSE_HIP(ctx, hipGetLastError());
   }
   // Which block step runs the sweeps: the column kernel in LDS (k_jacobi_block) where the column blocks of X and V fit
-  // (nn <= 256 complex, 512 real), the Gram kernel (k_jacobi_gram) for wider blocks.  MPSE_SVD_GRAM=2: the Gram kernel
-  // for every size (read per call: tests switch it).
+  // the granted dynamic LDS (4 JB_COLS columns of the widest block: nn <= 300 complex, 600 real at 150 KB; 128 / 256
+  // where the runtime keeps the kernel to 64 KB), the Gram kernel (k_jacobi_gram) for wider blocks.  MPSE_SVD_GRAM=2:
+  // the Gram kernel for every size (read per call: tests switch it).  mpse_block_svd_stats says which one ran.
   const bool gram_all = [] {
     const char* e = getenv("MPSE_SVD_GRAM");
     return e && atoi(e) >= 2;
@@ -992,8 +995,10 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
       (void)hipGetLastError();
       return a == hipSuccess && b == hipSuccess;
     }();
-    const bool cols_fit = blk_lds <= (lds_attr ? size_t(150) : size_t(64)) * 1024;
+    const size_t col_lds = (lds_attr ? size_t(150) : size_t(64)) * 1024;
+    const bool cols_fit = blk_lds <= col_lds;
     const bool use_gram = gram_all || !cols_fit;
+    ctx->svd_stats[mpse_ctx::SV_COL_LDS] = (long long)col_lds;
     if (use_gram && !gram_attr)
       return mpse_fail(ctx, MPSE_ERR_HIP, "block_svd: the runtime refused %zu bytes of dynamic LDS to the Gram step",
                        gram_lds);
@@ -1013,7 +1018,10 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
       while (gram_R > 1 && (long long)gram_R * pairs * nblk > 1024) gram_R >>= 1;
       if (gram_R < 1) gram_R = 1;
       if (gram_R > 16) gram_R = 16;
+      ctx->svd_stats[mpse_ctx::SV_GRAM_R] = gram_R;
     }
+    ++ctx->svd_stats[mpse_ctx::SV_DECOMP];
+    ++ctx->svd_stats[use_gram ? mpse_ctx::SV_GRAM : mpse_ctx::SV_COLUMN];
     for (int sweep = 0; sweep < 60 && !all; ++sweep) {
       if (use_gram) {
         const int nbmax = ((maxnn + JG - 1) / JG + 1) & ~1;
@@ -1024,11 +1032,13 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
                              (const int*)done);
           cur ^= 1;
         }
+        ctx->svd_stats[mpse_ctx::SV_LAUNCHES] += nbmax - 1;
       } else {
         const int nbmax = ((maxnn + JB_COLS - 1) / JB_COLS + 1) & ~1;
         for (int step = 0; step < nbmax - 1; ++step)
           hipLaunchKernelGGL((k_jacobi_block<CPLX>), dim3(nbmax / 2, nblk), dim3(64 * JB_COLS), blk_lds, ctx->stream, xs,
                              vm, dsq, step, (const double*)null2, nrot, (const int*)done);
+        ctx->svd_stats[mpse_ctx::SV_LAUNCHES] += nbmax - 1;
       }
       hipLaunchKernelGGL(k_sweep_end, dim3((nblk + 255) / 256), dim3(256), 0, ctx->stream, nblk, nrot, done);
       MPSE_HIP(ctx, hipGetLastError());
@@ -1042,6 +1052,7 @@ int block_svd_batched(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t nco
       all = true;
       for (int b = 0; b < nblk; ++b) all = all && hdone[b];
       ++sweeps_done;
+      ++ctx->svd_stats[mpse_ctx::SV_SWEEPS];
     }
     if (!all) return mpse_fail(ctx, MPSE_ERR_NOCONV, "block_svd: Jacobi did not converge within 60 sweeps");
   }
@@ -1142,6 +1153,10 @@ int block_svd_impl(mpse_ctx* ctx, const void* coef, int64_t nrow, int64_t ncol, 
 }
 
 }  // namespace
+
+extern "C" int mpse_block_svd_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  return stats_out(ctx, &mpse_ctx::svd_stats, counts, n);
+}
 
 extern "C" int mpse_block_svd_full(mpse_ctx* ctx, int dtype, const void* coef, int64_t nrow, int64_t ncol, int nblocks,
                                    const int64_t* row_idx_host, const int64_t* row_off_host,

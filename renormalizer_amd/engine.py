@@ -219,6 +219,7 @@ _SIGNATURES = {
                        C.c_void_p, C.c_void_p, _dblp, C.c_int64],
     "mpse_block_svd_full": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, _i64p, _i64p, _i64p, _i64p,
                             _i64p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _dblp, C.c_int64],
+    "mpse_block_svd_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_gather_cols": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _i64p, _dblp, C.c_int64],
     "mpse_gather_rows": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _dblp, C.c_int64],
     "mpse_tda_create": [C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p), C.POINTER(C.c_int)] * 4 +
@@ -1204,6 +1205,15 @@ class Engine:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(self.lib.mpse_block_qr_stats(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    SVD_STATS = ("decompositions", "column", "gram", "sweeps", "launches", "gram_R", "column_lds")
+
+    def block_svd_stats(self):
+        """{name: count}: which block step ran the Jacobi sweeps of the block SVDs of this context, cumulative
+        (``mpse_block_svd_stats``; the names follow the order of include/mpsengine.h).  ``gram_R`` (row slabs of the
+        most recent Gram decomposition) and ``column_lds`` (bytes of dynamic LDS granted to the column kernel, 0 before
+        the first decomposition) are no counts."""
+        return self._stats_dict(self.lib.mpse_block_svd_stats, self.SVD_STATS)
 
     def heff_fused_stats(self):
         """(bond-matrix, two-level-site) effective-Hamiltonian applications that ran as the fused launch."""

@@ -817,19 +817,30 @@ def test_block_svd_shapes_and_rank(eng, cplx):
 
 @pytest.mark.parametrize("cplx", [False, True])
 def test_block_svd_wide_blocks_gram_step(eng, cplx, monkeypatch):
-    """Blocks wider than the column kernel's LDS holds (more than 256 complex / 512 real columns) run their sweeps through
-    the Gram-matrix block step (``k_jacobi_gram``: MFMA Gram tile, two-sided rotations on the 32 x 32 matrix, MFMA update
-    of the rows): values against LAPACK, both factors isometries, reconstruction - for a graded spectrum with a rank
-    deficit, two blocks of different width in one call (the narrower one idles through the extra steps), and
-    ``MPSE_SVD_GRAM=2`` sending EVERY size of ``test_block_svd_shapes_and_rank`` and the captured extreme-range input
-    through the same kernel (column counts that are no multiple of 16, single columns, a block narrower than one tile)."""
+    """Wide blocks and the Gram-matrix block step (``k_jacobi_gram``: MFMA Gram tile, two-sided rotations on the 32 x 32
+    matrix, MFMA update of the rows): values against LAPACK, both factors isometries, reconstruction.  The column kernel
+    takes whatever fits the dynamic LDS it is granted - 512 bytes per complex column, 256 per real one: up to 300
+    complex / 600 real columns at 150 KB - so the first two inputs (300 / 530 columns, a graded spectrum with a rank
+    deficit; then two blocks of different width in one call, the narrower one idling through the extra steps) run in the
+    COLUMN kernel at its widest, asserted from ``mpse_block_svd_stats`` when the runtime granted the 150 KB.  Then
+    ``MPSE_SVD_GRAM=2`` sends EVERY size of ``test_block_svd_shapes_and_rank`` through the Gram kernel (column counts
+    that are no multiple of 16, single columns, a block narrower than one tile; counter asserted for every call).  The
+    Gram kernel at the widths it is chosen for without the switch: tests/test_block_svd_gpu.py."""
     rng = np.random.default_rng(12)
 
-    def check(a, qnl, qnr, tol=1e-13, tol_o=1e-12):
+    def check(a, qnl, qnr, tol=1e-13, tol_o=1e-12, path=None):
         # (tol: 1e-13 up to ~250 columns as in the other tests of the decomposition; the wide blocks - 300 / 530 columns,
         # eleven sweeps of up to 530 rotations per column - are held to 1e-12: the column kernels give the same figures
         # on these inputs, 3.4e-13 at 530 columns)
+        c0 = eng.block_svd_stats()
         u, s, vt, blocks = dev_block_svd(eng, a, qnl, qnr, np.array([0]))
+        c1 = eng.block_svd_stats()
+        assert c1["decompositions"] - c0["decompositions"] == 1 and c1["launches"] > c0["launches"]
+        if path is None and c1["column_lds"] == 150 * 1024:
+            path = "column"
+        if path is not None:
+            other = "gram" if path == "column" else "column"
+            assert (c1[path] - c0[path], c1[other] - c0[other]) == (1, 0), (path, c0, c1)
         sref = np.concatenate([np.linalg.svd(a[np.ix_(ls, rs)], compute_uv=False) for _, _, ls, rs in blocks])
         assert np.abs(np.sort(s)[::-1] - np.sort(sref)[::-1]).max() < tol * sref.max()
         assert _relerr((u * s) @ vt, a) < tol
@@ -865,7 +876,7 @@ def test_block_svd_wide_blocks_gram_step(eng, cplx, monkeypatch):
             c = (u0 * s0) @ v0
         tall = max(mm, nn) > 4096                         # (5000 rows: see test_block_svd_shapes_and_rank)
         check(c, np.zeros((mm, 1), dtype=int), np.zeros((nn, 1), dtype=int), tol=2e-12 if tall else 1e-13,
-              tol_o=2e-12 if tall else 1e-12)
+              tol_o=2e-12 if tall else 1e-12, path="gram")
 
 
 @pytest.mark.parametrize("cplx", [False, True])
