@@ -951,6 +951,23 @@ int mpse_block_qr_check(mpse_ctx* ctx, int* tripped);
  * (diagnostics; bench.py reports the rate).  Either pointer may be NULL. */
 int mpse_block_qr_pass_stats(mpse_ctx* ctx, int64_t* blocks, int64_t* two_pass);
 
+/* Which decisions the Cholesky-QR path of mpse_block_qr took on this context, cumulative.  Per call: the whole call is
+ * factorised by the right-looking Cholesky kernel when its widest block has at most 160 columns, by the left-looking one
+ * otherwise.  Per block, on the device: pass 2 is the last pass when n max|G - I| <= 0.1 (as above); the factor of pass 2
+ * or 3 is the first-order one, R = I + striu(E) + diag(E) / 2 with E = G - I, when n max|G - I| <= 1e-9 (the triangular
+ * solve is then a product).  counts[i], i < n, receives (zeros beyond the last entry)
+ *    0  decompositions tried by the Cholesky-QR kernels (chol_calls of mpse_block_qr_stats)
+ *    1  of those, factorised by the right-looking kernel
+ *    2  of those, factorised by the left-looking kernel
+ *    3  of those, redone by the Householder kernels (chol_fallbacks of mpse_block_qr_stats)
+ *    4  blocks factorised (blocks of mpse_block_qr_pass_stats; the blocks of a decomposition that was redone count)
+ *    5  blocks that ended after two passes (two_pass of mpse_block_qr_pass_stats)
+ *    6  two-pass blocks whose pass-2 factor was the first-order one
+ *    7  three-pass blocks whose pass-3 factor was the first-order one
+ * Entries 0 - 3 are host counters, 4 - 7 device words summed by the scatter kernel of each decomposition and read here
+ * (synchronous).  Diagnostics for tests (tests/test_block_qr_chol_gpu.py); no reference counterpart. */
+int mpse_block_qr_path_stats(mpse_ctx* ctx, int64_t* counts, int n);
+
 /* Which kernels mpse_block_qr uses on this context: 0 Householder only (the column-by-column elimination of LAPACK's
  * geqrf, mps/svd_qn.py:171-185 calls scipy.linalg.qr: the SAME isometry as the reference up to rounding, also in the
  * directions of numerically zero singular values, where a QR factorisation is not unique), 1 Cholesky-QR for tall blocks

@@ -887,12 +887,21 @@ __global__ void k_cq_scatter(double* U, double* Vt, const double* __restrict__ w
   const CqBlk B = blks[blockIdx.y];
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
     dstat[0] = (double)status[0];
-    int n2 = 0;                                      // blocks that ended after two passes (diagnostics)
-    for (int b = 0; b < (int)gridDim.y; ++b) n2 += done[b] != 0;
+    // blocks that ended after two passes, and whose last factor was the first-order one: status[1 + b] is the mode of
+    // pass 2 for a two-pass block (pass 3 returned at once for it), of pass 3 for the others (diagnostics)
+    int n2 = 0, f2 = 0, f3 = 0;
+    for (int b = 0; b < (int)gridDim.y; ++b) {
+      const int d = done[b] != 0, f = status[1 + b] != 0;
+      n2 += d;
+      f2 += d & f;
+      f3 += (d ^ 1) & f;
+    }
     dstat[1] = (double)n2;
-    if (words) {       // the context's running counts (mpse_block_qr_pass_stats): blocks factorised, of them in two passes
+    if (words) {       // the context's running counts (mpse_block_qr_pass_stats, mpse_block_qr_path_stats)
       atomicAdd(words + 2, (int)gridDim.y);
       atomicAdd(words + 3, n2);
+      atomicAdd(words + 4, f2);
+      atomicAdd(words + 5, f3);
     }
   }
   const double* q = ws + B.ws_off * E;
@@ -1008,6 +1017,7 @@ int cholqr_run(mpse_ctx* ctx, double* ws, const QrBlk* blks, int nblk, const lon
     return e ? atof(e) : 0.1;
   }();
   const double* racc = nullptr;
+  ++(max_P <= 10 ? ctx->qr_chol_rl : ctx->qr_chol_ll);
   for (int pass = 1; pass <= 3; ++pass) {
     double* Rcur = Rb[pass - 1];
     const int* dn = pass == 3 ? done : nullptr;
@@ -1015,7 +1025,7 @@ int cholqr_run(mpse_ctx* ctx, double* ws, const QrBlk* blks, int nblk, const lon
                        status, pass == 1 ? 2 * nblk + 1 : 0, dn);
     hipLaunchKernelGGL((k_cq_reduce<CPLX>), dim3(max_T, nblk), dim3(256), 0, ctx->stream, (const double*)part, G, tinfo, dblk,
                        dn);
-    if (max_P <= 10)
+    if (max_P <= 10)      // (which of the two: mpse_block_qr_path_stats)
       hipLaunchKernelGGL((k_cq_chol_rl<CPLX>), dim3(nblk), dim3(512), 0, ctx->stream, (const double*)G,
                          (const double*)tinfo, Rcur, dblk, status, pass, gflag, nblk, theta, tau);
     else

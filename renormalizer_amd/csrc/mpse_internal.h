@@ -148,6 +148,8 @@ struct mpse_ctx {
   long long gemm_paths[GP_COUNT] = {0};
   // mpse_block_qr: decompositions that took the Cholesky-QR path / that fell back from it to Householder
   long long qr_chol_calls = 0, qr_chol_fallbacks = 0, qr_calls = 0;
+  // of qr_chol_calls: factorised by the right-looking / the left-looking Cholesky kernel (mpse_block_qr_path_stats)
+  long long qr_chol_rl = 0, qr_chol_ll = 0;
   // mpse_block_svd[_full]: which block step ran the sweeps (mpse_block_svd_stats; the order of include/mpsengine.h).
   // The last two are no counts: gram_R of the latest Gram decomposition, the dynamic LDS granted to the column kernel
   enum SvdStat { SV_DECOMP, SV_COLUMN, SV_GRAM, SV_SWEEPS, SV_LAUNCHES, SV_GRAM_R, SV_COL_LDS, SV_COUNT };
@@ -156,8 +158,11 @@ struct mpse_ctx {
   // instead of being read back per decomposition
   bool qr_optimistic = false;
   int qr_scheme = -1;            // mpse_block_qr_scheme: -1 environment default, 0 Householder only, 1 default rule, 2 every eligible shape
-  // four device words of the block QR: [0] sticky breakdown flag of the optimistic mode, [2] blocks factorised by the
-  // Cholesky-QR kernels, [3] of them finished after two passes (mpse_block_qr_pass_stats); allocated by qr_words()
+  // device words of the block QR (QR_WORDS of them): [0] sticky breakdown flag of the optimistic mode, [2] blocks
+  // factorised by the Cholesky-QR kernels, [3] of them finished after two passes (mpse_block_qr_pass_stats), [4] two-pass
+  // blocks whose pass-2 factor was the first-order one, [5] three-pass blocks whose pass-3 factor was
+  // (mpse_block_qr_path_stats); allocated by qr_words()
+  static constexpr int QR_WORDS = 8;
   int* qr_words_dev = nullptr;
   // mpse_expm_lanczos_batch: members solved by the batched kernels / through the single solve (mpse_expm_lanczos_batch_stats)
   long long lz_batch_members = 0, lz_batch_single = 0;

@@ -92,9 +92,9 @@ __global__ void k_scatter_blocks(double* U, double* Vt, const double* __restrict
 int qr_words(mpse_ctx* ctx) {
   if (ctx->qr_words_dev) return MPSE_OK;
   void* p = nullptr;
-  MPSE_TRY(mpse_malloc(ctx, 16, &p));
+  MPSE_TRY(mpse_malloc(ctx, mpse_ctx::QR_WORDS * sizeof(int), &p));
   ctx->qr_words_dev = static_cast<int*>(p);
-  return device_zero(ctx, ctx->qr_words_dev, 16);
+  return device_zero(ctx, ctx->qr_words_dev, mpse_ctx::QR_WORDS * sizeof(int));
 }
 
 namespace {
@@ -288,6 +288,16 @@ int mpse_block_qr_pass_stats(mpse_ctx* ctx, int64_t* blocks, int64_t* two_pass) 
   if (ctx->qr_words_dev) MPSE_TRY(mpse_memcpy_d2h(ctx, v, ctx->qr_words_dev, 16));
   if (blocks) *blocks = v[2];
   if (two_pass) *two_pass = v[3];
+  return MPSE_OK;
+}
+
+int mpse_block_qr_path_stats(mpse_ctx* ctx, int64_t* counts, int n) {
+  if (!ctx || n < 0 || (n > 0 && !counts)) return MPSE_ERR_ARG;
+  MPSE_BIND(ctx);
+  int v[mpse_ctx::QR_WORDS] = {0};
+  if (ctx->qr_words_dev) MPSE_TRY(mpse_memcpy_d2h(ctx, v, ctx->qr_words_dev, sizeof(v)));
+  const long long all[8] = {ctx->qr_chol_calls, ctx->qr_chol_rl, ctx->qr_chol_ll, ctx->qr_chol_fallbacks, v[2], v[3], v[4], v[5]};
+  for (int i = 0; i < n; ++i) counts[i] = i < 8 ? all[i] : 0;
   return MPSE_OK;
 }
 

@@ -113,6 +113,7 @@ _SIGNATURES = {
     "mpse_block_qr_scheme": [C.c_void_p, C.c_int],
     "mpse_block_qr_check": [C.c_void_p, C.POINTER(C.c_int)],
     "mpse_block_qr_pass_stats": [C.c_void_p] + [C.POINTER(C.c_int64)] * 2,
+    "mpse_block_qr_path_stats": [C.c_void_p, _i64p, C.c_int],
     "mpse_malloc": [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)],
     "mpse_free": [C.c_void_p, C.c_void_p],
     "mpse_pool_trim": [C.c_void_p],
@@ -1266,6 +1267,16 @@ class Engine:
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self.lib.mpse_block_qr_pass_stats(self.ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    QR_PATHS = ("chol_calls", "right_looking", "left_looking", "fallbacks", "blocks", "two_pass", "first_order_pass2",
+                "first_order_pass3")
+
+    def block_qr_path_stats(self, since=None):
+        """{name: count}: the decisions of the Cholesky-QR path of this context, cumulative (``mpse_block_qr_path_stats``;
+        the names follow the order of include/mpsengine.h) - or, with ``since`` (an earlier return value), the counts
+        since then.  Synchronous: four of the counters live on the device."""
+        now = self._stats_dict(self.lib.mpse_block_qr_path_stats, self.QR_PATHS)
+        return now if since is None else {k: now[k] - since[k] for k in self.QR_PATHS}
 
     def prof_get(self):
         """{variant: dict(ms, flops, bytes, launches)} for the contraction kernel variants."""

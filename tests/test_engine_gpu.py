@@ -563,13 +563,19 @@ def _with_cond(rng, m, n, cond, cplx, rank=None):
 
 @pytest.mark.parametrize("cplx", [True, False])
 def test_block_qr_cholesky_path(eng, cplx):
-    """The Cholesky-QR kernels of mpse_block_qr (mpse_cholqr.hip; default for tall blocks of 96 - 256 columns, here also
-    forced onto every shape they support, mpse_block_qr_scheme 2) against the same contract as the Householder path:
-    reconstruction and isometry to 1e-13, exactly triangular other factor - for two-block layouts like the headline's
-    sites, condition numbers up to 1e12 (three real passes), a well-conditioned input (first-order third pass), odd
-    sizes and column counts on both sides of the right-looking / left-looking Cholesky kernels (<= 160 / <= 256 columns);
-    an exactly zero column has to raise the device flag and come back through the Householder kernels; rank-deficient
-    and kappa = 1e18 inputs may do either (the result is held to the same contract).
+    """The Cholesky-QR kernels of mpse_block_qr (mpse_cholqr.hip; the default for a call whose blocks are all at least as
+    tall as wide and at most 256 columns wide, the tallest of at least 256 rows and the widest of at least 96 columns;
+    here also forced onto every shape they support, mpse_block_qr_scheme 2) against the same contract as the
+    Householder path: reconstruction and isometry to 1e-13, exactly triangular other factor - for two-block layouts
+    like the headline's sites, odd sizes and column counts on both sides of the right-looking / left-looking Cholesky
+    kernels (<= 160 / <= 256 columns).  What the blocks decide on the device, as mpse_block_qr_path_stats counts it
+    (scheme 2, both dtypes): condition 1e4 - 1e7 - two passes, plain factor at pass 2; condition 1e8 - three passes,
+    first-order factor at pass 3; condition 1e12 - three passes, plain factor at pass 3; the well-conditioned input
+    (condition 3) - TWO passes with the first-order factor at pass 2, no third pass at all; 182 and 256 columns go
+    through the left-looking kernel, the other calls through the right-looking one.  This test asserts none of that
+    (tests/test_block_qr_chol_gpu.py does, on blocks built to stay clear of the thresholds).  An exactly zero column
+    has to raise the device flag and come back through the Householder kernels; rank-deficient and kappa = 1e18 inputs
+    may do either (the result is held to the same contract).
     Which path ran is read from mpse_block_qr_stats."""
     rng = np.random.default_rng(77)
     cases = [  # rows of block 0 / 1, columns of block 0 / 1, condition, rank of block 0 (None = full), expected path
